@@ -9,9 +9,18 @@ One step = zero_grad + forward + MSELoss + backward (+ per-stage gradient all-re
 AdamW.step, on the PSFNoise 32-frame 64x64 configuration (ViT depth 4, dim 128, 4 heads, hidden 256, linear frame
 embedding, regression token) -- BASELINE.json configs[1] -- with synthetic sequences already resident in HBM.
 Weak scaling: the per-GPU batch is fixed, each rank draws its own shard (seed + rank).
-Prints ONE JSON line on rank 0 (see the contract in the task prompt), including `roofline` for the dominant
-kernel (timed with hipEvents inside the library over the timed region) and `cpu_baseline` (the oracle's plain
-PyTorch CPU restatement timed on this host, rank 0, N = 1 only).
+Prints ONE JSON line on rank 0: the headline figure (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = wall time of one timed step).  A plain run does only what that figure needs: set-up, warm-up, the
+--steps timed steps, the output dump and the line.
+
+    --full               adds everything else: `roofline` for the dominant kernel and the per-kernel tables (timed with
+                         hipEvents inside the library over the warm-up tail and the timed region), `val_mse_D`, the
+                         B=4096 / fp32-parity-mode / inference / trained-val side runs (N = 1) and `cpu_baseline` (the
+                         oracle's plain PyTorch CPU restatement timed on this host, rank 0, N = 1 only)
+    --dump-outputs DIR   after the timed steps, writes what the last timed step handed its caller (rank 0) as float32
+                         DIR/<name>.npy: `loss`, `pred` (the model output), `params` and `grads` (every parameter and its
+                         gradient after the optimizer step, flattened and concatenated in parameter order).  The inputs
+                         and the initial weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -85,6 +94,18 @@ def cpu_baseline(seconds=12.0):
                       f"train step, oracle/mivit_oracle.py on torch CPU fp32"}
 
 
+def dump_outputs(out_dir, model, loss, pred):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files (about 9 MB at the default
+    config: the parameters and their gradients are ~1.07 M values each, `pred` one value per sequence)."""
+    import numpy as np
+    params = list(model.parameters())
+    arrays = {"loss": loss, "pred": pred, "params": torch.cat([p.detach().reshape(-1) for p in params]),
+              "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def launch_ranks(n):
     """Start `n` ranks of this script (one per GPU) under torch.distributed.run and wait for them."""
     import socket
@@ -108,10 +129,18 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=int(os.environ.get("MIVIT_BENCH_BATCH", 16384)))
     ap.add_argument("--precision", default=os.environ.get("MIVIT_BENCH_PRECISION", "bf16"), choices=["bf16", "fp32"])
     ap.add_argument("--resident-batches", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the B=4096 / fp32-parity-mode / trained-val side runs")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel-category time table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also report per-kernel times / rooflines, val MSE(D), the side runs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the B=4096 / fp32-parity-mode / trained-val side runs")
+    ap.add_argument("--breakdown", action="store_true", help="with --full: print the per-kernel-category time table to stderr")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full (the per-kernel times are measured there)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -171,10 +200,11 @@ def main():
         def step(i):
             x, y = data[i % len(data)]
             opt.zero_grad(set_to_none=True)
-            loss = loss_fn(m(x), y)
+            out = m(x)
+            loss = loss_fn(out, y)
             loss.backward()
             opt.step()
-            return loss
+            return loss.detach(), out.detach()
         return step
 
     def barrier():
@@ -197,57 +227,65 @@ def main():
     data = [synth(Bg, T, P, 1234 + rank + 1000 * i, dev) for i in range(args.resident_batches)]
     step = make_step(model, opt, data)
 
-    # ---- warmup; the last warmup steps time every kernel category ----
+    # ---- warmup; under --full the last warmup steps time every kernel category.  Those steps restart at batch 0 with or
+    #      without --full, so both runs train on the same batch order ----
     nprof = min(2, args.warmup)
     for i in range(args.warmup - nprof):
         step(i)
     torch.cuda.synchronize()
-    N.lib.mivit_profile_enable(ctypes.c_uint64((1 << len(N.PROF_TAGS)) - 1))
+    if args.full:
+        N.lib.mivit_profile_enable(ctypes.c_uint64((1 << len(N.PROF_TAGS)) - 1))
     for i in range(nprof):
         step(i)
     torch.cuda.synchronize()
-    cat = {}
-    for t, name in enumerate(N.PROF_TAGS):
-        ms, cnt = ctypes.c_double(), ctypes.c_int()
-        N.lib.mivit_profile_collect(t, ctypes.byref(ms), ctypes.byref(cnt))
-        cat[name] = (ms.value / max(nprof, 1), cnt.value // max(nprof, 1))
-    # the kernel that owns the roofline entry: the single launch with the most time per step among the HBM-streaming ones
-    # (the frame-embedding forward); the encoder-layer family, which owns the largest SHARE of the step, gets `roofline_layers`
-    dominant = "embed_fwd"
-    if args.breakdown and rank == 0:
-        tot = sum(v[0] for v in cat.values())
-        for k, (ms, c) in sorted(cat.items(), key=lambda kv: -kv[1][0]):
-            print(f"  {k:14s} {ms:9.3f} ms/step  {c:4d} launches/step  {100 * ms / max(tot, 1e-9):5.1f}%", file=sys.stderr)
-    dom_tag = N.PROF_TAGS.index(dominant)
-    layer_tags = ("linear_fwd", "linear_dgrad", "linear_wgrad", "attn_fwd", "attn_bwd", "ln_fwd", "ln_bwd", "attn_block_fwd",
-                  "mlp_block_fwd", "mlp_block_bwd", "attn_out_bwd", "attn_core_bwd", "qkv_wgrad", "qkv_dgrad", "qkv_bwd")
-    N.lib.mivit_profile_enable(ctypes.c_uint64(1 << dom_tag))
+    if args.full:
+        cat = {}
+        for t, name in enumerate(N.PROF_TAGS):
+            ms, cnt = ctypes.c_double(), ctypes.c_int()
+            N.lib.mivit_profile_collect(t, ctypes.byref(ms), ctypes.byref(cnt))
+            cat[name] = (ms.value / max(nprof, 1), cnt.value // max(nprof, 1))
+        # the kernel that owns the roofline entry: the single launch with the most time per step among the HBM-streaming ones
+        # (the frame-embedding forward); the encoder-layer family, which owns the largest SHARE of the step, gets `roofline_layers`
+        dominant = "embed_fwd"
+        if args.breakdown and rank == 0:
+            tot = sum(v[0] for v in cat.values())
+            for k, (ms, c) in sorted(cat.items(), key=lambda kv: -kv[1][0]):
+                print(f"  {k:14s} {ms:9.3f} ms/step  {c:4d} launches/step  {100 * ms / max(tot, 1e-9):5.1f}%", file=sys.stderr)
+        dom_tag = N.PROF_TAGS.index(dominant)
+        layer_tags = ("linear_fwd", "linear_dgrad", "linear_wgrad", "attn_fwd", "attn_bwd", "ln_fwd", "ln_bwd", "attn_block_fwd",
+                      "mlp_block_fwd", "mlp_block_bwd", "attn_out_bwd", "attn_core_bwd", "qkv_wgrad", "qkv_dgrad", "qkv_bwd")
+        N.lib.mivit_profile_enable(ctypes.c_uint64(1 << dom_tag))
 
     # ---- timed region: EXACTLY --steps steps ----
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    ms, cnt = ctypes.c_double(), ctypes.c_int()
-    N.lib.mivit_profile_collect(dom_tag, ctypes.byref(ms), ctypes.byref(cnt))
-    N.lib.mivit_profile_enable(ctypes.c_uint64(0))
+    if args.full:
+        ms, cnt = ctypes.c_double(), ctypes.c_int()
+        N.lib.mivit_profile_collect(dom_tag, ctypes.byref(ms), ctypes.byref(cnt))
+        N.lib.mivit_profile_enable(ctypes.c_uint64(0))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, *last)
+    del last
 
-    # ---- val MSE(D) of the (untrained, K-step) benchmark model on a held-out synthetic shard ----
-    model.eval()
-    with torch.no_grad():
-        xv, yv = synth(min(Bg, 1024), T, P, 99991 + rank, dev)
-        val_mse = float(F.mse_loss(model(xv) * 10.0, yv * 10.0))
+    if args.full:
+        # ---- val MSE(D) of the (untrained, K-step) benchmark model on a held-out synthetic shard ----
+        model.eval()
+        with torch.no_grad():
+            xv, yv = synth(min(Bg, 1024), T, P, 99991 + rank, dev)
+            val_mse = float(F.mse_loss(model(xv) * 10.0, yv * 10.0))
     del model, opt, data, step
     torch.cuda.empty_cache()
 
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # (1) the SURVEY 8d batch point 4096 and the fp32 parity mode (v_mfma_f32_16x16x4_f32 kernels), short runs
         for tag, prec, bsz in (("batch_4096", args.precision, 4096), ("fp32_parity_mode", "fp32", 2048)):
             m2, o2 = build(prec)
@@ -297,81 +335,6 @@ def main():
     if rank == 0:
         seqs = args.steps * Bg * world
         fl = flops_per_seq(T, P, E, H, Fh, L)
-        k_ms = ms.value / max(cnt.value, 1)
-        ts = 2 if args.precision == "bf16" else 4
-        roof = None
-        if cnt.value:
-            # algorithmic bytes per launch: the fp32 frames of the per-GPU batch, read once, + weight + output
-            byt = Bg * T * P * P * 4 + E * P * P * 4 + Bg * T * E * ts
-            ach = byt / (k_ms * 1e-3) / 1e9
-            roof = {"kernel": dominant, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                    "launch_ms": round(k_ms, 4), "launches_timed": cnt.value,
-                    "algorithmic_bytes_per_launch": byt}
-        # encoder-layer family (everything between the embedding LayerNorm and the final norm, forward + backward): HBM-bound
-        # at these widths.  Two byte counts, in units of U = one [tokens, E] activation:
-        #  * design bytes -- what THIS design's launches must move given what it keeps for the backward: per layer forward 8 U
-        #    (attention block: x in, n1 + ctx + q|k|v out; feed-forward block: n1 in, n2 out), backward 25 U (feed-forward
-        #    block 4; LayerNorm-1 + out-projection 5; attention core 7; q|k|v wgrad 4 + dgrad 5) = 33 U;
-        #  * algorithmic floor -- inputs, outputs and the minimum saved set under full recompute: a layer reads x and writes
-        #    its output in the forward (2 U, the output being the next layer's saved input), and reads x and dy and writes dx
-        #    in the backward (3 U): 5 U per layer.  The gap between the two is activations this design saves instead of
-        #    recomputing; `frac_of_floor` is the honest distance from the roofline.
-        # The byte model belongs to the fused path (bf16, E 128 / F 256 / 4 heads, S <= 64): other paths report times only.
-        S = T + 1
-        U = Bg * S * E * ts
-        Mtok = Bg * S
-        fused_path = bool(args.precision == "bf16" and N.lib.mivit_fused_layer_supported(N.BF16, E, Fh, H, S)
-                          and not os.environ.get("MIVIT_NO_FUSED_LAYER"))
-        layer_ms = sum(cat[k][0] for k in layer_tags if k in cat)
-        roof_layers = None
-        if layer_ms > 0:
-            roof_layers = {"kernels": [k for k in layer_tags if cat.get(k, (0, 0))[0] > 0], "path": "fused" if fused_path else "general",
-                           "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "ms_per_step": round(layer_ms, 4),
-                           "share_of_step": round(layer_ms / (1e3 * dt / args.steps), 3), "traffic": None}
-            if fused_path:
-                # 33 U per layer as two q|k|v backward launches (9 U), 30 U with the one-pass kernel (6 U)
-                nu_layer = 30 if cat.get("qkv_bwd", (0.0, 0))[0] > 0 else 33
-                design, floor = L * nu_layer * U, L * 5 * U
-                roof_layers.update({
-                    "achieved": round(design / (layer_ms * 1e-3) / 1e9, 1), "frac": round(design / (layer_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                    "algorithmic_bytes_per_step": design, "bytes_model": f"design: {nu_layer} U per layer (what this design saves and re-reads)",
-                    "algorithmic_floor_bytes_per_step": floor, "floor_model": "5 U per layer (x, out | x, dy, dx; everything else recomputed)",
-                    "frac_of_floor": round(floor / (layer_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
-        # per-kernel table of the fused path: ms per step, design bytes, algorithmic FLOPs, fraction of both roofs
-        fused_kernels = None
-        if fused_path:
-            spec = {   # name: (U per layer, FLOPs per token and layer)
-                "attn_block_fwd": (6, 8 * E * E + 4 * S * E), "mlp_block_fwd": (2, 4 * E * Fh), "mlp_block_bwd": (4, 10 * E * Fh),
-                "attn_out_bwd": (5, 4 * E * E), "attn_core_bwd": (7, 10 * S * E), "qkv_wgrad": (4, 6 * E * E), "qkv_dgrad": (5, 6 * E * E),
-                "qkv_bwd": (6, 12 * E * E)}
-            fused_kernels = {}
-            for k, (nu, fl_tok) in spec.items():
-                ms_k = cat.get(k, (0.0, 0))[0]
-                if ms_k <= 0:
-                    continue
-                byt_k, fl_k = L * nu * U, L * fl_tok * Mtok
-                fused_kernels[k] = {"ms": round(ms_k, 4), "bytes": byt_k, "flops": fl_k,
-                                    "frac_hbm": round(byt_k / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "frac_mfma": round(fl_k / (ms_k * 1e-3) / 1e12 / MFMA_PEAK["bf16"], 4)}
-            if fused_kernels:
-                worst = min(fused_kernels, key=lambda k: max(fused_kernels[k]["frac_hbm"], fused_kernels[k]["frac_mfma"]))
-                fused_kernels["furthest_below_its_roof"] = worst
-        # HBM traffic from the PMC passes committed under profiles/ (rocprofv3 cannot run inside this process): used only
-        # when it was collected at this per-GPU batch
-        for fname in ("r03_pmc.json", "r02_pmc.json", "r01_pmc_embed.json"):
-            try:
-                with open(os.path.join(ROOT, "profiles", fname)) as fh:
-                    pmc = json.load(fh)
-                if pmc.get("per_gpu_batch") == Bg and args.precision == "bf16":
-                    if roof is not None and roof["traffic"] is None and dominant in pmc.get("kernels", {}):
-                        roof["traffic"] = pmc["kernels"][dominant]["hbm_bytes_per_launch"]
-                        roof["traffic_source"] = "profiles/" + fname
-                    if roof_layers is not None and fused_path and roof_layers["traffic"] is None and "layers_hbm_bytes_per_step" in pmc:
-                        roof_layers["traffic"] = pmc["layers_hbm_bytes_per_step"]
-                        roof_layers["traffic_source"] = "profiles/" + fname
-            except (OSError, ValueError, KeyError):
-                pass
         line = {
             "metric": "training image-sequences/sec", "value": round(seqs / dt, 1), "unit": "sequences/s",
             "n_gpus": world, "rccl_ranks": (dist.get_world_size() if world > 1 and backend == "nccl" else 0),
@@ -383,17 +346,95 @@ def main():
                                    "frame embedding + regression token; train step = fwd + MSE + bwd + AdamW",
                        "per_gpu_batch": Bg, "global_batch": Bg * world, "frames": T, "frame": f"{P}x{P}",
                        "parallelism": f"dp{world}", "input_dtype": "f32 frames resident in HBM"},
-            "val_mse_D": round(val_mse, 4),
             "model_tflops": round(3 * fl["total_fwd"] * seqs / dt / 1e12, 2),
             "attn_mlp_mfma_frac": round(3 * fl["attn_mlp_fwd"] * seqs / dt / 1e12 / world / MFMA_PEAK[args.precision], 5),
-            "roofline": roof,
-            "roofline_layers": roof_layers,
-            "fused_layer_kernels": fused_kernels,
-            "kernel_ms_per_step": {k: round(v[0], 4) for k, v in cat.items()},
         }
-        line.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            k_ms = ms.value / max(cnt.value, 1)
+            ts = 2 if args.precision == "bf16" else 4
+            roof = None
+            if cnt.value:
+                # algorithmic bytes per launch: the fp32 frames of the per-GPU batch, read once, + weight + output
+                byt = Bg * T * P * P * 4 + E * P * P * 4 + Bg * T * E * ts
+                ach = byt / (k_ms * 1e-3) / 1e9
+                roof = {"kernel": dominant, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                        "launch_ms": round(k_ms, 4), "launches_timed": cnt.value,
+                        "algorithmic_bytes_per_launch": byt}
+            # encoder-layer family (everything between the embedding LayerNorm and the final norm, forward + backward): HBM-bound
+            # at these widths.  Two byte counts, in units of U = one [tokens, E] activation:
+            #  * design bytes -- what THIS design's launches must move given what it keeps for the backward: per layer forward 8 U
+            #    (attention block: x in, n1 + ctx + q|k|v out; feed-forward block: n1 in, n2 out), backward 25 U (feed-forward
+            #    block 4; LayerNorm-1 + out-projection 5; attention core 7; q|k|v wgrad 4 + dgrad 5) = 33 U;
+            #  * algorithmic floor -- inputs, outputs and the minimum saved set under full recompute: a layer reads x and writes
+            #    its output in the forward (2 U, the output being the next layer's saved input), and reads x and dy and writes dx
+            #    in the backward (3 U): 5 U per layer.  The gap between the two is activations this design saves instead of
+            #    recomputing; `frac_of_floor` is the honest distance from the roofline.
+            # The byte model belongs to the fused path (bf16, E 128 / F 256 / 4 heads, S <= 64): other paths report times only.
+            S = T + 1
+            U = Bg * S * E * ts
+            Mtok = Bg * S
+            fused_path = bool(args.precision == "bf16" and N.lib.mivit_fused_layer_supported(N.BF16, E, Fh, H, S)
+                              and not os.environ.get("MIVIT_NO_FUSED_LAYER"))
+            layer_ms = sum(cat[k][0] for k in layer_tags if k in cat)
+            roof_layers = None
+            if layer_ms > 0:
+                roof_layers = {"kernels": [k for k in layer_tags if cat.get(k, (0, 0))[0] > 0], "path": "fused" if fused_path else "general",
+                               "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "ms_per_step": round(layer_ms, 4),
+                               "share_of_step": round(layer_ms / (1e3 * dt / args.steps), 3), "traffic": None}
+                if fused_path:
+                    # 33 U per layer as two q|k|v backward launches (9 U), 30 U with the one-pass kernel (6 U)
+                    nu_layer = 30 if cat.get("qkv_bwd", (0.0, 0))[0] > 0 else 33
+                    design, floor = L * nu_layer * U, L * 5 * U
+                    roof_layers.update({
+                        "achieved": round(design / (layer_ms * 1e-3) / 1e9, 1), "frac": round(design / (layer_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                        "algorithmic_bytes_per_step": design, "bytes_model": f"design: {nu_layer} U per layer (what this design saves and re-reads)",
+                        "algorithmic_floor_bytes_per_step": floor, "floor_model": "5 U per layer (x, out | x, dy, dx; everything else recomputed)",
+                        "frac_of_floor": round(floor / (layer_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
+            # per-kernel table of the fused path: ms per step, design bytes, algorithmic FLOPs, fraction of both roofs
+            fused_kernels = None
+            if fused_path:
+                spec = {   # name: (U per layer, FLOPs per token and layer)
+                    "attn_block_fwd": (6, 8 * E * E + 4 * S * E), "mlp_block_fwd": (2, 4 * E * Fh), "mlp_block_bwd": (4, 10 * E * Fh),
+                    "attn_out_bwd": (5, 4 * E * E), "attn_core_bwd": (7, 10 * S * E), "qkv_wgrad": (4, 6 * E * E), "qkv_dgrad": (5, 6 * E * E),
+                    "qkv_bwd": (6, 12 * E * E)}
+                fused_kernels = {}
+                for k, (nu, fl_tok) in spec.items():
+                    ms_k = cat.get(k, (0.0, 0))[0]
+                    if ms_k <= 0:
+                        continue
+                    byt_k, fl_k = L * nu * U, L * fl_tok * Mtok
+                    fused_kernels[k] = {"ms": round(ms_k, 4), "bytes": byt_k, "flops": fl_k,
+                                        "frac_hbm": round(byt_k / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                        "frac_mfma": round(fl_k / (ms_k * 1e-3) / 1e12 / MFMA_PEAK["bf16"], 4)}
+                if fused_kernels:
+                    worst = min(fused_kernels, key=lambda k: max(fused_kernels[k]["frac_hbm"], fused_kernels[k]["frac_mfma"]))
+                    fused_kernels["furthest_below_its_roof"] = worst
+            # HBM traffic from the PMC passes committed under profiles/ (rocprofv3 cannot run inside this process): used only
+            # when it was collected at this per-GPU batch
+            for fname in ("r03_pmc.json", "r02_pmc.json", "r01_pmc_embed.json"):
+                try:
+                    with open(os.path.join(ROOT, "profiles", fname)) as fh:
+                        pmc = json.load(fh)
+                    if pmc.get("per_gpu_batch") == Bg and args.precision == "bf16":
+                        if roof is not None and roof["traffic"] is None and dominant in pmc.get("kernels", {}):
+                            roof["traffic"] = pmc["kernels"][dominant]["hbm_bytes_per_launch"]
+                            roof["traffic_source"] = "profiles/" + fname
+                        if roof_layers is not None and fused_path and roof_layers["traffic"] is None and "layers_hbm_bytes_per_step" in pmc:
+                            roof_layers["traffic"] = pmc["layers_hbm_bytes_per_step"]
+                            roof_layers["traffic_source"] = "profiles/" + fname
+                except (OSError, ValueError, KeyError):
+                    pass
+            line.update({
+                "val_mse_D": round(val_mse, 4),
+                "roofline": roof,
+                "roofline_layers": roof_layers,
+                "fused_layer_kernels": fused_kernels,
+                "kernel_ms_per_step": {k: round(v[0], 4) for k, v in cat.items()},
+            })
+            line.update(extras)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
