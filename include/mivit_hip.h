@@ -25,7 +25,7 @@ extern "C" {
 
 #define MIVIT_ABI_VERSION 1
 
-enum { MIVIT_F32 = 0, MIVIT_BF16 = 1, MIVIT_F16 = 2 };
+enum { MIVIT_F32 = 0, MIVIT_BF16 = 1, MIVIT_F16 = 2, MIVIT_F64 = 3 };   /* F64: trajectory descriptors only */
 enum { MIVIT_ACT_NONE = 0, MIVIT_ACT_RELU = 1, MIVIT_ACT_LEAKY_RELU = 2, MIVIT_ACT_GELU = 3 };
 enum { MIVIT_EMBED_LINEAR = 0, MIVIT_EMBED_CNN = 1, MIVIT_EMBED_EXTERNAL = 2 };
 enum { MIVIT_FUSION_NONE = 0, MIVIT_FUSION_EARLY = 1, MIVIT_FUSION_LATE = 2 };
@@ -178,6 +178,19 @@ int mivit_mlp_block_bwd(const void *dy, const void *n2, const float *rstd2, cons
  * normalisation are element-wise torch ops on the caller's side (helpers/generation.py). */
 int mivit_render_frames(const float *traj_px, int N, int T, int npos, const float *sigmas, int nsig, int P, int up,
                         const float *amp, int center, float *out, void *stream);
+
+/* The 25 hand-crafted trajectory descriptors of the ImagesFeatures experiment (reference helpers/helpersFeatures.py:448-519
+ * compute_diffusion_features and :524-567 compute_features_for_multiple_trajectories, whose frame averaging :555-558 is fused
+ * in; Experiments/ImagesFeatures/trainModelsImagesFeatures.py:36-41 calls it per cycle), csrc/features.hip + csrc/trajfeat.h,
+ * one thread per trajectory, fp64.  traj [N, T, 2] positions, dtype MIVIT_F32 or MIVIT_F64; frames of npos sub-steps are
+ * averaged in that precision (1 <= npos <= T, T / npos <= 1024 frames, a remainder of T % npos sub-steps is ignored);
+ * feats [N, 25] fp64 in helpers/features.py feature_names order, NaN where the reference gives NaN (no nan_to_num); avg
+ * [N, T / npos, 2] in the input dtype receives the averaged positions (NULL: not written).  The alpha / D / r2 fit restates
+ * scipy's bounded 'trf' curve_fit path.  workspace: mivit_trajectory_features_workspace_bytes(N, T, npos).  Arguments are
+ * validated before any HIP call; N = 0 is a no-op. */
+size_t mivit_trajectory_features_workspace_bytes(int N, int T, int npos);
+int mivit_trajectory_features(const void *traj, int dtype, int N, int T, int npos, double dt, double *feats, void *avg,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:

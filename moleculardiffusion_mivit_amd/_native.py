@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_PKG, "libmivit_hip.so")
 
 ABI_VERSION = 1
 F32, BF16, F16 = 0, 1, 2
+F64 = 3                                     # trajectory descriptors only
 ACT_NONE, ACT_RELU, ACT_LEAKY_RELU, ACT_GELU = 0, 1, 2, 3
 EMBED_LINEAR, EMBED_CNN, EMBED_EXTERNAL = 0, 1, 2
 FUSION_NONE, FUSION_EARLY, FUSION_LATE = 0, 1, 2
@@ -122,6 +123,9 @@ SYMBOLS = {
     "mivit_mlp_block_bwd_set_waves": (c_int, [c_int]),
     "mivit_mlp_block_bwd": (c_int, [c_void_p] * 10 + [c_int, c_int] + [c_void_p] * 8 + [c_size_t, c_void_p]),
     "mivit_render_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "mivit_trajectory_features_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mivit_trajectory_features": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes": (c_size_t, [c_int]),
     "mivit_attn_out_bwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "mivit_embed_small_supported": (c_int, [c_int, c_int, c_int]),

@@ -10,9 +10,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_fast.hip", "embed.hip", "rowstream.hip", "wavestream.hip", "gemm_dma.hip", "wgrad_dma.hip", "wgrad_small.hip", "fused_fwd.hip", "fused_bwd.hip", "render.hip", "deepresnet.hip", "deepresnet_train.hip", "misc.hip", "engine.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_fast.hip", "embed.hip", "rowstream.hip", "wavestream.hip", "gemm_dma.hip", "wgrad_dma.hip", "wgrad_small.hip", "fused_fwd.hip", "fused_bwd.hip", "render.hip", "features.hip", "deepresnet.hip", "deepresnet_train.hip", "misc.hip", "engine.hip"]
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "stream_prims.h"), os.path.join(HERE, "elem.h"),
-           os.path.join(ROOT, "include", "mivit_hip.h")]
+           os.path.join(HERE, "trajfeat.h"), os.path.join(ROOT, "include", "mivit_hip.h")]
 # the streaming kernels whose element type is chosen per translation unit (elem.h): each is compiled a second time with
 # -DMIVIT_ELEM_F16 (IEEE half instead of bf16, every external suffixed _f16) and both objects go into the library
 ELEM_SOURCES = ["rowstream.hip", "wavestream.hip", "wgrad_dma.hip", "wgrad_small.hip", "attention_fast.hip", "embed.hip",
@@ -26,6 +26,10 @@ LIB = os.path.join(PKG, "libmivit_hip.so")
 # results; the product (_native.py) never loads it.  Only the sources that call wait_vm are compiled twice.
 LIB_STRICT = os.path.join(PKG, "libmivit_hip_strict.so")
 WAIT_SOURCES = ["embed.hip", "rowstream.hip", "gemm_dma.hip", "wgrad_dma.hip", "fused_bwd.hip"]
+# csrc/trajfeat.h (the trajectory descriptors of csrc/features.hip) compiled for the host by the host C++ compiler.
+# TEST INFRASTRUCTURE ONLY: tests/test_trajfeat_host.py holds it against scipy, tests/test_features_gpu.py holds the kernel
+# against it; the product never loads it.
+LIB_TRAJFEAT_HOST = os.path.join(PKG, "libmivit_trajfeat_host.so")
 OBJDIR = os.path.join(HERE, "build")
 # -amdgpu-mfma-vgpr-form: MFMA results in arch VGPRs where they fit.  By default the accumulators go to AGPRs and every value a
 # VALU instruction consumes afterwards (softmax, bias, packing, stores) costs a v_accvgpr_read first: attention_fast.hip 23 k
@@ -104,7 +108,24 @@ def build(force=False, verbose=True, strict=True):
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    _build_trajfeat_host(force, verbose)
     return LIB
+
+
+def _build_trajfeat_host(force=False, verbose=True):
+    src = os.path.join(HERE, "trajfeat_host.cpp")
+    if not (force or _stale(LIB_TRAJFEAT_HOST, [src, os.path.join(HERE, "trajfeat.h"), os.path.abspath(__file__)])):
+        return LIB_TRAJFEAT_HOST
+    cxx = os.environ.get("CXX") or "c++"
+    # no contraction into FMA: the fit follows scipy's operation order
+    cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", src,
+           "-o", LIB_TRAJFEAT_HOST]
+    if verbose:
+        print("[mivit build]", " ".join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"host build of trajfeat failed:\n{r.stdout}\n{r.stderr}")
+    return LIB_TRAJFEAT_HOST
 
 
 if __name__ == "__main__":

@@ -22,12 +22,14 @@ def predict_train(model, name, images, features):
 
 
 def run_training(num_cycles=100, N=64, TrainingDs_list=([1, 1], [3, 1], [5, 1], [7, 1], [9, 1]), seed=None, out_dir=".",
-                 save=True, device=None, verbose=False, model_filter=None, **model_kwargs):
+                 save=True, device=None, verbose=False, model_filter=None, feature_device=None, **model_kwargs):
+    """feature_device=None: the 25 descriptors on the CPU (scipy, the reference yardstick); "cuda": from the HIP kernel,
+    with videos, labels and every random draw unchanged."""
     g = torch.Generator().manual_seed(seed) if seed is not None else None
     models, optimizers, schedulers = S.getTrainingModels(**model_kwargs)
     if model_filter is not None:
         models = {k: v for k, v in models.items() if k in model_filter}
-    vals = S.load_validation_data(S.nFrames, skip_inorder=True, generator=g)[:5]
+    vals = S.load_validation_data(S.nFrames, skip_inorder=True, generator=g, feature_device=feature_device)[:5]
     val_sets = [((v, f), D) for (v, f, _), D in zip(vals, C.D_VALUES)]
 
     def make_batch_data(cycle):
@@ -36,7 +38,8 @@ def run_training(num_cycles=100, N=64, TrainingDs_list=([1, 1], [3, 1], [5, 1], 
             trajs, labels = gen.brownian_single_state(N, S.T, Ds=Ds, alphas=1, generator=g)
             labs.append(labels[0, :, 1].numpy())
             v, f, _ = S.create_video_and_feature_pairs(trajs.permute(1, 0, 2).numpy() / S.traj_div_factor, S.nPosPerFrame, S.center,
-                                                       S.image_props, generator=g)
+                                                       S.image_props, generator=g,
+                                                       feature_device=feature_device)
             vids.append(torch.as_tensor(v))
             feats.append(torch.as_tensor(f))
         raw = np.concatenate(labs)

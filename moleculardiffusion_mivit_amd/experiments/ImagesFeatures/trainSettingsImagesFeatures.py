@@ -125,9 +125,11 @@ def make_prediction(model, name, images, features, trajectories=None, msd_mult_f
 
 
 def create_video_and_feature_pairs(trajectories, nPosPerFrame, center, image_props, localization_uncertainty=(0, 0), dt=1.0,
-                                   generator=None):
+                                   generator=None, feature_device=None):
     """(N, T, 2) trajectories -> (normalised videos [N, nFrames, P, P], features [N, 25], (trajectories, frame-averaged,
-    frame-averaged + localisation error)) -- helpersGeneration.py:674-720."""
+    frame-averaged + localisation error)) -- helpersGeneration.py:674-720.  feature_device="cuda": the features come from
+    the HIP kernel (helpers/features.compute_features_for_trajectories); everything else, random draws included, is
+    unchanged."""
     traj = np.asarray(trajectories, dtype=np.float32)
     bg_mean, bg_sigma = image_props["background_intensity"]
     pm = image_props["particle_intensity"][0]
@@ -135,24 +137,27 @@ def create_video_and_feature_pairs(trajectories, nPosPerFrame, center, image_pro
     vid = gen.normalize_images(vid, bg_mean, bg_sigma, pm + bg_mean)[0]
     seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=generator)) if generator is not None else None
     feats, avg, noisy = ft.compute_features_for_trajectories(traj, nPosPerFrame, dt=dt, localization_uncertainty=localization_uncertainty,
-                                                             rng=np.random.default_rng(seed))
+                                                             rng=np.random.default_rng(seed), feature_device=feature_device)
     return np.asarray(vid, dtype=np.float32), feats.astype(np.float32), (traj, avg, noisy)
 
 
-def load_validation_data(length=20, skip_inorder=False, generator=None, n_synthetic=50):
+def load_validation_data(length=20, skip_inorder=False, generator=None, n_synthetic=50, feature_device=None):
     """((videos, features, trajectory triple) for D = 1, 3, 5, 7, 9, and the in-order set) -- reference :194-231.  Uses the
-    reference's validation_trajectories/*.npy when present (MIVIT_VALIDATION_ROOT), seeded Brownian sets otherwise."""
+    reference's validation_trajectories/*.npy when present (MIVIT_VALIDATION_ROOT), seeded Brownian sets otherwise.
+    feature_device: as in create_video_and_feature_pairs."""
     g = generator or torch.Generator().manual_seed(20250815)
     sets, tio = C.validation_trajectories(length, T, traj_div_factor, g, n_synthetic,
                                           None if skip_inorder else (val_d_in_order, N_in_order))
     out = []
     for tr in sets:
-        v, f, t = create_video_and_feature_pairs(tr, nPosPerFrame, center, image_props, localization_uncertainty, dt, g)
+        v, f, t = create_video_and_feature_pairs(tr, nPosPerFrame, center, image_props, localization_uncertainty, dt, g,
+                                                 feature_device)
         out.append((torch.Tensor(v), torch.Tensor(f), t))
     if skip_inorder:
         out.append((torch.zeros(1), torch.zeros(1), np.zeros(1)))
     else:
-        v, f, t = create_video_and_feature_pairs(tio, nPosPerFrame, center, image_props, localization_uncertainty, dt, g)
+        v, f, t = create_video_and_feature_pairs(tio, nPosPerFrame, center, image_props, localization_uncertainty, dt, g,
+                                                 feature_device)
         out.append((torch.Tensor(v).reshape(len(val_d_in_order), N_in_order, nFrames, patch_size, patch_size),
                     torch.Tensor(f).reshape(len(val_d_in_order), N_in_order, N_features), t))
     return tuple(out)

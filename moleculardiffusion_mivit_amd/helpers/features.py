@@ -109,11 +109,55 @@ def average_trajectories_frames(trajectories, nPosFrame):
     return t[:, :nf * nPosFrame].reshape(n, nf, nPosFrame, d).mean(axis=2)
 
 
-def compute_features_for_trajectories(trajectories, nPosPerFrame, dt=1.0, localization_uncertainty=(0, 0), rng=None):
+def compute_features_for_trajectories(trajectories, nPosPerFrame, dt=1.0, localization_uncertainty=(0, 0), rng=None,
+                                      feature_device=None):
     """What create_video_and_feature_pairs does on the trajectory side (helpersGeneration.py:703-718): frame-averaged
-    positions (+ the same with Gaussian localisation error) and the [N, 25] feature matrix of the averaged ones."""
+    positions (+ the same with Gaussian localisation error) and the [N, 25] feature matrix of the averaged ones.
+
+    feature_device=None / "cpu": the features come from compute_diffusion_features (scipy).  A CUDA device ("cuda",
+    "cuda:1", ...): only the feature matrix comes from the HIP kernel (ops.trajectory_features); the averaged and noisy
+    positions and the random draw are the same as on the CPU path."""
     avg = average_trajectories_frames(trajectories, nPosPerFrame)
     rng = rng or np.random.default_rng()
     noisy = avg + rng.normal(localization_uncertainty[0], localization_uncertainty[1], size=avg.shape)
-    feats = np.stack([compute_diffusion_features(a, dt=dt) for a in avg]) if len(avg) else np.zeros((0, N_features))
+    if feature_device is not None and str(feature_device) != "cpu":
+        import torch
+        from .. import ops
+        t = np.asarray(trajectories)
+        t = t if t.dtype in (np.float32, np.float64) else t.astype(np.float64)
+        feats = ops.trajectory_features(torch.as_tensor(t).to(feature_device), nPosPerFrame, dt).cpu().numpy()
+    else:
+        feats = np.stack([compute_diffusion_features(a, dt=dt) for a in avg]) if len(avg) else np.zeros((0, N_features))
     return feats, avg, noisy
+
+
+def compute_features_for_multiple_trajectories(trajectories, dt=1, nPosPerFrame=1):
+    """Drop-in for the reference's batch entry (helpers/helpersFeatures.py:524-567): (P, N, 2) positions -> (P, 25)
+    features of the frame-averaged trajectories (nPosPerFrame sub-steps per frame), NaN replaced as np.nan_to_num does.
+
+    The path follows the input: a numpy array runs compute_diffusion_features on the CPU and returns numpy; a CUDA tensor
+    runs the HIP kernel (csrc/features.hip) and returns a CUDA float64 tensor.  N must be a multiple of nPosPerFrame (the
+    reference's reshape fails otherwise)."""
+    try:
+        import torch
+        is_tensor = isinstance(trajectories, torch.Tensor)
+    except ImportError:                                            # pragma: no cover
+        is_tensor = False
+    steps = trajectories.shape[1]
+    if nPosPerFrame < 1 or steps % nPosPerFrame != 0:
+        raise ValueError(f"{steps} positions per trajectory are not a whole number of frames of {nPosPerFrame}")
+    if is_tensor:
+        if trajectories.device.type != "cuda":
+            raise ValueError("compute_features_for_multiple_trajectories: a tensor input must be on the GPU "
+                             "(pass a numpy array for the CPU path)")
+        from .. import ops
+        t = trajectories if trajectories.dtype in (torch.float32, torch.float64) else trajectories.double()
+        return torch.nan_to_num(ops.trajectory_features(t, nPosPerFrame, dt), nan=0.0)
+    t = np.asarray(trajectories)
+    features = np.zeros((t.shape[0], N_features))
+    for i in range(t.shape[0]):
+        traj = t[i]
+        if nPosPerFrame != 1:
+            traj = traj.reshape(steps // nPosPerFrame, nPosPerFrame, -1).mean(axis=1)
+        features[i] = np.nan_to_num(compute_diffusion_features(traj, dt), nan=0.0)
+    return features

@@ -465,3 +465,26 @@ def qkv_bwd(dqkv, x, Wqkv, res):
     N.check(_fused_entry("mivit_qkv_bwd", E)(*[_p(t) for t in args], M, _p(out["dx"]), _p(out["dW"]), _p(out["db"]), _p(ws), nbytes,
                                              _s(x)), "mivit_qkv_bwd")
     return out
+
+
+def trajectory_features(traj: torch.Tensor, nPosPerFrame: int = 1, dt: float = 1.0, return_average: bool = False):
+    """The 25 descriptors of helpers/features.compute_diffusion_features for every trajectory of a GPU batch (csrc/features.hip):
+    traj [N, T, 2] float32 / float64 sub-step positions -> features [N, 25] float64 (NaN where the reference gives NaN),
+    frames of nPosPerFrame sub-steps averaged in the input precision first; with return_average also the averaged positions
+    [N, T // nPosPerFrame, 2] in the input dtype."""
+    _gpu(traj)
+    if traj.dim() != 3 or traj.shape[-1] != 2:
+        raise ValueError(f"trajectories must be [N, T, 2], got {tuple(traj.shape)}")
+    if traj.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"unsupported dtype {traj.dtype} (float32 or float64)")
+    traj = traj.contiguous()
+    n, steps, _ = traj.shape
+    nf = steps // nPosPerFrame if nPosPerFrame >= 1 else 0
+    feats = torch.empty(n, 25, dtype=torch.float64, device=traj.device)
+    avg = torch.empty(n, nf, 2, dtype=traj.dtype, device=traj.device) if return_average else None
+    wsb = N.lib.mivit_trajectory_features_workspace_bytes(n, steps, nPosPerFrame)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=traj.device)
+    N.check(N.lib.mivit_trajectory_features(_p(traj), N.F32 if traj.dtype == torch.float32 else N.F64, n, steps,
+                                            nPosPerFrame, float(dt), _p(feats), _p(avg), _p(ws), ws.numel(), _s(traj)),
+            "mivit_trajectory_features")
+    return (feats, avg) if return_average else feats
