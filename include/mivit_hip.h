@@ -210,9 +210,19 @@ int mivit_attn_out_bwd(const void *dy, const void *n1, const float *rstd1, const
 size_t mivit_qkv_bwd_workspace_bytes(int M);
 int mivit_qkv_bwd(const void *dqkv, const void *x, const void *Wqkv_bf16, const void *res, int M, void *dx, float *dW, float *db,
                   void *workspace, size_t workspace_bytes, void *stream);
+/* The same with the projection's input given as x = fix_gamma * n + fix_beta, where `x` above holds n (a LayerNorm's normalised
+ * output, fix_gamma / fix_beta [E] fp32 its affine): dW = dqkv^T (fix_gamma * n + fix_beta) = (dqkv^T n) diag(fix_gamma) +
+ * db (x) fix_beta, applied to each workgroup's partial sums (the engine's path for every layer after the first); dx and db as
+ * above.  fix_gamma = fix_beta = NULL is mivit_qkv_bwd. */
+int mivit_qkv_bwd_affine(const void *dqkv, const void *x, const void *Wqkv_bf16, const void *res, int M, void *dx, float *dW,
+                         float *db, const float *fix_gamma, const float *fix_beta, void *workspace, size_t workspace_bytes,
+                         void *stream);
 size_t mivit_qkv_bwd_workspace_bytes_w64(int M);
 int mivit_qkv_bwd_w64(const void *dqkv, const void *x, const void *Wqkv_bf16, const void *res, int M, void *dx, float *dW, float *db,
                       void *workspace, size_t workspace_bytes, void *stream);
+int mivit_qkv_bwd_affine_w64(const void *dqkv, const void *x, const void *Wqkv_bf16, const void *res, int M, void *dx, float *dW,
+                             float *db, const float *fix_gamma, const float *fix_beta, void *workspace, size_t workspace_bytes,
+                             void *stream);
 
 /* The same five operators for the reference's shipped layer width: E = 64, F = 128, 4 heads of 16
  * (Experiments/Framerate/trainSettingsFramerate.py:42-47, Experiments/ImagesFeatures/...:112-188): csrc/fused_fwd.hip and
@@ -235,6 +245,60 @@ size_t mivit_attn_out_bwd_workspace_bytes_w64(int M);
 int mivit_attn_out_bwd_w64(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
                            const void *Wo_bf16, int M, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1,
                            float *dbeta1, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The five operators in IEEE half (fp16 models: the engine's fp16 layer path): csrc/fused_fwd.hip and csrc/fused_bwd.hip
+ * compiled with -DMIVIT_ELEM_F16, at width 128 (..._f16) and width 64 (..._w64_f16).  Same arguments and layouts as above with
+ * every 16-bit tensor (activations, gradients and weight copies) in fp16; biases, LayerNorm vectors, rstd / mean and the
+ * parameter gradients stay fp32.  mivit_mlp_block_bwd_set_waves_f16 is the fp16 width-128 build's kernel switch. */
+int mivit_fused_layer_supported_f16(int dtype, int embed_dim, int hidden_dim, int num_heads, int tokens);
+int mivit_attn_block_fwd_f16(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv,
+                             const float *bqkv, const void *Wo, const float *bo, const float *gamma_out,
+                             const float *beta_out, int B, int S, void *ctx, void *n_out, float *rstd, void *x_out,
+                             void *z_out, float *mean, void *qkv_out, void *stream);
+int mivit_mlp_block_fwd_f16(const void *n_in, const float *gamma_in, const float *beta_in, const void *W1,
+                            const float *b1, const void *W2, const float *b2, const float *gamma_out,
+                            const float *beta_out, int M, int act, void *n_out, float *rstd, void *x_out, void *z_out,
+                            float *mean, void *h_out, void *u_out, void *stream);
+size_t mivit_mlp_block_bwd_workspace_bytes_f16(int M);
+int mivit_mlp_block_bwd_f16(const void *dy, const void *n2, const float *rstd2, const float *gamma2, const void *n1,
+                            const float *gamma1, const float *beta1, const void *W1, const float *b1, const void *W2,
+                            int M, int act, void *dx1, float *dW1, float *db1, float *dW2, float *db2, float *dgamma2,
+                            float *dbeta2, void *workspace, size_t workspace_bytes, void *stream);
+size_t mivit_attn_out_bwd_workspace_bytes_f16(int M);
+int mivit_attn_out_bwd_f16(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+                           const void *Wo, int M, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1,
+                           float *dbeta1, void *workspace, size_t workspace_bytes, void *stream);
+size_t mivit_qkv_bwd_workspace_bytes_f16(int M);
+int mivit_qkv_bwd_f16(const void *dqkv, const void *x, const void *Wqkv, const void *res, int M, void *dx, float *dW, float *db,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int mivit_qkv_bwd_affine_f16(const void *dqkv, const void *x, const void *Wqkv, const void *res, int M, void *dx, float *dW,
+                             float *db, const float *fix_gamma, const float *fix_beta, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int mivit_mlp_block_bwd_set_waves_f16(int waves);
+int mivit_fused_layer_supported_w64_f16(int dtype, int embed_dim, int hidden_dim, int num_heads, int tokens);
+int mivit_attn_block_fwd_w64_f16(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv,
+                                 const float *bqkv, const void *Wo, const float *bo, const float *gamma_out,
+                                 const float *beta_out, int B, int S, void *ctx, void *n_out, float *rstd, void *x_out,
+                                 void *z_out, float *mean, void *qkv_out, void *stream);
+int mivit_mlp_block_fwd_w64_f16(const void *n_in, const float *gamma_in, const float *beta_in, const void *W1,
+                                const float *b1, const void *W2, const float *b2, const float *gamma_out,
+                                const float *beta_out, int M, int act, void *n_out, float *rstd, void *x_out, void *z_out,
+                                float *mean, void *h_out, void *u_out, void *stream);
+size_t mivit_mlp_block_bwd_workspace_bytes_w64_f16(int M);
+int mivit_mlp_block_bwd_w64_f16(const void *dy, const void *n2, const float *rstd2, const float *gamma2, const void *n1,
+                                const float *gamma1, const float *beta1, const void *W1, const float *b1, const void *W2,
+                                int M, int act, void *dx1, float *dW1, float *db1, float *dW2, float *db2, float *dgamma2,
+                                float *dbeta2, void *workspace, size_t workspace_bytes, void *stream);
+size_t mivit_attn_out_bwd_workspace_bytes_w64_f16(int M);
+int mivit_attn_out_bwd_w64_f16(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+                               const void *Wo, int M, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1,
+                               float *dbeta1, void *workspace, size_t workspace_bytes, void *stream);
+size_t mivit_qkv_bwd_workspace_bytes_w64_f16(int M);
+int mivit_qkv_bwd_w64_f16(const void *dqkv, const void *x, const void *Wqkv, const void *res, int M, void *dx, float *dW, float *db,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int mivit_qkv_bwd_affine_w64_f16(const void *dqkv, const void *x, const void *Wqkv, const void *res, int M, void *dx, float *dW,
+                                 float *db, const float *fix_gamma, const float *fix_beta, void *workspace, size_t workspace_bytes,
+                                 void *stream);
 
 /* DeepResNetEmbedding in inference mode (helpers/models.py:230-257; ResidualBlock :202-228): conv3x3(1->32)+BN+ReLU,
  * ResidualBlock(32->64), ResidualBlock(64->128), global average pool, Linear(128->E), fused in one kernel that keeps F

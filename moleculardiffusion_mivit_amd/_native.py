@@ -143,10 +143,19 @@ SYMBOLS = {
     "mivit_mlp_block_bwd_w64": (c_int, [c_void_p] * 10 + [c_int, c_int] + [c_void_p] * 8 + [c_size_t, c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes_w64": (c_size_t, [c_int]),
     "mivit_attn_out_bwd_w64": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "mivit_qkv_bwd_affine": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "mivit_qkv_bwd_affine_w64": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "mivit_mlp_block_bwd_set_waves_f16": (c_int, [c_int]),
     "mivit_profile_enable": (c_int, [ctypes.c_uint64]),
     "mivit_profile_collect": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(c_int)]),
     "mivit_profile_tag_name": (c_char_p, [c_int]),
 }
+# the fp16 builds of the fused blocks export the same operator set as the bf16 width-128 build, suffixed _f16 / _w64_f16
+for _sfx in ("_f16", "_w64_f16"):
+    for _name in ("mivit_fused_layer_supported", "mivit_attn_block_fwd", "mivit_mlp_block_fwd", "mivit_mlp_block_bwd_workspace_bytes",
+                  "mivit_mlp_block_bwd", "mivit_attn_out_bwd_workspace_bytes", "mivit_attn_out_bwd", "mivit_qkv_bwd_workspace_bytes",
+                  "mivit_qkv_bwd", "mivit_qkv_bwd_affine"):
+        SYMBOLS[_name + _sfx] = SYMBOLS[_name]
 PROF_TAGS = ["embed_fwd", "embed_wgrad", "linear_fwd", "linear_dgrad", "linear_wgrad", "attn_fwd", "attn_bwd",
              "ln_fwd", "ln_bwd", "op", "attn_block_fwd", "mlp_block_fwd", "mlp_block_bwd", "attn_out_bwd", "attn_core_bwd",
              "qkv_wgrad", "qkv_dgrad", "qkv_bwd"]

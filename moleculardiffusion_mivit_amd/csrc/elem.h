@@ -56,8 +56,9 @@ __device__ __forceinline__ float elem_hi(uint32_t w) { return __uint_as_float(w 
 
 // The fused encoder-layer blocks (fused_fwd.hip / fused_bwd.hip) are in addition compiled per LAYER WIDTH: as is for
 // E = 128 / F = 256 / head dim 32, and with -DMIVIT_WIDTH64 for the reference's shipped E = 64 / F = 128 / head dim 16
-// (Experiments/Framerate/trainSettingsFramerate.py:42-47).  Their externals carry _w64 and / or _f16; the bf16 builds also
-// export the operator-level C entry points (mivit_attn_block_fwd ..., include/mivit_hip.h), the width-64 one as ..._w64.
+// (Experiments/Framerate/trainSettingsFramerate.py:42-47).  Their externals carry _w64 and / or _f16, and so do the
+// operator-level C entry points every one of the four builds exports (mivit_attn_block_fwd, ..._w64, ..._f16, ..._w64_f16;
+// include/mivit_hip.h).
 #if defined(MIVIT_WIDTH64) && defined(MIVIT_ELEM_F16)
 #define MIVIT_FUSED_NAME(x) x##_w64_f16
 #elif defined(MIVIT_WIDTH64)
@@ -75,15 +76,15 @@ __device__ __forceinline__ float elem_hi(uint32_t w) { return __uint_as_float(w 
 #define launch_attn_out_bwd MIVIT_FUSED_NAME(launch_attn_out_bwd)
 #define qkv_bwd_ws_bytes MIVIT_FUSED_NAME(qkv_bwd_ws_bytes)
 #define launch_qkv_bwd MIVIT_FUSED_NAME(launch_qkv_bwd)
-#endif
-#if defined(MIVIT_WIDTH64) && !defined(MIVIT_ELEM_F16)
-#define mivit_fused_layer_supported mivit_fused_layer_supported_w64
-#define mivit_mlp_block_fwd mivit_mlp_block_fwd_w64
-#define mivit_attn_block_fwd mivit_attn_block_fwd_w64
-#define mivit_mlp_block_bwd_workspace_bytes mivit_mlp_block_bwd_workspace_bytes_w64
-#define mivit_mlp_block_bwd mivit_mlp_block_bwd_w64
-#define mivit_attn_out_bwd_workspace_bytes mivit_attn_out_bwd_workspace_bytes_w64
-#define mivit_attn_out_bwd mivit_attn_out_bwd_w64
-#define mivit_qkv_bwd_workspace_bytes mivit_qkv_bwd_workspace_bytes_w64
-#define mivit_qkv_bwd mivit_qkv_bwd_w64
+#define mivit_fused_layer_supported MIVIT_FUSED_NAME(mivit_fused_layer_supported)
+#define mivit_mlp_block_fwd MIVIT_FUSED_NAME(mivit_mlp_block_fwd)
+#define mivit_attn_block_fwd MIVIT_FUSED_NAME(mivit_attn_block_fwd)
+#define mivit_mlp_block_bwd_workspace_bytes MIVIT_FUSED_NAME(mivit_mlp_block_bwd_workspace_bytes)
+#define mivit_mlp_block_bwd_set_waves MIVIT_FUSED_NAME(mivit_mlp_block_bwd_set_waves)
+#define mivit_mlp_block_bwd MIVIT_FUSED_NAME(mivit_mlp_block_bwd)
+#define mivit_attn_out_bwd_workspace_bytes MIVIT_FUSED_NAME(mivit_attn_out_bwd_workspace_bytes)
+#define mivit_attn_out_bwd MIVIT_FUSED_NAME(mivit_attn_out_bwd)
+#define mivit_qkv_bwd_workspace_bytes MIVIT_FUSED_NAME(mivit_qkv_bwd_workspace_bytes)
+#define mivit_qkv_bwd MIVIT_FUSED_NAME(mivit_qkv_bwd)
+#define mivit_qkv_bwd_affine MIVIT_FUSED_NAME(mivit_qkv_bwd_affine)
 #endif

@@ -12,7 +12,9 @@
 //   phase 0 (all threads, element-wise): LayerNorm backward dy, n2 -> dz2 (LDS image DZ), n1 -> LDS image X; the
 //            column sums for dgamma2 / dbeta2 / db2 stay in registers; next tile's rows are already in flight.
 //   phase 1 (wave w owns hidden units 64w .. 64w+63; its slices of fc1 and fc2^T live in REGISTERS):
-//            u = n1 W1'^T + b1' (W1' = W1 * gamma1, b1' = b1 + W1 beta1: the LayerNorm affine is folded),
+//            u = x1 W1^T + b1 on the element-type image X of x1 = gamma1 * n1 + beta1 (phase 0 forms it; W1 is staged
+//            as stored: the backward does NOT fold the LayerNorm affine into the weights as the forward does, so the two
+//            round u differently),
 //            dh = (dz2 W2) * act'(u) -- both un-transposed, so the accumulators (lane = hidden unit, registers = rows)
 //            ARE the row-contraction operands of the weight gradients:  dW1 += dh^T n1,  dW2 += dz2^T h, whose other
 //            operand is a transposing LDS read (ds_read_b64_tr_b16) of X / DZ.  128 + 128 accumulator registers per
@@ -1093,7 +1095,7 @@ constexpr int NW8 = 8;
 #else
 static int g_mlp_bwd_waves = [] { const char *e = getenv("MIVIT_MLP_BWD_WAVES"); return e && atoi(e) == 4 ? 4 : 8; }();
 #endif
-#if !defined(MIVIT_ELEM_F16) && !defined(MIVIT_WIDTH64)
+#ifndef MIVIT_WIDTH64          // (exported as mivit_mlp_block_bwd_set_waves / ..._f16: one switch per element type)
 extern "C" int mivit_mlp_block_bwd_set_waves(int waves) {
     const int old = g_mlp_bwd_waves;
     if (waves == 4 || waves == 8) g_mlp_bwd_waves = waves;
@@ -1190,7 +1192,7 @@ int launch_mlp_block_bwd(const void *dy, const void *n2, const float *rstd2, con
     return 0;
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h; the width-64 build exports ..._w64)
+// operator-level C-ABI (include/mivit_hip.h): every build exports it, named by elem.h (..., _w64, _f16, _w64_f16)
 extern "C" size_t mivit_mlp_block_bwd_workspace_bytes(int M) { return mlp_block_bwd_ws_bytes(M); }
 extern "C" int mivit_mlp_block_bwd(const void *dy, const void *n2, const float *rstd2, const float *gamma2, const void *n1,
                                    const float *gamma1, const float *beta1, const void *W1_bf16, const float *b1,
@@ -1202,7 +1204,6 @@ extern "C" int mivit_mlp_block_bwd(const void *dy, const void *n2, const float *
                                 dbeta2, workspace, workspace_bytes, s);
 }
 
-#endif
 size_t attn_out_bwd_ws_bytes(int M) { return align_up((size_t)std::min(512, ceil_div(std::max(M, 1), R)) * AO_SL_TOTAL * sizeof(float), 256); }
 
 // dz1, dctx [M,E] bf16; dWo [E,E], dbo, dgamma1, dbeta1 [E] fp32 (overwritten)
@@ -1231,12 +1232,18 @@ int launch_attn_out_bwd(const void *dy, const void *n1, const float *rstd1, cons
     return 0;
 }
 
-#ifndef MIVIT_ELEM_F16
 extern "C" size_t mivit_qkv_bwd_workspace_bytes(int M) { return qkv_bwd_ws_bytes(M); }
 extern "C" int mivit_qkv_bwd(const void *dqkv, const void *x, const void *Wqkv_bf16, const void *res, int M, void *dx, float *dW, float *db,
                              void *workspace, size_t workspace_bytes, void *stream) {
     prof_set_tag(MIVIT_PROF_OP);
     return launch_qkv_bwd(dqkv, x, Wqkv_bf16, res, M, dx, dW, db, nullptr, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+extern "C" int mivit_qkv_bwd_affine(const void *dqkv, const void *x, const void *Wqkv_bf16, const void *res, int M, void *dx, float *dW,
+                                    float *db, const float *fix_gamma, const float *fix_beta, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+    prof_set_tag(MIVIT_PROF_OP);
+    return launch_qkv_bwd(dqkv, x, Wqkv_bf16, res, M, dx, dW, db, fix_gamma, fix_beta, workspace, workspace_bytes,
+                          static_cast<hipStream_t>(stream));
 }
 extern "C" size_t mivit_attn_out_bwd_workspace_bytes(int M) { return attn_out_bwd_ws_bytes(M); }
 extern "C" int mivit_attn_out_bwd(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
@@ -1246,4 +1253,3 @@ extern "C" int mivit_attn_out_bwd(const void *dy, const void *n1, const float *r
     return launch_attn_out_bwd(dy, n1, rstd1, gamma1, ctx, Wo_bf16, M, dz1, dctx, dWo, dbo, dgamma1, dbeta1, workspace, workspace_bytes,
                                static_cast<hipStream_t>(stream));
 }
-#endif

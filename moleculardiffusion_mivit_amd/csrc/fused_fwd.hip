@@ -869,8 +869,7 @@ int launch_attn_block_fwd(const void *nin, const float *gin, const float *bin, c
     return 0;
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h)
-// ---- operator-level C-ABI (tests, external callers) ----
+// ---- operator-level C-ABI (tests, external callers; include/mivit_hip.h): one set per build, named by elem.h ----
 extern "C" int mivit_fused_layer_supported(int dtype, int embed_dim, int hidden_dim, int num_heads, int tokens) {
     return fused_layer_supported(dtype, embed_dim, hidden_dim, num_heads, tokens) ? 1 : 0;
 }
@@ -890,4 +889,3 @@ extern "C" int mivit_attn_block_fwd(const void *n_in, const float *gamma_in, con
     return launch_attn_block_fwd(n_in, gamma_in, beta_in, Wqkv_bf16, bqkv, Wo_bf16, bo, gamma_out, beta_out, B, S, ctx, n_out,
                                  rstd, x_out, z_out, mean, qkv_out, static_cast<hipStream_t>(stream));
 }
-#endif

@@ -341,21 +341,36 @@ def deepresnet_infer(x, dtype, eps, running, params, chunk_frames: int = 8192):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# fused encoder-layer blocks (csrc/fused_fwd.hip / fused_bwd.hip), bf16 mode, 4 heads, E = 128 / F = 256 or E = 64 / F = 128
+# fused encoder-layer blocks (csrc/fused_fwd.hip / fused_bwd.hip), bf16 or fp16, 4 heads, E = 128 / F = 256 or E = 64 / F = 128
 # ---------------------------------------------------------------------------------------------------------------
-def _fused_entry(name: str, embed_dim: int, hidden_dim=None):
-    """the C entry point of a fused block for this layer width (the kernels are compiled per width: anything else is refused
-    here, before a launch that would index past the tensors)"""
+_FUSED_DTYPES = {torch.bfloat16: "", torch.float16: "_f16"}
+
+
+def _fused_entry(name: str, embed_dim: int, hidden_dim=None, dtype=torch.bfloat16):
+    """the C entry point of a fused block for this layer width and element type (the kernels are compiled per width and type:
+    anything else is refused here, before a launch that would index past the tensors or read them as the wrong type)"""
     if embed_dim not in (64, 128) or (hidden_dim is not None and hidden_dim != 2 * embed_dim):
         raise ValueError(f"{name}: fused blocks exist for E=128/F=256 and E=64/F=128, got E={embed_dim}"
                          + (f" F={hidden_dim}" if hidden_dim is not None else ""))
-    return getattr(N.lib, name + ("_w64" if embed_dim == 64 else ""))
+    if dtype not in _FUSED_DTYPES:
+        raise TypeError(f"{name}: fused blocks exist for bfloat16 and float16, got {dtype}")
+    return getattr(N.lib, name + ("_w64" if embed_dim == 64 else "") + _FUSED_DTYPES[dtype])
 
 
-def fused_layer_supported(embed_dim: int, hidden_dim: int, num_heads: int, tokens: int) -> bool:
-    if embed_dim not in (64, 128):
+def _same_dtype(name, *ts):
+    """the element type of a fused block's 16-bit tensors (all of them must share it)"""
+    dt = ts[0].dtype
+    for t in ts:
+        if t.dtype != dt:
+            raise TypeError(f"{name}: 16-bit operands must share one dtype, got {dt} and {t.dtype}")
+    return dt
+
+
+def fused_layer_supported(embed_dim: int, hidden_dim: int, num_heads: int, tokens: int, dtype=torch.bfloat16) -> bool:
+    if embed_dim not in (64, 128) or dtype not in _FUSED_DTYPES:
         return False
-    return bool(_fused_entry("mivit_fused_layer_supported", embed_dim)(N.BF16, embed_dim, hidden_dim, num_heads, tokens))
+    code = N.BF16 if dtype == torch.bfloat16 else N.F16
+    return bool(_fused_entry("mivit_fused_layer_supported", embed_dim, dtype=dtype)(code, embed_dim, hidden_dim, num_heads, tokens))
 
 
 def _f32(t):
@@ -364,106 +379,128 @@ def _f32(t):
 
 @torch.no_grad()
 def attn_block_fwd(n_in, gamma_in, beta_in, Wqkv, bqkv, Wo, bo, gamma_out, beta_out, extras=False):
-    """n_in [B,S,E] bf16 (normalised tokens; x = gamma_in * n_in + beta_in, or n_in itself when gamma_in is None);
-    Wqkv [3E,E] / Wo [E,E] bf16; returns dict(n, rstd, ctx[, x, z, mean, qkv]) -- reference models.py:33-59,100-102."""
+    """n_in [B,S,E] bf16 or fp16 (normalised tokens; x = gamma_in * n_in + beta_in, or n_in itself when gamma_in is None);
+    Wqkv [3E,E] / Wo [E,E] of the same dtype; returns dict(n, rstd, ctx[, x, z, mean, qkv]) -- reference models.py:33-59,100-102."""
     _gpu(n_in, Wqkv, Wo)
     B, S, E = n_in.shape
+    dt = _same_dtype("attn_block_fwd", n_in, Wqkv, Wo)
+    entry = _fused_entry("mivit_attn_block_fwd", E, dtype=dt)
     n_in = n_in.contiguous()
     dev = n_in.device
-    out = {"n": torch.empty(B, S, E, dtype=torch.bfloat16, device=dev), "rstd": torch.empty(B, S, device=dev),
-           "ctx": torch.empty(B, S, E, dtype=torch.bfloat16, device=dev)}
+    out = {"n": torch.empty(B, S, E, dtype=dt, device=dev), "rstd": torch.empty(B, S, device=dev),
+           "ctx": torch.empty(B, S, E, dtype=dt, device=dev)}
     if extras:
         out.update(x=torch.empty_like(out["n"]), z=torch.empty_like(out["n"]), mean=torch.empty(B, S, device=dev),
-                   qkv=torch.empty(B, S, 3 * E, dtype=torch.bfloat16, device=dev))
+                   qkv=torch.empty(B, S, 3 * E, dtype=dt, device=dev))
     gi, bi, go, bo_ = _f32(gamma_in), _f32(beta_in), _f32(gamma_out), _f32(beta_out)
     bq, bo2 = _f32(bqkv), _f32(bo)
     if tuple(Wqkv.shape) != (3 * E, E) or tuple(Wo.shape) != (E, E):
         raise ValueError(f"attn_block_fwd: weights {tuple(Wqkv.shape)}, {tuple(Wo.shape)} do not match E={E}")
-    N.check(_fused_entry("mivit_attn_block_fwd", E)(_p(n_in), _p(gi), _p(bi), _p(Wqkv.contiguous()), _p(bq), _p(Wo.contiguous()), _p(bo2),
-                                       _p(go), _p(bo_), B, S, _p(out["ctx"]), _p(out["n"]), _p(out["rstd"]), _p(out.get("x")),
-                                       _p(out.get("z")), _p(out.get("mean")), _p(out.get("qkv")), _s(n_in)),
+    N.check(entry(_p(n_in), _p(gi), _p(bi), _p(Wqkv.contiguous()), _p(bq), _p(Wo.contiguous()), _p(bo2),
+                  _p(go), _p(bo_), B, S, _p(out["ctx"]), _p(out["n"]), _p(out["rstd"]), _p(out.get("x")),
+                  _p(out.get("z")), _p(out.get("mean")), _p(out.get("qkv")), _s(n_in)),
             "mivit_attn_block_fwd")
     return out
 
 
 @torch.no_grad()
 def mlp_block_fwd(n_in, gamma_in, beta_in, W1, b1, W2, b2, gamma_out, beta_out, act=N.ACT_RELU, extras=False):
-    """n_in [M,E] bf16; W1 [F,E], W2 [E,F] bf16; returns dict(n, rstd[, x, z, mean, h, u]) -- models.py:72-77,104-106."""
+    """n_in [M,E] bf16 or fp16; W1 [F,E], W2 [E,F] of the same dtype; returns dict(n, rstd[, x, z, mean, h, u]) --
+    models.py:72-77,104-106."""
     _gpu(n_in, W1, W2)
     M, E = n_in.shape
     Fh = W1.shape[0]
+    dt = _same_dtype("mlp_block_fwd", n_in, W1, W2)
+    entry = _fused_entry("mivit_mlp_block_fwd", E, Fh, dtype=dt)
     n_in = n_in.contiguous()
     dev = n_in.device
-    out = {"n": torch.empty(M, E, dtype=torch.bfloat16, device=dev), "rstd": torch.empty(M, device=dev)}
+    out = {"n": torch.empty(M, E, dtype=dt, device=dev), "rstd": torch.empty(M, device=dev)}
     if extras:
         out.update(x=torch.empty_like(out["n"]), z=torch.empty_like(out["n"]), mean=torch.empty(M, device=dev),
-                   h=torch.empty(M, Fh, dtype=torch.bfloat16, device=dev), u=torch.empty(M, Fh, dtype=torch.bfloat16, device=dev))
+                   h=torch.empty(M, Fh, dtype=dt, device=dev), u=torch.empty(M, Fh, dtype=dt, device=dev))
     gi, bi, go, bo_ = _f32(gamma_in), _f32(beta_in), _f32(gamma_out), _f32(beta_out)
     b1f, b2f = _f32(b1), _f32(b2)
     if tuple(W1.shape) != (Fh, E) or tuple(W2.shape) != (E, Fh):
         raise ValueError(f"mlp_block_fwd: weights {tuple(W1.shape)}, {tuple(W2.shape)} do not match E={E}")
-    N.check(_fused_entry("mivit_mlp_block_fwd", E, Fh)(_p(n_in), _p(gi), _p(bi), _p(W1.contiguous()), _p(b1f), _p(W2.contiguous()), _p(b2f),
-                                      _p(go), _p(bo_), M, act, _p(out["n"]), _p(out["rstd"]), _p(out.get("x")), _p(out.get("z")),
-                                      _p(out.get("mean")), _p(out.get("h")), _p(out.get("u")), _s(n_in)), "mivit_mlp_block_fwd")
+    N.check(entry(_p(n_in), _p(gi), _p(bi), _p(W1.contiguous()), _p(b1f), _p(W2.contiguous()), _p(b2f),
+                  _p(go), _p(bo_), M, act, _p(out["n"]), _p(out["rstd"]), _p(out.get("x")), _p(out.get("z")),
+                  _p(out.get("mean")), _p(out.get("h")), _p(out.get("u")), _s(n_in)), "mivit_mlp_block_fwd")
     return out
 
 
 @torch.no_grad()
 def mlp_block_bwd(dy, n2, rstd2, gamma2, n1, gamma1, beta1, W1, b1, W2, act=N.ACT_RELU):
-    """Backward of the feed-forward block (see include/mivit_hip.h): returns dict(dx1, dW1, db1, dW2, db2, dgamma2, dbeta2)."""
+    """Backward of the feed-forward block (see include/mivit_hip.h), dy / n2 / n1 / W1 / W2 all bf16 or all fp16:
+    returns dict(dx1 [that dtype], dW1, db1, dW2, db2, dgamma2, dbeta2 [fp32])."""
     _gpu(dy, n2, n1, W1, W2)
     M, E = dy.shape
     Fh = W1.shape[0]
+    dt = _same_dtype("mlp_block_bwd", dy, n2, n1, W1, W2)
     dev = dy.device
-    out = {"dx1": torch.empty(M, E, dtype=torch.bfloat16, device=dev), "dW1": torch.empty(Fh, E, device=dev),
+    out = {"dx1": torch.empty(M, E, dtype=dt, device=dev), "dW1": torch.empty(Fh, E, device=dev),
            "db1": torch.empty(Fh, device=dev), "dW2": torch.empty(E, Fh, device=dev), "db2": torch.empty(E, device=dev),
            "dgamma2": torch.empty(E, device=dev), "dbeta2": torch.empty(E, device=dev)}
     if tuple(W1.shape) != (Fh, E) or tuple(W2.shape) != (E, Fh):
         raise ValueError(f"mlp_block_bwd: weights {tuple(W1.shape)}, {tuple(W2.shape)} do not match E={E}")
-    nbytes = _fused_entry("mivit_mlp_block_bwd_workspace_bytes", E, Fh)(M)
+    nbytes = _fused_entry("mivit_mlp_block_bwd_workspace_bytes", E, Fh, dtype=dt)(M)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     args = [dy.contiguous(), n2.contiguous(), _f32(rstd2), _f32(gamma2), n1.contiguous(), _f32(gamma1), _f32(beta1), W1.contiguous(),
             _f32(b1), W2.contiguous()]
-    N.check(_fused_entry("mivit_mlp_block_bwd", E, Fh)(*[_p(t) for t in args], M, act, _p(out["dx1"]), _p(out["dW1"]), _p(out["db1"]), _p(out["dW2"]),
-                                      _p(out["db2"]), _p(out["dgamma2"]), _p(out["dbeta2"]), _p(ws), nbytes, _s(dy)),
+    N.check(_fused_entry("mivit_mlp_block_bwd", E, Fh, dtype=dt)(
+                *[_p(t) for t in args], M, act, _p(out["dx1"]), _p(out["dW1"]), _p(out["db1"]), _p(out["dW2"]),
+                _p(out["db2"]), _p(out["dgamma2"]), _p(out["dbeta2"]), _p(ws), nbytes, _s(dy)),
             "mivit_mlp_block_bwd")
     return out
 
 
 @torch.no_grad()
 def attn_out_bwd(dy, n1, rstd1, gamma1, ctx, Wo):
-    """LayerNorm-1 backward + out-projection backward (include/mivit_hip.h): dict(dz1, dctx, dWo, dbo, dgamma1, dbeta1)."""
+    """LayerNorm-1 backward + out-projection backward (include/mivit_hip.h), dy / n1 / ctx / Wo all bf16 or all fp16:
+    dict(dz1, dctx [that dtype], dWo, dbo, dgamma1, dbeta1 [fp32])."""
     _gpu(dy, n1, ctx, Wo)
     M, E = dy.shape
+    dt = _same_dtype("attn_out_bwd", dy, n1, ctx, Wo)
     dev = dy.device
-    out = {"dz1": torch.empty(M, E, dtype=torch.bfloat16, device=dev), "dctx": torch.empty(M, E, dtype=torch.bfloat16, device=dev),
+    out = {"dz1": torch.empty(M, E, dtype=dt, device=dev), "dctx": torch.empty(M, E, dtype=dt, device=dev),
            "dWo": torch.empty(E, E, device=dev), "dbo": torch.empty(E, device=dev), "dgamma1": torch.empty(E, device=dev),
            "dbeta1": torch.empty(E, device=dev)}
     if tuple(Wo.shape) != (E, E):
         raise ValueError(f"attn_out_bwd: weight {tuple(Wo.shape)} does not match E={E}")
-    nbytes = _fused_entry("mivit_attn_out_bwd_workspace_bytes", E)(M)
+    nbytes = _fused_entry("mivit_attn_out_bwd_workspace_bytes", E, dtype=dt)(M)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     args = [dy.contiguous(), n1.contiguous(), _f32(rstd1), _f32(gamma1), ctx.contiguous(), Wo.contiguous()]
-    N.check(_fused_entry("mivit_attn_out_bwd", E)(*[_p(t) for t in args], M, _p(out["dz1"]), _p(out["dctx"]), _p(out["dWo"]), _p(out["dbo"]),
-                                     _p(out["dgamma1"]), _p(out["dbeta1"]), _p(ws), nbytes, _s(dy)), "mivit_attn_out_bwd")
+    N.check(_fused_entry("mivit_attn_out_bwd", E, dtype=dt)(
+                *[_p(t) for t in args], M, _p(out["dz1"]), _p(out["dctx"]), _p(out["dWo"]), _p(out["dbo"]),
+                _p(out["dgamma1"]), _p(out["dbeta1"]), _p(ws), nbytes, _s(dy)), "mivit_attn_out_bwd")
     return out
 
 
 @torch.no_grad()
-def qkv_bwd(dqkv, x, Wqkv, res):
-    """q|k|v projection backward in one pass over dqkv (include/mivit_hip.h): dict(dx, dW, db); dx = dqkv Wqkv + res."""
+def qkv_bwd(dqkv, x, Wqkv, res, fix_gamma=None, fix_beta=None):
+    """q|k|v projection backward in one pass over dqkv (include/mivit_hip.h), dqkv / x / Wqkv / res all bf16 or all fp16:
+    dict(dx, dW, db); dx = dqkv Wqkv + res.  With fix_gamma / fix_beta [E] the projection's input is fix_gamma * x + fix_beta
+    (x a LayerNorm's normalised output): dW = (dqkv^T x) diag(fix_gamma) + db (x) fix_beta."""
     _gpu(dqkv, x, Wqkv, res)
     M, E = x.shape
     if tuple(dqkv.shape) != (M, 3 * E) or tuple(Wqkv.shape) != (3 * E, E) or tuple(res.shape) != (M, E):
         raise ValueError(f"qkv_bwd: shapes {tuple(dqkv.shape)}, {tuple(Wqkv.shape)}, {tuple(res.shape)} do not match x {tuple(x.shape)}")
+    if (fix_gamma is None) != (fix_beta is None):
+        raise ValueError("qkv_bwd: the input affine needs both fix_gamma and fix_beta")
+    dt = _same_dtype("qkv_bwd", dqkv, x, Wqkv, res)
     dev = x.device
-    out = {"dx": torch.empty(M, E, dtype=torch.bfloat16, device=dev), "dW": torch.empty(3 * E, E, device=dev),
+    out = {"dx": torch.empty(M, E, dtype=dt, device=dev), "dW": torch.empty(3 * E, E, device=dev),
            "db": torch.empty(3 * E, device=dev)}
-    nbytes = _fused_entry("mivit_qkv_bwd_workspace_bytes", E)(M)
+    nbytes = _fused_entry("mivit_qkv_bwd_workspace_bytes", E, dtype=dt)(M)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     args = [dqkv.contiguous(), x.contiguous(), Wqkv.contiguous(), res.contiguous()]
-    N.check(_fused_entry("mivit_qkv_bwd", E)(*[_p(t) for t in args], M, _p(out["dx"]), _p(out["dW"]), _p(out["db"]), _p(ws), nbytes,
-                                             _s(x)), "mivit_qkv_bwd")
+    if fix_gamma is None:
+        N.check(_fused_entry("mivit_qkv_bwd", E, dtype=dt)(*[_p(t) for t in args], M, _p(out["dx"]), _p(out["dW"]), _p(out["db"]),
+                                                           _p(ws), nbytes, _s(x)), "mivit_qkv_bwd")
+    else:
+        fg, fb = _f32(fix_gamma), _f32(fix_beta)
+        N.check(_fused_entry("mivit_qkv_bwd_affine", E, dtype=dt)(*[_p(t) for t in args], M, _p(out["dx"]), _p(out["dW"]),
+                                                                  _p(out["db"]), _p(fg), _p(fb), _p(ws), nbytes, _s(x)),
+                "mivit_qkv_bwd_affine")
     return out
 
 
