@@ -192,6 +192,24 @@ size_t mivit_trajectory_features_workspace_bytes(int N, int T, int npos);
 int mivit_trajectory_features(const void *traj, int dtype, int N, int T, int npos, double dt, double *feats, void *avg,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/* Richardson-Lucy deconvolution with total-variation regularisation of every frame of a batch in one launch: the Denoising
+ * experiment's apply_rl_tv_tensor_iter_list -> richardson_lucy_tv_iter_list (reference helpers/helpersGeneration.py:542-589,
+ * :616-632; called from trajs_to_vid_norm_rl :635-660), csrc/deconv.hip, one workgroup per frame.  frames [B, S, H, W] fp32
+ * (device), psf [K, K] fp64 (device), snapshots: HOST array of n_snap strictly increasing 0-based iteration indices
+ * (1 <= n_snap <= 16); snapshots[n_snap - 1] + 1 iterations run and out [B, n_snap, S, H, W] fp32 receives the estimate
+ * after each listed iteration.  1 <= H, W <= 32, 1 <= K <= 15 (even K as fftconvolve 'same' centres it).  Convolutions and
+ * division in fp64, estimate and TV gradient in fp32, in the order of the host restatement (helpers/generation.py), with
+ * which it agrees bitwise.  Arguments are validated before any HIP call; B * S = 0 is a no-op. */
+int mivit_rl_tv_deconvolve(const float *frames, int B, int S, int H, int W, const double *psf, int K, const int *snapshots,
+                           int n_snap, float tv_weight, float *out, void *stream);
+
+/* scipy.ndimage.gaussian_filter(frame, sigma, mode='nearest', truncate) of every frame (what ski.filters.gaussian(frame,
+ * sigma=0.5) does for a float image, reference helpers/helpersGeneration.py:530), csrc/deconv.hip: in / out [N, H, W] fp32,
+ * 1 <= H, W <= 32, separable fp64 passes (axis 0, then axis 1) with replicated borders, radius int(truncate * sigma + 0.5)
+ * <= 15, sigma > 0.  N = 0 is a no-op. */
+int mivit_gaussian_filter_frames(const float *in, int N, int H, int W, double sigma, double truncate, float *out,
+                                 void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -126,6 +126,10 @@ SYMBOLS = {
     "mivit_trajectory_features_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mivit_trajectory_features": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),
+    "mivit_rl_tv_deconvolve": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_float,
+                                       c_void_p, c_void_p]),
+    "mivit_gaussian_filter_frames": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p,
+                                             c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes": (c_size_t, [c_int]),
     "mivit_attn_out_bwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "mivit_embed_small_supported": (c_int, [c_int, c_int, c_int]),

@@ -33,11 +33,11 @@ def validation_root():
     return None
 
 
-def validation_trajectories(length, T, traj_div_factor, generator, n_synthetic=50, in_order=None):
-    """[(N,T,2) array for D in 1,3,5,7,9] (+ the in-order set when `in_order` = (d_values, n_per_d))."""
+def validation_trajectories(length, T, traj_div_factor, generator, n_synthetic=50, in_order=None, d_values=D_VALUES):
+    """[(N,T,2) array for D in d_values (1,3,5,7,9)] (+ the in-order set when `in_order` = (d_values, n_per_d))."""
     root = validation_root()
     sets = []
-    for D in D_VALUES:
+    for D in d_values:
         if root is not None:
             sets.append(np.load(os.path.join(root, str(length), f"val{D}.npy")) / traj_div_factor)
         else:
@@ -130,9 +130,10 @@ def backward_and_step(loss, optimizer, scaler=None, model=None, parallel=None):
 
 
 def run_cycles(S, models, optimizers, schedulers, make_batch_data, predict, num_cycles, val_sets, results_name,
-               batch_size=None, device=None, out_dir=".", save=True, shuffle=True, generator=None, verbose=False):
+               batch_size=None, device=None, out_dir=".", save=True, shuffle=True, generator=None, verbose=False,
+               d_values=D_VALUES):
     """The reference's cycle loop.  `make_batch_data(cycle)` -> (tensors..., labels, raw_labels);
-    `predict(model, name, *batch_tensors)` -> predictions; `val_sets` = list of (tensors tuple, D value)."""
+    `predict(model, name, *batch_tensors)` -> predictions; `val_sets` = list of (tensors tuple, D value), D in d_values."""
     device = device or S.device
     for name in models:
         if models[name] is not None:
@@ -143,7 +144,7 @@ def run_cycles(S, models, optimizers, schedulers, make_batch_data, predict, num_
     save = save and par.rank == 0
     if batch_size is None:
         batch_size = 1 if S.adaptive_batch_size != -1 else 16
-    validation_losses = {name: {**{f"val_{float(D)}": [] for D in D_VALUES}, "val_avg": []} for name in models}
+    validation_losses = {name: {**{f"val_{float(D)}": [] for D in d_values}, "val_avg": []} for name in models}
     all_gen_labels = np.array([])
     scalers = {}
     print("StartTime: ", datetime.datetime.now())

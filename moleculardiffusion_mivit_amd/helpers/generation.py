@@ -15,6 +15,11 @@ on the host or directly on the GPU (no andi_datasets / skimage dependency):
   frame costs O(p * (G + P^2)) instead of O(p * G^2) and the Python triple loop disappears.
 * noise models: clipped-Gaussian background + Poisson, in both variants the reference uses.
 * ``normalize_images`` = ``helpersGeneration.py:356-400``.
+* the Denoising experiment's data (``helpersGeneration.py:422-660``): ``trajectories_to_video_multiple_settings`` (no
+  noise / background / Poisson / Gaussian-filtered Poisson), Richardson-Lucy deconvolution with total-variation
+  regularisation (``richardson_lucy_tv*``, ``apply_rl_tv_tensor*``, ``tv_gradient``, ``create_gaussian_psf``) and
+  ``trajs_to_vid_norm_rl``.  GPU tensors go to csrc/deconv.hip; numpy / CPU input to a numpy restatement vectorised over
+  frames that sums in the kernel's order (bitwise the kernel's result; within FFT rounding of the reference's).
 
 The reference draws from the unseeded global numpy RNG, so agreement is distributional; the deterministic part
 (noise-free rendering) is pinned against a naive per-pixel loop in ``tests/test_generation.py``.
@@ -24,6 +29,7 @@ from __future__ import annotations
 import math
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 DEFAULT_IMAGE_PROPS = {
@@ -180,3 +186,233 @@ def normalize_images(images, background_mean=None, background_sigma=None, theore
     if clip_image:
         out = out.clamp(0, 1.5)
     return out, (background_mean, background_sigma, theoretical_max)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Denoising experiment: multi-setting videos, Gaussian filter, RL-TV deconvolution (helpersGeneration.py:422-660)
+# ------------------------------------------------------------------------------------------------------------------------
+
+def create_gaussian_psf(size=9, sigma=1.3):
+    """Normalised Gaussian PSF of odd side (an even size grows by one), float64 (helpersGeneration.py:591-600)."""
+    if size % 2 == 0:
+        size += 1
+    ax = np.arange(-(size // 2), size // 2 + 1)
+    x, y = np.meshgrid(ax, ax)
+    psf = np.exp(-(x ** 2 + y ** 2) / (2 * sigma ** 2))
+    psf /= psf.sum()
+    return psf
+
+
+def tv_gradient(image):
+    """Gradient of the total variation over the last two axes (helpersGeneration.py:542-555), in image's dtype: forward
+    differences with the last column / row repeated, normalised by sqrt(dx^2 + dy^2 + 1e-8)."""
+    image = np.asarray(image)
+    dt = image.dtype.type
+    dx = np.zeros_like(image)
+    dy = np.zeros_like(image)
+    dx[..., :, :-1] = image[..., :, 1:] - image[..., :, :-1]
+    dy[..., :-1, :] = image[..., 1:, :] - image[..., :-1, :]
+    mag = np.sqrt((dx * dx + dy * dy) + dt(1e-8))
+    dxn, dyn = dx / mag, dy / mag
+    grad = np.zeros_like(image)
+    grad[..., :, :-1] -= dxn[..., :, :-1]
+    grad[..., :, 1:] += dxn[..., :, :-1]
+    grad[..., :-1, :] -= dyn[..., :-1, :]
+    grad[..., 1:, :] += dyn[..., :-1, :]
+    return grad
+
+
+def _conv_same(x, k):
+    """scipy.signal.fftconvolve(x, k, mode='same') over the last two axes as a zero-padded direct sum in float64, taps in
+    row-major (a, b) order from 0.0, one multiply and one add each -- the order of csrc/deconv.hip."""
+    K = k.shape[0]
+    H, W = x.shape[-2:]
+    halo = K - 1 - (K - 1) // 2
+    xp = np.zeros(x.shape[:-2] + (H + K - 1, W + K - 1), np.float64)
+    xp[..., halo:halo + H, halo:halo + W] = x
+    acc = np.zeros(x.shape, np.float64)
+    for a in range(K):
+        for b in range(K):
+            acc += k[a, b] * xp[..., K - 1 - a:K - 1 - a + H, K - 1 - b:K - 1 - b + W]
+    return acc
+
+
+def _check_iterations(iterations_list):
+    its = [int(i) for i in iterations_list]
+    if not its or its[0] < 0 or any(b <= a for a, b in zip(its, its[1:])):
+        raise ValueError(f"iterations_list must be non-empty, non-negative and strictly increasing, got {list(iterations_list)}")
+    return its
+
+
+def _rl_tv_frames(frames, psf, iterations_list, tv_weight):
+    """Host RL-TV of a stack of frames [..., H, W] -> [len(iterations_list), ..., H, W] float32: the estimate after every
+    listed (0-based) iteration.  Same precision per step as richardson_lucy_tv_iter_list (helpersGeneration.py:571-589):
+    fp64 convolutions and division, fp32 estimate and TV gradient."""
+    its = _check_iterations(iterations_list)
+    psf = np.asarray(psf, np.float64)
+    if psf.ndim != 2 or psf.shape[0] != psf.shape[1]:
+        raise ValueError(f"psf must be square [K, K], got {psf.shape}")
+    image = np.clip(np.asarray(frames, np.float32), np.float32(1e-6), None).astype(np.float64)
+    mirror = psf[::-1, ::-1]
+    tvw = np.float32(tv_weight)
+    est = np.full(image.shape, 0.5, np.float32)
+    out = np.empty((len(its),) + image.shape, np.float32)
+    for i in range(its[-1] + 1):
+        rel = image / (_conv_same(est, psf) + 1e-6)
+        est = (est.astype(np.float64) * _conv_same(rel, mirror)).astype(np.float32)
+        est = np.clip(est - tvw * tv_gradient(est), np.float32(0), np.float32(1))
+        if i in its:
+            out[its.index(i)] = est
+    return out
+
+
+def richardson_lucy_tv(image, psf, iterations=20, tv_weight=0.01):
+    """RL-TV estimate after `iterations` iterations, float32 (helpersGeneration.py:557-568)."""
+    image = np.asarray(image)
+    if iterations <= 0:
+        return np.full(image.shape, 0.5, np.float32)
+    return _rl_tv_frames(image, psf, [iterations - 1], tv_weight)[0]
+
+
+def richardson_lucy_tv_iter_list(image, psf, iterations_list, out_array, tv_weight=0.01):
+    """RL-TV with a snapshot after each listed 0-based iteration written to out_array[k]; returns the final estimate
+    (helpersGeneration.py:571-589).  Unlike the reference the list must be strictly increasing (ValueError otherwise:
+    the reference leaves slots of out_array unwritten)."""
+    snaps = _rl_tv_frames(image, psf, iterations_list, tv_weight)
+    for k in range(len(snaps)):
+        out_array[k] = snaps[k]
+    return snaps[-1]
+
+
+def _rl_tv_batch(tensor, psf, iterations_list, tv_weight):
+    """[B, S, H, W] -> [B, len(iterations_list), S, H, W]: the kernel for GPU tensors, the host restatement otherwise."""
+    its = _check_iterations(iterations_list)
+    if isinstance(tensor, torch.Tensor) and tensor.device.type == "cuda":
+        from .. import ops
+        return ops.rl_tv_deconvolve(tensor.float(), psf, its, tv_weight)
+    arr = tensor.detach().cpu().numpy() if isinstance(tensor, torch.Tensor) else np.asarray(tensor)
+    return np.moveaxis(_rl_tv_frames(arr, psf, its, tv_weight), 0, 1)
+
+
+def apply_rl_tv_tensor(tensor, psf, n_iters=10, tv_weight=0.01):
+    """richardson_lucy_tv of every 9x9 frame of a [B, seq, 9, 9] tensor, same dtype and device
+    (helpersGeneration.py:603-613)."""
+    B, seq, H, W = tensor.shape
+    assert H == 9 and W == 9, "Only images of shape 9x9 are supported"
+    if n_iters <= 0:
+        return torch.full(tuple(tensor.shape), 0.5, dtype=tensor.dtype, device=tensor.device)
+    out = _rl_tv_batch(tensor, psf, [n_iters - 1], tv_weight)[:, 0]
+    return torch.as_tensor(out).to(dtype=tensor.dtype, device=tensor.device)
+
+
+def apply_rl_tv_tensor_iter_list(tensor, psf, iterations_list=[2, 5, 10], tv_weight=0.01):
+    """[B, seq, 9, 9] -> [B, len(iterations_list), seq, 9, 9]: RL-TV snapshots of every frame (helpersGeneration.py:616-632).
+    numpy / CPU input gives numpy in the input's dtype, as the reference; a GPU tensor gives a GPU float32 tensor (the
+    reference always returns numpy).  The list must be strictly increasing."""
+    B, seq, H, W = tensor.shape
+    assert H == 9 and W == 9, "Only images of shape 9x9 are supported"
+    out = _rl_tv_batch(tensor, psf, iterations_list, tv_weight)
+    if isinstance(out, torch.Tensor):
+        return out
+    dtype = tensor.detach().cpu().numpy().dtype if isinstance(tensor, torch.Tensor) else np.asarray(tensor).dtype
+    return out.astype(dtype, copy=False)
+
+
+def _gaussian_weights(sigma, truncate):
+    """scipy.ndimage._filters._gaussian_kernel1d(sigma, 0, int(truncate * sigma + 0.5)): w[0] centre .. w[r]."""
+    r = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return phi[r:]
+
+
+def gaussian_filter_frames(frames, sigma, truncate=4.0):
+    """scipy.ndimage.gaussian_filter(frame, sigma, mode='nearest', truncate) of every [H, W] frame, float32 out: what
+    ski.filters.gaussian(frame, sigma) does for a float frame (helpersGeneration.py:530).  GPU tensors go to
+    csrc/deconv.hip; anything else to the same separable fp64 passes in numpy (axis 0, then axis 1, replicated borders,
+    symmetric taps summed from the outermost in as scipy's correlate1d does)."""
+    if isinstance(frames, torch.Tensor) and frames.device.type == "cuda":
+        from .. import ops
+        return ops.gaussian_filter_frames(frames.float(), sigma, truncate)
+    is_t = isinstance(frames, torch.Tensor)
+    x = (frames.detach().cpu().numpy() if is_t else np.asarray(frames)).astype(np.float64)
+    w = _gaussian_weights(sigma, truncate)
+    for axis in (-2, -1):
+        n = x.shape[axis]
+        idx = np.arange(n)
+        acc = x * w[0]
+        for k in range(len(w) - 1, 0, -1):
+            lo = np.take(x, np.clip(idx - k, 0, n - 1), axis=axis)
+            hi = np.take(x, np.clip(idx + k, 0, n - 1), axis=axis)
+            acc = acc + (lo + hi) * w[k]
+        x = acc
+    out = x.astype(np.float32)
+    return torch.from_numpy(out) if is_t else out
+
+
+def _normal(shape, mean, std, generator, device):
+    """mean + std * N(0, 1), drawn on the generator's device and moved to `device`."""
+    gdev = generator.device if generator is not None else device
+    return (mean + std * torch.randn(shape, generator=generator, device=gdev)).to(device)
+
+
+def _poisson(rate, generator):
+    gdev = generator.device if generator is not None else rate.device
+    return torch.poisson(rate.to(gdev), generator=generator).to(rate.device)
+
+
+def trajectories_to_video_multiple_settings(trajectories, nPosPerFrame, center=False, image_props={}, generator=None,
+                                            device=None):
+    """(N, T, 2) trajectories -> four (N, T / nPosPerFrame, P, P) float32 videos of the same frames
+    (helpersGeneration.py:422-536): no noise, + clipped Gaussian background, Poisson(frame * pn) / pn of that, and
+    gaussian_filter(Poisson frame, sigma=0.5).  One particle intensity ~ N(mean, std) per frame, shared by its
+    sub-positions (:506-513).  This function's own defaults apply (poisson_noise 1, :440-456).  The y axis is flipped as
+    the reference does, without mutating the caller's array."""
+    props = dict(DEFAULT_IMAGE_PROPS)
+    props["poisson_noise"] = 1
+    props.update(image_props or {})
+    traj = _as_tensor(trajectories, device).clone()
+    dev = traj.device
+    traj[:, :, 1] *= -1
+    N, T, _ = traj.shape
+    if T % nPosPerFrame != 0:
+        raise Exception("T is not divisble by posPerFrame")
+    if props["trajectory_unit"] != -1:
+        traj = traj * props["trajectory_unit"] * 1e-9 / props["resolution"]
+    F_ = T // nPosPerFrame
+    pm, ps = props["particle_intensity"]
+    bm, bs = props["background_intensity"]
+    frame_int = _normal((N, F_, 1), pm, ps, generator, dev)
+    if pm > 1e-4 and ps > 1e-4:
+        amp = (frame_int / nPosPerFrame).expand(N, F_, nPosPerFrame)
+    else:
+        amp = torch.zeros(N, F_, nPosPerFrame, device=dev)
+    clean = render_frames(traj, nPosPerFrame, [psf_sigma_hr(props)], props["output_size"], props["upsampling_factor"],
+                          amp, center)[:, 0].float()
+    bg = _normal(clean.shape, bm, bs, generator, dev).clamp(0.0, bm + 3 * bs) if bs > 0 else \
+        torch.full(clean.shape, float(max(bm, 0.0)), device=dev)
+    noisy = clean + bg
+    pn = props["poisson_noise"]
+    poisson = _poisson(noisy * pn, generator) / pn
+    filtered = gaussian_filter_frames(poisson, 0.5)
+    return clean, noisy, poisson, torch.as_tensor(filtered).to(dev)
+
+
+def trajs_to_vid_norm_rl(trajectories, nPosPerFrame, center, image_props, rl_iterations, poisson_index=2, generator=None,
+                         device=None):
+    """(N, T, 2) -> (N, 4 + len(rl_iterations), F, P, P) float32 (helpersGeneration.py:635-660): the four settings of
+    trajectories_to_video_multiple_settings normalised by normalize_images(bg_mean, bg_sigma, part_mean + bg_mean), then
+    RL-TV snapshots (create_gaussian_psf(sigma=1)) of channel `poisson_index`.  numpy input gives numpy (the reference);
+    a GPU tensor (or device="cuda") keeps everything on the GPU and gives a GPU tensor."""
+    bg_mean, bg_sigma = image_props["background_intensity"]
+    part_mean = image_props["particle_intensity"][0]
+    psf = create_gaussian_psf(sigma=1)
+    videos = torch.stack(trajectories_to_video_multiple_settings(trajectories, nPosPerFrame, center=center,
+                                                                 image_props=image_props, generator=generator,
+                                                                 device=device), dim=1)
+    videos, _ = normalize_images(videos, bg_mean, bg_sigma, part_mean + bg_mean)
+    videos = videos.float()
+    rl = apply_rl_tv_tensor_iter_list(videos[:, poisson_index], psf, rl_iterations)
+    out = torch.cat([videos, torch.as_tensor(rl).to(videos.device)], dim=1)
+    return out if out.device.type == "cuda" else out.numpy()

@@ -525,3 +525,43 @@ def trajectory_features(traj: torch.Tensor, nPosPerFrame: int = 1, dt: float = 1
                                             nPosPerFrame, float(dt), _p(feats), _p(avg), _p(ws), ws.numel(), _s(traj)),
             "mivit_trajectory_features")
     return (feats, avg) if return_average else feats
+
+
+def _frames_f32(x, name):
+    _gpu(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: frames must be float32, got {x.dtype}")
+    return x.contiguous()
+
+
+def rl_tv_deconvolve(frames: torch.Tensor, psf, iterations_list, tv_weight: float = 0.01) -> torch.Tensor:
+    """Richardson-Lucy + total-variation deconvolution of every frame (csrc/deconv.hip, mivit_rl_tv_deconvolve), the batched
+    helpers/generation.richardson_lucy_tv_iter_list: frames [B, S, H, W] float32 on the GPU, psf [K, K] (any float dtype,
+    used in float64), iterations_list strictly increasing 0-based iteration indices -> [B, len(iterations_list), S, H, W]
+    float32, the estimate after each listed iteration (iterations_list[-1] + 1 iterations run)."""
+    frames = _frames_f32(frames, "rl_tv_deconvolve")
+    if frames.dim() != 4:
+        raise ValueError(f"frames must be [B, S, H, W], got {tuple(frames.shape)}")
+    psf = torch.as_tensor(psf).to(device=frames.device, dtype=torch.float64).contiguous()
+    if psf.dim() != 2 or psf.shape[0] != psf.shape[1]:
+        raise ValueError(f"psf must be square [K, K], got {tuple(psf.shape)}")
+    snaps = [int(i) for i in iterations_list]
+    B, S, H, W = frames.shape
+    out = torch.empty(B, len(snaps), S, H, W, dtype=torch.float32, device=frames.device)
+    arr = (ctypes.c_int * max(1, len(snaps)))(*snaps)
+    N.check(N.lib.mivit_rl_tv_deconvolve(_p(frames), B, S, H, W, _p(psf), psf.shape[0], arr, len(snaps),
+                                         float(tv_weight), _p(out), _s(frames)), "mivit_rl_tv_deconvolve")
+    return out
+
+
+def gaussian_filter_frames(frames: torch.Tensor, sigma: float, truncate: float = 4.0) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(frame, sigma, mode='nearest', truncate) of every [H, W] frame of a float32 GPU tensor
+    [..., H, W] (csrc/deconv.hip, mivit_gaussian_filter_frames; fp64 inside, float32 out)."""
+    frames = _frames_f32(frames, "gaussian_filter_frames")
+    if frames.dim() < 2:
+        raise ValueError(f"frames must be [..., H, W], got {tuple(frames.shape)}")
+    H, W = frames.shape[-2:]
+    out = torch.empty_like(frames)
+    N.check(N.lib.mivit_gaussian_filter_frames(_p(frames), frames.numel() // max(1, H * W), H, W, float(sigma),
+                                               float(truncate), _p(out), _s(frames)), "mivit_gaussian_filter_frames")
+    return out
