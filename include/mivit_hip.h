@@ -210,6 +210,38 @@ int mivit_rl_tv_deconvolve(const float *frames, int B, int S, int H, int W, cons
 int mivit_gaussian_filter_frames(const float *in, int N, int H, int W, double sigma, double truncate, float *out,
                                  void *stream);
 
+/* Particle detection for a whole movie: the reference's detect_particles (helpers/helpersTracking.py:12-57, per frame two
+ * scipy.ndimage.gaussian_filter calls, their difference, skimage.feature.peak_local_max(dog, min_distance, threshold_abs =
+ * threshold_percentage * dog.max(), exclude_border=False)), csrc/tracking.hip, four launches whatever F is.
+ * movie [F, H, W] fp32 (device); w1 / w2: HOST arrays of r1 + 1 / r2 + 1 fp64 Gaussian weights, w[0] the centre and w[k] the
+ * weight at distance k (the caller builds them as scipy's _gaussian_kernel1d does, radius int(4 sigma + 0.5)),
+ * 0 <= r1 <= r2 <= 16 and H, W > r2 (one reflection at the border).  Each filter is two separable passes (axis 0, then
+ * axis 1) with scipy's 'reflect' borders, fp64 sums in correlate1d's symmetric order, each pass rounded to fp32; dog = g1 - g2
+ * in fp32.  A pixel is a candidate when no pixel of its (2 min_distance + 1)^2 window exceeds it and it is strictly greater
+ * than threshold_percentage * max(dog of its frame) (one fp32 product); a frame whose pixels are all equal has none.
+ * Candidates are ordered by value descending, ties by row-major index ascending, and kept greedily unless an already kept
+ * one lies within Chebyshev distance min_distance (1 .. 16).  cap (1 .. 2048) is the capacity per frame, of candidates and
+ * of peaks.  out: count [F] int32 peaks kept, n_candidates [F] int32 candidates before spacing (may exceed cap: then the
+ * frame's result is incomplete and the caller must raise), coords [F, cap, 2] int32 (y, x), values [F, cap] fp32, dog
+ * [F, H, W] fp32 (NULL: not returned; it then lives in the workspace).  Entries beyond count are not written.  workspace:
+ * mivit_dog_peaks_workspace_bytes(F, H, W, cap, dog != NULL).  Arguments are validated before any HIP call; F = 0 is a no-op.
+ * The movie must be finite. */
+size_t mivit_dog_peaks_workspace_bytes(int F, int H, int W, int cap, int store_dog);
+int mivit_dog_peaks(const float *movie, int F, int H, int W, const double *w1, int r1, const double *w2, int r2,
+                    float threshold_percentage, int min_distance, int cap, int *count, int *n_candidates, int *coords,
+                    float *values, float *dog, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Sub-pixel localisation: the five-parameter fit inside the reference's add_refined_localization_to_dataframe
+ * (helpers/helpersTracking.py:555-604, one scipy.optimize.curve_fit per patch), csrc/tracking.hip, one thread per patch.
+ * patches [N, P, P] fp32, P odd, 3 .. 15.  Model offset + amplitude exp(-((x - x0)^2 + (y - y0)^2) / (2 sigma^2)) on the
+ * pixel grid 0 .. P-1, start (patch.max(), P / 2, P / 2, 1.0, patch.min()), Levenberg-Marquardt in fp64 with the analytic
+ * Jacobian, stopped when every parameter's undamped step is below xtol relative to its scale (0 < xtol <= 1.49012e-8, MINPACK's
+ * default) or after 100 iterations.  out: params [N, 5] fp64 (amplitude, x0, y0, sigma, offset), peak [N] fp32 = patch.max(),
+ * status [N] int32: 0 converged, 1 damping exhausted, 2 iteration cap, 3 non-finite patch.  The reference's fallback for a
+ * failed fit is the caller's business.  Arguments are validated before any HIP call; N = 0 is a no-op. */
+int mivit_refine_gaussian(const float *patches, int N, int P, double xtol, double *params, float *peak, int *status,
+                          void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

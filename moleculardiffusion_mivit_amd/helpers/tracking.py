@@ -1,6 +1,16 @@
 """Real-data patch extraction (reference helpers/helpersTracking.py:513-550 ``extract_particle_patches``): square patches around
 every tracked position, zero-padded at the image border -- the tensors a trained MiViT consumes on experimental movies
-(SURVEY section 8 row f4).  One gather for all positions of a track; works on CPU or GPU tensors."""
+(SURVEY section 8 row f4).  One gather for all positions of a track; works on CPU or GPU tensors.
+
+The rest of the reference's real-movie front end (helpers/helpersTracking.py) is here too: detect_particles (:12-57),
+link_particles (:123-178), track_particles (:180-336), analyze_microscopy_sequence (:436-510),
+add_refined_localization_to_dataframe (:555-604), compute_displacement (:608-647), tracks_to_dataframe (:653-681).  A CUDA
+movie goes to the kernels of csrc/tracking.hip (detection for the whole movie at once, one Gaussian fit per patch) and what
+the reference returns as images stays a CUDA tensor; anything else goes to the numpy restatement in this file, which computes
+the filter in the kernel's order (bitwise equal) and the fit with the kernel's algorithm.  Linking is a Hungarian assignment
+on a few dozen points per frame and runs on the host either way.  Movies are filtered as float32.  pandas and scipy are only
+imported by the functions that need them: detect_particles_movie, track_particles_flat, extract_patches_flat and
+refine_localizations need neither pandas nor (except for linking) scipy."""
 from typing import Dict, Sequence, Tuple
 
 import numpy as np
@@ -33,3 +43,480 @@ def extract_particle_patches(image_3d, tracks: Dict[object, Sequence[Tuple[int, 
         g = torch.where(ok, g, torch.zeros((), dtype=img.dtype, device=img.device))
         out[tid] = g.numpy() if is_np else g
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# detection
+# ----------------------------------------------------------------------------------------------------------------------
+FIT_XTOL = 1e-11          # every parameter's undamped step relative to its scale (MINPACK's default would be 1.49e-8)
+FIT_MAX_ITER = 100
+FIT_COST_SLACK = 1.0 + 1e-13
+FALLBACK_PSF_SIZE = 10    # the reference's psf_size for a patch whose fit failed
+
+
+def gaussian_half_kernel(sigma, truncate=4.0):
+    """The weights scipy.ndimage.gaussian_filter uses (scipy.ndimage._filters._gaussian_kernel1d, order 0), centre first:
+    w[0] the centre, w[k] the weight at distance k, radius int(truncate * sigma + 0.5)."""
+    sd = float(sigma)
+    if not sd > 0:
+        raise ValueError(f"sigma must be positive, got {sigma}")
+    radius = int(truncate * sd + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sd * sd) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:])
+
+
+def _is_cuda(x):
+    return torch.is_tensor(x) and x.device.type == "cuda"
+
+
+def _correlate_axis(x32, w, axis):
+    """scipy.ndimage.correlate1d of a float32 [F, H, W] array along one axis with a symmetric kernel, mode 'reflect': fp64 sum
+    in scipy's order (centre, then the outermost pair inwards), rounded to float32."""
+    r = len(w) - 1
+    n = x32.shape[axis]
+    pad = [(0, 0)] * 3
+    pad[axis] = (r, r)
+    xp = np.pad(x32, pad, mode="symmetric").astype(np.float64)
+
+    def at(o):
+        idx = [slice(None)] * 3
+        idx[axis] = slice(r + o, r + o + n)
+        return xp[tuple(idx)]
+
+    acc = at(0) * w[0]
+    for k in range(r, 0, -1):
+        acc = acc + (at(-k) + at(k)) * w[k]
+    return acc.astype(np.float32)
+
+
+def _dog_numpy(movie32, w1, w2, chunk=16):
+    """gaussian_filter(frame, sigma1) - gaussian_filter(frame, sigma2) of every float32 frame, in the kernel's order."""
+    out = np.empty(movie32.shape, np.float32)
+    for f0 in range(0, movie32.shape[0], chunk):
+        x = movie32[f0:f0 + chunk]
+        g1 = _correlate_axis(_correlate_axis(x, w1, 1), w1, 2)
+        g2 = _correlate_axis(_correlate_axis(x, w2, 1), w2, 2)
+        out[f0:f0 + chunk] = (g1 - g2) + np.float32(0.0)          # + 0: -0.0 and +0.0 are one value, as in the kernel
+    return out
+
+
+def _window_max(frame, m):
+    """Maximum over the (2 m + 1) square window with replicated borders (scipy.ndimage.maximum_filter, mode 'nearest')."""
+    H, W = frame.shape
+    p = np.pad(frame, ((m, m), (0, 0)), mode="edge")
+    v = p[0:H]
+    for k in range(1, 2 * m + 1):
+        v = np.maximum(v, p[k:k + H])
+    p = np.pad(v, ((0, 0), (m, m)), mode="edge")
+    v = p[:, 0:W]
+    for k in range(1, 2 * m + 1):
+        v = np.maximum(v, p[:, k:k + W])
+    return v
+
+
+def _peaks_numpy(dog, threshold_percentage, min_distance):
+    """peak_local_max(dog, min_distance, threshold_abs=threshold_percentage * dog.max(), exclude_border=False) of one float32
+    frame -> (coords [n, 2] int64 (y, x), number of candidates before spacing)."""
+    thr = np.float32(threshold_percentage) * dog.max()             # one float32 product, as numpy 2 does it
+    mask = dog == _window_max(dog, min_distance)
+    if mask.all():                                                 # a flat frame has no peak
+        return np.zeros((0, 2), np.int64), 0
+    mask &= dog > thr
+    ys, xs = np.nonzero(mask)                                      # row-major
+    order = np.argsort(-dog[ys, xs], kind="stable")                # value descending, ties by row-major index
+    ys, xs = ys[order], xs[order]
+    ky, kx = np.empty(len(ys), np.int64), np.empty(len(ys), np.int64)
+    n = 0
+    for y, x in zip(ys, xs):
+        if n == 0 or not np.any((np.abs(ky[:n] - y) <= min_distance) & (np.abs(kx[:n] - x) <= min_distance)):
+            ky[n], kx[n] = y, x
+            n += 1
+    return np.stack([ky[:n], kx[:n]], axis=1), len(ys)
+
+
+def _check_detection_args(shape, sigma1, sigma2, min_distance):
+    if len(shape) != 3:
+        raise ValueError(f"movie must be [F, H, W], got {tuple(shape)}")
+    if not (0 < float(sigma1) <= float(sigma2)):
+        raise ValueError(f"need 0 < sigma1 <= sigma2, got {sigma1}, {sigma2}")
+    if int(min_distance) != min_distance or not 1 <= min_distance <= 16:
+        raise ValueError(f"min_distance must be an integer from 1 to 16, got {min_distance}")
+    w1, w2 = gaussian_half_kernel(sigma1), gaussian_half_kernel(sigma2)
+    r2 = len(w2) - 1
+    if r2 > 16:
+        raise ValueError(f"sigma2 = {sigma2} gives a filter radius of {r2} > 16")
+    if shape[1] <= r2 or shape[2] <= r2:
+        raise ValueError(f"frames of {shape[1]} x {shape[2]} are not larger than the filter radius {r2} of sigma2 = {sigma2}")
+    return w1, w2
+
+
+def detect_particles_movie(movie, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
+                           max_peaks_per_frame=512, return_dog=True):
+    """detect_particles of every frame of a movie [F, H, W] at once -> (list of F coordinate arrays [n_f, 2] int64 (y, x),
+    strongest first, and the DoG movie [F, H, W] float32 of the input's kind, or None with return_dog=False).  A CUDA tensor
+    runs on the GPU (ops.dog_peaks) and raises if a frame has more than max_peaks_per_frame candidates."""
+    w1, w2 = _check_detection_args(movie.shape, sigma1, sigma2, min_distance)
+    if _is_cuda(movie):
+        from .. import ops
+        count, coords, _, dog = ops.dog_peaks(movie.float(), w1, w2, threshold_percentage, int(min_distance),
+                                              max_peaks_per_frame, return_dog)
+        count = count.cpu().numpy()
+        top = int(count.max()) if len(count) else 0
+        coords = coords[:, :top].cpu().numpy().astype(np.int64)
+        return [coords[f, :count[f]] for f in range(len(count))], dog
+    was_tensor = torch.is_tensor(movie)
+    arr = np.ascontiguousarray(movie.detach().numpy() if was_tensor else np.asarray(movie), dtype=np.float32)
+    dog = _dog_numpy(arr, w1, w2)
+    coords = [_peaks_numpy(dog[f], threshold_percentage, int(min_distance))[0] for f in range(len(dog))]
+    if not return_dog:
+        return coords, None
+    return coords, (torch.from_numpy(dog) if was_tensor else dog)
+
+
+def detect_particles(image, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3):
+    """Reference detect_particles: one frame [H, W] -> (coordinates [n, 2] (y, x), dog_image)."""
+    if len(image.shape) != 2:
+        raise ValueError(f"image must be [H, W], got {tuple(image.shape)}; use detect_particles_movie for a movie")
+    coords, dog = detect_particles_movie(image[None], sigma1, sigma2, threshold_percentage, min_distance)
+    return coords[0], dog[0]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# linking
+# ----------------------------------------------------------------------------------------------------------------------
+def link_particles(coords_t0, coords_t1, max_distance=15):
+    """Reference link_particles: Hungarian assignment on the Euclidean distances, links longer than max_distance dropped ->
+    (links [(i0, i1), ...], unlinked_t0, unlinked_t1)."""
+    n0, n1 = len(coords_t0), len(coords_t1)
+    if n0 == 0 or n1 == 0:
+        return [], list(range(n0)), list(range(n1))
+    from scipy.optimize import linear_sum_assignment
+    c0, c1 = np.asarray(coords_t0), np.asarray(coords_t1)
+    cost = np.sqrt(((c0[:, None, :] - c1[None, :, :]) ** 2).sum(axis=2)).astype(np.float64)
+    rows, cols = linear_sum_assignment(cost, maximize=False)
+    links = [(int(i), int(j)) for i, j in zip(rows, cols) if cost[i, j] <= max_distance]
+    used0, used1 = {i for i, _ in links}, {j for _, j in links}
+    return links, [i for i in range(n0) if i not in used0], [j for j in range(n1) if j not in used1]
+
+
+def _link_tracks(all_coordinates, max_linking_distance, min_track_length, verbose=False):
+    """The book-keeping of the reference's track_particles (:225-336) on per-frame coordinate arrays -> (tracks
+    {id: [(frame, y, x), ...]} with sequential ids for tracks of >= min_track_length positions, detections as four int64
+    arrays frame / y / x / track_id in the reference's row order, number of tracks before the length filter)."""
+    tracks, active, rows = {}, {}, []          # active: track id -> (position, frame), in insertion order
+    next_id = 0
+
+    def start(frame, pos):
+        nonlocal next_id
+        tracks[next_id] = [(frame, pos[0], pos[1])]
+        active[next_id] = (pos, frame)
+        rows.append((frame, pos[0], pos[1], next_id))
+        next_id += 1
+
+    for frame, current in enumerate(all_coordinates):
+        if frame == 0:
+            for pos in current:
+                start(0, pos)
+            continue
+        ids = list(active.keys())
+        if ids and len(current) > 0:
+            previous = np.array([active[i][0] for i in ids])
+            links, _, fresh = link_particles(previous, current, max_distance=max_linking_distance)
+            for i0, i1 in links:
+                pos = current[i1]
+                tracks[ids[i0]].append((frame, pos[0], pos[1]))
+                active[ids[i0]] = (pos, frame)
+                rows.append((frame, pos[0], pos[1], ids[i0]))
+            for i1 in fresh:
+                start(frame, current[i1])
+            if verbose:
+                print(f"Frame {frame}: {len(links)} links, {len(fresh)} new tracks")
+        elif len(current) > 0:
+            for pos in current:
+                start(frame, pos)
+        for i in [i for i, (_, last) in active.items() if last < frame]:       # a track that misses a frame ends
+            del active[i]
+    long_ids = sorted(i for i, t in tracks.items() if len(t) >= min_track_length)
+    new_id = {old: new for new, old in enumerate(long_ids)}
+    det = np.array(rows, dtype=np.int64).reshape(-1, 4)
+    # the reference renumbers only the long tracks in the detections table; a short track keeps its first id
+    det[:, 3] = [new_id.get(i, i) for i in det[:, 3]]
+    return ({new_id[i]: tracks[i] for i in long_ids},
+            {"frame": det[:, 0].copy(), "y": det[:, 1].copy(), "x": det[:, 2].copy(), "track_id": det[:, 3].copy()},
+            len(tracks))
+
+
+def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
+                         max_linking_distance=15, min_track_length=3, verbose=False, max_peaks_per_frame=512):
+    """track_particles without pandas: (tracks, detections as a dict of int64 arrays frame / y / x / track_id, DoG movie
+    [F, H, W])."""
+    movie = image_sequence
+    if not torch.is_tensor(movie) and not isinstance(movie, np.ndarray):
+        movie = np.stack([np.asarray(f) for f in movie])
+    coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
+    if verbose:
+        for f, c in enumerate(coords):
+            print(f"Frame {f}: {len(c)} particles detected")
+    tracks, det, n_all = _link_tracks(coords, max_linking_distance, min_track_length, verbose)
+    print(f"Tracking complete: {n_all} total tracks, {len(tracks)} tracks with ≥{min_track_length} frames")
+    return tracks, det, dog
+
+
+def track_particles(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
+                    max_linking_distance=15, min_track_length=3, verbose=False):
+    """Reference track_particles -> (tracks {id: [(frame, y, x), ...]}, all_detections DataFrame with columns frame, y, x,
+    track_id, filtered_images: the DoG movie [F, H, W], one image per frame when iterated).  Detection runs for the whole
+    movie at once."""
+    import pandas as pd
+    tracks, det, dog = track_particles_flat(image_sequence, sigma1, sigma2, threshold_percentage, min_distance,
+                                            max_linking_distance, min_track_length, verbose)
+    return tracks, pd.DataFrame(det, columns=["frame", "y", "x", "track_id"]), dog
+
+
+def analyze_microscopy_sequence(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
+                                max_linking_distance=15, min_track_length=3, visualize=False, verbose=False,
+                                output_prefix=None):
+    """Reference analyze_microscopy_sequence: track_particles, and with output_prefix the files <prefix>_detections.csv and
+    <prefix>_tracks.pkl.  Plotting is not part of this package: visualize defaults to False and True raises."""
+    if visualize:
+        raise NotImplementedError("visualize=True needs the reference's visualize_tracks (helpers/helpersTracking.py), "
+                                  "which this package does not restate; plot the returned tracks yourself")
+    tracks, all_detections, filtered = track_particles(image_sequence, sigma1=sigma1, sigma2=sigma2,
+                                                       threshold_percentage=threshold_percentage, min_distance=min_distance,
+                                                       max_linking_distance=max_linking_distance,
+                                                       min_track_length=min_track_length, verbose=verbose)
+    if output_prefix:
+        import pickle
+        all_detections.to_csv(f"{output_prefix}_detections.csv", index=False)
+        with open(f"{output_prefix}_tracks.pkl", "wb") as fh:
+            pickle.dump(tracks, fh)
+        print(f"Results saved with prefix: {output_prefix}")
+    return tracks, all_detections, filtered
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# sub-pixel localisation
+# ----------------------------------------------------------------------------------------------------------------------
+def extract_patches_flat(movie, frames, ys, xs, patch_size=7):
+    """One gather for all localisations of all tracks: movie [F, H, W] array / tensor, frames / ys / xs [N] -> patches
+    [N, patch_size, patch_size] of the movie's kind and dtype, centred on the rounded positions (round-half-to-even), pixels
+    outside the frame read as 0: extract_particle_patches without the dictionaries."""
+    if patch_size % 2 != 1:
+        raise ValueError("patch_size must be an odd number")
+    is_np = not torch.is_tensor(movie)
+    img = torch.as_tensor(np.asarray(movie)) if is_np else movie
+    if img.dim() != 3:
+        raise ValueError(f"movie must be [F, H, W], got {tuple(img.shape)}")
+    _, H, W = img.shape
+    half = patch_size // 2
+    fr = torch.as_tensor(np.asarray(frames).astype(np.int64), device=img.device)
+    yy = torch.as_tensor(np.rint(np.asarray(ys, dtype=np.float64)).astype(np.int64), device=img.device)
+    xx = torch.as_tensor(np.rint(np.asarray(xs, dtype=np.float64)).astype(np.int64), device=img.device)
+    if not (len(fr) == len(yy) == len(xx)):
+        raise ValueError("frames, ys and xs must have one entry per localisation")
+    off = torch.arange(-half, half + 1, device=img.device)
+    py, px = yy[:, None] + off[None, :], xx[:, None] + off[None, :]
+    ok = ((py >= 0) & (py < H))[:, :, None] & ((px >= 0) & (px < W))[:, None, :]
+    g = img[fr[:, None, None], py.clamp(0, H - 1)[:, :, None], px.clamp(0, W - 1)[:, None, :]]
+    g = torch.where(ok, g, torch.zeros((), dtype=img.dtype, device=img.device))
+    return g.numpy() if is_np else g
+
+
+def _fit_normal(patch, p):
+    """Residual sum of squares, J^T r and J^T J of the model at p [n, 5] for patches [n, P, P] float64."""
+    n, P, _ = patch.shape
+    ix, iy = np.arange(P, dtype=np.float64)[None, None, :], np.arange(P, dtype=np.float64)[None, :, None]
+    c = [p[:, k, None, None] for k in range(5)]
+    with np.errstate(all="ignore"):
+        dx, dy = ix - c[1], iy - c[2]
+        r2 = dx * dx + dy * dy
+        s2 = c[3] * c[3]
+        s3 = s2 * c[3]
+        e = np.exp(-(r2 / (2.0 * s2)))
+        ae = c[0] * e
+        r = ((c[4] + ae) - patch).reshape(n, -1)
+        J = np.stack([e, ae * dx / s2, ae * dy / s2, ae * r2 / s3, np.ones_like(e)], axis=1).reshape(n, 5, -1)
+        return (r * r).sum(axis=1), np.einsum("nip,np->ni", J, r), np.einsum("nip,njp->nij", J, J)
+
+
+def _fit_solve(A, g, lam):
+    """(A + lam diag(A)) d = -g by Cholesky for every patch -> (d [n, 5], ok [n])."""
+    n = len(g)
+    L = np.zeros((n, 5, 5))
+    ok = np.ones(n, bool)
+    with np.errstate(all="ignore"):
+        for i in range(5):
+            for j in range(i + 1):
+                s = A[:, i, j].copy()
+                if i == j:
+                    s = s + lam * s
+                for k in range(j):
+                    s = s - L[:, i, k] * L[:, j, k]
+                if i == j:
+                    ok &= (s > 0.0) & (s < 1e300)
+                    L[:, i, i] = np.sqrt(np.where(ok, s, 1.0))
+                else:
+                    L[:, i, j] = s / L[:, j, j]
+        z = np.zeros((n, 5))
+        for i in range(5):
+            s = -g[:, i]
+            for k in range(i):
+                s = s - L[:, i, k] * z[:, k]
+            z[:, i] = s / L[:, i, i]
+        d = np.zeros((n, 5))
+        for i in range(4, -1, -1):
+            s = z[:, i]
+            for k in range(i + 1, 5):
+                s = s - L[:, k, i] * d[:, k]
+            d[:, i] = s / L[:, i, i]
+    return d, ok
+
+
+def _refine_numpy(patches, xtol=FIT_XTOL, max_iter=FIT_MAX_ITER):
+    """The fit of csrc/tracking.hip::rg_kernel for patches [N, P, P] on the host, all patches side by side -> (params [N, 5]
+    float64 (amplitude, x0, y0, sigma, offset), peak [N] = patch.max() in the patches' dtype, status [N] int32)."""
+    raw = np.asarray(patches)
+    N, P, _ = raw.shape
+    x = raw.astype(np.float64)
+    flat = raw.reshape(N, -1)
+    peak = flat.max(axis=1) if N else flat[:, 0]
+    p = np.stack([x.reshape(N, -1).max(axis=1), np.full(N, float(P // 2)), np.full(N, float(P // 2)), np.ones(N),
+                  x.reshape(N, -1).min(axis=1)], axis=1) if N else np.zeros((0, 5))
+    status = np.full(N, 2, np.int32)
+    if N == 0:
+        return p, peak, status
+    cost, g, A = _fit_normal(x, p)
+    status[~(cost < 1e300)] = 3
+    lam = np.full(N, 1e-3)
+    for _ in range(max_iter):
+        act = np.nonzero(status == 2)[0]
+        if len(act) == 0:
+            break
+        d, ok = _fit_solve(A[act], g[act], lam[act])
+        bad = act[~ok]
+        lam[bad] *= 10.0
+        status[bad[lam[bad] > 1e10]] = 1
+        act, d = act[ok], d[ok]
+        if len(act) == 0:
+            continue
+        pa = p[act]
+        a0, a4 = np.abs(pa[:, 0]), np.abs(pa[:, 4])
+        scale = np.stack([a0, np.maximum(np.abs(pa[:, 1]), 1.0), np.maximum(np.abs(pa[:, 2]), 1.0), np.abs(pa[:, 3]),
+                          np.maximum(a4, a0)], axis=1)
+        d0, ok0 = _fit_solve(A[act], g[act], 0.0)                 # the undamped step measures the distance to the optimum
+        with np.errstate(invalid="ignore"):
+            small = ok0 & (np.abs(d0) <= xtol * scale).all(axis=1)
+        q = pa + d
+        cq, gq, Aq = _fit_normal(x[act], q)
+        # accepted unless the cost rises by more than its own rounding error: close to the optimum a step changes the cost by
+        # less than that, and a strict test would stop the iteration at sqrt(eps) of the parameters
+        with np.errstate(invalid="ignore"):
+            better = cq <= cost[act] * FIT_COST_SLACK
+        up = act[better]
+        p[up], cost[up], g[up], A[up] = q[better], cq[better], gq[better], Aq[better]
+        lam[up] = np.maximum(lam[up] * 0.1, 1e-12)
+        down = act[~better]
+        lam[down] *= 10.0
+        status[down[lam[down] > 1e10]] = 1
+        status[act[small]] = 0
+    return p, peak, status
+
+
+def refine_gaussian_patches(patches, xtol=FIT_XTOL):
+    """Five-parameter Gaussian fit of patches [N, P, P] (P odd, 3 .. 15): CUDA float tensors go to the kernel
+    (ops.refine_gaussian), anything else to the host restatement -> (params [N, 5] float64, peak [N], status [N] int32) of
+    the input's kind."""
+    if len(patches.shape) != 3 or patches.shape[1] != patches.shape[2]:
+        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    P = patches.shape[1]
+    if P % 2 != 1 or not 3 <= P <= 15:
+        raise ValueError(f"patch side must be odd and from 3 to 15, got {P}")
+    if not 0 < xtol <= 1.49012e-8:
+        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
+    if _is_cuda(patches):
+        from .. import ops
+        return ops.refine_gaussian(patches.float(), xtol)
+    if torch.is_tensor(patches):
+        p, peak, st = _refine_numpy(patches.detach().numpy(), xtol)
+        return torch.from_numpy(p), torch.from_numpy(np.ascontiguousarray(peak)), torch.from_numpy(st)
+    return _refine_numpy(patches, xtol)
+
+
+def refine_localizations(patches, ys, xs):
+    """Sub-pixel positions of N localisations without pandas: patches [N, P, P] (extract_patches_flat) around the integer
+    positions ys / xs [N] -> dict of numpy arrays x_refined, y_refined, psf_size (float64), max_intensity (the patches' dtype)
+    and status (int32).  Where the fit failed (status != 0) the reference's fallback applies: the integer position and
+    psf_size 10."""
+    params, peak, status = refine_gaussian_patches(patches)
+    if torch.is_tensor(params):
+        params, peak, status = params.cpu().numpy(), peak.cpu().numpy(), status.cpu().numpy()
+    half = patches.shape[1] // 2
+    ys, xs = np.asarray(ys), np.asarray(xs)
+    okf = status == 0
+    return {"x_refined": np.where(okf, xs - half + params[:, 1], xs.astype(np.float64)),
+            "y_refined": np.where(okf, ys - half + params[:, 2], ys.astype(np.float64)),
+            "psf_size": np.where(okf, params[:, 3], float(FALLBACK_PSF_SIZE)),
+            "max_intensity": peak, "status": status}
+
+
+def add_refined_localization_to_dataframe(df_tracks, tracks, patches, patch_size):
+    """Reference add_refined_localization_to_dataframe: adds x_refined, y_refined, psf_size and max_intensity to a DataFrame
+    indexed by (track_id, frame).  All patches of all tracks are fitted in one call."""
+    import pandas as pd
+    keys, ys, xs, stack = [], [], [], []
+    for tid, positions in tracks.items():
+        tp = patches[tid]
+        for i, (frame, y, x) in enumerate(positions):
+            keys.append((tid, frame))
+            ys.append(y)
+            xs.append(x)
+            stack.append(tp[i])
+    if not keys:
+        for col in ("x_refined", "y_refined", "psf_size", "max_intensity"):
+            df_tracks[col] = pd.Series(dtype=np.float64)
+        return df_tracks
+    allp = torch.stack(stack) if torch.is_tensor(stack[0]) else np.stack(stack)
+    if allp.shape[1] != patch_size:
+        raise ValueError(f"patches of side {allp.shape[1]} with patch_size = {patch_size}")
+    res = refine_localizations(allp, np.asarray(ys), np.asarray(xs))
+    for col in ("x_refined", "y_refined", "psf_size", "max_intensity"):
+        df_tracks[col] = pd.Series(dict(zip(keys, res[col])))
+    return df_tracks
+
+
+def compute_displacement(df_tracks):
+    """Reference compute_displacement: per-step displacement of the refined positions (0 at a track's first frame) and the
+    per-track columns mean_displacement, mean_psf_size, max_intensity_over_track, mean_max_intensity_over_track,
+    std_max_intensity_over_track."""
+    df = df_tracks.reset_index()
+    per_track = {k: {} for k in ("mean_displacement", "mean_psf_size", "max_intensity_over_track",
+                                 "mean_max_intensity_over_track", "std_max_intensity_over_track")}
+    for tid, group in df.groupby("track_id"):
+        group = group.sort_values("frame")
+        x, y = group["x_refined"].to_numpy(), group["y_refined"].to_numpy()
+        steps = [0] + list(np.sqrt((x[1:] - x[:-1]) ** 2 + (y[1:] - y[:-1]) ** 2))
+        df.loc[group.index, "displacement"] = steps
+        per_track["mean_displacement"][tid] = np.mean(steps)
+        per_track["mean_psf_size"][tid] = group["psf_size"].mean()
+        per_track["max_intensity_over_track"][tid] = group["max_intensity"].max()
+        per_track["mean_max_intensity_over_track"][tid] = group["max_intensity"].mean()
+        per_track["std_max_intensity_over_track"][tid] = group["max_intensity"].std()
+    df.set_index(["track_id", "frame"], inplace=True)
+    ids = df.index.get_level_values("track_id")
+    for col, values in per_track.items():
+        df[col] = ids.map(values)
+    return df
+
+
+def tracks_to_dataframe(tracks, patches, patch_size):
+    """Reference tracks_to_dataframe: tracks {id: [(frame, y, x), ...]} and their patches -> DataFrame indexed by (track_id,
+    frame) with nbr_frames, x, y, the refined localisation and the displacement columns."""
+    import pandas as pd
+    data = [(tid, frame, len(positions), x, y) for tid, positions in tracks.items() for frame, y, x in positions]
+    df = pd.DataFrame(data, columns=["track_id", "frame", "nbr_frames", "x", "y"])
+    df.set_index(["track_id", "frame"], inplace=True)
+    df.sort_index(inplace=True)
+    df = add_refined_localization_to_dataframe(df, tracks, patches, patch_size=patch_size)
+    return compute_displacement(df)

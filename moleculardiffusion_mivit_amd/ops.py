@@ -565,3 +565,58 @@ def gaussian_filter_frames(frames: torch.Tensor, sigma: float, truncate: float =
     N.check(N.lib.mivit_gaussian_filter_frames(_p(frames), frames.numel() // max(1, H * W), H, W, float(sigma),
                                                float(truncate), _p(out), _s(frames)), "mivit_gaussian_filter_frames")
     return out
+
+
+DOG_PEAKS_MAX_RADIUS, DOG_PEAKS_MAX_CAPACITY = 16, 2048
+
+
+def dog_peaks(movie: torch.Tensor, w1, w2, threshold_percentage: float = 0.1, min_distance: int = 3,
+              max_peaks_per_frame: int = 512, return_dog: bool = True):
+    """Difference-of-Gaussians particle detection of a whole movie (csrc/tracking.hip, mivit_dog_peaks): movie [F, H, W]
+    float32 on the GPU; w1 / w2 the half kernels (w[0] centre, w[k] weight at distance k, float64) of the narrow and the wide
+    Gaussian, as helpers/tracking.gaussian_half_kernel builds them -> (count [F] int32, coords [F, cap, 2] int32 (y, x),
+    values [F, cap] float32, dog [F, H, W] float32 or None).  Peaks of a frame are ordered by value descending, ties by
+    row-major index.  Raises if a frame has more candidates than max_peaks_per_frame: nothing is truncated silently."""
+    movie = _frames_f32(movie, "dog_peaks")
+    if movie.dim() != 3:
+        raise ValueError(f"movie must be [F, H, W], got {tuple(movie.shape)}")
+    import numpy as np
+    w1 = np.ascontiguousarray(w1, dtype=np.float64)
+    w2 = np.ascontiguousarray(w2, dtype=np.float64)
+    if w1.ndim != 1 or w2.ndim != 1 or w1.size < 1 or w2.size < 1:
+        raise ValueError("w1 / w2 must be 1-D half kernels (centre weight first)")
+    F, H, W = movie.shape
+    cap = int(max_peaks_per_frame)
+    dev = movie.device
+    count = torch.zeros(F, dtype=torch.int32, device=dev)
+    ncand = torch.zeros(F, dtype=torch.int32, device=dev)
+    coords = torch.zeros(F, max(cap, 0), 2, dtype=torch.int32, device=dev)
+    values = torch.zeros(F, max(cap, 0), dtype=torch.float32, device=dev)
+    dog = torch.empty(F, H, W, dtype=torch.float32, device=dev) if return_dog else None
+    wsb = N.lib.mivit_dog_peaks_workspace_bytes(F, H, W, cap, 1 if return_dog else 0)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    N.check(N.lib.mivit_dog_peaks(_p(movie), F, H, W, w1.ctypes.data_as(ctypes.c_void_p), w1.size - 1,
+                                  w2.ctypes.data_as(ctypes.c_void_p), w2.size - 1, float(threshold_percentage),
+                                  int(min_distance), cap, _p(count), _p(ncand), _p(coords), _p(values), _p(dog), _p(ws),
+                                  ws.numel(), _s(movie)), "mivit_dog_peaks")
+    worst = int(ncand.max()) if F else 0
+    if worst > cap:
+        raise RuntimeError(f"dog_peaks: a frame has {worst} peak candidates but max_peaks_per_frame = {cap}; raise "
+                           f"max_peaks_per_frame (up to {DOG_PEAKS_MAX_CAPACITY}) or the threshold")
+    return count, coords, values, dog
+
+
+def refine_gaussian(patches: torch.Tensor, xtol: float = 1e-11):
+    """Five-parameter Gaussian fit of every patch (csrc/tracking.hip, mivit_refine_gaussian): patches [N, P, P] float32 on the
+    GPU, P odd, 3 .. 15 -> (params [N, 5] float64 (amplitude, x0, y0, sigma, offset), peak [N] float32 = patch.max(),
+    status [N] int32, 0 where the fit converged)."""
+    patches = _frames_f32(patches, "refine_gaussian")
+    if patches.dim() != 3 or patches.shape[1] != patches.shape[2]:
+        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    n, P, _ = patches.shape
+    params = torch.zeros(n, 5, dtype=torch.float64, device=patches.device)
+    peak = torch.zeros(n, dtype=torch.float32, device=patches.device)
+    status = torch.zeros(n, dtype=torch.int32, device=patches.device)
+    N.check(N.lib.mivit_refine_gaussian(_p(patches), n, P, float(xtol), _p(params), _p(peak), _p(status), _s(patches)),
+            "mivit_refine_gaussian")
+    return params, peak, status

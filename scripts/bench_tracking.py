@@ -1,0 +1,147 @@
+"""Wall time of the real-movie front end (helpers/tracking.py): detection (csrc/tracking.hip through ops.dog_peaks), the
+Gaussian fit (ops.refine_gaussian) and a whole track_particles_flat on the GPU, device tensor in, timed with events on the
+stream after a warm-up (minimum of the repetitions; track_particles_flat ends on the host, so it is timed with the wall
+clock around a synchronise); the numpy restatement; and a reference-style per-frame loop on the CPU (two
+scipy.ndimage.gaussian_filter calls and the peak_local_max statement per frame, one scipy.optimize.curve_fit per patch).
+Two shapes: the fixture's 30 x 128 x 128 movie with 12 particles, and 1 000 x 512 x 512 with about 50 particles per frame;
+on the large one the CPU paths run on the first --cpu-frames frames and the time is reported per frame.
+
+    python scripts/bench_tracking.py [--small-only] [--cpu-frames N] [--json OUT]
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+from contextlib import redirect_stdout
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+import numpy as np
+import torch
+
+import tracking_common as tc
+from moleculardiffusion_mivit_amd import ops
+from moleculardiffusion_mivit_amd.helpers import tracking as T
+
+W1, W2 = T.gaussian_half_kernel(1.0), T.gaussian_half_kernel(2.0)
+PATCH = tc.PATCH_SIZE
+
+
+def gpu_movie(frames, H, W, particles, seed=0):
+    """Gaussian spots on Brownian paths, background, Poisson noise, rendered on the device: float32 [frames, H, W]."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    start = torch.rand(1, particles, 2, generator=g, device="cuda") * torch.tensor([H - 40.0, W - 40.0], device="cuda") + 20
+    pos = start + torch.cumsum(torch.randn(frames, particles, 2, generator=g, device="cuda") * 0.3, dim=0)
+    out = torch.empty(frames, H, W, device="cuda")
+    yy, xx = torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32)
+    for f0 in range(0, frames, 50):
+        p = pos[f0:f0 + 50]
+        gy = torch.exp(-(yy[None, None, :] - p[:, :, 0:1]) ** 2 / (2 * 1.3 ** 2))
+        gx = torch.exp(-(xx[None, None, :] - p[:, :, 1:2]) ** 2 / (2 * 1.3 ** 2))
+        out[f0:f0 + 50] = torch.poisson(200.0 * torch.einsum("fpy,fpx->fyx", gy, gx) + 20.0, generator=g)
+    return out
+
+
+def t_events(fn, reps=5):
+    fn()                                                     # warm-up: code object load, allocator
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        best = min(best, a.elapsed_time(b) * 1e-3)
+    return best
+
+
+def t_wall(fn, reps=1):
+    best = float("inf")
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def quiet(fn):
+    def run():
+        with redirect_stdout(io.StringIO()):
+            return fn()
+    return run
+
+
+def reference_style_detection(mov):
+    from scipy import ndimage
+    for frame in mov:
+        dog = ndimage.gaussian_filter(frame, sigma=1.0) - ndimage.gaussian_filter(frame, sigma=2.0)
+        tc.peak_local_max(dog, min_distance=3, threshold_abs=0.1 * np.max(dog), exclude_border=False)
+
+
+def reference_style_fit(patches):
+    from scipy.optimize import curve_fit
+    P = patches.shape[1]
+    x, y = np.meshgrid(np.arange(P), np.arange(P))
+
+    def model(c, amplitude, x0, y0, sigma, offset):
+        return (offset + amplitude * np.exp(-((c[0] - x0) ** 2 + (c[1] - y0) ** 2) / (2 * sigma ** 2))).ravel()
+
+    for p in patches:
+        try:
+            curve_fit(model, (x, y), p.ravel(), p0=(p.max(), P // 2, P // 2, 1.0, p.min()))
+        except RuntimeError:
+            pass
+
+
+def bench(name, mov_gpu, cpu_frames):
+    F, H, W = mov_gpu.shape
+    res = {"shape": [F, H, W]}
+    res["gpu_detect_s"] = t_events(lambda: ops.dog_peaks(mov_gpu, W1, W2, 0.1, 3, 512, True))
+    tracks, det, _ = quiet(lambda: T.track_particles_flat(mov_gpu))()
+    res["detections"], res["tracks"] = int(len(det["frame"])), len(tracks)
+    rows = np.array([(fr, y, x) for pos in tracks.values() for fr, y, x in pos]).reshape(-1, 3)
+    patches = T.extract_patches_flat(mov_gpu, rows[:, 0], rows[:, 1], rows[:, 2], PATCH)
+    res["fits"] = int(len(rows))
+    res["gpu_fit_s"] = t_events(lambda: ops.refine_gaussian(patches))
+    _, _, st = ops.refine_gaussian(patches)
+    res["fits_not_converged"] = int((st != 0).sum())
+
+    def whole():
+        T.track_particles_flat(mov_gpu)
+        torch.cuda.synchronize()
+    res["gpu_track_particles_s"] = t_wall(quiet(whole), reps=2)
+    n = min(F, cpu_frames)
+    res["cpu_frames"] = n
+    mov = mov_gpu[:n].cpu().numpy()
+    res["numpy_detect_s_per_frame"] = t_wall(lambda: T.detect_particles_movie(mov)) / n
+    res["reference_style_detect_s_per_frame"] = t_wall(lambda: reference_style_detection(mov)) / n
+    m = min(len(rows), 2000)
+    pat = patches[:m].cpu().numpy()
+    res["cpu_fits"] = m
+    res["numpy_fit_s_per_patch"] = t_wall(lambda: T._refine_numpy(pat)) / max(m, 1)
+    res["reference_style_fit_s_per_patch"] = t_wall(lambda: reference_style_fit(pat[:500])) / max(min(m, 500), 1)
+    if n == F:
+        res["numpy_track_particles_s"] = t_wall(quiet(lambda: T.track_particles_flat(mov)))
+    print(name, json.dumps(res), flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--small-only", action="store_true")
+    ap.add_argument("--cpu-frames", type=int, default=20)
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    out = {"fixture": bench("fixture", torch.from_numpy(tc.movie("main")).cuda(), 30)}
+    if not a.small_only:
+        out["large"] = bench("large", gpu_movie(1000, 512, 512, 50), a.cpu_frames)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
