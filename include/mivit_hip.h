@@ -242,6 +242,27 @@ int mivit_dog_peaks(const float *movie, int F, int H, int W, const double *w1, i
 int mivit_refine_gaussian(const float *patches, int N, int P, double xtol, double *params, float *peak, int *status,
                           void *stream);
 
+/* Linking of a whole movie: the reference's link_particles (helpers/helpersTracking.py:123-177, one
+ * scipy.optimize.linear_sum_assignment per frame) for all F - 1 pairs of consecutive frames in one launch, csrc/linking.hip.
+ * coords [F, cap, 2] int32 (y, x) and count [F] int32 as mivit_dog_peaks leaves them (device); movie_start [F] bytes or NULL:
+ * a non-zero entry marks the first frame of a movie, which gets no links (frame 0 always is one).  Per frame f the full
+ * rectangular assignment between the detections of f - 1 and of f is solved exactly on the Euclidean distance (shortest
+ * augmenting paths with duals, fp64; the side with fewer detections plays rows, f - 1 on equality; ties by path cost, then
+ * free column first, then column index), and only then links longer than max_distance are dropped.  out: link [F, cap] int32,
+ * for every detection of frame f the index of its partner in frame f - 1 or -1; every entry is written.  1 <= cap <= 1024.
+ * Arguments are validated before any HIP call; F = 0 is a no-op, empty frames are valid. */
+int mivit_link_frames(const int *coords, const int *count, const unsigned char *movie_start, int F, int cap,
+                      double max_distance, int *link, void *stream);
+
+/* Track ids from the links: the book-keeping of the reference's track_particles (helpers/helpersTracking.py:225-336),
+ * csrc/linking.hip, one workgroup looping over the frames.  A linked detection inherits its partner's id, an unlinked one takes
+ * the next free id in ascending detection index; frame 0 and every movie_start frame start one track per detection.  out: ids
+ * [F, cap] int32 (entries beyond count[f] are not written), lengths [>= number of tracks; F * cap always suffices] int32,
+ * the number of positions of each track, n_tracks [1] int32.  1 <= cap <= 1024.  Arguments are validated before any HIP call;
+ * F = 0 only clears n_tracks. */
+int mivit_chain_tracks(const int *link, const int *count, const unsigned char *movie_start, int F, int cap, int *ids,
+                       int *lengths, int *n_tracks, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -1,7 +1,7 @@
 // Real-movie front end on the GPU: particle detection for a whole movie and the sub-pixel Gaussian fit of every localisation,
 // the counterparts of the reference's per-frame Python in helpers/helpersTracking.py -- detect_particles (:12-57, two
 // scipy.ndimage.gaussian_filter calls + skimage.feature.peak_local_max per frame) and the scipy.optimize.curve_fit inside
-// add_refined_localization_to_dataframe (:555-604).  Linking (a Hungarian assignment on a few dozen points) stays on the host.
+// add_refined_localization_to_dataframe (:555-604).  Linking is in csrc/linking.hip.
 //
 // mivit_dog_peaks, four launches whatever the frame count:
 //   1. tk_init_kernel    per frame: max / min keys and the candidate counter.

@@ -8,7 +8,9 @@ add_refined_localization_to_dataframe (:555-604), compute_displacement (:608-647
 movie goes to the kernels of csrc/tracking.hip (detection for the whole movie at once, one Gaussian fit per patch) and what
 the reference returns as images stays a CUDA tensor; anything else goes to the numpy restatement in this file, which computes
 the filter in the kernel's order (bitwise equal) and the fit with the kernel's algorithm.  Linking is a Hungarian assignment
-on a few dozen points per frame and runs on the host either way.  Movies are filtered as float32.  pandas and scipy are only
+per frame pair: by default (linking="host") scipy's, in a loop over the frames on the host, as the reference does it; with
+linking="device" all frame pairs of a movie are solved in one launch of csrc/linking.hip and the track ids are chained on the
+device (link_particles_movie, chain_tracks, track_particles_tensors).  Movies are filtered as float32.  pandas and scipy are only
 imported by the functions that need them: detect_particles_movie, track_particles_flat, extract_patches_flat and
 refine_localizations need neither pandas nor (except for linking) scipy."""
 from typing import Dict, Sequence, Tuple
@@ -248,13 +250,279 @@ def _link_tracks(all_coordinates, max_linking_distance, min_track_length, verbos
             len(tracks))
 
 
+LINK_MAX_DETECTIONS = 1024   # per frame, the limit of csrc/linking.hip (ops.LINK_MAX_DETECTIONS)
+
+
+def _assign_pair_numpy(c0, c1):
+    """The solver of csrc/linking.hip::lk_link_kernel on the host, same roles, same tie rule, same order of fp64 operations:
+    exact rectangular assignment between c0 [n0, 2] and c1 [n1, 2] (integers, (y, x)) on the Euclidean distance by shortest
+    augmenting paths with duals.  The side with fewer points plays rows (c0 on equality), rows are augmented in ascending
+    index, and the closest unvisited column is the minimum of (path cost, column already matched, column index)
+    -> (partner [n1] int64: index into c0 or -1, BEFORE the max_distance filter; distance [n1] float64 of each link)."""
+    c0, c1 = np.asarray(c0, dtype=np.int64).reshape(-1, 2), np.asarray(c1, dtype=np.int64).reshape(-1, 2)
+    n0, n1 = len(c0), len(c1)
+    partner, dist = np.full(n1, -1, np.int64), np.zeros(n1)
+    if n0 == 0 or n1 == 0:
+        return partner, dist
+    rows_prev = n0 <= n1
+    R, C = (c0, c1) if rows_prev else (c1, c0)
+    d = (R[:, None, :] - C[None, :, :]).astype(np.float64)
+    cost = np.sqrt(d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1])
+    nr, nc = cost.shape
+    u, v = np.zeros(nr), np.zeros(nc)
+    col4row, row4col = np.full(nr, -1, np.int64), np.full(nc, -1, np.int64)
+    for cur in range(nr):
+        spc, path = np.full(nc, np.inf), np.full(nc, -1, np.int64)
+        SR, SC = np.zeros(nr, bool), np.zeros(nc, bool)
+        min_val, i, sink = 0.0, cur, -1
+        while sink < 0:
+            SR[i] = True
+            r = ((min_val + cost[i]) - u[i]) - v
+            upd = ~SC & (r < spc)
+            spc[upd] = r[upd]
+            path[upd] = i
+            low = spc[~SC].min()
+            tie = np.flatnonzero(~SC & (spc == low))
+            free = tie[row4col[tie] < 0]
+            j = int(free[0]) if len(free) else int(tie[0])
+            min_val = low
+            if row4col[j] < 0:
+                sink = j
+            else:
+                i = int(row4col[j])
+            SC[j] = True
+        others = np.flatnonzero(SR)
+        others = others[others != cur]
+        u[others] = u[others] + (min_val - spc[col4row[others]])
+        u[cur] = u[cur] + min_val
+        v[SC] = v[SC] - (min_val - spc[SC])
+        j = sink
+        while True:
+            r_ = int(path[j])
+            row4col[j] = r_
+            col4row[r_], j = j, int(col4row[r_])
+            if r_ == cur:
+                break
+    if rows_prev:
+        has = row4col >= 0
+        partner[has] = row4col[has]
+        dist[has] = cost[row4col[has], np.flatnonzero(has)]
+    else:
+        partner[:] = col4row
+        dist[:] = cost[np.arange(nr), col4row]
+    return partner, dist
+
+
+def _padded_detections(coords, counts):
+    """Per-frame coordinate arrays, or a padded [F, cap, 2] array with counts [F] -> (padded int32 [F, cap, 2], counts int32)."""
+    if counts is None:
+        frames = [np.asarray(c).reshape(-1, 2) for c in coords]
+        counts = np.array([len(c) for c in frames], np.int32)
+        cap = max(1, int(counts.max()) if len(frames) else 1)
+        padded = np.zeros((len(frames), cap, 2), np.int32)
+        for f, c in enumerate(frames):
+            padded[f, :len(c)] = c
+        return padded, counts
+    if torch.is_tensor(coords):
+        coords = coords.detach().cpu().numpy()
+    if torch.is_tensor(counts):
+        counts = counts.detach().cpu().numpy()
+    padded, counts = np.asarray(coords), np.asarray(counts)
+    if padded.ndim != 3 or padded.shape[2] != 2:
+        raise ValueError(f"coords must be [F, cap, 2], got {tuple(padded.shape)}")
+    if counts.shape != (padded.shape[0],):
+        raise ValueError(f"counts must be [{padded.shape[0]}], got {tuple(counts.shape)}")
+    if len(counts) and (counts.min() < 0 or counts.max() > padded.shape[1]):
+        raise ValueError(f"counts must lie in 0 .. {padded.shape[1]}")
+    return padded.astype(np.int32), counts.astype(np.int32)
+
+
+def _check_movie_start(movie_start, F):
+    if movie_start is None:
+        return None
+    ms = movie_start.detach().cpu().numpy() if torch.is_tensor(movie_start) else np.asarray(movie_start)
+    if ms.shape != (F,):
+        raise ValueError(f"movie_start must have one entry per frame, got {tuple(ms.shape)} for {F} frames")
+    return ms != 0
+
+
+def link_particles_movie(coords, counts=None, max_distance=15, movie_start=None):
+    """link_particles for every pair of consecutive frames of a movie at once.  coords [F, cap, 2] (y, x) with counts [F], as
+    ops.dog_peaks returns them, or (counts=None) a list of per-frame arrays [n_f, 2]; movie_start [F] (optional): a true entry
+    opens a new movie, whose first frame gets no links -> link [F, cap] int32 of the input's kind: for every detection of
+    frame f the index of its partner in frame f - 1, or -1.  CUDA tensors go to the kernel (ops.link_frames), anything else
+    to its restatement (_assign_pair_numpy).  Every pair is solved in full in detection order and links longer than
+    max_distance are dropped afterwards, as the reference does; where a pair has several optimal assignments the choice may
+    differ from scipy's (link_particles), whose choice depends on the order of its rows."""
+    if float(max_distance) != float(max_distance):
+        raise ValueError("max_distance is NaN")
+    if _is_cuda(coords):
+        if counts is None or not _is_cuda(counts):
+            raise ValueError("CUDA coords [F, cap, 2] need CUDA counts [F]")
+        if coords.dim() != 3 or coords.shape[2] != 2:
+            raise ValueError(f"coords must be [F, cap, 2], got {tuple(coords.shape)}")
+        if coords.shape[1] > LINK_MAX_DETECTIONS:
+            raise ValueError(f"{coords.shape[1]} detections per frame, the linking kernel's limit is {LINK_MAX_DETECTIONS} "
+                             f"(LINK_MAX_DETECTIONS)")
+        from .. import ops
+        return ops.link_frames(coords.int(), counts.int(), float(max_distance), movie_start)
+    as_tensor = torch.is_tensor(coords)
+    padded, counts = _padded_detections(coords, counts)
+    F, cap = padded.shape[:2]
+    if cap > LINK_MAX_DETECTIONS:
+        raise ValueError(f"{cap} detections per frame, the linking kernel's limit is {LINK_MAX_DETECTIONS} "
+                         f"(LINK_MAX_DETECTIONS)")
+    ms = _check_movie_start(movie_start, F)
+    link = np.full((F, cap), -1, np.int32)
+    for f in range(1, F):
+        if ms is not None and ms[f]:
+            continue
+        partner, dist = _assign_pair_numpy(padded[f - 1, :counts[f - 1]], padded[f, :counts[f]])
+        link[f, :counts[f]] = np.where((partner >= 0) & (dist <= max_distance), partner, -1)
+    return torch.from_numpy(link) if as_tensor else link
+
+
+def _chain_numpy(link, counts, ms):
+    """csrc/linking.hip::lk_chain_kernel on the host -> (ids [F, cap] int32, -1 beyond counts; lengths [F * cap] int32;
+    number of tracks)."""
+    F, cap = link.shape
+    ids, lengths = np.full((F, cap), -1, np.int32), np.zeros(F * cap, np.int32)
+    next_id, n_prev = 0, 0
+    for f in range(F):
+        n = int(counts[f])
+        l = link[f, :n].astype(np.int64) if f > 0 and not (ms is not None and ms[f]) else np.full(n, -1, np.int64)
+        l = np.where(l >= n_prev, -1, l)
+        new = l < 0
+        cur = np.where(new, next_id + np.cumsum(new) - 1, ids[f - 1, np.maximum(l, 0)] if f > 0 else 0)
+        ids[f, :n] = cur
+        lengths[cur] = np.where(new, 1, lengths[cur] + 1)
+        next_id += int(new.sum())
+        n_prev = n
+    return ids, lengths, next_id
+
+
+def chain_tracks(link, counts, movie_start=None):
+    """Track ids from the links of link_particles_movie: a linked detection inherits its partner's id, an unlinked one takes
+    the next free id in ascending detection index, frame 0 (and every movie_start frame) starts one track per detection: the
+    numbering of the reference's track_particles.  link [F, cap], counts [F] -> (ids [F, cap] int32, -1 beyond counts;
+    lengths [F * cap] int32, the number of positions of track i at index i; n_tracks [1] int32) of the input's kind.  CUDA
+    tensors go to the kernel (ops.chain_tracks)."""
+    if _is_cuda(link):
+        if not _is_cuda(counts):
+            raise ValueError("a CUDA link tensor needs CUDA counts")
+        from .. import ops
+        return ops.chain_tracks(link.int(), counts.int(), movie_start)
+    as_tensor = torch.is_tensor(link)
+    link = link.detach().numpy() if as_tensor else np.asarray(link)
+    counts = counts.detach().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if link.ndim != 2:
+        raise ValueError(f"link must be [F, cap], got {tuple(link.shape)}")
+    F, cap = link.shape
+    if counts.shape != (F,):
+        raise ValueError(f"counts must be [{F}], got {tuple(counts.shape)}")
+    if F and (counts.min() < 0 or counts.max() > cap):
+        raise ValueError(f"counts must lie in 0 .. {cap}")
+    ids, lengths, n = _chain_numpy(link, counts, _check_movie_start(movie_start, F))
+    n = np.array([n], np.int32)
+    return (torch.from_numpy(ids), torch.from_numpy(lengths), torch.from_numpy(n)) if as_tensor else (ids, lengths, n)
+
+
+def _detections_table(coords, counts, ids, lengths, min_track_length):
+    """The detections table from chained ids, torch ops on the tensors' device: coords [F, cap, 2], counts [F], ids [F, cap],
+    lengths [>= tracks] -> (frame, y, x, track_id, in_long_track), int64 / bool [N], in the reference's row order: frames
+    ascending and, within a frame, ascending id as handed out (linked detections in the order of their tracks, then the new
+    ones in detection order: new ids are larger than every older one).  Tracks of at least min_track_length positions are
+    renumbered 0, 1, ... in ascending first id; a shorter track keeps its first id in the table, as in the reference."""
+    F, cap = ids.shape
+    valid = torch.arange(cap, device=ids.device)[None, :] < counts[:, None]
+    fr, j = valid.nonzero(as_tuple=True)
+    tid = ids[fr, j].long()
+    order = torch.argsort(fr * (lengths.numel() + 1) + tid, stable=True)
+    fr, j, tid = fr[order], j[order], tid[order]
+    is_long = (lengths > 0) & (lengths >= min_track_length)
+    new_id = torch.cumsum(is_long, 0) - 1
+    in_long = is_long[tid]
+    return fr, coords[fr, j, 0].long(), coords[fr, j, 1].long(), torch.where(in_long, new_id[tid], tid), in_long
+
+
+def track_particles_tensors(movie, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
+                            max_linking_distance=15, min_track_length=3, max_peaks_per_frame=512, movie_start=None,
+                            return_dog=True):
+    """Detection, linking, chaining, length filter and renumbering of a CUDA movie [F, H, W] without a copy of the
+    coordinates to the host -> (dict of CUDA tensors frame, y, x, track_id (int64 [N], the reference's detections table in its
+    row order), in_long_track (bool [N]: the rows whose track has >= min_track_length positions and so carries a renumbered
+    id), n_tracks ([1] int32, before the length filter); DoG movie or None).  frame / y / x of the rows with in_long_track feed
+    extract_patches_flat and refine_localizations as they are.  movie_start [F] marks the first frames of several movies
+    concatenated along F."""
+    if not _is_cuda(movie):
+        raise ValueError("track_particles_tensors needs a CUDA movie; use track_particles_flat(..., linking='device') on the host")
+    w1, w2 = _check_detection_args(movie.shape, sigma1, sigma2, min_distance)
+    if max_peaks_per_frame > LINK_MAX_DETECTIONS:
+        raise ValueError(f"max_peaks_per_frame = {max_peaks_per_frame}, the linking kernel's limit is {LINK_MAX_DETECTIONS} "
+                         f"(LINK_MAX_DETECTIONS)")
+    from .. import ops
+    count, coords, _, dog = ops.dog_peaks(movie.float(), w1, w2, threshold_percentage, int(min_distance), max_peaks_per_frame,
+                                          return_dog)
+    link = ops.link_frames(coords, count, float(max_linking_distance), movie_start)
+    ids, lengths, n_tracks = ops.chain_tracks(link, count, movie_start)
+    fr, y, x, tid, in_long = _detections_table(coords, count, ids, lengths, min_track_length)
+    return {"frame": fr, "y": y, "x": x, "track_id": tid, "in_long_track": in_long, "n_tracks": n_tracks}, dog
+
+
+def _tracks_from_table(fr, y, x, tid, in_long):
+    """The tracks dictionary {id: [(frame, y, x), ...]} of the long tracks from the detections table (host arrays)."""
+    fr, y, x, tid = fr[in_long], y[in_long], x[in_long], tid[in_long]
+    order = np.argsort(tid, kind="stable")                           # rows are in frame order already
+    fr, y, x, tid = fr[order], y[order], x[order], tid[order]
+    cuts = np.flatnonzero(np.diff(tid)) + 1
+    starts, ends = np.concatenate([[0], cuts]), np.concatenate([cuts, [len(tid)]])
+    frames = fr.tolist()
+    return {int(tid[a]): list(zip(frames[a:b], y[a:b], x[a:b])) for a, b in zip(starts, ends) if b > a}
+
+
+def _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance, max_linking_distance, min_track_length, verbose,
+                  max_peaks_per_frame):
+    """track_particles_flat with linking="device": the kernels for a CUDA movie, their restatements for anything else."""
+    if _is_cuda(movie):
+        t, dog = track_particles_tensors(movie, sigma1, sigma2, threshold_percentage, min_distance, max_linking_distance,
+                                         min_track_length, max_peaks_per_frame)
+        keys = ("frame", "y", "x", "track_id", "in_long_track")
+        packed = torch.stack([t[k].long() for k in keys]).cpu().numpy()          # the one copy to the host
+        fr, y, x, tid, in_long = packed[0], packed[1], packed[2], packed[3], packed[4].astype(bool)
+        n_all = int(t["n_tracks"])
+    else:
+        coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
+        padded, counts = _padded_detections(coords, None)
+        link = link_particles_movie(padded, counts, max_linking_distance)
+        ids, lengths, n_all = _chain_numpy(link, counts, None)
+        fr, y, x, tid, in_long = (a.numpy() for a in _detections_table(
+            torch.from_numpy(padded), torch.from_numpy(counts), torch.from_numpy(ids), torch.from_numpy(lengths),
+            min_track_length))
+    if verbose:
+        per_frame = np.bincount(fr, minlength=len(movie))
+        for f, n in enumerate(per_frame):
+            print(f"Frame {f}: {n} particles detected")
+    det = {"frame": fr.copy(), "y": y.copy(), "x": x.copy(), "track_id": tid.copy()}
+    return _tracks_from_table(fr, y, x, tid, in_long), det, dog, n_all
+
+
 def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
-                         max_linking_distance=15, min_track_length=3, verbose=False, max_peaks_per_frame=512):
+                         max_linking_distance=15, min_track_length=3, verbose=False, max_peaks_per_frame=512, linking="host"):
     """track_particles without pandas: (tracks, detections as a dict of int64 arrays frame / y / x / track_id, DoG movie
-    [F, H, W])."""
+    [F, H, W]).  linking="host" (default): scipy's assignment per frame in a loop on the host, rows in the order of the
+    reference's active tracks.  linking="device": all frame pairs in one launch of csrc/linking.hip and the ids chained on the
+    device for a CUDA movie (one copy to the host, for the dictionaries), the kernels' restatement for a host movie; same
+    result wherever every frame pair has a single optimal assignment (see link_particles_movie)."""
+    if linking not in ("host", "device"):
+        raise ValueError(f"linking must be 'host' or 'device', got {linking!r}")
     movie = image_sequence
     if not torch.is_tensor(movie) and not isinstance(movie, np.ndarray):
         movie = np.stack([np.asarray(f) for f in movie])
+    if linking == "device":
+        tracks, det, dog, n_all = _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance,
+                                                max_linking_distance, min_track_length, verbose, max_peaks_per_frame)
+        print(f"Tracking complete: {n_all} total tracks, {len(tracks)} tracks with ≥{min_track_length} frames")
+        return tracks, det, dog
     coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
     if verbose:
         for f, c in enumerate(coords):
@@ -265,19 +533,19 @@ def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_perce
 
 
 def track_particles(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
-                    max_linking_distance=15, min_track_length=3, verbose=False):
+                    max_linking_distance=15, min_track_length=3, verbose=False, linking="host"):
     """Reference track_particles -> (tracks {id: [(frame, y, x), ...]}, all_detections DataFrame with columns frame, y, x,
     track_id, filtered_images: the DoG movie [F, H, W], one image per frame when iterated).  Detection runs for the whole
-    movie at once."""
+    movie at once; linking as in track_particles_flat."""
     import pandas as pd
     tracks, det, dog = track_particles_flat(image_sequence, sigma1, sigma2, threshold_percentage, min_distance,
-                                            max_linking_distance, min_track_length, verbose)
+                                            max_linking_distance, min_track_length, verbose, linking=linking)
     return tracks, pd.DataFrame(det, columns=["frame", "y", "x", "track_id"]), dog
 
 
 def analyze_microscopy_sequence(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
                                 max_linking_distance=15, min_track_length=3, visualize=False, verbose=False,
-                                output_prefix=None):
+                                output_prefix=None, linking="host"):
     """Reference analyze_microscopy_sequence: track_particles, and with output_prefix the files <prefix>_detections.csv and
     <prefix>_tracks.pkl.  Plotting is not part of this package: visualize defaults to False and True raises."""
     if visualize:
@@ -286,7 +554,8 @@ def analyze_microscopy_sequence(image_sequence, sigma1=1.0, sigma2=2.0, threshol
     tracks, all_detections, filtered = track_particles(image_sequence, sigma1=sigma1, sigma2=sigma2,
                                                        threshold_percentage=threshold_percentage, min_distance=min_distance,
                                                        max_linking_distance=max_linking_distance,
-                                                       min_track_length=min_track_length, verbose=verbose)
+                                                       min_track_length=min_track_length, verbose=verbose,
+                                                       linking=linking)
     if output_prefix:
         import pickle
         all_detections.to_csv(f"{output_prefix}_detections.csv", index=False)
@@ -311,9 +580,13 @@ def extract_patches_flat(movie, frames, ys, xs, patch_size=7):
         raise ValueError(f"movie must be [F, H, W], got {tuple(img.shape)}")
     _, H, W = img.shape
     half = patch_size // 2
-    fr = torch.as_tensor(np.asarray(frames).astype(np.int64), device=img.device)
-    yy = torch.as_tensor(np.rint(np.asarray(ys, dtype=np.float64)).astype(np.int64), device=img.device)
-    xx = torch.as_tensor(np.rint(np.asarray(xs, dtype=np.float64)).astype(np.int64), device=img.device)
+    if _is_cuda(frames) and _is_cuda(ys) and _is_cuda(xs):       # positions already on the device (track_particles_tensors)
+        fr = frames.to(img.device, torch.int64)
+        yy, xx = torch.round(ys.double()).to(img.device, torch.int64), torch.round(xs.double()).to(img.device, torch.int64)
+    else:
+        fr = torch.as_tensor(np.asarray(frames).astype(np.int64), device=img.device)
+        yy = torch.as_tensor(np.rint(np.asarray(ys, dtype=np.float64)).astype(np.int64), device=img.device)
+        xx = torch.as_tensor(np.rint(np.asarray(xs, dtype=np.float64)).astype(np.int64), device=img.device)
     if not (len(fr) == len(yy) == len(xx)):
         raise ValueError("frames, ys and xs must have one entry per localisation")
     off = torch.arange(-half, half + 1, device=img.device)
@@ -453,6 +726,8 @@ def refine_localizations(patches, ys, xs):
     if torch.is_tensor(params):
         params, peak, status = params.cpu().numpy(), peak.cpu().numpy(), status.cpu().numpy()
     half = patches.shape[1] // 2
+    if _is_cuda(ys):
+        ys, xs = ys.cpu(), xs.cpu()
     ys, xs = np.asarray(ys), np.asarray(xs)
     okf = status == 0
     return {"x_refined": np.where(okf, xs - half + params[:, 1], xs.astype(np.float64)),

@@ -620,3 +620,61 @@ def refine_gaussian(patches: torch.Tensor, xtol: float = 1e-11):
     N.check(N.lib.mivit_refine_gaussian(_p(patches), n, P, float(xtol), _p(params), _p(peak), _p(status), _s(patches)),
             "mivit_refine_gaussian")
     return params, peak, status
+
+
+LINK_MAX_DETECTIONS = 1024
+
+
+def _link_args(count, cap, movie_start, name):
+    if count.dtype != torch.int32 or count.dim() != 1 or count.device.type != "cuda":
+        raise ValueError(f"{name}: count must be a 1-D int32 GPU tensor")
+    if not 1 <= cap <= LINK_MAX_DETECTIONS:
+        raise ValueError(f"{name}: capacity of {cap} detections per frame, the kernel's limit is {LINK_MAX_DETECTIONS} "
+                         f"(LINK_MAX_DETECTIONS); detect with max_peaks_per_frame <= {LINK_MAX_DETECTIONS}")
+    if movie_start is None:
+        return count.contiguous(), None
+    ms = torch.as_tensor(movie_start, device=count.device)
+    if ms.shape != count.shape:
+        raise ValueError(f"{name}: movie_start must have one entry per frame, got {tuple(ms.shape)} for {count.shape[0]} frames")
+    return count.contiguous(), (ms != 0).to(torch.uint8).contiguous()
+
+
+def link_frames(coords: torch.Tensor, count: torch.Tensor, max_distance: float = 15.0, movie_start=None) -> torch.Tensor:
+    """Exact linear assignment between the detections of every pair of consecutive frames (csrc/linking.hip,
+    mivit_link_frames): coords [F, cap, 2] int32 (y, x) and count [F] int32 on the GPU, as dog_peaks returns them; movie_start
+    [F] (optional): a true entry opens a new movie, whose first frame gets no links -> link [F, cap] int32, for every
+    detection of frame f the index of its partner in frame f - 1, or -1 (also beyond count[f]).  The full problem is solved,
+    then links longer than max_distance are dropped.  cap <= LINK_MAX_DETECTIONS."""
+    if coords.dtype != torch.int32 or coords.dim() != 3 or coords.shape[2] != 2 or coords.device.type != "cuda":
+        raise ValueError("link_frames: coords must be an int32 GPU tensor [F, cap, 2]")
+    F, cap = coords.shape[0], coords.shape[1]
+    if count.shape != (F,):
+        raise ValueError(f"link_frames: count must be [{F}], got {tuple(count.shape)}")
+    count, ms = _link_args(count, cap, movie_start, "link_frames")
+    if not float(max_distance) == float(max_distance):
+        raise ValueError("link_frames: max_distance is NaN")
+    coords = coords.contiguous()
+    link = torch.empty(F, cap, dtype=torch.int32, device=coords.device)
+    N.check(N.lib.mivit_link_frames(_p(coords), _p(count), _p(ms), F, cap, float(max_distance), _p(link), _s(coords)),
+            "mivit_link_frames")
+    return link
+
+
+def chain_tracks(link: torch.Tensor, count: torch.Tensor, movie_start=None):
+    """Track ids from the links (csrc/linking.hip, mivit_chain_tracks): link [F, cap] int32 (link_frames), count [F] int32 ->
+    (ids [F, cap] int32, -1 beyond count[f]; lengths [F * cap] int32, the number of positions of track i at index i, 0 beyond
+    the last track; n_tracks [1] int32).  Ids are handed out as the reference does: frame 0 (and every movie_start frame) one
+    per detection, later a linked detection inherits, an unlinked one takes the next id in ascending detection index."""
+    if link.dtype != torch.int32 or link.dim() != 2 or link.device.type != "cuda":
+        raise ValueError("chain_tracks: link must be an int32 GPU tensor [F, cap]")
+    F, cap = link.shape
+    if count.shape != (F,):
+        raise ValueError(f"chain_tracks: count must be [{F}], got {tuple(count.shape)}")
+    count, ms = _link_args(count, cap, movie_start, "chain_tracks")
+    link = link.contiguous()
+    ids = torch.full((F, cap), -1, dtype=torch.int32, device=link.device)
+    lengths = torch.zeros(F * cap, dtype=torch.int32, device=link.device)
+    n_tracks = torch.zeros(1, dtype=torch.int32, device=link.device)
+    N.check(N.lib.mivit_chain_tracks(_p(link), _p(count), _p(ms), F, cap, _p(ids), _p(lengths), _p(n_tracks), _s(link)),
+            "mivit_chain_tracks")
+    return ids, lengths, n_tracks

@@ -4,7 +4,12 @@ stream after a warm-up (minimum of the repetitions; track_particles_flat ends on
 clock around a synchronise); the numpy restatement; and a reference-style per-frame loop on the CPU (two
 scipy.ndimage.gaussian_filter calls and the peak_local_max statement per frame, one scipy.optimize.curve_fit per patch).
 Two shapes: the fixture's 30 x 128 x 128 movie with 12 particles, and 1 000 x 512 x 512 with about 50 particles per frame;
-on the large one the CPU paths run on the first --cpu-frames frames and the time is reported per frame.
+on the large one the CPU paths run on the first --cpu-frames frames and the time is reported per frame.  A third movie,
+1 000 x 512 x 512 with about 200 particles, is used for the linking rows only.
+Linking rows: the host loop (_link_tracks: scipy per frame), the numpy restatement of csrc/linking.hip
+(link_particles_movie on host arrays, on the first --cpu-frames frames), the device (ops.link_frames + ops.chain_tracks +
+the table, events), and the whole track_particles_flat with linking="host" and linking="device" (wall clock around a
+synchronise, minimum of 5).
 
     python scripts/bench_tracking.py [--small-only] [--cpu-frames N] [--json OUT]
 """
@@ -96,6 +101,29 @@ def reference_style_fit(patches):
             pass
 
 
+def bench_linking(mov_gpu, cpu_frames):
+    """Linking alone on the detections of a movie: host loop, restatement, device."""
+    res = {}
+    count, coords, _, _ = ops.dog_peaks(mov_gpu, W1, W2, 0.1, 3, 512, False)
+    res["detections_per_frame"] = float(count.float().mean())
+    res["gpu_link_frames_s"] = t_events(lambda: ops.link_frames(coords, count, 15.0))
+    link = ops.link_frames(coords, count, 15.0)
+    res["gpu_chain_tracks_s"] = t_events(lambda: ops.chain_tracks(link, count))
+
+    def device_linking():
+        lk = ops.link_frames(coords, count, 15.0)
+        ids, lengths, _ = ops.chain_tracks(lk, count)
+        T._detections_table(coords, count, ids, lengths, 3)
+    res["gpu_linking_s"] = t_events(device_linking)
+    n = count.cpu().numpy()
+    host = coords.cpu().numpy().astype(np.int64)
+    per_frame = [host[f, :n[f]] for f in range(len(n))]
+    res["host_loop_linking_s"] = t_wall(lambda: T._link_tracks(per_frame, 15, 3), reps=2)
+    m = min(len(n), cpu_frames)
+    res["restatement_linking_s_per_frame"] = t_wall(lambda: T.link_particles_movie(per_frame[:m], None, 15)) / max(m, 1)
+    return res
+
+
 def bench(name, mov_gpu, cpu_frames):
     F, H, W = mov_gpu.shape
     res = {"shape": [F, H, W]}
@@ -109,10 +137,13 @@ def bench(name, mov_gpu, cpu_frames):
     _, _, st = ops.refine_gaussian(patches)
     res["fits_not_converged"] = int((st != 0).sum())
 
-    def whole():
-        T.track_particles_flat(mov_gpu)
+    def whole(linking="host"):
+        T.track_particles_flat(mov_gpu, linking=linking)
         torch.cuda.synchronize()
-    res["gpu_track_particles_s"] = t_wall(quiet(whole), reps=2)
+    res["gpu_track_particles_s"] = t_wall(quiet(whole), reps=5)
+    quiet(lambda: whole("device"))()
+    res["gpu_track_particles_device_linking_s"] = t_wall(quiet(lambda: whole("device")), reps=5)
+    res.update(bench_linking(mov_gpu, cpu_frames))
     n = min(F, cpu_frames)
     res["cpu_frames"] = n
     mov = mov_gpu[:n].cpu().numpy()
@@ -138,6 +169,16 @@ def main():
     out = {"fixture": bench("fixture", torch.from_numpy(tc.movie("main")).cuda(), 30)}
     if not a.small_only:
         out["large"] = bench("large", gpu_movie(1000, 512, 512, 50), a.cpu_frames)
+        dense = gpu_movie(1000, 512, 512, 200, seed=1)
+        out["dense"] = {"shape": list(dense.shape), **bench_linking(dense, a.cpu_frames)}
+
+        def whole(linking):
+            T.track_particles_flat(dense, linking=linking)
+            torch.cuda.synchronize()
+        quiet(lambda: whole("device"))()
+        out["dense"]["gpu_track_particles_s"] = t_wall(quiet(lambda: whole("host")), reps=2)
+        out["dense"]["gpu_track_particles_device_linking_s"] = t_wall(quiet(lambda: whole("device")), reps=5)
+        print("dense", json.dumps(out["dense"]), flush=True)
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(out, fh, indent=1)
