@@ -263,6 +263,34 @@ int mivit_link_frames(const int *coords, const int *count, const unsigned char *
 int mivit_chain_tracks(const int *link, const int *count, const unsigned char *movie_start, int F, int cap, int *ids,
                        int *lengths, int *n_tracks, void *stream);
 
+/* Ragged mean square displacement and both classical estimates of the diffusion coefficient for every track of a linked
+ * movie in one launch (the reference's mean_square_displacement, helpers/helpersMSD.py:7-26, estimateDfromMSDs, :110-129, and
+ * estimateDfromMSDsWeighted, :131-157, per track), csrc/diffusion.hip, one workgroup per track, one thread per lag.
+ * pos [N, 2] fp64 sorted by track and by frame within a track; offsets [n_tracks + 1] int32 (CSR); a lag in rows is a lag in
+ * frames (tracks have no gaps).  Per track of L rows, M = L - 1, or min(L - 1, max_lag) with max_lag > 0:
+ *   msd[tau] = (sum_{i ascending} (dy * dy + dx * dx)) / (L - tau) for tau = 1 .. M, every other entry of the row 0;
+ *   d_lstsq = (sum_tau (tau dt) msd[tau]) / (sum_tau (tau dt)^2) / 4, the line through the origin;
+ *   d_weighted = (sum_tau (msd[tau] / tau) (M + 1 - tau)) / ((M + 1)(M + 2) / 2) / 4: the weight sum includes lag 0 and the lag
+ *   is counted in steps, as in the reference;
+ * all sums in ascending index in fp64 without contraction, so the result is independent of the launch geometry.  M < 1 gives a
+ * zero row and NaN for both estimates.  out: msd [n_tracks, Lmax] fp64 (every entry written; Lmax >= the longest track, lags
+ * beyond Lmax - 1 are not computed), d_lstsq / d_weighted [n_tracks] fp64.  Tracks of up to 4096 rows are staged in LDS.
+ * Arguments are validated before any HIP call; n_tracks = 0 is a no-op. */
+int mivit_track_msd(const double *pos, int N, const int *offsets, int n_tracks, double dt, int max_lag, int Lmax, double *msd,
+                    double *d_lstsq, double *d_weighted, void *stream);
+
+/* The model's input from the detections table in one launch: the reference's extract_particle_patches
+ * (helpers/helpersTracking.py:513-550) followed by normalize_images (helpers/helpersGeneration.py:356-400), cut into windows of
+ * T rows, csrc/diffusion.hip, one thread per output element.  movie [F, H, W] fp32; frame / y / x [N] int32 per table row
+ * (positions already rounded); seq_row [n_seq] int32, the row where each window starts; P odd, 3 .. 15.  out: seq
+ * [n_seq, T, P, P] fp32, patch t of window s centred on row seq_row[s] + t; pixels outside the frame read as 0 BEFORE the
+ * normalisation (v - lo) / denom (IEEE fp32 division; skipped with normalize = 0).  A row outside [0, N) or with a frame
+ * outside [0, F) gives a zero patch: nothing is read out of bounds whatever the index values are.  Arguments are validated
+ * before any HIP call; n_seq = 0 is a no-op. */
+int mivit_track_sequences(const float *movie, int F, int H, int W, const int *frame, const int *y, const int *x, int N,
+                          const int *seq_row, int n_seq, int T, int P, float lo, float denom, int normalize, float *seq,
+                          void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -795,3 +795,194 @@ def tracks_to_dataframe(tracks, patches, patch_size):
     df.sort_index(inplace=True)
     df = add_refined_localization_to_dataframe(df, tracks, patches, patch_size=patch_size)
     return compute_displacement(df)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# from the table to one diffusion coefficient per track
+# ----------------------------------------------------------------------------------------------------------------------
+def tracks_table_by_track(table):
+    """The dict track_particles_tensors returns -> (frame, y, x, track_id [N'] int64, offsets [n_tracks + 1] int64), tensors on
+    the table's device: the rows with in_long_track, stably sorted by track_id (the table is in frame order, so every track
+    stays in frame order), and the CSR offsets of the tracks in ascending id."""
+    keep = torch.as_tensor(table["in_long_track"]).bool()
+    cols = [torch.as_tensor(table[k]).to(keep.device)[keep] for k in ("frame", "y", "x", "track_id")]
+    if not (len(cols[0]) == len(cols[1]) == len(cols[2]) == len(cols[3])):
+        raise ValueError("frame, y, x and track_id must have one entry per row")
+    order = torch.argsort(cols[3], stable=True)
+    fr, y, x, tid = (c[order].long() for c in cols)
+    _, counts = torch.unique_consecutive(tid, return_counts=True)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=tid.device), torch.cumsum(counts, 0)])
+    return fr, y, x, tid, offsets
+
+
+def _check_sequence_args(seq_len, tail, patch_size=None):
+    if patch_size is not None and (int(patch_size) != patch_size or patch_size % 2 != 1 or not 3 <= patch_size <= 15):
+        raise ValueError(f"patch_size must be an odd number from 3 to 15, got {patch_size}")
+    if int(seq_len) != seq_len or seq_len < 1:
+        raise ValueError(f"seq_len must be an integer >= 1, got {seq_len}")
+    if tail not in ("drop", "overlap"):
+        raise ValueError(f"tail must be 'drop' or 'overlap', got {tail!r}")
+
+
+def _check_csr(offsets, n=None):
+    if len(offsets.shape) != 1 or offsets.shape[0] < 1:
+        raise ValueError(f"offsets must be [n_tracks + 1], got {tuple(offsets.shape)}")
+    first, last = int(offsets[0]), int(offsets[-1])
+    if first != 0 or (n is not None and last != n):
+        raise ValueError(f"offsets must start at 0 and end at the number of rows{'' if n is None else f' {n}'}, "
+                         f"got {first} .. {last}")
+    if offsets.shape[0] > 1 and bool((offsets[1:] < offsets[:-1]).any()):
+        raise ValueError("offsets must not decrease")
+
+
+def plan_sequences(offsets, seq_len, tail="drop"):
+    """Windows of seq_len consecutive rows per track: offsets [n_tracks + 1] (CSR, array or tensor) -> (seq_row [n_seq], the
+    table row where each window starts, seq_track [n_seq], the index of its track), int64, of the input's kind and device.
+    Per track of L rows L // seq_len windows side by side from the track's start; tail="drop" leaves the remaining rows out,
+    tail="overlap" adds one window aligned to the track's end when L % seq_len != 0 and L >= seq_len (it overlaps the one
+    before).  A track shorter than seq_len gives no window.  The windows of a track are contiguous in the output and in
+    ascending row, tracks in ascending order.  No loop over the tracks."""
+    _check_sequence_args(seq_len, tail)
+    is_t = torch.is_tensor(offsets)
+    off = offsets.long() if is_t else np.asarray(offsets).astype(np.int64)
+    _check_csr(off)
+    T = int(seq_len)
+    lengths = off[1:] - off[:-1]
+    n_full = lengths // T
+    n_win = n_full
+    if tail == "overlap":
+        extra = (lengths % T != 0) & (lengths >= T)
+        n_win = n_full + (extra.long() if is_t else extra.astype(np.int64))
+    first = (torch.cumsum(n_win, 0) if is_t else np.cumsum(n_win)) - n_win
+    if is_t:
+        seq_track = torch.repeat_interleave(torch.arange(len(lengths), device=off.device), n_win)
+        j = torch.arange(len(seq_track), device=off.device) - first[seq_track]
+        where = torch.where
+    else:
+        seq_track = np.repeat(np.arange(len(lengths), dtype=np.int64), n_win)
+        j = np.arange(len(seq_track), dtype=np.int64) - first[seq_track]
+        where = np.where
+    seq_row = off[:-1][seq_track] + where(j < n_full[seq_track], j * T, lengths[seq_track] - T)
+    return seq_row, seq_track
+
+
+def _rounded_int32(v, device):
+    """Positions rounded half-to-even as extract_patches_flat rounds them, as an int32 tensor on `device`."""
+    if torch.is_tensor(v):
+        v = v if not v.is_floating_point() else torch.round(v.double())
+        return v.to(device=device, dtype=torch.int32)
+    return torch.as_tensor(np.rint(np.asarray(v, dtype=np.float64)).astype(np.int32), device=device)
+
+
+def track_sequences(movie, frames, ys, xs, offsets, seq_len, patch_size=7, norm=None, tail="drop"):
+    """The normalised patch sequences a GeneralTransformer consumes, from the table sorted by track (tracks_table_by_track):
+    movie [F, H, W] float32, frames / ys / xs [N], offsets [n_tracks + 1] -> (seq [n_seq, seq_len, patch_size, patch_size]
+    float32, seq_track [n_seq], seq_row [n_seq]); the windows are plan_sequences(offsets, seq_len, tail).  The patch of step t
+    of window s is centred on the position of row seq_row[s] + t, rounded half-to-even; pixels outside the frame read as 0.
+    norm = (background_mean, background_sigma, theoretical_max) as helpers/generation.normalize_images takes them: every pixel
+    (the zeros outside the frame included) becomes (v - lo) / denom with lo = background_mean - background_sigma and
+    denom = theoretical_max - lo; norm=None returns the raw patches.  A row whose frame lies outside the movie gives a zero
+    patch.  A CUDA movie goes to the kernel (ops.track_sequences, one launch) and returns CUDA tensors; anything else goes to
+    extract_patches_flat and the same arithmetic in torch on the CPU, bitwise equal, and returns the movie's kind."""
+    _check_sequence_args(seq_len, tail, patch_size)
+    if len(movie.shape) != 3:
+        raise ValueError(f"movie must be [F, H, W], got {tuple(movie.shape)}")
+    if not (len(frames) == len(ys) == len(xs)):
+        raise ValueError("frames, ys and xs must have one entry per row")
+    _check_csr(offsets if torch.is_tensor(offsets) else np.asarray(offsets), len(frames))
+    lo, denom = 0.0, 1.0
+    if norm is not None:
+        background_mean, background_sigma, theoretical_max = (float(v) for v in norm)
+        lo = background_mean - background_sigma
+        denom = theoretical_max - lo
+        if denom == 0:
+            raise ValueError("Denominator in normalization is zero. Check your inputs.")
+    T, P = int(seq_len), int(patch_size)
+    if _is_cuda(movie):
+        from .. import ops
+        dev = movie.device
+        off = torch.as_tensor(offsets, device=dev)
+        seq_row, seq_track = plan_sequences(off, T, tail)
+        seq = ops.track_sequences(movie, torch.as_tensor(frames).to(dev, torch.int32), _rounded_int32(ys, dev),
+                                  _rounded_int32(xs, dev), seq_row.int(), T, P, lo, denom, norm is not None)
+        return seq, seq_track, seq_row
+    is_np = not torch.is_tensor(movie)
+    img = torch.as_tensor(np.asarray(movie)) if is_np else movie.detach()
+    if img.dtype != torch.float32:
+        raise TypeError(f"movie must be float32, got {img.dtype}")
+    host = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)      # noqa: E731
+    seq_row, seq_track = plan_sequences(host(offsets), T, tail)
+    rows = (seq_row[:, None] + np.arange(T, dtype=np.int64)[None, :]).reshape(-1)
+    fr = host(frames).astype(np.int64)[rows]
+    inside = (fr >= 0) & (fr < img.shape[0])
+    patches = extract_patches_flat(img, np.where(inside, fr, 0), host(ys)[rows], host(xs)[rows], P)
+    if norm is not None:
+        patches = (patches - lo) / denom
+    patches = torch.where(torch.from_numpy(inside)[:, None, None], patches, torch.zeros((), dtype=patches.dtype))
+    seq = patches.reshape(len(seq_row), T, P, P)
+    if is_np:
+        return seq.numpy(), seq_track, seq_row
+    return seq, torch.from_numpy(seq_track), torch.from_numpy(seq_row)
+
+
+def refine_localizations_tensors(patches, ys, xs):
+    """refine_localizations without the copy to the host: CUDA patches [N, P, P] (extract_patches_flat) around the integer
+    positions ys / xs [N] -> dict of CUDA tensors x_refined, y_refined, psf_size (float64), max_intensity (float32) and status
+    (int32), with the same fallback where the fit failed (status != 0): the integer position and psf_size 10."""
+    if not _is_cuda(patches):
+        raise ValueError("refine_localizations_tensors needs CUDA patches; use refine_localizations on the host")
+    params, peak, status = refine_gaussian_patches(patches)
+    half = patches.shape[1] // 2
+    ys, xs = torch.as_tensor(ys).to(patches.device), torch.as_tensor(xs).to(patches.device)
+    if not (len(ys) == len(xs) == len(params)):
+        raise ValueError("patches, ys and xs must have one entry per localisation")
+    okf = status == 0
+    return {"x_refined": torch.where(okf, xs - half + params[:, 1], xs.double()),
+            "y_refined": torch.where(okf, ys - half + params[:, 2], ys.double()),
+            "psf_size": torch.where(okf, params[:, 3], torch.full_like(params[:, 3], float(FALLBACK_PSF_SIZE))),
+            "max_intensity": peak, "status": status}
+
+
+def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
+                             batch_size=4096, **tracking_kwargs):
+    """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
+    it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
+    (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
+    the integer positions with refine=False --, track_sequences(..., seq_len, patch_size, norm, tail), model.eval() under
+    torch.no_grad() in chunks of batch_size sequences, and the mean of the model's first output column over the sequences of
+    each track (float64, in sequence order: deterministic).  -> dict of CUDA tensors track_id, length, n_sequences (int64
+    [n_tracks]), D_model (float64; NaN where n_sequences == 0), D_msd, D_msd_weighted (float64, in pixels^2 per unit of dt) and
+    msd [n_tracks, longest track].  D_model is the model's output in the units it was trained in: no scale factor is applied
+    here."""
+    if not _is_cuda(movie):
+        raise ValueError("estimate_track_diffusion needs a CUDA movie; move it to the GPU (movie.cuda())")
+    _check_sequence_args(seq_len, tail, patch_size)
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError(f"batch_size must be an integer >= 1, got {batch_size}")
+    from .. import ops
+    tracking_kwargs.setdefault("return_dog", False)
+    table, _ = track_particles_tensors(movie, **tracking_kwargs)
+    fr, y, x, tid, offsets = tracks_table_by_track(table)
+    lengths = offsets[1:] - offsets[:-1]
+    n_tracks = len(lengths)
+    movie = movie.float()
+    if refine:
+        fit = refine_localizations_tensors(extract_patches_flat(movie, fr, y, x, patch_size), y, x)
+        pos = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1)
+    else:
+        pos = torch.stack([y, x], dim=1).double()
+    msd, d_lstsq, d_weighted = ops.track_msd(pos, offsets.int(), float(dt), 0)
+    seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
+    n_sequences = torch.bincount(seq_track, minlength=n_tracks)
+    model.eval()
+    outs = []
+    with torch.no_grad():
+        for b0 in range(0, len(seq), int(batch_size)):
+            out = model(seq[b0:b0 + int(batch_size)])
+            outs.append(out.reshape(len(out), -1)[:, 0].double())
+    per_seq = torch.cat(outs) if outs else torch.zeros(0, dtype=torch.float64, device=movie.device)
+    d_model = torch.full((n_tracks,), float("nan"), dtype=torch.float64, device=movie.device)
+    if len(per_seq):
+        d_model = torch.where(n_sequences > 0, torch.segment_reduce(per_seq, "mean", lengths=n_sequences), d_model)
+    return {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
+            "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}

@@ -678,3 +678,70 @@ def chain_tracks(link: torch.Tensor, count: torch.Tensor, movie_start=None):
     N.check(N.lib.mivit_chain_tracks(_p(link), _p(count), _p(ms), F, cap, _p(ids), _p(lengths), _p(n_tracks), _s(link)),
             "mivit_chain_tracks")
     return ids, lengths, n_tracks
+
+
+MSD_LDS_ROWS = 4096          # csrc/diffusion.hip: tracks of up to this many rows are staged in LDS
+
+
+def _dev_tensor(t, dtype, ndim, name, what):
+    if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype or t.dim() != ndim:
+        raise ValueError(f"{name}: {what} must be a {ndim}-D {str(dtype).replace('torch.', '')} GPU tensor")
+    return t.contiguous()
+
+
+def track_msd(pos: torch.Tensor, offsets: torch.Tensor, dt: float = 1.0, max_lag: int = 0, Lmax: int = None):
+    """Mean square displacement and both classical estimates of D for every track (csrc/diffusion.hip, mivit_track_msd): pos
+    [N, 2] float64 on the GPU, sorted by track and by frame within a track; offsets [n_tracks + 1] int32 (CSR, from 0 to N);
+    max_lag 0 means all lags; Lmax the width of the rows (default: the longest track, which costs one copy of a number to the
+    host) -> (msd [n_tracks, Lmax] float64, d_lstsq [n_tracks], d_weighted [n_tracks]).  See helpers/msd.track_msd for the
+    arithmetic; a track with fewer than two rows gets a zero row and NaN."""
+    pos = _dev_tensor(pos, torch.float64, 2, "track_msd", "pos [N, 2]")
+    offsets = _dev_tensor(offsets, torch.int32, 1, "track_msd", "offsets [n_tracks + 1]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"track_msd: pos must be [N, 2], got {tuple(pos.shape)}")
+    if offsets.numel() < 1:
+        raise ValueError("track_msd: offsets must have n_tracks + 1 entries")
+    if int(max_lag) != max_lag or max_lag < 0:
+        raise ValueError(f"track_msd: max_lag must be an integer >= 0 (0: all lags), got {max_lag}")
+    n, n_tracks = pos.shape[0], offsets.numel() - 1
+    if Lmax is None:
+        Lmax = int((offsets[1:] - offsets[:-1]).max()) if n_tracks else 0
+    if int(Lmax) != Lmax or Lmax < 0:
+        raise ValueError(f"track_msd: Lmax must be an integer >= 0, got {Lmax}")
+    msd = torch.empty(n_tracks, int(Lmax), dtype=torch.float64, device=pos.device)
+    d_lstsq = torch.empty(n_tracks, dtype=torch.float64, device=pos.device)
+    d_weighted = torch.empty(n_tracks, dtype=torch.float64, device=pos.device)
+    N.check(N.lib.mivit_track_msd(_p(pos), n, _p(offsets), n_tracks, float(dt), int(max_lag), int(Lmax), _p(msd), _p(d_lstsq),
+                                  _p(d_weighted), _s(pos)), "mivit_track_msd")
+    return msd, d_lstsq, d_weighted
+
+
+def track_sequences(movie: torch.Tensor, frame: torch.Tensor, y: torch.Tensor, x: torch.Tensor, seq_row: torch.Tensor,
+                    seq_len: int, patch_size: int = 7, lo: float = 0.0, denom: float = 1.0, normalize: bool = False):
+    """The model's input from the table sorted by track (csrc/diffusion.hip, mivit_track_sequences): movie [F, H, W] float32 on
+    the GPU; frame / y / x [N] int32 (rounded positions); seq_row [n_seq] int32, the table row where each window of seq_len
+    rows starts -> [n_seq, seq_len, patch_size, patch_size] float32.  Pixels outside the frame read as 0, then (with
+    normalize) every pixel becomes (v - lo) / denom in float32; a row whose frame is outside the movie gives a zero patch."""
+    movie = _frames_f32(movie, "track_sequences")
+    if movie.dim() != 3:
+        raise ValueError(f"track_sequences: movie must be [F, H, W], got {tuple(movie.shape)}")
+    frame = _dev_tensor(frame, torch.int32, 1, "track_sequences", "frame [N]")
+    y = _dev_tensor(y, torch.int32, 1, "track_sequences", "y [N]")
+    x = _dev_tensor(x, torch.int32, 1, "track_sequences", "x [N]")
+    seq_row = _dev_tensor(seq_row, torch.int32, 1, "track_sequences", "seq_row [n_seq]")
+    if not (frame.numel() == y.numel() == x.numel()):
+        raise ValueError("track_sequences: frame, y and x must have one entry per row")
+    T, P = int(seq_len), int(patch_size)
+    if T != seq_len or T < 1:
+        raise ValueError(f"track_sequences: seq_len must be an integer >= 1, got {seq_len}")
+    if P != patch_size or P % 2 != 1 or not 3 <= P <= 15:
+        raise ValueError(f"track_sequences: patch_size must be odd and from 3 to 15, got {patch_size}")
+    if normalize and not (float(denom) != 0.0 and float(denom) == float(denom) and float(lo) == float(lo)):
+        raise ValueError(f"track_sequences: cannot normalise with lo = {lo}, denom = {denom}")
+    F, H, W = movie.shape
+    n_seq = seq_row.numel()
+    seq = torch.empty(n_seq, T, P, P, dtype=torch.float32, device=movie.device)
+    N.check(N.lib.mivit_track_sequences(_p(movie), F, H, W, _p(frame), _p(y), _p(x), frame.numel(), _p(seq_row), n_seq, T, P,
+                                        float(lo), float(denom), 1 if normalize else 0, _p(seq), _s(movie)),
+            "mivit_track_sequences")
+    return seq

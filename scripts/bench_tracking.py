@@ -10,6 +10,10 @@ Linking rows: the host loop (_link_tracks: scipy per frame), the numpy restateme
 (link_particles_movie on host arrays, on the first --cpu-frames frames), the device (ops.link_frames + ops.chain_tracks +
 the table, events), and the whole track_particles_flat with linking="host" and linking="device" (wall clock around a
 synchronise, minimum of 5).
+Diffusion rows (both movie sizes): the stage from the detections table to the model's input and the MSD estimates on the device
+(tracks_table_by_track + refine_localizations_tensors + ops.track_msd + track_sequences; csrc/diffusion.hip) against the
+host-shaped way of doing the same (extract_patches_flat + normalize_images, refine_localizations on the host, a Python loop of
+helpers/msd calls per track), events, minimum of 5, and the two kernels alone.
 
     python scripts/bench_tracking.py [--small-only] [--cpu-frames N] [--json OUT]
 """
@@ -124,6 +128,63 @@ def bench_linking(mov_gpu, cpu_frames):
     return res
 
 
+NORM = (20.0, 4.5, 260.0)       # background mean, background sigma, theoretical maximum of the synthetic movies
+SEQ_LEN = 5
+
+
+def bench_diffusion(mov_gpu):
+    """The stage after the front end, from the detections table on the device to the model's input and the MSD estimates:
+    tracks_table_by_track + the fit (refine_localizations_tensors) + ops.track_msd + track_sequences, against what the same
+    took before csrc/diffusion.hip: extract_patches_flat + normalize_images, refine_localizations on the host and a Python
+    loop of helpers/msd calls per track.  Events around each, minimum of 5; the second ends on the host."""
+    from moleculardiffusion_mivit_amd.helpers import msd as MSD
+    from moleculardiffusion_mivit_amd.helpers.generation import normalize_images
+    res = {}
+    table, _ = T.track_particles_tensors(mov_gpu, return_dog=False)
+    fr, y, x, tid, off = T.tracks_table_by_track(table)
+    off32 = off.int()
+    fit = T.refine_localizations_tensors(T.extract_patches_flat(mov_gpu, fr, y, x, PATCH), y, x)
+    pos = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1)
+    lengths = (off[1:] - off[:-1]).cpu().numpy()
+    res["diffusion_tracks"], res["diffusion_rows"] = int(len(lengths)), int(len(fr))
+    res["diffusion_longest_track"] = int(lengths.max()) if len(lengths) else 0
+    res["gpu_track_msd_s"] = t_events(lambda: ops.track_msd(pos, off32, 1.0, 0, res["diffusion_longest_track"]))
+    res["gpu_track_sequences_s"] = t_events(lambda: T.track_sequences(mov_gpu, fr, y, x, off, SEQ_LEN, PATCH, NORM))
+    res["diffusion_sequences"] = int(len(T.plan_sequences(off, SEQ_LEN)[0]))
+
+    def device_stage():
+        f, yy, xx, _, o = T.tracks_table_by_track(table)
+        ft = T.refine_localizations_tensors(T.extract_patches_flat(mov_gpu, f, yy, xx, PATCH), yy, xx)
+        ops.track_msd(torch.stack([ft["y_refined"], ft["x_refined"]], dim=1), o.int(), 1.0, 0)
+        T.track_sequences(mov_gpu, f, yy, xx, o, SEQ_LEN, PATCH, NORM)
+
+    def host_shaped_stage():
+        keep = table["in_long_track"]
+        cols = [table[k][keep] for k in ("frame", "y", "x", "track_id")]
+        order = torch.argsort(cols[3], stable=True)
+        f, yy, xx, ids = (c[order] for c in cols)
+        patches = T.extract_patches_flat(mov_gpu, f, yy, xx, PATCH)
+        normed, _ = normalize_images(patches, *NORM)
+        ft = T.refine_localizations(patches, yy, xx)
+        p = np.stack([ft["y_refined"], ft["x_refined"]], axis=1)
+        ids = ids.cpu().numpy()
+        cuts = np.flatnonzero(np.diff(ids)) + 1
+        seqs = []
+        for a, b in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [len(ids)]])):
+            msd = MSD.mean_square_displacements(p[None, a:b])
+            t = np.arange(b - a) * 1.0
+            MSD.estimateDfromMSDs(msd, t)
+            MSD.estimateDfromMSDsWeighted(msd, t)
+            n = (b - a) // SEQ_LEN
+            seqs.append(normed[a:a + n * SEQ_LEN].reshape(n, SEQ_LEN, PATCH, PATCH))
+        if seqs:
+            torch.cat(seqs)
+
+    res["gpu_diffusion_stage_s"] = t_events(device_stage)
+    res["host_shaped_diffusion_stage_s"] = t_events(host_shaped_stage)
+    return res
+
+
 def bench(name, mov_gpu, cpu_frames):
     F, H, W = mov_gpu.shape
     res = {"shape": [F, H, W]}
@@ -144,6 +205,7 @@ def bench(name, mov_gpu, cpu_frames):
     quiet(lambda: whole("device"))()
     res["gpu_track_particles_device_linking_s"] = t_wall(quiet(lambda: whole("device")), reps=5)
     res.update(bench_linking(mov_gpu, cpu_frames))
+    res.update(bench_diffusion(mov_gpu))
     n = min(F, cpu_frames)
     res["cpu_frames"] = n
     mov = mov_gpu[:n].cpu().numpy()
