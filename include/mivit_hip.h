@@ -471,8 +471,13 @@ int mivit_wgrad_small(const void *dy, int64_t lddy, const void *x, int64_t ldx, 
 /* Row LayerNorm over E, eps 1e-5, biased variance, affine (nn.LayerNorm: models.py:88-89,134,301).
  * Row r of the output goes to row  (r / rows_per_seq) * out_seq_stride + r % rows_per_seq + out_row_off  when
  * rows_per_seq > 0 (token assembly behind the regression token, models.py:347), else to row r.
- * `pos` (optional, fp32 [>=out rows per sequence, E]) is added after the affine (models.py:137-138).
- * mean/rstd (fp32 [M]) are saved for backward. */
+ * `pos` (optional, fp32 [out_seq_stride, E]) is added after the affine (models.py:137-138).  It is indexed by the position
+ * in the OUTPUT sequence, offset included: row r gets pos[(output row) % out_seq_stride], so with out_row_off = 1 the first
+ * token of a sequence gets pos[1] and pos[0] (the regression token's) is never read.  With rows_per_seq == 0 there is no
+ * sequence structure and every row gets pos[0].
+ * mean/rstd (fp32 [M], optional) are saved for backward, indexed by the input row r (never mapped).
+ * ldz/ldy in elements; the 16-byte vector kernels run when E, ldz and ldy are multiples of 16 / sizeof(T), z and y are
+ * 16-byte aligned and E <= 1024 -- any other layout takes the scalar kernels, same results up to fp32 summation order. */
 int mivit_layernorm_fwd(int dtype, const void *z, int64_t ldz, const float *gamma, const float *beta,
                         int M, int E, void *y, int64_t ldy, int rows_per_seq, int out_seq_stride, int out_row_off,
                         const float *pos, float *mean, float *rstd, void *stream);
