@@ -179,6 +179,27 @@ int mivit_mlp_block_bwd(const void *dy, const void *n2, const float *rstd2, cons
 int mivit_render_frames(const float *traj_px, int N, int T, int npos, const float *sigmas, int nsig, int P, int up,
                         const float *amp, int center, float *out, void *stream);
 
+/* Noise-free rendering of a whole field of view with many particles (csrc/movie.hip): one spot of the reference's image model
+ * (helpers/helpersGeneration.py:283-310: Gaussian on the `up` times finer grid, rescaled to its peak there, mean-pooled),
+ * extended by linearity to Np particles in one movie.  pos [Np, F * npos, 2] fp32 positions (y, x) = (row, column) in camera
+ * pixels with pixel centres at integers -- the convention of the tracking tables, no flip and no unit conversion --, npos
+ * sub-positions per frame; amp [Np, F, npos] the intensity of every sub-position; first / last [Np] int32, or both NULL:
+ * particle p is rendered in the frames first[p] .. last[p] inclusive (any values; an empty or outside range renders nothing).
+ * With u = c up + (up - 1) / 2, g* = rint(u) and dpk = g* - u, the pooled peak-normalised profile of a position c is
+ *   prof(i; c) = (1 / up) sum_{k < up} exp(-(((i up + k) - u)^2 - dpk^2) / (2 sigma_hr^2)),
+ * and a sub-position adds amp prof(y; c_y) prof(x; c_x) to the pixels with |y - rint(c_y)| <= radius and
+ * |x - rint(c_x)| <= radius, nothing elsewhere.  For odd P up this is mivit_render_frames (center = 0) on a P x P field with
+ * c = c_ref + (P - 1) / 2, except at the border: the peak is taken on the UNBOUNDED fine grid, so a particle that leaves the
+ * field fades out, where the reference (and mivit_render_frames) rescales it to full intensity on the border pixel.
+ * movie [F, H, W] fp32: every element is written exactly once (0 where no window reaches), each pixel summed by one thread,
+ * particles ascending and sub-positions ascending within a particle, without atomics: bitwise repeatable.  A sub-position
+ * whose position or amplitude is not finite, or whose |coordinate| >= 2^30, contributes nothing.  Limits: 0 <= radius <= 64,
+ * 1 <= npos <= 256, 1 <= up <= 64, H, W <= 2^24, sigma_hr > 0 with finite 1 / (2 sigma_hr^2), F * ceil(H / 32) * ceil(W / 64)
+ * < 2^31.  Arguments are validated before any HIP call; Np = 0 gives a zero movie.  No index value is read from memory, so no
+ * input value can make the kernel read or write out of bounds. */
+int mivit_render_movie(const float *pos, const float *amp, const int *first, const int *last, int Np, int F, int npos,
+                       float sigma_hr, int up, int radius, int H, int W, float *movie, void *stream);
+
 /* The 25 hand-crafted trajectory descriptors of the ImagesFeatures experiment (reference helpers/helpersFeatures.py:448-519
  * compute_diffusion_features and :524-567 compute_features_for_multiple_trajectories, whose frame averaging :555-558 is fused
  * in; Experiments/ImagesFeatures/trainModelsImagesFeatures.py:36-41 calls it per cycle), csrc/features.hip + csrc/trajfeat.h,

@@ -123,6 +123,8 @@ SYMBOLS = {
     "mivit_mlp_block_bwd_set_waves": (c_int, [c_int]),
     "mivit_mlp_block_bwd": (c_int, [c_void_p] * 10 + [c_int, c_int] + [c_void_p] * 8 + [c_size_t, c_void_p]),
     "mivit_render_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "mivit_render_movie": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_void_p]),
     "mivit_trajectory_features_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mivit_trajectory_features": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),

@@ -20,6 +20,10 @@ on the host or directly on the GPU (no andi_datasets / skimage dependency):
   regularisation (``richardson_lucy_tv*``, ``apply_rl_tv_tensor*``, ``tv_gradient``, ``create_gaussian_psf``) and
   ``trajs_to_vid_norm_rl``.  GPU tensors go to csrc/deconv.hip; numpy / CPU input to a numpy restatement vectorised over
   frames that sums in the kernel's order (bitwise the kernel's result; within FFT rounding of the reference's).
+* whole fields of view with known truth (no counterpart in the reference, whose real movies carry none): ``render_movie``
+  (the same image model for many particles in one [F, H, W] movie; GPU tensors go to csrc/movie.hip, anything else to a
+  float64 restatement) and ``simulate_movie`` (Brownian particles, lifetimes, background, Poisson gain, and the truth table
+  ``helpers/tracking.score_tracking`` scores a detections table against).
 
 The reference draws from the unseeded global numpy RNG, so agreement is distributional; the deterministic part
 (noise-free rendering) is pinned against a naive per-pixel loop in ``tests/test_generation.py``.
@@ -416,3 +420,221 @@ def trajs_to_vid_norm_rl(trajectories, nPosPerFrame, center, image_props, rl_ite
     rl = apply_rl_tv_tensor_iter_list(videos[:, poisson_index], psf, rl_iterations)
     out = torch.cat([videos, torch.as_tensor(rl).to(videos.device)], dim=1)
     return out if out.device.type == "cuda" else out.numpy()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Whole fields of view: many particles in one [F, H, W] movie, with the truth table (csrc/movie.hip)
+# ------------------------------------------------------------------------------------------------------------------------
+MOVIE_MAX_RADIUS = 64        # limits of csrc/movie.hip (ops.MOVIE_MAX_RADIUS, ops.MOVIE_MAX_NPOS, ops.MOVIE_MAX_UP)
+MOVIE_MAX_NPOS = 256
+MOVIE_MAX_UP = 64
+_MOVIE_MAX_COORD = 2.0 ** 30
+
+
+def default_movie_radius(sigma_hr: float, upsampling_factor: int) -> int:
+    """ceil(5 sigma_hr / up) + 1 camera pixels: beyond it a spot is below exp(-12.5) = 4e-6 of its peak."""
+    return int(math.ceil(5.0 * float(sigma_hr) / int(upsampling_factor))) + 1
+
+
+def _check_movie_args(pos_shape, amp_shape, sigma_hr, H, W, up, radius, first, last):
+    if len(amp_shape) != 3:
+        raise ValueError(f"amp must be [Np, F, nPosPerFrame], got {tuple(amp_shape)}")
+    Np, F_, npos = (int(v) for v in amp_shape)
+    if len(pos_shape) != 3 or pos_shape[2] != 2 or pos_shape[0] != Np:
+        raise ValueError(f"pos_yx must be [{Np}, T, 2], got {tuple(pos_shape)}")
+    if npos < 1 or pos_shape[1] % npos != 0:
+        raise ValueError("T is not divisble by posPerFrame")
+    if pos_shape[1] // npos != F_ or F_ < 1:
+        raise ValueError(f"pos_yx holds {pos_shape[1] // npos} frames of {npos} sub-positions, amp {F_}; at least one is needed")
+    if npos > MOVIE_MAX_NPOS:
+        raise ValueError(f"nPosPerFrame = {npos}, the limit is {MOVIE_MAX_NPOS} (MOVIE_MAX_NPOS)")
+    if int(up) != up or not 1 <= up <= MOVIE_MAX_UP:
+        raise ValueError(f"upsampling_factor must be an integer from 1 to {MOVIE_MAX_UP}, got {up}")
+    if int(H) != H or int(W) != W or not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+        raise ValueError(f"H and W must be integers from 1 to 2^24, got {H}, {W}")
+    s = float(sigma_hr)
+    if not (s > 0 and math.isfinite(s) and 0 < np.float32(1) / (np.float32(2) * np.float32(s) * np.float32(s)) < np.inf):
+        raise ValueError(f"sigma_hr = {sigma_hr} is not a usable width")
+    if radius is None:
+        radius = default_movie_radius(s, up)
+    if isinstance(radius, bool) or int(radius) != radius or not 0 <= radius <= MOVIE_MAX_RADIUS:
+        raise ValueError(f"radius must be an integer from 0 to {MOVIE_MAX_RADIUS} (MOVIE_MAX_RADIUS), got {radius}")
+    if (first is None) != (last is None):
+        raise ValueError("first and last must both be given or both be None")
+    if first is not None:
+        fi, la = torch.as_tensor(first), torch.as_tensor(last)
+        if fi.shape != (Np,) or la.shape != (Np,) or fi.is_floating_point() or la.is_floating_point():
+            raise ValueError(f"first and last must be integer [{Np}]")
+        if bool((fi > la).any()):
+            raise ValueError("first > last")
+    return Np, F_, npos, int(up), int(radius)
+
+
+def _movie_profile(idx, c, up, sigma_hr):
+    """prof(i; c) of csrc/movie.hip in float64 for camera pixels idx [..., n] and positions c [..., 1]."""
+    u = c * up + (up - 1) / 2.0
+    dpk = torch.round(u) - u                                   # round-half-to-even = rint
+    g = idx.unsqueeze(-1) * up + torch.arange(up, dtype=torch.float64, device=c.device)      # [..., n, up]
+    d = g - u.unsqueeze(-1)
+    return torch.exp(-(d * d - (dpk * dpk).unsqueeze(-1)) / (2.0 * sigma_hr * sigma_hr)).mean(dim=-1)
+
+
+def render_movie(pos_yx, amp, sigma_hr: float, H: int, W: int, upsampling_factor: int, radius: Optional[int] = None,
+                 first=None, last=None) -> torch.Tensor:
+    """Noise-free movie [F, H, W] of Np particles in one field of view.  pos_yx [Np, F * p, 2]: positions (y, x) = (row,
+    column) in camera pixels, pixel centres at integers (the convention of the tracking tables; no flip, no unit conversion),
+    p sub-positions per frame; amp [Np, F, p]: the intensity of every sub-position; first / last [Np] integers (optional):
+    particle n is rendered in the frames first[n] .. last[n] inclusive.
+
+    The image model is one spot of the reference (helpersGeneration.py:283-310) -- a Gaussian of sigma_hr on the
+    upsampling_factor-times finer grid, rescaled to its PEAK on that grid, mean-pooled -- summed over sub-positions and
+    particles: fine sample g = i up + k of pixel i sits at g, a position c at u = c up + (up - 1) / 2, g* = rint(u),
+    dpk = g* - u, prof(i; c) = mean_k exp(-((g - u)^2 - dpk^2) / (2 sigma_hr^2)), and a sub-position adds
+    amp prof(y; c_y) prof(x; c_x) to the pixels with |y - rint(c_y)| <= radius and |x - rint(c_x)| <= radius, nothing
+    elsewhere (default radius ceil(5 sigma_hr / up) + 1; at most MOVIE_MAX_RADIUS).  For odd P up this is
+    render_frames(center=False) on a P x P field with c = c_ref + (P - 1) / 2 and x / y swapped, except that the peak is taken
+    on the unbounded grid: a particle that leaves the field fades out instead of being rescaled onto the border.  A
+    sub-position whose position or amplitude is not finite (or |coordinate| >= 2^30) contributes nothing.
+
+    CUDA tensors go to the kernel (csrc/movie.hip, mivit_render_movie; float32 in and out).  Anything else (CPU tensors, numpy)
+    goes to a vectorised float64 restatement of the same definition, truncation included, and returns a float64 CPU tensor:
+    the kernel's yardstick."""
+    is_cuda = torch.is_tensor(pos_yx) and pos_yx.device.type == "cuda"
+    pos = pos_yx if torch.is_tensor(pos_yx) else torch.as_tensor(np.asarray(pos_yx))
+    am = amp if torch.is_tensor(amp) else torch.as_tensor(np.asarray(amp))
+    Np, F_, npos, up, radius = _check_movie_args(pos.shape, am.shape, sigma_hr, H, W, upsampling_factor, radius, first, last)
+    H, W = int(H), int(W)
+    if is_cuda:
+        from .. import ops
+        dev = pos.device
+        fi = la = None
+        if first is not None:
+            fi = torch.as_tensor(first).to(dev, torch.int32).contiguous()
+            la = torch.as_tensor(last).to(dev, torch.int32).contiguous()
+        return ops.render_movie(pos.float().contiguous(), am.to(dev).float().contiguous(), float(sigma_hr), up, radius, H, W,
+                                fi, la)
+    pos = pos.detach().to("cpu", torch.float64).reshape(Np, F_, npos, 2)
+    am = am.detach().to("cpu", torch.float64)
+    sigma = float(sigma_hr)
+    ok = torch.isfinite(pos).all(dim=-1) & (pos.abs() < _MOVIE_MAX_COORD).all(dim=-1) & torch.isfinite(am)
+    if first is not None:
+        fr = torch.arange(F_).view(1, F_, 1)
+        ok &= (torch.as_tensor(first).long().view(Np, 1, 1) <= fr) & (fr <= torch.as_tensor(last).long().view(Np, 1, 1))
+    movie = torch.zeros(F_ * H * W, dtype=torch.float64)
+    off = torch.arange(-radius, radius + 1, dtype=torch.float64)
+    frame_base = (torch.arange(F_) * (H * W)).view(F_, 1, 1, 1)
+    for n in range(Np):                                       # particles ascending; one scatter-add per particle
+        c = torch.where(ok[n].unsqueeze(-1), pos[n], torch.zeros((), dtype=torch.float64))      # [F, p, 2]
+        centre = torch.round(c)
+        rows, cols = centre[..., 0:1] + off, centre[..., 1:2] + off                              # [F, p, 2 r + 1]
+        py = _movie_profile(rows, c[..., 0:1], up, sigma) * torch.where(ok[n], am[n], torch.zeros((), dtype=torch.float64)).unsqueeze(-1)
+        px = _movie_profile(cols, c[..., 1:2], up, sigma)
+        inside = ((rows >= 0) & (rows < H)).unsqueeze(-1) & ((cols >= 0) & (cols < W)).unsqueeze(-2) & ok[n].view(F_, npos, 1, 1)
+        val = py.unsqueeze(-1) * px.unsqueeze(-2)                                               # [F, p, 2 r + 1, 2 r + 1]
+        idx = frame_base + rows.long().clamp(0, H - 1).unsqueeze(-1) * W + cols.long().clamp(0, W - 1).unsqueeze(-2)
+        movie.index_add_(0, idx[inside], val[inside])
+    return movie.view(F_, H, W)
+
+
+def _draw_diffusion_coefficients(n, Ds, generator, gdev):
+    """Per-particle D: a tensor / array of n values as given, a number for all, or a (mean, var) pair drawn as
+    brownian_single_state draws it (N(mean, var), redrawn until positive)."""
+    if torch.is_tensor(Ds) or isinstance(Ds, np.ndarray):
+        D = torch.as_tensor(Ds).detach().to("cpu", torch.float64).reshape(-1)
+        if D.numel() != n:
+            raise ValueError(f"Ds must hold one coefficient per particle ({n}), got {D.numel()}")
+    elif isinstance(Ds, (int, float)):
+        D = torch.full((n,), float(Ds), dtype=torch.float64)
+    elif len(Ds) == 2:
+        mean, var = float(Ds[0]), float(Ds[1])
+        D = torch.full((n,), mean, device=gdev)
+        if var > 0:
+            D = mean + math.sqrt(var) * torch.randn(n, generator=generator, device=gdev)
+            for _ in range(64):
+                bad = D <= 1e-4
+                if not bool(bad.any()):
+                    break
+                D = torch.where(bad, mean + math.sqrt(var) * torch.randn(n, generator=generator, device=gdev), D)
+            D = D.clamp_min(1e-4)
+        D = D.to("cpu", torch.float64)
+    else:
+        raise ValueError("Ds must be a (mean, var) pair, a number, or a tensor / array with one coefficient per particle")
+    if not bool(torch.isfinite(D).all()) or bool((D < 0).any()):
+        raise ValueError("diffusion coefficients must be finite and >= 0")
+    return D
+
+
+def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
+                   margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu"):
+    """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
+
+    n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
+    (default margin: the rendering radius, so every spot starts inside), nPosPerFrame sub-positions per frame with steps
+    N(0, 2 D / nPosPerFrame) per axis, D per particle in pixels^2 per frame (Ds: see _draw_diffusion_coefficients).  lifetimes
+    [Np, 2] integers (first, last): the frames 0 <= first <= last < n_frames in which a particle is visible (default: all).
+    Image: render_movie with the PSF of image_props (psf_sigma_hr, upsampling_factor), then, in the order and with the helpers
+    of trajectories_to_video, amplitudes particle_intensity / nPosPerFrame per sub-position (zero unless mean and std exceed
+    1e-4, as there), + clipped_background, * Poisson(poisson_noise) / poisson_noise; poisson_noise = -1 and a zero background
+    std give a noise-free movie.  output_size, resolution's unit conversion and the y flip of trajectories_to_video do not
+    apply: positions are pixel indices (y, x).  A generator must live on `device`; the same seed gives the same movie on the
+    same device.
+
+    truth: dict of tensors on `device`: frame (int64), y, x (float64: the mean of the frame's sub-positions), particle_id
+    (int64), one row per visible particle-frame sorted by particle and then by frame; offsets [Np + 1] int64, CSR over those
+    rows (the layout of tracking.tracks_table_by_track: msd.track_msd(stack([y, x], 1), offsets) runs on it as it is); D [Np]
+    float64; pos [Np, F * nPosPerFrame, 2] float32 and amp [Np, F, nPosPerFrame] float32, what was rendered; first, last [Np]
+    int64."""
+    props = dict(DEFAULT_IMAGE_PROPS)
+    props.update(image_props or {})
+    Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
+    if Np < 0 or F_ < 1 or npos < 1:
+        raise ValueError(f"need n_particles >= 0, n_frames >= 1, nPosPerFrame >= 1, got {n_particles}, {n_frames}, {nPosPerFrame}")
+    dev = torch.device(device)
+    up, sigma = props["upsampling_factor"], psf_sigma_hr(props)
+    radius = default_movie_radius(sigma, up)
+    margin = float(radius) if margin is None else float(margin)
+    if not (margin >= 0 and 2 * margin <= min(H, W) - 1):
+        raise ValueError(f"margin = {margin} leaves no room in a field of {H} x {W}")
+    if lifetimes is None:
+        first = torch.zeros(Np, dtype=torch.int64)
+        last = torch.full((Np,), F_ - 1, dtype=torch.int64)
+    else:
+        lt = torch.as_tensor(lifetimes).detach().cpu()
+        if lt.is_floating_point() or tuple(lt.shape) != (Np, 2):
+            raise ValueError(f"lifetimes must be integer [{Np}, 2] (first, last), got {tuple(lt.shape)}")
+        first, last = lt[:, 0].long(), lt[:, 1].long()
+        if bool((first > last).any()):
+            raise ValueError("first > last")
+        if bool((first < 0).any()) or bool((last >= F_).any()):
+            raise ValueError(f"lifetimes must lie in 0 .. {F_ - 1}")
+    gdev = generator.device if generator is not None else dev
+    if gdev != dev and not (gdev.type == dev.type and dev.index is None):
+        raise ValueError(f"the generator lives on {gdev}, the movie on {dev}")
+    D = _draw_diffusion_coefficients(Np, Ds, generator, gdev)
+    T = F_ * npos
+    span = torch.tensor([H - 1 - 2 * margin, W - 1 - 2 * margin], device=gdev)
+    start = margin + torch.rand(Np, 2, generator=generator, device=gdev) * span
+    steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
+    if T:
+        steps[:, 0] = 0.0
+    pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
+    pm, ps = props["particle_intensity"]
+    bm, bs = props["background_intensity"]
+    if pm > 1e-4 and ps > 1e-4:
+        amp = pm / npos + (ps / npos) * torch.randn(Np, F_, npos, generator=generator, device=gdev)
+    else:
+        amp = torch.zeros(Np, F_, npos, device=gdev)
+    amp = amp.float().to(dev)
+    vid = render_movie(pos, amp, sigma, H, W, up, radius, first, last).to(dev)
+    vid = vid + clipped_background(vid.shape, bm, bs, generator, dev)
+    pn = props["poisson_noise"]
+    if pn != -1:
+        vid = vid * torch.poisson(torch.full(vid.shape, float(pn), device=dev), generator=generator) / pn
+    first, last = first.to(dev), last.to(dev)
+    fr = torch.arange(F_, device=dev).view(1, F_)
+    pid, frame = ((first.view(Np, 1) <= fr) & (fr <= last.view(Np, 1))).nonzero(as_tuple=True)
+    mean_pos = pos.double().view(Np, F_, npos, 2).mean(dim=2)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(last - first + 1, 0)])
+    truth = {"frame": frame, "y": mean_pos[pid, frame, 0], "x": mean_pos[pid, frame, 1], "particle_id": pid, "offsets": offsets,
+             "D": D.to(dev), "pos": pos, "amp": amp, "first": first, "last": last}
+    return vid.float(), truth

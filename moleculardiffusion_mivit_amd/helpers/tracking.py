@@ -986,3 +986,72 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         d_model = torch.where(n_sequences > 0, torch.segment_reduce(per_seq, "mean", lengths=n_sequences), d_model)
     return {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
             "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# scoring against a simulated field of view (helpers/generation.simulate_movie)
+# ----------------------------------------------------------------------------------------------------------------------
+def score_tracking(frame, y, x, track_id, truth, max_distance=2.0):
+    """How well a detections table (frame, y, x, track_id [N]; arrays or tensors, integer or refined positions) recovers the
+    truth table of generation.simulate_movie.  Torch ops on the inputs' device, no loop over frames or tracks.
+
+    Every detection is matched to the nearest truth particle visible in its frame (ties: the lowest particle_id), if that is
+    within max_distance pixels.  -> dict of tensors on that device:
+      recall      distinct truth rows that some detection matched / truth rows           (0-dim float64; NaN without truth rows)
+      precision   distinct truth rows matched / detections: a second detection on the same particle-frame counts against it
+      rmse        root mean square distance over the matched detections                   (NaN without a match)
+      n_detections, n_truth, n_matched (0-dim int64; n_matched counts detections)
+      matched_particle [N] int64, the particle each detection was matched to or -1
+      track_id [n_tracks] the distinct ids ascending, and per track: n_rows, particle_id (the particle most of its rows were
+      matched to; ties: the lowest; -1 if none was matched), purity (rows matched to that particle / all rows of the track)
+      and D_true (truth["D"] of that particle, NaN for -1)."""
+    dev = None
+    for v in (frame, y, x, track_id):
+        if torch.is_tensor(v):
+            dev = v.device
+            break
+    fr = torch.as_tensor(frame, device=dev).long()
+    dev = fr.device
+    yy, xx = torch.as_tensor(y, device=dev).double(), torch.as_tensor(x, device=dev).double()
+    tid = torch.as_tensor(track_id, device=dev).long()
+    if not (fr.dim() == 1 and fr.shape == yy.shape == xx.shape == tid.shape):
+        raise ValueError("frame, y, x and track_id must be 1-D with one entry per detection")
+    md = float(max_distance)
+    if not md >= 0:
+        raise ValueError(f"max_distance must be >= 0, got {max_distance}")
+    t_fr, t_pid = truth["frame"].to(dev).long(), truth["particle_id"].to(dev).long()
+    t_y, t_x, t_D = truth["y"].to(dev).double(), truth["x"].to(dev).double(), truth["D"].to(dev).double()
+    Np, n_truth, n_det = t_D.numel(), t_fr.numel(), fr.numel()
+    n_frames = int(torch.cat([t_fr, fr]).max()) + 1 if n_truth + n_det else 1
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    if Np and n_det:
+        ty = torch.full((n_frames, Np), float("inf"), dtype=torch.float64, device=dev)      # inf: not visible in that frame
+        tx = torch.full((n_frames, Np), float("inf"), dtype=torch.float64, device=dev)
+        ty[t_fr, t_pid], tx[t_fr, t_pid] = t_y, t_x
+        inside = fr >= 0
+        f_ = fr.clamp_min(0)
+        d2 = (ty[f_] - yy[:, None]) ** 2 + (tx[f_] - xx[:, None]) ** 2                      # [N, Np]
+        dmin2, who = d2.min(dim=1)                                                          # first minimum: lowest particle_id
+        ok = inside & (dmin2 <= md * md)
+    else:
+        dmin2 = torch.zeros(n_det, dtype=torch.float64, device=dev)
+        who = torch.zeros(n_det, dtype=torch.int64, device=dev)
+        ok = torch.zeros(n_det, dtype=torch.bool, device=dev)
+    matched = torch.where(ok, who, torch.full_like(who, -1))
+    n_matched = ok.sum()
+    distinct = torch.unique(fr[ok] * max(Np, 1) + who[ok]).numel()
+    distinct = torch.full((), float(distinct), dtype=torch.float64, device=dev)
+    tracks, tidx = torch.unique(tid, return_inverse=True)
+    n_tracks = tracks.numel()
+    n_rows = torch.bincount(tidx, minlength=n_tracks)
+    votes = torch.bincount(tidx[ok] * max(Np, 1) + who[ok], minlength=n_tracks * max(Np, 1)).view(n_tracks, max(Np, 1))
+    top, major = votes.max(dim=1) if n_tracks else (n_rows, n_rows)
+    major = torch.where(top > 0, major, torch.full_like(major, -1))
+    d_true = torch.where(major >= 0, t_D[major.clamp_min(0)], nan) if Np else torch.full((n_tracks,), float("nan"),
+                                                                                       dtype=torch.float64, device=dev)
+    return {"recall": distinct / n_truth if n_truth else nan, "precision": distinct / n_det if n_det else nan,
+            "rmse": torch.sqrt(dmin2[ok].sum() / n_matched) if n_det else nan,
+            "n_detections": torch.full((), n_det, dtype=torch.int64, device=dev),
+            "n_truth": torch.full((), n_truth, dtype=torch.int64, device=dev), "n_matched": n_matched,
+            "matched_particle": matched, "track_id": tracks, "n_rows": n_rows, "particle_id": major,
+            "purity": top.double() / n_rows.double().clamp_min(1.0), "D_true": d_true}

@@ -745,3 +745,33 @@ def track_sequences(movie: torch.Tensor, frame: torch.Tensor, y: torch.Tensor, x
                                         float(lo), float(denom), 1 if normalize else 0, _p(seq), _s(movie)),
             "mivit_track_sequences")
     return seq
+
+
+MOVIE_MAX_RADIUS = 64        # csrc/movie.hip: limits of mivit_render_movie
+MOVIE_MAX_NPOS = 256
+MOVIE_MAX_UP = 64
+MOVIE_PARTICLE_CHUNK = 256   # (particle, sub-position) pairs the kernel culls per pass
+
+
+def render_movie(pos: torch.Tensor, amp: torch.Tensor, sigma_hr: float, up: int, radius: int, H: int, W: int, first=None,
+                 last=None) -> torch.Tensor:
+    """Noise-free movie of a whole field of view (csrc/movie.hip, mivit_render_movie): pos [Np, F * npos, 2] float32 (y, x) in
+    camera pixels, amp [Np, F, npos] float32, first / last [Np] int32 or both None (frames first .. last inclusive), all on the
+    GPU -> movie [F, H, W] float32.  See include/mivit_hip.h for the image model and helpers/generation.render_movie for the
+    float64 restatement."""
+    pos = _dev_tensor(pos, torch.float32, 3, "render_movie", "pos [Np, F * npos, 2]")
+    amp = _dev_tensor(amp, torch.float32, 3, "render_movie", "amp [Np, F, npos]")
+    Np, F, npos = amp.shape
+    if tuple(pos.shape) != (Np, F * npos, 2):
+        raise ValueError(f"render_movie: pos must be [{Np}, {F * npos}, 2] for amp {tuple(amp.shape)}, got {tuple(pos.shape)}")
+    if (first is None) != (last is None):
+        raise ValueError("render_movie: first and last must both be given or both be None")
+    if first is not None:
+        first = _dev_tensor(first, torch.int32, 1, "render_movie", "first [Np]")
+        last = _dev_tensor(last, torch.int32, 1, "render_movie", "last [Np]")
+        if first.numel() != Np or last.numel() != Np:
+            raise ValueError(f"render_movie: first and last must be [{Np}]")
+    movie = torch.empty(F, int(H), int(W), dtype=torch.float32, device=amp.device)
+    N.check(N.lib.mivit_render_movie(_p(pos), _p(amp), _p(first), _p(last), Np, F, npos, float(sigma_hr), int(up), int(radius),
+                                     int(H), int(W), _p(movie), _s(movie)), "mivit_render_movie")
+    return movie

@@ -1,0 +1,73 @@
+"""How the front end plus a model behave on a field of view whose diffusion coefficients are known: simulate_movie
+(helpers/generation.py, csrc/movie.hip), estimate_track_diffusion (helpers/tracking.py) and score_tracking, on the GPU.  Prints
+one JSON line: the tracking scores and, per track, D_true (of the particle most of its rows were matched to), D_msd,
+D_msd_weighted and D_model, all in the units of estimate_track_diffusion (pixels^2 per frame for the MSD estimates; the
+model's own output units for D_model).  A tool, not a test: it asserts no accuracy.
+
+    python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
+                                          [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
+
+Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
+about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import torch
+import torch.nn.functional as F
+
+from moleculardiffusion_mivit_amd.helpers import generation as gen
+from moleculardiffusion_mivit_amd.helpers import models as M
+from moleculardiffusion_mivit_amd.helpers import tracking as trk
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--checkpoint")
+    ap.add_argument("--particles", type=int, default=20)
+    ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--size", type=int, nargs=2, default=[256, 256], metavar=("H", "W"))
+    ap.add_argument("--D", type=float, nargs=2, default=[0.05, 0.0004], metavar=("MEAN", "VAR"))
+    ap.add_argument("--npos", type=int, default=10)
+    ap.add_argument("--seq-len", type=int, default=30)
+    ap.add_argument("--patch-size", type=int, default=9)
+    ap.add_argument("--max-distance", type=float, default=2.0)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--noise-free", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_movie_accuracy.py needs a GPU")
+    props = dict(gen.DEFAULT_IMAGE_PROPS)
+    if args.noise_free:
+        props.update({"background_intensity": [props["background_intensity"][0], 0.0], "poisson_noise": -1})
+    H, W = args.size
+    g = torch.Generator(device="cuda").manual_seed(args.seed)
+    movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props,
+                                      generator=g, device="cuda")
+    model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
+                                 M.MLPHead, F.relu).cuda()
+    if args.checkpoint:
+        model.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
+    bm, bs = props["background_intensity"]
+    norm = (bm, bs, props["particle_intensity"][0] + bm)
+    est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm)
+    table, _ = trk.track_particles_tensors(movie, return_dog=False)
+    fr, y, x, tid, _ = trk.tracks_table_by_track(table)
+    score = trk.score_tracking(fr, y, x, tid, truth, max_distance=args.max_distance)
+    assert torch.equal(score["track_id"], est["track_id"])
+    out = {"recall": float(score["recall"]), "precision": float(score["precision"]), "rmse": float(score["rmse"]),
+           "n_tracks": int(len(est["track_id"])), "n_particles": args.particles,
+           "tracks": [{"track_id": int(t), "length": int(n), "particle_id": int(p), "purity": float(pu), "D_true": float(dt),
+                       "D_msd": float(a), "D_msd_weighted": float(b), "D_model": float(c)}
+                      for t, n, p, pu, dt, a, b, c in zip(est["track_id"].tolist(), est["length"].tolist(),
+                                                          score["particle_id"].tolist(), score["purity"].tolist(),
+                                                          score["D_true"].tolist(), est["D_msd"].tolist(),
+                                                          est["D_msd_weighted"].tolist(), est["D_model"].tolist())]}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
