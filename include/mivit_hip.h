@@ -111,6 +111,13 @@ int mivit_wavestream_fwd(const void *x, int64_t ldx, const void *W_bf16, const f
 int mivit_wavestream_dgrad(const void *dy, int64_t lddy, const void *W_bf16, int M, int N, int K, int act,
                            const void *saved, int64_t lds, const void *dres, int64_t lddr, void *dx, int64_t lddx,
                            void *stream);
+/* Which launches mivit_rowstream_fwd / _dgrad (and the engine) hand to the wave-stream kernels: 0 = never, 1 = whenever
+ * wave-stream supports the shape, 2 = the measured picks (default; initial value from MIVIT_WAVESTREAM).  In mode 2 the mask
+ * (initial value from MIVIT_WAVESTREAM_MASK, default 7) enables them one by one: bit 0 the K = 128 forward with fused
+ * LayerNorm, bit 1 the K = 128 dgrad with act'(saved), bit 2 every K = 256 dgrad.  For A/B runs and so that tests reach the
+ * row-stream kernels behind the picks.  Each returns the previous value. */
+int mivit_rowstream_set_wavestream(int mode);
+int mivit_rowstream_set_wavestream_mask(int mask);
 
 /* Wide layers (K, N of 512-class models), bf16: LDS-DMA ring GEMMs with 256 x 128 workgroup tiles.
  * fwd:   y = act(x W^T + bias) (+ resid), optional pre-activation copy;   dgrad: dx = (dy W) * act'(saved) (+ dres).
@@ -127,6 +134,45 @@ int mivit_gemm_dma_dgrad(const void *dy, int64_t lddy, const void *W_bf16, int M
 size_t mivit_wgrad_bf16_workspace_bytes(int M, int N, int K);
 int mivit_wgrad_bf16(const void *dy, int64_t lddy, const void *x, int64_t ldx, int M, int N, int K, float *dW, float *db,
                      void *workspace, size_t workspace_bytes, void *stream);
+/* Ring configuration of mivit_wgrad_bf16: 0 = by size (default; initial value from MIVIT_WGRAD_DMA_CFG), otherwise
+ * 10 * ring slots + rows per stage / 32: 21, 22, 31, 32.  Returns the previous value. */
+int mivit_wgrad_bf16_set_config(int cfg);
+
+/* The streaming operators above in IEEE half: csrc/rowstream.hip, wavestream.hip, wgrad_dma.hip, wgrad_small.hip and embed.hip
+ * compiled with -DMIVIT_ELEM_F16 export the same entries suffixed _f16 (the engine's fp16 models run on these kernels).  Same
+ * arguments with every 16-bit tensor in fp16; the setters act on the fp16 build's own switches. */
+int mivit_rowstream_fwd_f16(const void *x, int64_t ldx, const void *W_f16, const float *bias, int M, int N, int K, int act,
+                            const void *resid, int64_t ldr, void *y, int64_t ldy, void *y_preact, const float *ln_gamma,
+                            const float *ln_beta, void *ln_out, float *mean, float *rstd, void *stream);
+int mivit_rowstream_dgrad_f16(const void *dy, int64_t lddy, const void *W_f16, int M, int N, int K, int act,
+                              const void *saved, int64_t lds, const void *dres, int64_t lddr, void *dx, int64_t lddx,
+                              void *stream);
+int mivit_wavestream_fwd_f16(const void *x, int64_t ldx, const void *W_f16, const float *bias, int M, int N, int K, int act,
+                             const void *resid, int64_t ldr, void *y, int64_t ldy, void *y_preact, const float *ln_gamma,
+                             const float *ln_beta, void *ln_out, float *mean, float *rstd, void *stream);
+int mivit_wavestream_dgrad_f16(const void *dy, int64_t lddy, const void *W_f16, int M, int N, int K, int act,
+                               const void *saved, int64_t lds, const void *dres, int64_t lddr, void *dx, int64_t lddx,
+                               void *stream);
+int mivit_rowstream_set_wavestream_f16(int mode);
+int mivit_rowstream_set_wavestream_mask_f16(int mask);
+size_t mivit_wgrad_bf16_workspace_bytes_f16(int M, int N, int K);
+int mivit_wgrad_bf16_f16(const void *dy, int64_t lddy, const void *x, int64_t ldx, int M, int N, int K, float *dW, float *db,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int mivit_wgrad_bf16_set_config_f16(int cfg);
+size_t mivit_wgrad_small_workspace_bytes_f16(int M, int N, int K);
+int mivit_wgrad_small_f16(const void *dy, int64_t lddy, const void *x, int64_t ldx, int M, int N, int K, float *dW,
+                          float *db, void *workspace, size_t workspace_bytes, void *stream);
+int mivit_embed_small_supported_f16(int M, int K, int E);
+int mivit_embed_small_fwd_f16(const float *x, const void *W_f16, const float *bias, int M, int K, int E, void *y_f16, void *stream);
+size_t mivit_embed_small_wgrad_workspace_bytes_f16(int M, int K, int E);
+int mivit_embed_small_wgrad_f16(const void *dy_f16, const float *x, int M, int K, int E, float *dW, float *db, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int mivit_embed_fwd_bf16_f16(const float *x, const void *W_f16, const float *bias, int M, int K, int E, void *y_f16,
+                             void *stream);
+int mivit_embed_set_variant_f16(int variant);
+size_t mivit_embed_wgrad_bf16_workspace_bytes_f16(int M, int K, int E);
+int mivit_embed_wgrad_bf16_f16(const void *dy_f16, const float *x, int M, int K, int E, float *dW, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* Fused forward of the two halves of the post-norm encoder layer (helpers/models.py:97-108), bf16 mode, model width
  * E = 128, feed-forward width F = 256, 4 heads of 32 (the PSFNoise 32x64x64 configuration); csrc/fused_fwd.hip.

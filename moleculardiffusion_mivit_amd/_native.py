@@ -172,6 +172,16 @@ for _sfx in ("_f16", "_w64_f16"):
                   "mivit_mlp_block_bwd", "mivit_attn_out_bwd_workspace_bytes", "mivit_attn_out_bwd", "mivit_qkv_bwd_workspace_bytes",
                   "mivit_qkv_bwd", "mivit_qkv_bwd_affine"):
         SYMBOLS[_name + _sfx] = SYMBOLS[_name]
+# setters of the streaming kernels' switches, and the fp16 builds of the streaming operators: same signatures, suffixed _f16
+SYMBOLS["mivit_rowstream_set_wavestream"] = SYMBOLS["mivit_rowstream_set_wavestream_mask"] = (c_int, [c_int])
+SYMBOLS["mivit_wgrad_bf16_set_config"] = (c_int, [c_int])
+for _name in ("mivit_rowstream_fwd", "mivit_rowstream_dgrad", "mivit_wavestream_fwd", "mivit_wavestream_dgrad",
+              "mivit_rowstream_set_wavestream", "mivit_rowstream_set_wavestream_mask", "mivit_wgrad_bf16_workspace_bytes",
+              "mivit_wgrad_bf16", "mivit_wgrad_bf16_set_config", "mivit_wgrad_small_workspace_bytes", "mivit_wgrad_small",
+              "mivit_embed_small_supported", "mivit_embed_small_fwd", "mivit_embed_small_wgrad_workspace_bytes",
+              "mivit_embed_small_wgrad", "mivit_embed_fwd_bf16", "mivit_embed_set_variant",
+              "mivit_embed_wgrad_bf16_workspace_bytes", "mivit_embed_wgrad_bf16"):
+    SYMBOLS[_name + "_f16"] = SYMBOLS[_name]
 PROF_TAGS = ["embed_fwd", "embed_wgrad", "linear_fwd", "linear_dgrad", "linear_wgrad", "attn_fwd", "attn_bwd",
              "ln_fwd", "ln_bwd", "op", "attn_block_fwd", "mlp_block_fwd", "mlp_block_bwd", "attn_out_bwd", "attn_core_bwd",
              "qkv_wgrad", "qkv_dgrad", "qkv_bwd"]

@@ -730,9 +730,7 @@ int fwd_dma_launch(const EmbFwdArgs &a, hipStream_t s) {
 // forward tiling, selectable for A/B runs and so that the tests reach every launcher branch at small sizes:
 // MIVIT_EMBED_FWD_VARIANT / mivit_embed_set_variant (0 = by problem size)
 static int g_embed_variant = getenv("MIVIT_EMBED_FWD_VARIANT") ? atoi(getenv("MIVIT_EMBED_FWD_VARIANT")) : 0;
-#ifndef MIVIT_ELEM_F16
 extern "C" int mivit_embed_set_variant(int v) { const int old = g_embed_variant; g_embed_variant = v; return old; }
-#endif
 
 bool embed_dma_supported(int dtype, int M, int K, int E) {
     return dtype == MIVIT_ELEM_DTYPE && E % 128 == 0 && K % 128 == 0 && K >= 256 && M >= 128;
@@ -810,22 +808,21 @@ int launch_embed_wgrad_dma(const void *dY_bf16, const float *X, float *dW, int M
     return launch_slab_reduce(static_cast<const float *>(ws), nz, (int64_t)E * K, dW, 0, s);
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h)
+// operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
 extern "C" int mivit_embed_fwd_bf16(const float *x, const void *W_bf16, const float *bias, int M, int K, int E,
                                     void *y_bf16, void *stream) {
     MIVIT_CHECK(x && W_bf16 && y_bf16, "embed_fwd_bf16: null pointer");
-    if (!embed_dma_supported(MIVIT_BF16, M, K, E)) { mivit_set_error("embed_fwd_bf16: unsupported shape"); return 3; }
+    if (!embed_dma_supported(MIVIT_ELEM_DTYPE, M, K, E)) { mivit_set_error("embed_fwd_bf16: unsupported shape"); return 3; }
     prof_set_tag(MIVIT_PROF_OP);
     return launch_embed_fwd_dma(x, W_bf16, bias, y_bf16, M, K, E, static_cast<hipStream_t>(stream));
 }
 extern "C" size_t mivit_embed_wgrad_bf16_workspace_bytes(int M, int K, int E) {
-    return embed_dma_supported(MIVIT_BF16, M, K, E) ? embed_wgrad_dma_ws_bytes(M, K, E) : 0;
+    return embed_dma_supported(MIVIT_ELEM_DTYPE, M, K, E) ? embed_wgrad_dma_ws_bytes(M, K, E) : 0;
 }
 extern "C" int mivit_embed_wgrad_bf16(const void *dy_bf16, const float *x, int M, int K, int E, float *dW,
                                       void *workspace, size_t workspace_bytes, void *stream) {
     MIVIT_CHECK(dy_bf16 && x && dW && workspace, "embed_wgrad_bf16: null pointer");
-    if (!embed_dma_supported(MIVIT_BF16, M, K, E)) { mivit_set_error("embed_wgrad_bf16: unsupported shape"); return 3; }
+    if (!embed_dma_supported(MIVIT_ELEM_DTYPE, M, K, E)) { mivit_set_error("embed_wgrad_bf16: unsupported shape"); return 3; }
     prof_set_tag(MIVIT_PROF_OP);
     return launch_embed_wgrad_dma(dy_bf16, x, dW, M, K, E, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
-#endif

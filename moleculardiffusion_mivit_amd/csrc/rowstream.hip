@@ -302,6 +302,11 @@ int rs_launch(const RsArgs &a, hipStream_t s) {
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// wave-stream pick of launch_rowstream: MIVIT_WAVESTREAM / mivit_rowstream_set_wavestream (0 never, 1 whenever supported, 2 = the
+// measured picks, selected by the bits of MIVIT_WAVESTREAM_MASK / mivit_rowstream_set_wavestream_mask)
+int g_use_ws = getenv("MIVIT_WAVESTREAM") ? atoi(getenv("MIVIT_WAVESTREAM")) : 2;
+int g_ws_mask = getenv("MIVIT_WAVESTREAM_MASK") ? atoi(getenv("MIVIT_WAVESTREAM_MASK")) : 7;      // (A/B: which of the three picks)
+
 }  // namespace
 
 bool rowstream_supported(int M, int N, int K, bool dgrad, int64_t lda, int64_t ldw, const void *A, const void *W) {
@@ -320,9 +325,8 @@ int launch_rowstream(bool dgrad, const void *A, int64_t lda, const void *W_bf16,
     // wave-stream variant (wavestream.hip): MIVIT_WAVESTREAM = 0 never, 1 whenever supported, default 2 = the launches where
     // it measured faster at the headline shape (out-proj + LayerNorm 81 -> 74 us, FC2 dgrad with act' 124 -> 93 us,
     // K = 256 dgrad 71 -> 68 us; the plain forward slices and FC2 + LayerNorm stay on the DMA ring: 61 vs 70, 88 vs 94 us)
-    static const int use_ws = getenv("MIVIT_WAVESTREAM") ? atoi(getenv("MIVIT_WAVESTREAM")) : 2;
+    const int use_ws = g_use_ws, ws_mask = g_ws_mask;
     const bool rs_shape = (K == 128 || K == 256 || (K == 384 && dgrad)) && N % 128 == 0;     // what the DMA-ring kernels cover
-    static const int ws_mask = getenv("MIVIT_WAVESTREAM_MASK") ? atoi(getenv("MIVIT_WAVESTREAM_MASK")) : 7;      // (A/B: which of the three picks)
     const bool ws_pick = !rs_shape || use_ws == 1 || (use_ws == 2 && (((ws_mask & 1) && K == 128 && !dgrad && gamma) ||
                                                                       ((ws_mask & 2) && K == 128 && dgrad && dact) ||
                                                                       ((ws_mask & 4) && K == 256 && dgrad)));
@@ -357,7 +361,9 @@ int launch_rowstream(bool dgrad, const void *A, int64_t lda, const void *W_bf16,
 #undef RS_GO
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h)
+// operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
+extern "C" int mivit_rowstream_set_wavestream(int mode) { const int old = g_use_ws; g_use_ws = mode; return old; }
+extern "C" int mivit_rowstream_set_wavestream_mask(int mask) { const int old = g_ws_mask; g_ws_mask = mask; return old; }
 extern "C" int mivit_rowstream_fwd(const void *x, int64_t ldx, const void *W_bf16, const float *bias, int M, int N, int K,
                                    int act, const void *resid, int64_t ldr, void *y, int64_t ldy, void *y_preact,
                                    const float *ln_gamma, const float *ln_beta, void *ln_out, float *mean, float *rstd,
@@ -378,4 +384,3 @@ extern "C" int mivit_rowstream_dgrad(const void *dy, int64_t lddy, const void *W
                             lds, act, dres, lddr, dx, lddx, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                             static_cast<hipStream_t>(stream));
 }
-#endif

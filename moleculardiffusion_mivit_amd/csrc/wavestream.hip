@@ -331,7 +331,7 @@ int launch_embed_small_fwd(const float *X, const void *W_bf16, const float *bias
     MIVIT_FAIL("embed_small_fwd: unsupported frame size %d", K);
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h)
+// operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
 extern "C" int mivit_embed_small_supported(int M, int K, int E) {
     return frame_kp(K) != 0 && (E == 64 || E == 128) && M >= 256 && (int64_t)M * K * 4 < (1ll << 32) && !getenv("MIVIT_NO_EMBED_SMALL");
 }
@@ -361,4 +361,3 @@ extern "C" int mivit_wavestream_dgrad(const void *dy, int64_t lddy, const void *
                              lds, act, dres, lddr, dx, lddx, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                              static_cast<hipStream_t>(stream));
 }
-#endif

@@ -171,6 +171,9 @@ int dma_splits(int M, int N, int K) {
     return s < 1 ? 1 : (int)s;
 }
 
+// ring configuration of launch_wgrad_dma: MIVIT_WGRAD_DMA_CFG / mivit_wgrad_bf16_set_config (0 = by size; 10 * slots + rows / 32)
+int g_cfg = getenv("MIVIT_WGRAD_DMA_CFG") ? atoi(getenv("MIVIT_WGRAD_DMA_CFG")) : 0;
+
 }  // namespace
 
 bool wgrad_dma_supported(int M, int N, int K, int64_t lddy, int64_t ldx, const void *dy, const void *x) {
@@ -198,7 +201,7 @@ int launch_wgrad_dma(const void *dy, int64_t lddy, const void *x, int64_t ldx, i
     // headline shape 3 slots x 64 rows (96 KB, one workgroup = 4 waves per CU) 2.35 ms/step, 2 slots (64 KB, two
     // workgroups) 1.68 ms.  MIVIT_WGRAD_DMA_CFG = 10 * slots + rows / 32 selects another point.
     // wide (MFMA-bound) layers prefer 32-row stages (32 KB ring, more workgroups per CU): c4 step 21.15 -> 20.2 ms.
-    static const int forced = getenv("MIVIT_WGRAD_DMA_CFG") ? atoi(getenv("MIVIT_WGRAD_DMA_CFG")) : 0;
+    const int forced = g_cfg;
     const int cfg = forced ? forced : ((long)N * K >= 512L * 512L ? 21 : 22);
     size_t bytes;
     void (*kern)(const WgArgs);
@@ -219,7 +222,8 @@ int launch_wgrad_dma(const void *dy, int64_t lddy, const void *x, int64_t ldx, i
     return launch_slab_reduce(bias_part, nz, N, db, 0, s);
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h)
+// operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
+extern "C" int mivit_wgrad_bf16_set_config(int cfg) { const int old = g_cfg; g_cfg = cfg; return old; }
 extern "C" size_t mivit_wgrad_bf16_workspace_bytes(int M, int N, int K) {
     return (N % TILE == 0 && K % TILE == 0) ? wgrad_dma_ws_bytes(M, N, K) : 0;
 }
@@ -230,4 +234,3 @@ extern "C" int mivit_wgrad_bf16(const void *dy, int64_t lddy, const void *x, int
     prof_set_tag(MIVIT_PROF_OP);
     return launch_wgrad_dma(dy, lddy, x, ldx, M, N, K, dW, db, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
-#endif

@@ -262,7 +262,7 @@ int launch_wgrad_small(const void *dy, int64_t lddy, const void *x, int64_t ldx,
     return db ? launch_slab_reduce(bias_slabs, parts, N, db, 0, s) : 0;
 }
 
-#ifndef MIVIT_ELEM_F16      // operator-level C-ABI: declared for bf16 (include/mivit_hip.h)
+// operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
 extern "C" size_t mivit_embed_small_wgrad_workspace_bytes(int M, int K, int E) { return embed_small_wgrad_ws_bytes(M, E, K); }
 extern "C" int mivit_embed_small_wgrad(const void *dY_bf16, const float *X, int M, int K, int E, float *dW, float *db, void *workspace,
                                        size_t workspace_bytes, void *stream) {
@@ -281,4 +281,3 @@ extern "C" int mivit_wgrad_small(const void *dy, int64_t lddy, const void *x, in
     prof_set_tag(MIVIT_PROF_OP);
     return launch_wgrad_small(dy, lddy, x, ldx, M, N, K, dW, db, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
-#endif

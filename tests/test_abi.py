@@ -33,6 +33,38 @@ def test_library_exports_every_declared_symbol():
     assert N.lib.mivit_device_count() >= 0
 
 
+def test_streaming_setters_and_f16_entries():
+    """the switches of the streaming launchers (host-side state, no kernel is launched): every fp16 streaming unit exports its
+    operator entries suffixed _f16; with nothing set in the environment the setters report the defaults the launchers always
+    used (wave-stream mode 2, mask 7, ring configuration by size), per element type, and return the previous value"""
+    from moleculardiffusion_mivit_amd import _native as N
+    declared = _declared_symbols()
+    base = ["mivit_rowstream_fwd", "mivit_rowstream_dgrad", "mivit_wavestream_fwd", "mivit_wavestream_dgrad",
+            "mivit_rowstream_set_wavestream", "mivit_rowstream_set_wavestream_mask", "mivit_wgrad_bf16_workspace_bytes",
+            "mivit_wgrad_bf16", "mivit_wgrad_bf16_set_config", "mivit_wgrad_small_workspace_bytes", "mivit_wgrad_small",
+            "mivit_embed_small_supported", "mivit_embed_small_fwd", "mivit_embed_small_wgrad_workspace_bytes",
+            "mivit_embed_small_wgrad", "mivit_embed_fwd_bf16", "mivit_embed_set_variant", "mivit_embed_wgrad_bf16_workspace_bytes",
+            "mivit_embed_wgrad_bf16"]
+    for name in base:
+        for n in (name, name + "_f16"):
+            assert n in declared and n in N.SYMBOLS, n
+            assert N.SYMBOLS[n] == N.SYMBOLS[name]
+    env = {"mivit_rowstream_set_wavestream": ("MIVIT_WAVESTREAM", 2), "mivit_rowstream_set_wavestream_mask": ("MIVIT_WAVESTREAM_MASK", 7),
+           "mivit_wgrad_bf16_set_config": ("MIVIT_WGRAD_DMA_CFG", 0), "mivit_embed_set_variant": ("MIVIT_EMBED_FWD_VARIANT", 0)}
+    for name, (var, default) in env.items():
+        default = int(os.environ.get(var, default))
+        for sfx in ("", "_f16"):
+            f = getattr(N.lib, name + sfx)
+            assert f(31) == default, (name + sfx)
+            other = getattr(N.lib, name + ("" if sfx else "_f16"))
+            old_other = other(default)
+            assert old_other in (default, 31)                 # the two element types hold separate switches
+            assert f(default) == 31
+            other(old_other if old_other == default else default)
+    assert N.lib.mivit_wgrad_bf16_workspace_bytes_f16(1000, 128, 128) == N.lib.mivit_wgrad_bf16_workspace_bytes(1000, 128, 128) > 0
+    assert N.lib.mivit_embed_small_supported_f16(256, 81, 64) == 1 and N.lib.mivit_embed_small_supported_f16(255, 81, 64) == 0
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     """No silent fallback: a missing .so makes the binding raise ImportError with build instructions."""
     import importlib.util
