@@ -330,6 +330,31 @@ int mivit_link_frames(const int *coords, const int *count, const unsigned char *
 int mivit_chain_tracks(const int *link, const int *count, const unsigned char *movie_start, int F, int cap, int *ids,
                        int *lengths, int *n_tracks, void *stream);
 
+/* Gap closing: the end of a track is linked to the start of a later track across up to max_gap missed frames (1 .. 8),
+ * csrc/linking.hip.  coords / count / movie_start as for mivit_link_frames, link [F, cap] as it wrote it (a value outside
+ * 0 .. count[f - 1] - 1 counts as -1).  An open start is a detection without a link and without a gap link, an open end one
+ * that no detection of the next frame links to and no gap link points at.  Passes g = 2 .. max_gap + 1, one launch each of F
+ * one-wave workgroups: workgroup f solves the full rectangular assignment between the open ends of frame f - g and the open
+ * starts of frame f, both in ascending detection index, with the solver, roles and tie rule of mivit_link_frames, then drops
+ * the pairs longer than max_distance; an accepted pair closes both ends, a dropped one leaves them open for the later passes.
+ * A pair of frames is skipped when f - g < 0 or one of the frames f - g + 1 .. f carries a movie_start flag.  out: gap_partner
+ * [F, cap] int32, the index in frame f - g or -1, gap_frames [F, cap] int32, g or 0; every entry is defined (the first launch
+ * clears both, a pass overwrites an entry at most once).  workspace: workspace_bytes >= F * cap bytes on the device, the
+ * open-end state.  1 <= cap <= 1024.  Arguments are validated before any HIP call; F = 0 is a no-op. */
+int mivit_close_gaps(const int *coords, const int *count, const int *link, const unsigned char *movie_start, int F, int cap,
+                     int max_gap, double max_distance, int *gap_partner, int *gap_frames, unsigned char *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/* mivit_chain_tracks with gap links: a detection with a link inherits the id of its partner in frame f - 1, otherwise one with
+ * gap_frames = g in 2 .. max_gap + 1 the id of detection gap_partner of frame f - g, otherwise it takes the next free id; frame
+ * 0 and every movie_start frame start one track per detection.  A link or gap partner outside the partner frame's count, or a
+ * g outside 2 .. max_gap + 1 or beyond frame 0, counts as absent.  out: ids [F, cap] int32 (entries beyond count[f] are not
+ * written), lengths [F * cap] int32, cleared here, the number of DETECTIONS of each track, n_tracks [1] int32.
+ * 1 <= max_gap <= 8, 1 <= cap <= 1024.  Arguments are validated before any HIP call; F = 0 only clears n_tracks. */
+int mivit_chain_tracks_gaps(const int *link, const int *gap_partner, const int *gap_frames, const int *count,
+                            const unsigned char *movie_start, int F, int cap, int max_gap, int *ids, int *lengths,
+                            int *n_tracks, void *stream);
+
 /* Ragged mean square displacement and both classical estimates of the diffusion coefficient for every track of a linked
  * movie in one launch (the reference's mean_square_displacement, helpers/helpersMSD.py:7-26, estimateDfromMSDs, :110-129, and
  * estimateDfromMSDsWeighted, :131-157, per track), csrc/diffusion.hip, one workgroup per track, one thread per lag.

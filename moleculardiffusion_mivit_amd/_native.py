@@ -138,6 +138,10 @@ SYMBOLS = {
     "mivit_refine_gaussian": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mivit_link_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "mivit_chain_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mivit_close_gaps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "mivit_chain_tracks_gaps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
     "mivit_track_msd": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "mivit_track_sequences": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -565,7 +565,8 @@ def _draw_diffusion_coefficients(n, Ds, generator, gdev):
 
 
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
-                   margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu"):
+                   margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
+                   blink=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -583,7 +584,14 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     (int64), one row per visible particle-frame sorted by particle and then by frame; offsets [Np + 1] int64, CSR over those
     rows (the layout of tracking.tracks_table_by_track: msd.track_msd(stack([y, x], 1), offsets) runs on it as it is); D [Np]
     float64; pos [Np, F * nPosPerFrame, 2] float32 and amp [Np, F, nPosPerFrame] float32, what was rendered; first, last [Np]
-    int64."""
+    int64.
+
+    blink (default None: no dark frames, the code path without it): a float in [0, 1), the probability that a particle is dark
+    in a frame of its lifetime, drawn from `generator` after the amplitudes and before rendering; or a bool [Np, F] mask, True
+    = dark.  A dark particle-frame has all its sub-position amplitudes set to zero.  truth keeps one row per frame of the
+    lifetime (offsets is unchanged) and gains visible (bool per row, False on a dark frame); truth["amp"] is the zeroed one.
+    tracking.score_tracking therefore counts a dark frame as a truth row: a filled row of a gap-closed track that lands on it
+    is a match, an unfilled gap a miss."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -607,6 +615,16 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError("first > last")
         if bool((first < 0).any()) or bool((last >= F_).any()):
             raise ValueError(f"lifetimes must lie in 0 .. {F_ - 1}")
+    blink_p = dark = None
+    if blink is not None:
+        if torch.is_tensor(blink) or isinstance(blink, np.ndarray):
+            dark = torch.as_tensor(blink).detach().cpu()
+            if dark.dtype != torch.bool or tuple(dark.shape) != (Np, F_):
+                raise ValueError(f"a blink mask must be bool [{Np}, {F_}], got {dark.dtype} {tuple(dark.shape)}")
+        elif isinstance(blink, bool) or not isinstance(blink, (int, float)) or not 0.0 <= float(blink) < 1.0:
+            raise ValueError(f"blink must be a probability in [0, 1) or a bool mask [{Np}, {F_}], got {blink!r}")
+        else:
+            blink_p = float(blink)
     gdev = generator.device if generator is not None else dev
     if gdev != dev and not (gdev.type == dev.type and dev.index is None):
         raise ValueError(f"the generator lives on {gdev}, the movie on {dev}")
@@ -625,6 +643,11 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     else:
         amp = torch.zeros(Np, F_, npos, device=gdev)
     amp = amp.float().to(dev)
+    if blink is not None:
+        if blink_p is not None:
+            dark = torch.rand(Np, F_, generator=generator, device=gdev) < blink_p
+        dark = dark.to(dev)
+        amp = torch.where(dark.unsqueeze(-1), torch.zeros((), dtype=amp.dtype, device=dev), amp)
     vid = render_movie(pos, amp, sigma, H, W, up, radius, first, last).to(dev)
     vid = vid + clipped_background(vid.shape, bm, bs, generator, dev)
     pn = props["poisson_noise"]
@@ -637,4 +660,6 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(last - first + 1, 0)])
     truth = {"frame": frame, "y": mean_pos[pid, frame, 0], "x": mean_pos[pid, frame, 1], "particle_id": pid, "offsets": offsets,
              "D": D.to(dev), "pos": pos, "amp": amp, "first": first, "last": last}
+    if blink is not None:
+        truth["visible"] = ~dark[pid, frame]
     return vid.float(), truth

@@ -104,8 +104,10 @@ def track_msd(positions, offsets, dt=1.0, max_lag=None):
     [n_tracks]), float64, Lmax the longest track.  CUDA tensors go to the kernel (ops.track_msd, one launch), numpy arrays and
     CPU tensors to its numpy restatement, bitwise equal; the output is of the input's kind.
 
-    A lag is counted in ROWS.  Tracks from this package's linking have no gaps (a track that is not linked in a frame ends),
-    so a lag in rows is a lag in frames; tracks from elsewhere must be gap-free too.  Per track of L rows, with M = L - 1 or
+    A lag is counted in ROWS.  Tracks from this package's frame-to-frame linking have no gaps (a track that is not linked in a
+    frame ends), and the tables of gap closing (max_gap > 0) are FILLED: tracking.fill_gaps adds a row for every missed frame,
+    so a lag in rows is a lag in frames.  A table that is gap-closed but not filled must not be passed, and tracks from
+    elsewhere must be gap-free too.  Per track of L rows, with M = L - 1 or
     min(L - 1, max_lag), all sums in ascending index:
         msd[tau]   = (sum_i (dy * dy + dx * dx)) / (L - tau), tau = 1 .. M; entry 0 and the entries past M are 0
         d_lstsq    = (sum_tau (tau dt) msd[tau]) / (sum_tau (tau dt)^2) / 4     estimateDfromMSDs: a line through the origin

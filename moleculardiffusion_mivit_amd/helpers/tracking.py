@@ -10,7 +10,9 @@ the reference returns as images stays a CUDA tensor; anything else goes to the n
 the filter in the kernel's order (bitwise equal) and the fit with the kernel's algorithm.  Linking is a Hungarian assignment
 per frame pair: by default (linking="host") scipy's, in a loop over the frames on the host, as the reference does it; with
 linking="device" all frame pairs of a movie are solved in one launch of csrc/linking.hip and the track ids are chained on the
-device (link_particles_movie, chain_tracks, track_particles_tensors).  Movies are filtered as float32.  pandas and scipy are only
+device (link_particles_movie, chain_tracks, track_particles_tensors); with max_gap > 0 the end of a track is then linked to the
+start of a later one across up to max_gap missed frames (close_gaps_movie) and the missed frames become rows with an
+interpolated position (fill_gaps), so that every track stays contiguous in frames.  Movies are filtered as float32.  pandas and scipy are only
 imported by the functions that need them: detect_particles_movie, track_particles_flat, extract_patches_flat and
 refine_localizations need neither pandas nor (except for linking) scipy."""
 from typing import Dict, Sequence, Tuple
@@ -251,6 +253,7 @@ def _link_tracks(all_coordinates, max_linking_distance, min_track_length, verbos
 
 
 LINK_MAX_DETECTIONS = 1024   # per frame, the limit of csrc/linking.hip (ops.LINK_MAX_DETECTIONS)
+LINK_MAX_GAP = 8             # missed frames a gap link may bridge (ops.LINK_MAX_GAP)
 
 
 def _assign_pair_numpy(c0, c1):
@@ -382,18 +385,96 @@ def link_particles_movie(coords, counts=None, max_distance=15, movie_start=None)
     return torch.from_numpy(link) if as_tensor else link
 
 
-def _chain_numpy(link, counts, ms):
-    """csrc/linking.hip::lk_chain_kernel on the host -> (ids [F, cap] int32, -1 beyond counts; lengths [F * cap] int32;
-    number of tracks)."""
+def _check_max_gap(max_gap, allow_zero=False):
+    lo = 0 if allow_zero else 1
+    if isinstance(max_gap, bool) or not isinstance(max_gap, (int, float, np.integer, np.floating)) \
+            or int(max_gap) != max_gap or not lo <= max_gap <= LINK_MAX_GAP:
+        raise ValueError(f"max_gap must be an integer from {lo} to {LINK_MAX_GAP} (LINK_MAX_GAP), got {max_gap!r}")
+    return int(max_gap)
+
+
+def _close_gaps_numpy(padded, counts, link, max_gap, max_distance, ms):
+    """csrc/linking.hip::gc_init_kernel / gc_pass_kernel on the host, pass by pass and frame by frame -> (gap_partner [F, cap]
+    int32, gap_frames [F, cap] int32)."""
+    F, cap = link.shape
+    gap_partner, gap_frames = np.full((F, cap), -1, np.int32), np.zeros((F, cap), np.int32)
+    has_succ, linked = np.zeros((F, cap), bool), np.zeros((F, cap), bool)
+    for f in range(1, F):
+        if ms is not None and ms[f]:
+            continue
+        l = link[f, :counts[f]].astype(np.int64)
+        ok = (l >= 0) & (l < counts[f - 1])                   # a link outside the frame before counts as none
+        linked[f, :counts[f]] = ok
+        has_succ[f - 1, l[ok]] = True
+    for g in range(2, max_gap + 2):                           # shortest gaps first
+        for f in range(g, F):
+            if ms is not None and ms[f - g + 1:f + 1].any():
+                continue
+            ends = np.flatnonzero(~has_succ[f - g, :counts[f - g]])
+            starts = np.flatnonzero(~linked[f, :counts[f]] & (gap_frames[f, :counts[f]] == 0))
+            partner, dist = _assign_pair_numpy(padded[f - g, ends], padded[f, starts])
+            ok = (partner >= 0) & (dist <= max_distance)      # solve first, filter afterwards
+            gap_partner[f, starts[ok]] = ends[partner[ok]]
+            gap_frames[f, starts[ok]] = g
+            has_succ[f - g, ends[partner[ok]]] = True
+    return gap_partner, gap_frames
+
+
+def close_gaps_movie(coords, counts, link, max_gap, max_distance=15, movie_start=None):
+    """Gap closing after link_particles_movie: the end of a track is linked to the start of a later track across up to max_gap
+    (1 .. LINK_MAX_GAP) missed frames.  coords [F, cap, 2] (y, x), counts [F], link [F, cap] -> (gap_partner [F, cap] int32,
+    gap_frames [F, cap] int32) of the input's kind: detection (f, j) continues the track that ended at detection
+    gap_partner[f, j] of frame f - gap_frames[f, j]; -1 and 0 everywhere else, beyond counts too.
+
+    An open start is a detection with link < 0 and no gap link yet; an open end one that no detection of the next frame links
+    to and no gap link points at yet.  Passes g = 2, 3, ..., max_gap + 1, shortest gaps first: for every frame f with
+    f - g >= 0 and no movie_start flag in the frames f - g + 1 .. f, the full rectangular assignment between the open ends
+    of frame f - g and the open starts of frame f (both in ascending detection index) is solved exactly as
+    link_particles_movie solves a frame pair (_assign_pair_numpy), then pairs longer than max_distance are dropped: they stay
+    open for the later passes, an accepted pair closes both its ends.  CUDA tensors go to the kernel (ops.close_gaps),
+    anything else to its restatement."""
+    max_gap = _check_max_gap(max_gap)
+    if float(max_distance) != float(max_distance):
+        raise ValueError("max_distance is NaN")
+    if _is_cuda(coords):
+        if not (_is_cuda(counts) and _is_cuda(link)):
+            raise ValueError("CUDA coords [F, cap, 2] need CUDA counts [F] and a CUDA link [F, cap]")
+        from .. import ops
+        return ops.close_gaps(coords.int(), counts.int(), link.int(), max_gap, float(max_distance), movie_start)
+    as_tensor = torch.is_tensor(coords)
+    padded, counts = _padded_detections(coords, counts)
+    F, cap = padded.shape[:2]
+    if cap > LINK_MAX_DETECTIONS:
+        raise ValueError(f"{cap} detections per frame, the linking kernel's limit is {LINK_MAX_DETECTIONS} "
+                         f"(LINK_MAX_DETECTIONS)")
+    link = link.detach().cpu().numpy() if torch.is_tensor(link) else np.asarray(link)
+    if link.shape != (F, cap):
+        raise ValueError(f"link must be [{F}, {cap}], got {tuple(link.shape)}")
+    gp, gf = _close_gaps_numpy(padded, counts, link, max_gap, float(max_distance), _check_movie_start(movie_start, F))
+    return (torch.from_numpy(gp), torch.from_numpy(gf)) if as_tensor else (gp, gf)
+
+
+def _chain_numpy(link, counts, ms, gap_partner=None, gap_frames=None):
+    """csrc/linking.hip::lk_chain_kernel (with gap tensors: lk_chain_gaps_kernel) on the host -> (ids [F, cap] int32, -1
+    beyond counts; lengths [F * cap] int32, detections per track; number of tracks)."""
     F, cap = link.shape
     ids, lengths = np.full((F, cap), -1, np.int32), np.zeros(F * cap, np.int32)
     next_id, n_prev = 0, 0
     for f in range(F):
         n = int(counts[f])
-        l = link[f, :n].astype(np.int64) if f > 0 and not (ms is not None and ms[f]) else np.full(n, -1, np.int64)
+        fresh = f == 0 or (ms is not None and ms[f])
+        l = link[f, :n].astype(np.int64) if not fresh else np.full(n, -1, np.int64)
         l = np.where(l >= n_prev, -1, l)
         new = l < 0
-        cur = np.where(new, next_id + np.cumsum(new) - 1, ids[f - 1, np.maximum(l, 0)] if f > 0 else 0)
+        cur = np.where(new, 0, ids[f - 1, np.maximum(l, 0)] if f > 0 else 0)
+        if gap_frames is not None and not fresh:
+            g, p = gap_frames[f, :n].astype(np.int64), gap_partner[f, :n].astype(np.int64)
+            ok = new & (g >= 2) & (g <= LINK_MAX_GAP + 1) & (f - g >= 0)
+            src = np.where(ok, f - g, 0)
+            ok &= (p >= 0) & (p < np.asarray(counts)[src])   # never read past the partner frame
+            cur = np.where(ok, ids[src, np.where(ok, p, 0)], cur)
+            new = new & ~ok
+        cur = np.where(new, next_id + np.cumsum(new) - 1, cur)
         ids[f, :n] = cur
         lengths[cur] = np.where(new, 1, lengths[cur] + 1)
         next_id += int(new.sum())
@@ -401,17 +482,25 @@ def _chain_numpy(link, counts, ms):
     return ids, lengths, next_id
 
 
-def chain_tracks(link, counts, movie_start=None):
+def chain_tracks(link, counts, movie_start=None, gap_partner=None, gap_frames=None):
     """Track ids from the links of link_particles_movie: a linked detection inherits its partner's id, an unlinked one takes
     the next free id in ascending detection index, frame 0 (and every movie_start frame) starts one track per detection: the
     numbering of the reference's track_particles.  link [F, cap], counts [F] -> (ids [F, cap] int32, -1 beyond counts;
     lengths [F * cap] int32, the number of positions of track i at index i; n_tracks [1] int32) of the input's kind.  CUDA
-    tensors go to the kernel (ops.chain_tracks)."""
+    tensors go to the kernel (ops.chain_tracks).  With gap_partner / gap_frames [F, cap] (close_gaps_movie) an unlinked
+    detection with gap_frames = g > 0 inherits the id of detection gap_partner of frame f - g instead of opening a track;
+    lengths counts detections, not the rows fill_gaps adds."""
+    if (gap_partner is None) != (gap_frames is None):
+        raise ValueError("gap_partner and gap_frames must both be given or both be None")
     if _is_cuda(link):
         if not _is_cuda(counts):
             raise ValueError("a CUDA link tensor needs CUDA counts")
         from .. import ops
-        return ops.chain_tracks(link.int(), counts.int(), movie_start)
+        if gap_partner is None:
+            return ops.chain_tracks(link.int(), counts.int(), movie_start)
+        if not (_is_cuda(gap_partner) and _is_cuda(gap_frames)):
+            raise ValueError("a CUDA link tensor needs CUDA gap_partner and gap_frames")
+        return ops.chain_tracks(link.int(), counts.int(), movie_start, gap_partner.int(), gap_frames.int())
     as_tensor = torch.is_tensor(link)
     link = link.detach().numpy() if as_tensor else np.asarray(link)
     counts = counts.detach().numpy() if torch.is_tensor(counts) else np.asarray(counts)
@@ -422,7 +511,12 @@ def chain_tracks(link, counts, movie_start=None):
         raise ValueError(f"counts must be [{F}], got {tuple(counts.shape)}")
     if F and (counts.min() < 0 or counts.max() > cap):
         raise ValueError(f"counts must lie in 0 .. {cap}")
-    ids, lengths, n = _chain_numpy(link, counts, _check_movie_start(movie_start, F))
+    if gap_partner is not None:
+        gap_partner = gap_partner.detach().cpu().numpy() if torch.is_tensor(gap_partner) else np.asarray(gap_partner)
+        gap_frames = gap_frames.detach().cpu().numpy() if torch.is_tensor(gap_frames) else np.asarray(gap_frames)
+        if gap_partner.shape != (F, cap) or gap_frames.shape != (F, cap):
+            raise ValueError(f"gap_partner and gap_frames must be [{F}, {cap}]")
+    ids, lengths, n = _chain_numpy(link, counts, _check_movie_start(movie_start, F), gap_partner, gap_frames)
     n = np.array([n], np.int32)
     return (torch.from_numpy(ids), torch.from_numpy(lengths), torch.from_numpy(n)) if as_tensor else (ids, lengths, n)
 
@@ -445,17 +539,67 @@ def _detections_table(coords, counts, ids, lengths, min_track_length):
     return fr, coords[fr, j, 0].long(), coords[fr, j, 1].long(), torch.where(in_long, new_id[tid], tid), in_long
 
 
+def fill_gaps(coords, counts, ids, lengths, gap_partner, gap_frames, min_track_length=1):
+    """_detections_table with the frames a gap link bridges filled in, torch ops on the tensors' device: coords [F, cap, 2],
+    counts [F], ids [F, cap] and lengths from chain_tracks(..., gap_partner, gap_frames) -> (frame, y, x, track_id,
+    in_long_track, filled), int64 / bool [N].  A gap link from detection gap_partner[f, j] of frame f - g at (y0, x0) to
+    detection (f, j) at (y1, x1) adds the rows of the frames f - g + k, k = 1 .. g - 1, at rint(y0 + (y1 - y0) * k / g) and the
+    same for x (float64, round-half-to-even, the rounding of extract_patches_flat), with the track's id and filled = True.
+    Rows are in the table's order, frames ascending and ascending id within a frame, so every track is contiguous in frames:
+    msd.track_msd and track_sequences take the filled table as it is.  Tracks of at least min_track_length DETECTIONS (lengths
+    does not count the added rows) are renumbered as _detections_table renumbers them."""
+    F, cap = ids.shape
+    dev = ids.device
+    valid = torch.arange(cap, device=dev)[None, :] < counts[:, None]
+    fr, j = valid.nonzero(as_tuple=True)
+    tid = ids[fr, j].long()
+    y, x = coords[fr, j, 0].long(), coords[fr, j, 1].long()
+    g = gap_frames[fr, j].long()
+    has = g > 1
+    sf, sg, stid = fr[has], g[has], tid[has]
+    f0 = (sf - sg).clamp_min(0)
+    p = gap_partner[sf, j[has]].long().clamp(0, cap - 1)
+    y0, x0 = coords[f0, p, 0].double(), coords[f0, p, 1].double()
+    y1, x1 = y[has].double(), x[has].double()
+    n_add = sg - 1
+    which = torch.repeat_interleave(torch.arange(len(sg), device=dev), n_add)
+    k = torch.arange(len(which), device=dev) - (torch.cumsum(n_add, 0) - n_add)[which] + 1
+    kd, gd = k.double(), sg[which].double()
+    fy = torch.round(y0[which] + (y1[which] - y0[which]) * kd / gd).long()
+    fx = torch.round(x0[which] + (x1[which] - x0[which]) * kd / gd).long()
+    fr = torch.cat([fr, f0[which] + k])
+    y, x, tid = torch.cat([y, fy]), torch.cat([x, fx]), torch.cat([tid, stid[which]])
+    filled = torch.cat([torch.zeros(len(j), dtype=torch.bool, device=dev), torch.ones(len(which), dtype=torch.bool, device=dev)])
+    order = torch.argsort(fr * (lengths.numel() + 1) + tid, stable=True)
+    fr, y, x, tid, filled = fr[order], y[order], x[order], tid[order], filled[order]
+    is_long = (lengths > 0) & (lengths >= min_track_length)
+    new_id = torch.cumsum(is_long, 0) - 1
+    in_long = is_long[tid]
+    return fr, y, x, torch.where(in_long, new_id[tid], tid), in_long, filled
+
+
+def _check_gap_args(max_gap, max_gap_distance, max_linking_distance):
+    max_gap = _check_max_gap(max_gap, allow_zero=True)
+    dist = max_linking_distance if max_gap_distance is None else max_gap_distance
+    if float(dist) != float(dist):
+        raise ValueError("max_gap_distance is NaN")
+    return max_gap, float(dist)
+
+
 def track_particles_tensors(movie, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
                             max_linking_distance=15, min_track_length=3, max_peaks_per_frame=512, movie_start=None,
-                            return_dog=True):
+                            return_dog=True, max_gap=0, max_gap_distance=None):
     """Detection, linking, chaining, length filter and renumbering of a CUDA movie [F, H, W] without a copy of the
     coordinates to the host -> (dict of CUDA tensors frame, y, x, track_id (int64 [N], the reference's detections table in its
     row order), in_long_track (bool [N]: the rows whose track has >= min_track_length positions and so carries a renumbered
     id), n_tracks ([1] int32, before the length filter); DoG movie or None).  frame / y / x of the rows with in_long_track feed
     extract_patches_flat and refine_localizations as they are.  movie_start [F] marks the first frames of several movies
-    concatenated along F."""
+    concatenated along F.  max_gap > 0 (up to LINK_MAX_GAP) closes gaps of up to that many missed frames within
+    max_gap_distance pixels (default: max_linking_distance; close_gaps_movie) and fills them (fill_gaps): the dict gains
+    filled (bool [N], the interpolated rows), and min_track_length keeps counting detections."""
     if not _is_cuda(movie):
         raise ValueError("track_particles_tensors needs a CUDA movie; use track_particles_flat(..., linking='device') on the host")
+    max_gap, gap_distance = _check_gap_args(max_gap, max_gap_distance, max_linking_distance)
     w1, w2 = _check_detection_args(movie.shape, sigma1, sigma2, min_distance)
     if max_peaks_per_frame > LINK_MAX_DETECTIONS:
         raise ValueError(f"max_peaks_per_frame = {max_peaks_per_frame}, the linking kernel's limit is {LINK_MAX_DETECTIONS} "
@@ -464,6 +608,12 @@ def track_particles_tensors(movie, sigma1=1.0, sigma2=2.0, threshold_percentage=
     count, coords, _, dog = ops.dog_peaks(movie.float(), w1, w2, threshold_percentage, int(min_distance), max_peaks_per_frame,
                                           return_dog)
     link = ops.link_frames(coords, count, float(max_linking_distance), movie_start)
+    if max_gap > 0:
+        gap_partner, gap_frames = ops.close_gaps(coords, count, link, max_gap, gap_distance, movie_start)
+        ids, lengths, n_tracks = ops.chain_tracks(link, count, movie_start, gap_partner, gap_frames)
+        fr, y, x, tid, in_long, filled = fill_gaps(coords, count, ids, lengths, gap_partner, gap_frames, min_track_length)
+        return {"frame": fr, "y": y, "x": x, "track_id": tid, "in_long_track": in_long, "filled": filled,
+                "n_tracks": n_tracks}, dog
     ids, lengths, n_tracks = ops.chain_tracks(link, count, movie_start)
     fr, y, x, tid, in_long = _detections_table(coords, count, ids, lengths, min_track_length)
     return {"frame": fr, "y": y, "x": x, "track_id": tid, "in_long_track": in_long, "n_tracks": n_tracks}, dog
@@ -481,46 +631,66 @@ def _tracks_from_table(fr, y, x, tid, in_long):
 
 
 def _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance, max_linking_distance, min_track_length, verbose,
-                  max_peaks_per_frame):
+                  max_peaks_per_frame, max_gap=0, gap_distance=None):
     """track_particles_flat with linking="device": the kernels for a CUDA movie, their restatements for anything else."""
+    filled = None
     if _is_cuda(movie):
         t, dog = track_particles_tensors(movie, sigma1, sigma2, threshold_percentage, min_distance, max_linking_distance,
-                                         min_track_length, max_peaks_per_frame)
-        keys = ("frame", "y", "x", "track_id", "in_long_track")
+                                         min_track_length, max_peaks_per_frame, max_gap=max_gap, max_gap_distance=gap_distance)
+        keys = ("frame", "y", "x", "track_id", "in_long_track") + (("filled",) if max_gap > 0 else ())
         packed = torch.stack([t[k].long() for k in keys]).cpu().numpy()          # the one copy to the host
         fr, y, x, tid, in_long = packed[0], packed[1], packed[2], packed[3], packed[4].astype(bool)
+        if max_gap > 0:
+            filled = packed[5].astype(bool)
         n_all = int(t["n_tracks"])
     else:
         coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
         padded, counts = _padded_detections(coords, None)
         link = link_particles_movie(padded, counts, max_linking_distance)
-        ids, lengths, n_all = _chain_numpy(link, counts, None)
-        fr, y, x, tid, in_long = (a.numpy() for a in _detections_table(
-            torch.from_numpy(padded), torch.from_numpy(counts), torch.from_numpy(ids), torch.from_numpy(lengths),
-            min_track_length))
+        if max_gap > 0:
+            gp, gf = _close_gaps_numpy(padded, counts, link, max_gap, gap_distance, None)
+            ids, lengths, n_all = _chain_numpy(link, counts, None, gp, gf)
+            fr, y, x, tid, in_long, filled = (a.numpy() for a in fill_gaps(
+                torch.from_numpy(padded), torch.from_numpy(counts), torch.from_numpy(ids), torch.from_numpy(lengths),
+                torch.from_numpy(gp), torch.from_numpy(gf), min_track_length))
+        else:
+            ids, lengths, n_all = _chain_numpy(link, counts, None)
+            fr, y, x, tid, in_long = (a.numpy() for a in _detections_table(
+                torch.from_numpy(padded), torch.from_numpy(counts), torch.from_numpy(ids), torch.from_numpy(lengths),
+                min_track_length))
     if verbose:
         per_frame = np.bincount(fr, minlength=len(movie))
         for f, n in enumerate(per_frame):
             print(f"Frame {f}: {n} particles detected")
     det = {"frame": fr.copy(), "y": y.copy(), "x": x.copy(), "track_id": tid.copy()}
+    if filled is not None:
+        det["filled"] = filled.copy()
     return _tracks_from_table(fr, y, x, tid, in_long), det, dog, n_all
 
 
 def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
-                         max_linking_distance=15, min_track_length=3, verbose=False, max_peaks_per_frame=512, linking="host"):
+                         max_linking_distance=15, min_track_length=3, verbose=False, max_peaks_per_frame=512, linking="host",
+                         max_gap=0, max_gap_distance=None):
     """track_particles without pandas: (tracks, detections as a dict of int64 arrays frame / y / x / track_id, DoG movie
     [F, H, W]).  linking="host" (default): scipy's assignment per frame in a loop on the host, rows in the order of the
     reference's active tracks.  linking="device": all frame pairs in one launch of csrc/linking.hip and the ids chained on the
     device for a CUDA movie (one copy to the host, for the dictionaries), the kernels' restatement for a host movie; same
-    result wherever every frame pair has a single optimal assignment (see link_particles_movie)."""
+    result wherever every frame pair has a single optimal assignment (see link_particles_movie).  max_gap > 0 (with
+    linking="device" only) closes gaps of up to max_gap missed frames within max_gap_distance pixels (default:
+    max_linking_distance) and fills them with interpolated positions: tracks and detections include the filled rows, and the
+    detections gain the bool column filled."""
     if linking not in ("host", "device"):
         raise ValueError(f"linking must be 'host' or 'device', got {linking!r}")
+    max_gap, gap_distance = _check_gap_args(max_gap, max_gap_distance, max_linking_distance)
+    if max_gap > 0 and linking != "device":
+        raise ValueError(f"max_gap = {max_gap} needs linking=\"device\": the host loop links frame to frame only")
     movie = image_sequence
     if not torch.is_tensor(movie) and not isinstance(movie, np.ndarray):
         movie = np.stack([np.asarray(f) for f in movie])
     if linking == "device":
         tracks, det, dog, n_all = _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance,
-                                                max_linking_distance, min_track_length, verbose, max_peaks_per_frame)
+                                                max_linking_distance, min_track_length, verbose, max_peaks_per_frame,
+                                                max_gap, gap_distance)
         print(f"Tracking complete: {n_all} total tracks, {len(tracks)} tracks with ≥{min_track_length} frames")
         return tracks, det, dog
     coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
@@ -533,19 +703,22 @@ def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_perce
 
 
 def track_particles(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
-                    max_linking_distance=15, min_track_length=3, verbose=False, linking="host"):
+                    max_linking_distance=15, min_track_length=3, verbose=False, linking="host", max_gap=0,
+                    max_gap_distance=None):
     """Reference track_particles -> (tracks {id: [(frame, y, x), ...]}, all_detections DataFrame with columns frame, y, x,
     track_id, filtered_images: the DoG movie [F, H, W], one image per frame when iterated).  Detection runs for the whole
-    movie at once; linking as in track_particles_flat."""
+    movie at once; linking, max_gap and max_gap_distance as in track_particles_flat (with max_gap > 0 the DataFrame gains the
+    column filled)."""
     import pandas as pd
     tracks, det, dog = track_particles_flat(image_sequence, sigma1, sigma2, threshold_percentage, min_distance,
-                                            max_linking_distance, min_track_length, verbose, linking=linking)
-    return tracks, pd.DataFrame(det, columns=["frame", "y", "x", "track_id"]), dog
+                                            max_linking_distance, min_track_length, verbose, linking=linking,
+                                            max_gap=max_gap, max_gap_distance=max_gap_distance)
+    return tracks, pd.DataFrame(det, columns=["frame", "y", "x", "track_id"] + (["filled"] if "filled" in det else [])), dog
 
 
 def analyze_microscopy_sequence(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
                                 max_linking_distance=15, min_track_length=3, visualize=False, verbose=False,
-                                output_prefix=None, linking="host"):
+                                output_prefix=None, linking="host", max_gap=0, max_gap_distance=None):
     """Reference analyze_microscopy_sequence: track_particles, and with output_prefix the files <prefix>_detections.csv and
     <prefix>_tracks.pkl.  Plotting is not part of this package: visualize defaults to False and True raises."""
     if visualize:
@@ -555,7 +728,8 @@ def analyze_microscopy_sequence(image_sequence, sigma1=1.0, sigma2=2.0, threshol
                                                        threshold_percentage=threshold_percentage, min_distance=min_distance,
                                                        max_linking_distance=max_linking_distance,
                                                        min_track_length=min_track_length, verbose=verbose,
-                                                       linking=linking)
+                                                       linking=linking, max_gap=max_gap,
+                                                       max_gap_distance=max_gap_distance)
     if output_prefix:
         import pickle
         all_detections.to_csv(f"{output_prefix}_detections.csv", index=False)
@@ -803,8 +977,17 @@ def tracks_to_dataframe(tracks, patches, patch_size):
 def tracks_table_by_track(table):
     """The dict track_particles_tensors returns -> (frame, y, x, track_id [N'] int64, offsets [n_tracks + 1] int64), tensors on
     the table's device: the rows with in_long_track, stably sorted by track_id (the table is in frame order, so every track
-    stays in frame order), and the CSR offsets of the tracks in ascending id."""
+    stays in frame order), and the CSR offsets of the tracks in ascending id.  A table with the column filled
+    (track_particles_tensors(..., max_gap > 0)) returns a sixth tensor, filled [N'] bool, in the same row order."""
     keep = torch.as_tensor(table["in_long_track"]).bool()
+    if "filled" in table:
+        fr, y, x, tid, offsets = tracks_table_by_track({k: v for k, v in table.items() if k != "filled"})
+        filled = torch.as_tensor(table["filled"]).to(keep.device)
+        if filled.shape != keep.shape:
+            raise ValueError("filled must have one entry per row")
+        filled = filled[keep]
+        return fr, y, x, tid, offsets, filled[torch.argsort(torch.as_tensor(table["track_id"]).to(keep.device)[keep],
+                                                            stable=True)].bool()
     cols = [torch.as_tensor(table[k]).to(keep.device)[keep] for k in ("frame", "y", "x", "track_id")]
     if not (len(cols[0]) == len(cols[1]) == len(cols[2]) == len(cols[3])):
         raise ValueError("frame, y, x and track_id must have one entry per row")
@@ -953,7 +1136,9 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     each track (float64, in sequence order: deterministic).  -> dict of CUDA tensors track_id, length, n_sequences (int64
     [n_tracks]), D_model (float64; NaN where n_sequences == 0), D_msd, D_msd_weighted (float64, in pixels^2 per unit of dt) and
     msd [n_tracks, longest track].  D_model is the model's output in the units it was trained in: no scale factor is applied
-    here."""
+    here.  With max_gap > 0 among the tracking arguments the tracks are gap-closed and filled: length counts rows, the filled
+    ones included, the result gains n_filled (int64 [n_tracks], the filled rows of each track), and with refine the filled
+    rows are fitted on their patch like any other row (a failed fit falls back to the interpolated position)."""
     if not _is_cuda(movie):
         raise ValueError("estimate_track_diffusion needs a CUDA movie; move it to the GPU (movie.cuda())")
     _check_sequence_args(seq_len, tail, patch_size)
@@ -962,7 +1147,8 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     from .. import ops
     tracking_kwargs.setdefault("return_dog", False)
     table, _ = track_particles_tensors(movie, **tracking_kwargs)
-    fr, y, x, tid, offsets = tracks_table_by_track(table)
+    by_track = tracks_table_by_track(table)
+    fr, y, x, tid, offsets = by_track[:5]
     lengths = offsets[1:] - offsets[:-1]
     n_tracks = len(lengths)
     movie = movie.float()
@@ -984,8 +1170,12 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     d_model = torch.full((n_tracks,), float("nan"), dtype=torch.float64, device=movie.device)
     if len(per_seq):
         d_model = torch.where(n_sequences > 0, torch.segment_reduce(per_seq, "mean", lengths=n_sequences), d_model)
-    return {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
-            "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}
+    res = {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
+           "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}
+    if len(by_track) > 5:
+        row_track = torch.repeat_interleave(torch.arange(n_tracks, device=movie.device), lengths)
+        res["n_filled"] = torch.bincount(row_track[by_track[5]], minlength=n_tracks)
+    return res
 
 
 # ----------------------------------------------------------------------------------------------------------------------

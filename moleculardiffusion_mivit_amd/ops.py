@@ -660,23 +660,75 @@ def link_frames(coords: torch.Tensor, count: torch.Tensor, max_distance: float =
     return link
 
 
-def chain_tracks(link: torch.Tensor, count: torch.Tensor, movie_start=None):
+LINK_MAX_GAP = 8             # csrc/linking.hip: missed frames a gap link may bridge
+
+
+def _check_max_gap(max_gap, name):
+    if isinstance(max_gap, bool) or not isinstance(max_gap, (int, float)) or int(max_gap) != max_gap \
+            or not 1 <= max_gap <= LINK_MAX_GAP:
+        raise ValueError(f"{name}: max_gap must be an integer from 1 to {LINK_MAX_GAP} (LINK_MAX_GAP), got {max_gap!r}")
+    return int(max_gap)
+
+
+def close_gaps(coords: torch.Tensor, count: torch.Tensor, link: torch.Tensor, max_gap: int, max_distance: float = 15.0,
+               movie_start=None):
+    """Links across missed detections (csrc/linking.hip, mivit_close_gaps): coords [F, cap, 2] int32, count [F] int32 and link
+    [F, cap] int32 (link_frames) on the GPU -> (gap_partner [F, cap] int32, gap_frames [F, cap] int32): the start of a track
+    at (f, j) continues the track that ended at detection gap_partner[f, j] of frame f - gap_frames[f, j], with
+    gap_frames - 1 <= max_gap frames missed in between; -1 / 0 everywhere else.  Passes g = 2 .. max_gap + 1, shortest gaps
+    first; per pass and frame the full assignment between the open ends of frame f - g and the open starts of frame f is
+    solved as link_frames solves it, then pairs longer than max_distance are dropped and stay open for the later passes.  No
+    gap link crosses a movie_start frame.  1 <= max_gap <= LINK_MAX_GAP."""
+    if coords.dtype != torch.int32 or coords.dim() != 3 or coords.shape[2] != 2 or coords.device.type != "cuda":
+        raise ValueError("close_gaps: coords must be an int32 GPU tensor [F, cap, 2]")
+    F, cap = coords.shape[0], coords.shape[1]
+    if count.shape != (F,):
+        raise ValueError(f"close_gaps: count must be [{F}], got {tuple(count.shape)}")
+    if not torch.is_tensor(link) or link.dtype != torch.int32 or link.device.type != "cuda" or link.shape != (F, cap):
+        raise ValueError(f"close_gaps: link must be an int32 GPU tensor [{F}, {cap}]")
+    count, ms = _link_args(count, cap, movie_start, "close_gaps")
+    max_gap = _check_max_gap(max_gap, "close_gaps")
+    if not float(max_distance) == float(max_distance):
+        raise ValueError("close_gaps: max_distance is NaN")
+    coords, link = coords.contiguous(), link.contiguous()
+    gap_partner = torch.empty(F, cap, dtype=torch.int32, device=coords.device)
+    gap_frames = torch.empty(F, cap, dtype=torch.int32, device=coords.device)
+    ws = torch.empty(max(F * cap, 1), dtype=torch.uint8, device=coords.device)
+    N.check(N.lib.mivit_close_gaps(_p(coords), _p(count), _p(link), _p(ms), F, cap, max_gap, float(max_distance),
+                                   _p(gap_partner), _p(gap_frames), _p(ws), ws.numel(), _s(coords)), "mivit_close_gaps")
+    return gap_partner, gap_frames
+
+
+def chain_tracks(link: torch.Tensor, count: torch.Tensor, movie_start=None, gap_partner=None, gap_frames=None):
     """Track ids from the links (csrc/linking.hip, mivit_chain_tracks): link [F, cap] int32 (link_frames), count [F] int32 ->
     (ids [F, cap] int32, -1 beyond count[f]; lengths [F * cap] int32, the number of positions of track i at index i, 0 beyond
     the last track; n_tracks [1] int32).  Ids are handed out as the reference does: frame 0 (and every movie_start frame) one
-    per detection, later a linked detection inherits, an unlinked one takes the next id in ascending detection index."""
+    per detection, later a linked detection inherits, an unlinked one takes the next id in ascending detection index.  With
+    gap_partner / gap_frames [F, cap] int32 (close_gaps; mivit_chain_tracks_gaps) an unlinked detection with a gap link
+    inherits the id of its partner gap_frames frames earlier; lengths keeps counting detections."""
     if link.dtype != torch.int32 or link.dim() != 2 or link.device.type != "cuda":
         raise ValueError("chain_tracks: link must be an int32 GPU tensor [F, cap]")
     F, cap = link.shape
     if count.shape != (F,):
         raise ValueError(f"chain_tracks: count must be [{F}], got {tuple(count.shape)}")
     count, ms = _link_args(count, cap, movie_start, "chain_tracks")
+    if (gap_partner is None) != (gap_frames is None):
+        raise ValueError("chain_tracks: gap_partner and gap_frames must both be given or both be None")
+    for name, t in (("gap_partner", gap_partner), ("gap_frames", gap_frames)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int32 or t.device.type != "cuda"
+                              or t.shape != (F, cap)):
+            raise ValueError(f"chain_tracks: {name} must be an int32 GPU tensor [{F}, {cap}]")
     link = link.contiguous()
     ids = torch.full((F, cap), -1, dtype=torch.int32, device=link.device)
     lengths = torch.zeros(F * cap, dtype=torch.int32, device=link.device)
     n_tracks = torch.zeros(1, dtype=torch.int32, device=link.device)
-    N.check(N.lib.mivit_chain_tracks(_p(link), _p(count), _p(ms), F, cap, _p(ids), _p(lengths), _p(n_tracks), _s(link)),
-            "mivit_chain_tracks")
+    if gap_partner is None:
+        N.check(N.lib.mivit_chain_tracks(_p(link), _p(count), _p(ms), F, cap, _p(ids), _p(lengths), _p(n_tracks), _s(link)),
+                "mivit_chain_tracks")
+    else:
+        gap_partner, gap_frames = gap_partner.contiguous(), gap_frames.contiguous()
+        N.check(N.lib.mivit_chain_tracks_gaps(_p(link), _p(gap_partner), _p(gap_frames), _p(count), _p(ms), F, cap, LINK_MAX_GAP,
+                                              _p(ids), _p(lengths), _p(n_tracks), _s(link)), "mivit_chain_tracks_gaps")
     return ids, lengths, n_tracks
 
 

@@ -9,7 +9,9 @@ on the large one the CPU paths run on the first --cpu-frames frames and the time
 Linking rows: the host loop (_link_tracks: scipy per frame), the numpy restatement of csrc/linking.hip
 (link_particles_movie on host arrays, on the first --cpu-frames frames), the device (ops.link_frames + ops.chain_tracks +
 the table, events), and the whole track_particles_flat with linking="host" and linking="device" (wall clock around a
-synchronise, minimum of 5).
+synchronise, minimum of 5).  Gap closing: ops.close_gaps alone at max_gap 2 and 8 (events), and the whole
+track_particles_flat(linking="device") at max_gap 0 and 2; the movies of this script have no dark frames, so the gaps closed
+are the detector's own misses.
 Diffusion rows (both movie sizes): the stage from the detections table to the model's input and the MSD estimates on the device
 (tracks_table_by_track + refine_localizations_tensors + ops.track_msd + track_sequences; csrc/diffusion.hip) against the
 host-shaped way of doing the same (extract_patches_flat + normalize_images, refine_localizations on the host, a Python loop of
@@ -119,6 +121,9 @@ def bench_linking(mov_gpu, cpu_frames):
         ids, lengths, _ = ops.chain_tracks(lk, count)
         T._detections_table(coords, count, ids, lengths, 3)
     res["gpu_linking_s"] = t_events(device_linking)
+    for max_gap in (2, ops.LINK_MAX_GAP):
+        res[f"gpu_close_gaps_{max_gap}_s"] = t_events(lambda: ops.close_gaps(coords, count, link, max_gap, 15.0))
+    res["gap_links_2"] = int((ops.close_gaps(coords, count, link, 2, 15.0)[1] > 0).sum())
     n = count.cpu().numpy()
     host = coords.cpu().numpy().astype(np.int64)
     per_frame = [host[f, :n[f]] for f in range(len(n))]
@@ -198,12 +203,15 @@ def bench(name, mov_gpu, cpu_frames):
     _, _, st = ops.refine_gaussian(patches)
     res["fits_not_converged"] = int((st != 0).sum())
 
-    def whole(linking="host"):
-        T.track_particles_flat(mov_gpu, linking=linking)
+    def whole(linking="host", max_gap=0):
+        T.track_particles_flat(mov_gpu, linking=linking, max_gap=max_gap)
         torch.cuda.synchronize()
     res["gpu_track_particles_s"] = t_wall(quiet(whole), reps=5)
     quiet(lambda: whole("device"))()
     res["gpu_track_particles_device_linking_s"] = t_wall(quiet(lambda: whole("device")), reps=5)
+    res["gpu_track_particles_device_linking_max_gap_0_s"] = t_wall(quiet(lambda: whole("device", 0)), reps=5)
+    quiet(lambda: whole("device", 2))()
+    res["gpu_track_particles_device_linking_max_gap_2_s"] = t_wall(quiet(lambda: whole("device", 2)), reps=5)
     res.update(bench_linking(mov_gpu, cpu_frames))
     res.update(bench_diffusion(mov_gpu))
     n = min(F, cpu_frames)

@@ -2,10 +2,15 @@
 (helpers/generation.py, csrc/movie.hip), estimate_track_diffusion (helpers/tracking.py) and score_tracking, on the GPU.  Prints
 one JSON line: the tracking scores and, per track, D_true (of the particle most of its rows were matched to), D_msd,
 D_msd_weighted and D_model, all in the units of estimate_track_diffusion (pixels^2 per frame for the MSD estimates; the
-model's own output units for D_model).  A tool, not a test: it asserts no accuracy.
+model's own output units for D_model), and how the particles were cut into tracks: tracks_per_particle (the mean over the
+particles that got a track of the bincount of score_tracking's particle_id), median_track_length (rows, filled ones
+included) and n_filled.  --blink P makes every particle dark with probability P in each frame of its life (simulate_movie's
+blink), --max-gap N closes and fills gaps of up to N missed frames (track_particles_tensors' max_gap).  A tool, not a test: it
+asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
+                                          [--blink 0.05] [--max-gap 2]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -37,6 +42,8 @@ def main():
     ap.add_argument("--max-distance", type=float, default=2.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--noise-free", action="store_true")
+    ap.add_argument("--blink", type=float, default=None)
+    ap.add_argument("--max-gap", type=int, default=0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
@@ -46,20 +53,27 @@ def main():
     H, W = args.size
     g = torch.Generator(device="cuda").manual_seed(args.seed)
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props,
-                                      generator=g, device="cuda")
+                                      generator=g, device="cuda", blink=args.blink)
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     bm, bs = props["background_intensity"]
     norm = (bm, bs, props["particle_intensity"][0] + bm)
-    est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm)
-    table, _ = trk.track_particles_tensors(movie, return_dog=False)
-    fr, y, x, tid, _ = trk.tracks_table_by_track(table)
+    est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap)
+    table, _ = trk.track_particles_tensors(movie, return_dog=False, max_gap=args.max_gap)
+    fr, y, x, tid = trk.tracks_table_by_track(table)[:4]
     score = trk.score_tracking(fr, y, x, tid, truth, max_distance=args.max_distance)
     assert torch.equal(score["track_id"], est["track_id"])
+    matched = score["particle_id"][score["particle_id"] >= 0]
+    per_particle = torch.bincount(matched, minlength=args.particles)
     out = {"recall": float(score["recall"]), "precision": float(score["precision"]), "rmse": float(score["rmse"]),
-           "n_tracks": int(len(est["track_id"])), "n_particles": args.particles,
+           "n_tracks": int(len(est["track_id"])), "n_particles": args.particles, "blink": args.blink, "max_gap": args.max_gap,
+           "tracks_per_particle": float(per_particle[per_particle > 0].double().mean()) if len(matched) else float("nan"),
+           "particles_without_track": int((per_particle == 0).sum()),
+           "median_track_length": float(est["length"].double().median()) if len(est["length"]) else float("nan"),
+           "n_sequences": int(est["n_sequences"].sum()),
+           "n_filled": int(est["n_filled"].sum()) if "n_filled" in est else 0,
            "tracks": [{"track_id": int(t), "length": int(n), "particle_id": int(p), "purity": float(pu), "D_true": float(dt),
                        "D_msd": float(a), "D_msd_weighted": float(b), "D_model": float(c)}
                       for t, n, p, pu, dt, a, b, c in zip(est["track_id"].tolist(), est["length"].tolist(),
