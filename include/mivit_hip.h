@@ -643,8 +643,9 @@ int mivit_forward(const mivit_plan *plan, const float *params, const float *x, c
                   float *out, void *stream);
 
 /* Runs backward stages [stage_begin, stage_end).  dout: fp32 [B,output_dim].  grads: fp32 arena, same
- * layout as params; every float of a stage's range is OVERWRITTEN (no accumulation).  dfeatures (fp32
- * [B,Fg]) and dx_tokens (fp32 [B,T,E], _EXTERNAL only) may be NULL when not needed. */
+ * layout as params; every parameter element of a stage's range is OVERWRITTEN (no accumulation; the rows of
+ * transformer.pos_embedding beyond the sequence with 0), the alignment padding between tensors is never
+ * written.  dfeatures (fp32 [B,Fg]) and dx_tokens (fp32 [B,T,E], _EXTERNAL only) may be NULL when not needed. */
 int mivit_backward(const mivit_plan *plan, const float *params, const float *x, const float *features,
                    int B, int T, void *workspace, size_t workspace_bytes, const float *dout,
                    float *grads, float *dfeatures, float *dx_tokens,

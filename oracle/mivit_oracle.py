@@ -307,16 +307,25 @@ def encoder_layer(x, p, pre, H, act, trace=None):
     return x2
 
 
+def embed(p: Dict[str, torch.Tensor], cfg: MiViTConfig, x, training=True, bn_stats_out: Optional[dict] = None):
+    """The embedding step of GeneralTransformer.forward (models.py:331): frames [B,T,P,P] -> pre-norm tokens [B,T,E]."""
+    if cfg.embedding == "linear":
+        return embed_linear(x, p["embedding.proj.weight"], p["embedding.proj.bias"])
+    if cfg.embedding == "cnn":
+        return embed_cnn(x, p["embedding.conv.weight"], p["embedding.conv.bias"])
+    return embed_deepresnet(x, p, training, bn_stats_out)
+
+
 def forward(p: Dict[str, torch.Tensor], cfg: MiViTConfig, x, features=None, training=True,
             trace: Optional[dict] = None, bn_stats_out: Optional[dict] = None):
     """GeneralTransformer.forward (models.py:328-361) + Transformer.forward (:136-141)."""
+    return forward_from_tokens(p, cfg, embed(p, cfg, x, training, bn_stats_out), features, trace)
+
+
+def forward_from_tokens(p: Dict[str, torch.Tensor], cfg: MiViTConfig, tok, features=None, trace: Optional[dict] = None):
+    """Everything behind the embedding (models.py:334-361): the trunk on pre-norm tokens [B,T,E].  No ``embedding.*``
+    parameter is read, so autograd through ``tok`` gives the d(tokens) an external embedding receives."""
     act = _ACTS[cfg.activation]
-    if cfg.embedding == "linear":
-        tok = embed_linear(x, p["embedding.proj.weight"], p["embedding.proj.bias"])
-    elif cfg.embedding == "cnn":
-        tok = embed_cnn(x, p["embedding.conv.weight"], p["embedding.conv.bias"])
-    else:
-        tok = embed_deepresnet(x, p, training, bn_stats_out)
     tok_n = layer_norm(tok, p["norm.weight"], p["norm.bias"])                  # :334
     B = tok_n.shape[0]
 
