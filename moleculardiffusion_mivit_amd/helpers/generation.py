@@ -105,16 +105,21 @@ def render_frames(traj_px: torch.Tensor, nPosPerFrame: int, sigmas: Sequence[flo
     for s in sigmas:
         # spot / spot_max per axis, as ONE exponential of the difference of squared distances: the reference divides two
         # float64 Gaussians (a spot that left the frame still peaks at full intensity on the border); fp32 factors would
-        # underflow to 0 / 0 there
-        dx2 = (axis.view(1, 1, 1, G) - seg[..., 0:1]) ** 2
-        dy2 = (axis.view(1, 1, 1, G) - seg[..., 1:2]) ** 2
-        prof = torch.exp(-(dx2 - dx2.amin(dim=-1, keepdim=True)) / (2 * s * s))       # x profile (N,F,p,G), peak-normalised
-        profy = torch.exp(-(dy2 - dy2.amin(dim=-1, keepdim=True)) / (2 * s * s))      # y profile
+        # underflow to 0 / 0 there.  The difference is taken as (d - dpk) (d + dpk), dpk the distance to the nearest grid
+        # point: for a spot hundreds of grid steps outside the frame the two squares are near 1e5 and their fp32 roundings
+        # do not cancel (2e-5 in the argument under a PSF of 3 pixels), while d - dpk is a difference of grid points
+        prof, profy = (_peak_normalised_profile(axis.view(1, 1, 1, G) - seg[..., k:k + 1], s) for k in (0, 1))   # (N,F,p,G)
         px = prof.reshape(N, F_, p, P, up).mean(dim=-1)                   # mean pooling of each 1-D profile
         py = profy.reshape(N, F_, p, P, up).mean(dim=-1)
         # frame[y, x] = sum_p a_p * py_p[y] * px_p[x]
         out.append(torch.einsum("nfp,nfpy,nfpx->nfyx", spot_intensity, py, px))
     return torch.stack(out, dim=1)
+
+
+def _peak_normalised_profile(d, s):
+    """exp(-(d^2 - min d^2) / 2 s^2) along the last axis"""
+    dpk = torch.gather(d, -1, d.abs().argmin(dim=-1, keepdim=True))
+    return torch.exp(-((d - dpk) * (d + dpk)) / (2 * s * s))
 
 
 def _render_frames_hip(traj_px, nPosPerFrame, sigmas, output_size, upsampling_factor, spot_intensity, center):
