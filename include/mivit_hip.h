@@ -383,6 +383,23 @@ int mivit_track_sequences(const float *movie, int F, int H, int W, const int *fr
                           const int *seq_row, int n_seq, int T, int P, float lo, float denom, int normalize, float *seq,
                           void *stream);
 
+/* Fractional Gaussian noise, the increments of anomalous diffusion with MSD ~ t^alpha (the displacement law of the reference's
+ * disp_fbm, Experiments/mitochondria_simulation/mitochnodria.py:436-476, which draws them from the `fbm` package), csrc/fbm.hip,
+ * one workgroup per trajectory.  z [N, T, C] fp64 standard normals, 1 <= C <= 4 axes that share one exponent; gamma [U, T] fp64,
+ * one autocovariance row per distinct exponent, gamma[k] = (|k+1|^alpha - 2 |k|^alpha + |k-1|^alpha) / 2 computed by the caller
+ * (helpers/generation.fgn_autocovariance: no device pow); gamma_row [N] int32 in [0, U) names each trajectory's row (an entry
+ * outside is clamped: nothing is read out of bounds).  out [N, T, C] fp64 = L z per trajectory and axis, L the lower Cholesky
+ * factor of the T x T Toeplitz matrix of gamma, by the Durbin-Levinson recursion with all three sums of a step taken on the
+ * previous step's coefficients (v_0 = gamma[0], g_0 = sqrt(v_0) z_0, phi empty):
+ *   A = sum_j phi[j] gamma[n-j],  B = sum_j phi[j] g[n-j],  R = sum_j phi[n-j] g[n-j],  j = 1 .. n-1
+ *   kappa = (gamma[n] - A) / v;  v = v (1 - kappa^2);  g[n] = ((B - kappa R) + kappa g[0]) + sqrt(v) z[n]
+ *   phi[j] = phi[j] - kappa phi[n-j] (j < n),  phi[n] = kappa
+ * in fp64 without contraction; lane j mod 256 owns term j and the partial sums go through one fixed tree, so a trajectory's
+ * result is bitwise the same alone, in any batch and in every launch.  gamma = (1, 0, 0, ...) (alpha = 1) returns z.
+ * T <= 2048 (gamma, phi and the C histories live in LDS, (2 + C) T doubles); a larger T is an error, never a launch.
+ * Arguments are validated before any HIP call; N = 0 or T = 0 is a no-op. */
+int mivit_fgn(const double *z, const double *gamma, const int *gamma_row, int N, int T, int C, int U, double *out, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -8,6 +8,8 @@ on the host or directly on the GPU (no andi_datasets / skimage dependency):
   increments ``sqrt(2 D dt) N(0,1)`` (the law spelled out in ``mitochondria_simulation/mitochnodria.py:470-474``),
   per-particle ``D ~ N(mean, var)`` redrawn until positive; returns ``(T, N, 2)`` trajectories and ``(T, N, 3)``
   labels ``[alpha, D, state]``.
+* ``fbm_single_state`` / ``fractional_gaussian_noise``: the same with an anomalous exponent, ``single_state(..., alphas=a)``:
+  exact fractional Gaussian noise by the Durbin-Levinson recursion, csrc/fbm.hip for GPU tensors, numpy otherwise.
 * ``render_frames`` is the noiseless image model of ``helpers/helpersGeneration.py:283-308`` /
   ``trainSettingsPSFNoise.py:265-292``: each frame is the sum of ``nPosPerFrame`` peak-normalised Gaussian spots on a
   ``upsampling_factor``-times finer grid, mean-pooled back.  A peak-normalised 2-D Gaussian on a grid is an outer
@@ -58,7 +60,10 @@ def _as_tensor(x, device=None, dtype=torch.float32):
 
 def brownian_single_state(N: int, T: int, Ds=(1.0, 0.0), alphas: float = 1.0, dt: float = 1.0,
                           generator: Optional[torch.Generator] = None, device="cpu"):
-    """(T, N, 2) trajectories and (T, N, 3) labels [alpha, D, state=0] of freely diffusing particles."""
+    """(T, N, 2) trajectories and (T, N, 3) labels [alpha, D, state=0] of freely diffusing particles.  Any alphas other than
+    the number 1 is anomalous diffusion: fbm_single_state."""
+    if not (isinstance(alphas, (int, float)) and not isinstance(alphas, bool) and float(alphas) == 1.0):
+        return fbm_single_state(N, T, Ds, alphas, dt, generator, device)
     mean, var = float(Ds[0]), float(Ds[1])
     D = torch.full((N,), mean, device=device)
     if var > 0:
@@ -73,6 +78,148 @@ def brownian_single_state(N: int, T: int, Ds=(1.0, 0.0), alphas: float = 1.0, dt
     steps[0] = 0.0
     trajs = torch.cumsum(steps, dim=0)
     labels = torch.stack([torch.full((T, N), float(alphas), device=device), D.view(1, N).expand(T, N),
+                          torch.zeros(T, N, device=device)], dim=-1)
+    return trajs, labels
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Anomalous diffusion: fractional Brownian motion, MSD = 2 D dt k^alpha per axis (csrc/fbm.hip)
+# ------------------------------------------------------------------------------------------------------------------------
+ALPHA_MIN = 0.05             # the Toeplitz matrix of the autocovariance gets ill-conditioned towards alpha = 2; the accuracy of
+ALPHA_MAX = 1.95             # the recursion against Cholesky (tests/test_fbm.py) was measured on this range
+
+
+def fgn_autocovariance(alphas, T: int) -> np.ndarray:
+    """gamma [U, T] float64 of unit-variance fractional Gaussian noise, one row per exponent (Hurst H = alpha / 2):
+    gamma[k] = (|k + 1|^alpha - 2 |k|^alpha + |k - 1|^alpha) / 2, gamma[0] = 1.  THE function both the kernel and the host
+    restatement take gamma from.  At alpha = 1 every entry past the first is exactly 0."""
+    a = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1, 1)
+    k = np.arange(int(T), dtype=np.float64).reshape(1, -1)
+    return 0.5 * (np.power(k + 1.0, a) - 2.0 * np.power(k, a) + np.power(np.abs(k - 1.0), a))
+
+
+def _fgn_host(z: np.ndarray, gam: np.ndarray) -> np.ndarray:
+    """The recursion of csrc/fbm.hip in numpy, vectorised over trajectories: z [N, T, C], gam [N, T] float64 -> g [N, T, C].
+    Durbin-Levinson with the three sums of step n taken on the coefficients of step n - 1 (include/mivit_hip.h, mivit_fgn);
+    differs from the kernel in the order of the sums only."""
+    N, T, C = z.shape
+    g = np.empty((N, T, C), np.float64)
+    if N == 0 or T == 0:
+        return g
+    phi = np.zeros((N, T), np.float64)
+    v = gam[:, 0].copy()
+    g[:, 0] = np.sqrt(v)[:, None] * z[:, 0]
+    for n in range(1, T):
+        p, pr = phi[:, 1:n], phi[:, n - 1:0:-1]                            # phi[j], phi[n - j], j = 1 .. n - 1
+        gv = g[:, n - 1:0:-1]                                              # g[n - j]
+        A = (p * gam[:, n - 1:0:-1]).sum(axis=1)
+        B = (p[:, :, None] * gv).sum(axis=1)
+        R = (pr[:, :, None] * gv).sum(axis=1)
+        kappa = (gam[:, n] - A) / v
+        v = v * (1.0 - kappa * kappa)
+        k1 = kappa[:, None]
+        g[:, n] = ((B - k1 * R) + k1 * g[:, 0]) + np.sqrt(v)[:, None] * z[:, n]
+        phi[:, 1:n] = p - k1 * pr                                          # the right side is a new array: no aliasing
+        phi[:, n] = kappa
+    return g
+
+
+def _alpha_vector(alphas, n: int) -> torch.Tensor:
+    """alphas, a number or [n] values, as a float64 CPU tensor [n] inside [ALPHA_MIN, ALPHA_MAX] (ValueError otherwise)."""
+    if torch.is_tensor(alphas):
+        a = alphas.detach().to("cpu", torch.float64).reshape(-1)
+    else:
+        a = torch.as_tensor(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    if a.numel() == 1 and n != 1:
+        a = a.expand(n).clone()
+    if a.numel() != n:
+        raise ValueError(f"alphas must be a number or hold one exponent per trajectory ({n}), got {a.numel()}")
+    if n and not bool(((a >= ALPHA_MIN) & (a <= ALPHA_MAX)).all()):        # NaN fails both comparisons
+        raise ValueError(f"alphas must lie in [{ALPHA_MIN}, {ALPHA_MAX}] (ALPHA_MIN, ALPHA_MAX), got {float(a.min())} .. "
+                         f"{float(a.max())}")
+    return a
+
+
+def fractional_gaussian_noise(z, alphas):
+    """Unit-variance fractional Gaussian noise from standard normals: z [N, T, C], alphas a number or [N] (one exponent per
+    trajectory, shared by its C axes) -> float64 of z's shape and kind, row n = L(alpha_n) z[n] with L the lower Cholesky factor
+    of the Toeplitz matrix of fgn_autocovariance(alpha_n, T).  Its cumulative sum is fractional Brownian motion with
+    <x^2(k)> = k^alpha.  CUDA tensors go to the kernel (csrc/fbm.hip, one launch, equal exponents share a row of gamma;
+    T <= ops.FGN_MAX_T, 1 <= C <= ops.FGN_MAX_C), anything else to the numpy restatement of the same recursion.  At
+    alpha = 1 the result is z."""
+    is_t = torch.is_tensor(z)
+    if len(z.shape) != 3:
+        raise ValueError(f"z must be [N, T, C], got {tuple(z.shape)}")
+    N, T, C = (int(s) for s in z.shape)
+    a = _alpha_vector(alphas, N)
+    uniq, inv = torch.unique(a, return_inverse=True)
+    if is_t and z.device.type == "cuda":
+        from .. import ops
+        if T > ops.FGN_MAX_T:
+            raise ValueError(f"T = {T} steps on a GPU tensor, the kernel's limit is {ops.FGN_MAX_T} (ops.FGN_MAX_T)")
+        if not 1 <= C <= ops.FGN_MAX_C:
+            raise ValueError(f"z holds {C} axes, the kernel takes 1 .. {ops.FGN_MAX_C} (ops.FGN_MAX_C)")
+        gamma = torch.from_numpy(fgn_autocovariance(uniq.numpy(), T)).to(z.device)
+        return ops.fgn(z.detach().double().contiguous(), gamma, inv.to(z.device, torch.int32))
+    zz = z.detach().double().numpy() if is_t else np.asarray(z, dtype=np.float64)
+    out = _fgn_host(zz, fgn_autocovariance(uniq.numpy(), T)[inv.numpy()])
+    return torch.from_numpy(out) if is_t else out
+
+
+def _redrawn_normal(n, mean, var, lo, hi, generator, device):
+    """n draws of N(mean, var), redrawn until inside [lo, hi] (64 rounds, then clamped), float32 on `device`."""
+    x = mean + math.sqrt(var) * torch.randn(n, generator=generator, device=device)
+    for _ in range(64):
+        bad = (x < lo) | (x > hi)
+        if not bool(bad.any()):
+            break
+        x = torch.where(bad, mean + math.sqrt(var) * torch.randn(n, generator=generator, device=device), x)
+    return x.clamp(lo, hi)
+
+
+def _draw_alphas(n, alphas, generator, gdev) -> torch.Tensor:
+    """Per-particle exponents, float64 on the CPU: a number for all, a tensor / array of n values as given, or a (mean, var)
+    pair (tuple or list) drawn N(mean, var) and redrawn until inside [ALPHA_MIN, ALPHA_MAX]; var = 0 draws nothing."""
+    if isinstance(alphas, (tuple, list)):
+        if len(alphas) != 2:
+            raise ValueError("alphas must be a number, a (mean, var) pair, or a tensor / array with one exponent per particle")
+        mean, var = float(alphas[0]), float(alphas[1])
+        if var < 0 or not ALPHA_MIN <= mean <= ALPHA_MAX:
+            raise ValueError(f"alphas = (mean {mean}, var {var}): the mean must lie in [{ALPHA_MIN}, {ALPHA_MAX}], var >= 0")
+        if var > 0:
+            return _redrawn_normal(n, mean, var, ALPHA_MIN, ALPHA_MAX, generator, gdev).to("cpu", torch.float64)
+        alphas = mean
+    return _alpha_vector(alphas, n)
+
+
+def fbm_single_state(N: int, T: int, Ds=(1.0, 0.0), alphas=1.0, dt: float = 1.0,
+                     generator: Optional[torch.Generator] = None, device="cpu"):
+    """(T, N, 2) trajectories and (T, N, 3) labels [alpha, D, state=0] of fractional Brownian particles: stands in for
+    ``andi_datasets.models_phenom().single_state(N, L=0, T, Ds=[mean, var], alphas=...)``.  alphas: a number, [N] values, or a
+    (mean, var) pair drawn per particle (_draw_alphas).  Draws, in this order: D exactly as brownian_single_state draws it,
+    the exponents of a pair with var > 0, torch.randn(T, N, 2).  Position 0 is 0 and the increments 1 .. T - 1 are
+    fractional_gaussian_noise(z[1:]) * sqrt(2 D dt): per-axis increment variance 2 D dt, the law of disp_fbm
+    (mitochondria_simulation/mitochnodria.py:436-476), and ensemble per-axis MSD 2 D dt k^alpha.  A scalar alphas = 1 gives
+    brownian_single_state's trajectories bit for bit for the same seed.  device="cuda" runs csrc/fbm.hip."""
+    mean, var = float(Ds[0]), float(Ds[1])
+    D = torch.full((N,), mean, device=device)
+    if var > 0:
+        D = mean + math.sqrt(var) * torch.randn(N, generator=generator, device=device)
+        for _ in range(64):                      # redraw non-positive coefficients (AnDi constrains D > 0)
+            bad = D <= 1e-4
+            if not bool(bad.any()):
+                break
+            D = torch.where(bad, mean + math.sqrt(var) * torch.randn(N, generator=generator, device=device), D)
+        D = D.clamp_min(1e-4)
+    alpha = _draw_alphas(N, alphas, generator, device)
+    z = torch.randn(T, N, 2, generator=generator, device=device)
+    steps = torch.empty_like(z)
+    if T:
+        steps[0] = 0.0
+        noise = fractional_gaussian_noise(z[1:].double().permute(1, 0, 2).contiguous(), alpha)          # [N, T - 1, 2]
+        steps[1:] = noise.permute(1, 0, 2).float() * torch.sqrt(2.0 * D * dt).view(1, N, 1)
+    trajs = torch.cumsum(steps, dim=0)
+    labels = torch.stack([alpha.to(z.device, torch.float32).view(1, N).expand(T, N), D.view(1, N).expand(T, N),
                           torch.zeros(T, N, device=device)], dim=-1)
     return trajs, labels
 
@@ -571,7 +718,7 @@ def _draw_diffusion_coefficients(n, Ds, generator, gdev):
 
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
-                   blink=None):
+                   blink=None, alphas=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -596,7 +743,13 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     = dark.  A dark particle-frame has all its sub-position amplitudes set to zero.  truth keeps one row per frame of the
     lifetime (offsets is unchanged) and gains visible (bool per row, False on a dark frame); truth["amp"] is the zeroed one.
     tracking.score_tracking therefore counts a dark frame as a truth row: a filled row of a gap-closed track that lands on it
-    is a match, an unfilled gap a miss."""
+    is a match, an unfilled gap a miss.
+
+    alphas (default None: Brownian motion, the code path without it): the anomalous exponent per particle, a number, [Np]
+    values or a (mean, var) pair (_draw_alphas; a pair is drawn from `generator` right after D).  The sub-position steps are
+    then fractional_gaussian_noise(z) * sqrt(2 D / nPosPerFrame^alpha) with z = randn(Np, T, 2) drawn where the Brownian steps
+    are, so the MSD per axis after k frames is 2 D k^alpha; on a GPU generator T = F * nPosPerFrame <= ops.FGN_MAX_T.  truth
+    gains alpha [Np] float64.  alphas = ones gives the movie and truth of alphas = None bit for bit."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -634,10 +787,18 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     if gdev != dev and not (gdev.type == dev.type and dev.index is None):
         raise ValueError(f"the generator lives on {gdev}, the movie on {dev}")
     D = _draw_diffusion_coefficients(Np, Ds, generator, gdev)
+    alpha = None if alphas is None else _draw_alphas(Np, alphas, generator, gdev)
     T = F_ * npos
     span = torch.tensor([H - 1 - 2 * margin, W - 1 - 2 * margin], device=gdev)
     start = margin + torch.rand(Np, 2, generator=generator, device=gdev) * span
-    steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
+    if alpha is None:
+        steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
+    else:
+        # variance 2 D / npos^alpha per sub-step, so that a frame of npos sub-steps keeps the MSD 2 D: written as the Brownian
+        # variance times npos^(1 - alpha), a factor taken on the host in float64 that is exactly 1 at alpha = 1
+        rescale = torch.from_numpy(np.power(float(npos), 1.0 - alpha.numpy())).to(gdev).float()
+        z = torch.randn(Np, T, 2, generator=generator, device=gdev)
+        steps = fractional_gaussian_noise(z.double(), alpha).float() * torch.sqrt(2.0 * D.to(gdev).float() / npos * rescale).view(Np, 1, 1)
     if T:
         steps[:, 0] = 0.0
     pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
@@ -667,4 +828,6 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
              "D": D.to(dev), "pos": pos, "amp": amp, "first": first, "last": last}
     if blink is not None:
         truth["visible"] = ~dark[pid, frame]
+    if alpha is not None:
+        truth["alpha"] = alpha.to(dev)
     return vid.float(), truth

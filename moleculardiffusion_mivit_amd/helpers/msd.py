@@ -48,6 +48,33 @@ def estimateDfromMSDsWeighted(msds, time_range):
     return (msds / lag[np.newaxis, :]) @ weights / np.sum(weights) / 4
 
 
+def estimate_alpha(msds, max_lag=None):
+    """Anomalous exponent of every track: the least-squares slope of log MSD against log lag over the lags 1 .. max_lag
+    (default: all) of msds [n_tracks, Lmax], the rows track_msd returns (entry 0 is lag 0 and not used) -> alpha [n_tracks].
+    Lags whose MSD is not positive are skipped (the zero padding of a short track's row, a track that did not move); a
+    track with fewer than two usable lags gets NaN.  Plain torch ops on the input's device; numpy in, numpy out."""
+    is_t = torch.is_tensor(msds)
+    m = msds if is_t else torch.as_tensor(np.asarray(msds))
+    if m.dim() != 2:
+        raise ValueError(f"msds must be [n_tracks, Lmax], got {tuple(m.shape)}")
+    M = m.shape[1] - 1
+    if max_lag is not None:
+        if int(max_lag) != max_lag or max_lag < 1:
+            raise ValueError(f"max_lag must be None or an integer >= 1, got {max_lag}")
+        M = min(M, int(max_lag))
+    m = m[:, 1:M + 1].double()
+    ok = m > 0                                                  # NaN is not usable either
+    w = ok.double()
+    x = torch.log(torch.arange(1, M + 1, dtype=torch.float64, device=m.device)).view(1, -1)
+    y = torch.log(torch.where(ok, m, torch.ones((), dtype=torch.float64, device=m.device)))
+    cnt = w.sum(dim=1, keepdim=True)
+    xm, ym = (w * x).sum(dim=1, keepdim=True) / cnt, (w * y).sum(dim=1, keepdim=True) / cnt
+    dx = w * (x - xm)
+    alpha = (dx * (y - ym)).sum(dim=1) / (dx * (x - xm)).sum(dim=1)
+    alpha = torch.where(cnt.view(-1) >= 2, alpha, torch.full((), float("nan"), dtype=torch.float64, device=m.device))
+    return alpha if is_t else alpha.numpy()
+
+
 def mean_square_displacement(traj):
     """Reference mean_square_displacement (helpers/helpersMSD.py:7-26): one trajectory [num_steps, 2] -> MSD [num_steps]."""
     traj = np.asarray(traj)

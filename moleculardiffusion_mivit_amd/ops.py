@@ -799,6 +799,33 @@ def track_sequences(movie: torch.Tensor, frame: torch.Tensor, y: torch.Tensor, x
     return seq
 
 
+FGN_MAX_T = 2048             # csrc/fbm.hip: steps of a trajectory whose recursion state fits in LDS
+FGN_MAX_C = 4
+
+
+def fgn(z: torch.Tensor, gamma: torch.Tensor, gamma_row: torch.Tensor) -> torch.Tensor:
+    """Fractional Gaussian noise (csrc/fbm.hip, mivit_fgn): z [N, T, C] float64 standard normals, 1 <= C <= FGN_MAX_C, gamma
+    [U, T] float64 autocovariance rows (helpers/generation.fgn_autocovariance), gamma_row [N] int32 in [0, U), all on the GPU
+    -> [N, T, C] float64, the Cholesky factor of gamma's Toeplitz matrix applied to every trajectory and axis.  T <=
+    FGN_MAX_T.  See include/mivit_hip.h for the recursion and helpers/generation.fractional_gaussian_noise for the front end."""
+    z = _dev_tensor(z, torch.float64, 3, "fgn", "z [N, T, C]")
+    gamma = _dev_tensor(gamma, torch.float64, 2, "fgn", "gamma [U, T]")
+    gamma_row = _dev_tensor(gamma_row, torch.int32, 1, "fgn", "gamma_row [N]")
+    n, T, C = z.shape
+    U = gamma.shape[0]
+    if not 1 <= C <= FGN_MAX_C:
+        raise ValueError(f"fgn: z holds {C} axes, 1 .. {FGN_MAX_C} (FGN_MAX_C) are supported")
+    if T > FGN_MAX_T:
+        raise ValueError(f"fgn: T = {T} steps, the kernel's limit is {FGN_MAX_T} (FGN_MAX_T)")
+    if gamma.shape[1] != T or gamma_row.numel() != n:
+        raise ValueError(f"fgn: gamma must be [U, {T}] and gamma_row [{n}], got {tuple(gamma.shape)} and {tuple(gamma_row.shape)}")
+    if n and T and (U < 1 or int(gamma_row.min()) < 0 or int(gamma_row.max()) >= U):
+        raise ValueError(f"fgn: gamma_row must lie in [0, {U})")
+    out = torch.empty_like(z)
+    N.check(N.lib.mivit_fgn(_p(z), _p(gamma), _p(gamma_row), n, T, C, U, _p(out), _s(z)), "mivit_fgn")
+    return out
+
+
 MOVIE_MAX_RADIUS = 64        # csrc/movie.hip: limits of mivit_render_movie
 MOVIE_MAX_NPOS = 256
 MOVIE_MAX_UP = 64

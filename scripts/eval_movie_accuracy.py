@@ -5,12 +5,14 @@ D_msd_weighted and D_model, all in the units of estimate_track_diffusion (pixels
 model's own output units for D_model), and how the particles were cut into tracks: tracks_per_particle (the mean over the
 particles that got a track of the bincount of score_tracking's particle_id), median_track_length (rows, filled ones
 included) and n_filled.  --blink P makes every particle dark with probability P in each frame of its life (simulate_movie's
-blink), --max-gap N closes and fills gaps of up to N missed frames (track_particles_tensors' max_gap).  A tool, not a test: it
-asserts no accuracy.
+blink), --max-gap N closes and fills gaps of up to N missed frames (track_particles_tensors' max_gap).  --alpha A simulates
+fractional Brownian particles of that anomalous exponent (simulate_movie's alphas, csrc/fbm.hip) and adds, per track,
+alpha_true and alpha_msd = msd.estimate_alpha of the recovered track's MSD over the lags 1 .. --alpha-max-lag, its median
+over the tracks of at least 20 rows, and the same estimator's median on the truth table and on the truth without motion blur.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
-                                          [--blink 0.05] [--max-gap 2]
+                                          [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -26,6 +28,7 @@ import torch.nn.functional as F
 
 from moleculardiffusion_mivit_amd.helpers import generation as gen
 from moleculardiffusion_mivit_amd.helpers import models as M
+from moleculardiffusion_mivit_amd.helpers import msd as MSD
 from moleculardiffusion_mivit_amd.helpers import tracking as trk
 
 
@@ -44,6 +47,8 @@ def main():
     ap.add_argument("--noise-free", action="store_true")
     ap.add_argument("--blink", type=float, default=None)
     ap.add_argument("--max-gap", type=int, default=0)
+    ap.add_argument("--alpha", type=float, default=None)
+    ap.add_argument("--alpha-max-lag", type=int, default=10)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
@@ -53,7 +58,7 @@ def main():
     H, W = args.size
     g = torch.Generator(device="cuda").manual_seed(args.seed)
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props,
-                                      generator=g, device="cuda", blink=args.blink)
+                                      generator=g, device="cuda", blink=args.blink, alphas=args.alpha)
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
@@ -80,6 +85,24 @@ def main():
                                                           score["particle_id"].tolist(), score["purity"].tolist(),
                                                           score["D_true"].tolist(), est["D_msd"].tolist(),
                                                           est["D_msd_weighted"].tolist(), est["D_model"].tolist())]}
+    if args.alpha is not None:
+        a_msd = MSD.estimate_alpha(est["msd"], max_lag=args.alpha_max_lag)
+        pid = score["particle_id"]
+        a_true = torch.where(pid >= 0, truth["alpha"][pid.clamp_min(0)], torch.full_like(a_msd, float("nan")))
+        for row, at, am in zip(out["tracks"], a_true.tolist(), a_msd.tolist()):
+            row["alpha_true"], row["alpha_msd"] = at, am
+        long = (est["length"] >= 20) & ~torch.isnan(a_msd)
+        out["alpha"] = args.alpha
+        out["alpha_max_lag"] = args.alpha_max_lag
+        out["alpha_msd_median"] = float(a_msd[long].median()) if bool(long.any()) else float("nan")
+        out["alpha_msd_n_tracks"] = int(long.sum())
+        # the same estimator on the truth, which separates its own bias from what detection and linking add: on the truth
+        # table (frame-mean positions: the motion blur of the camera is in them) and on one sub-position per frame (no blur)
+        t_msd = MSD.track_msd(torch.stack([truth["y"], truth["x"]], dim=1), truth["offsets"])[0]
+        out["alpha_msd_truth_table_median"] = float(MSD.estimate_alpha(t_msd, max_lag=args.alpha_max_lag).nanmedian())
+        sharp = truth["pos"][:, ::args.npos].double()
+        s_msd = MSD.mean_square_displacements(sharp)
+        out["alpha_msd_truth_unblurred_median"] = float(MSD.estimate_alpha(s_msd, max_lag=args.alpha_max_lag).nanmedian())
     print(json.dumps(out))
 
 
