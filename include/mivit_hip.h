@@ -400,6 +400,30 @@ int mivit_track_sequences(const float *movie, int F, int H, int W, const int *fr
  * Arguments are validated before any HIP call; N = 0 or T = 0 is a no-op. */
 int mivit_fgn(const double *z, const double *gamma, const int *gamma_row, int N, int T, int C, int U, double *out, void *stream);
 
+/* Confined diffusion on filament geometries: 1-D displacements along a polyline become 2-D positions (the reference's
+ * Geometry.map_displacements, Experiments/mitochondria_simulation/mitochnodria.py:339-378, with get_edge_at_length, :231-264,
+ * and Edge.get_position_at_distance, :87-102), csrc/confine.hip, one workgroup per particle, one launch.
+ * disp [N, T] fp64 steps along the filament, s0 [N] fp64 start arcs, geom_of [N] int32 in [0, G).  The G polylines are packed
+ * by the caller (helpers/geometry.pack_geometries, the one host function: no device sqrt): verts [V, 2] fp64, vert_offsets
+ * [G + 1] int32 (geometry g owns vertices vert_offsets[g] .. vert_offsets[g + 1] - 1 and one edge fewer), lengths [V] fp64
+ * (lengths[v] = |verts[v + 1] - verts[v]|, the last slot of a geometry unused), totals [G] fp64.  With L = totals[geom_of[n]]:
+ *   clamp(m): m = (L < m) ? L : m;  m = (m > 0) ? m : 0                 (Python's max(0, min(m, L)); NaN -> 0)
+ *   mode 0, clamp (the reference):  s = clamp(s0);  per step s = clamp(s + d[t])
+ *   mode 1, reflect:  fold(m): P = 2 L; m = fmod(m, P); if (m < 0) m = m + P; if (m > L) m = P - m; m = clamp(m)
+ *                     s = fold(s0);  per step s = fold(s + d[t])        (per step on the position, not on the free sum)
+ *   lookup: rem = s; the first edge e in order with rem <= lengths[e] is the edge (the earlier one at a vertex), otherwise
+ *   rem = rem - lengths[e]; pos = verts[e] + (clamp of rem to [0, lengths[e]] / lengths[e]) * (verts[e + 1] - verts[e]); no edge
+ *   found (the remainder ends a few ulps above the last length): pos = the last vertex, edge = the last edge
+ * in fp64 without contraction, the steps of a particle walked in ascending t by one thread, so a particle's result is bitwise
+ * the same alone, in any batch and in every launch, and bitwise that of the numpy restatement (helpers/geometry).
+ * out: pos [N, T, 2] fp64 (the vertex components in the order given), arc [N, T] fp64 (s after step t) or NULL, edge [N, T] int32
+ * (index within the geometry) or NULL.  No limit on T.  A geometry has at most 512 edges (it is staged in LDS); geom_of and
+ * vert_offsets are clamped before use, so nothing is read out of bounds whatever they hold, and sizes that prove a longer
+ * polyline are an error, never a launch.  Arguments are validated before any HIP call; N = 0 or T = 0 is a no-op. */
+int mivit_map_displacements(const double *disp, const double *s0, const int *geom_of, const double *verts, const double *lengths,
+                            const int *vert_offsets, const double *totals, int N, int T, int G, int V, int mode, double *pos,
+                            double *arc, int *edge, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -716,9 +716,37 @@ def _draw_diffusion_coefficients(n, Ds, generator, gdev):
     return D
 
 
+def _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin):
+    """simulate_movie's filaments: (the packed geometries with the vertices flipped to (row, col) = (y, x), geometry id [Np]
+    int64).  ValueError for a vertex outside the margin, a geometry_of outside [0, G) and an unknown boundary."""
+    from . import geometry as _geometry
+    if boundary not in _geometry.BOUNDARIES:
+        raise ValueError(f"boundary must be one of {_geometry.BOUNDARIES}, got {boundary!r}")
+    geoms = [geometry] if isinstance(geometry, _geometry.Geometry) else list(geometry)
+    packed = _geometry.pack_geometries(geoms)
+    G = len(geoms)
+    for g in range(G):
+        for v in range(packed["vert_offsets"][g], packed["vert_offsets"][g + 1]):
+            x, y = packed["verts"][v]
+            if not (margin <= x <= W - 1 - margin and margin <= y <= H - 1 - margin):
+                raise ValueError(f"geometry {g}: vertex {v - packed['vert_offsets'][g]} at (x, y) = ({x}, {y}) lies outside "
+                                 f"[{margin}, {W - 1 - margin}] x [{margin}, {H - 1 - margin}]")
+    if geometry_of is None:
+        geom_id = np.arange(Np, dtype=np.int64) % G
+    else:
+        gof = torch.as_tensor(geometry_of).detach().cpu()
+        if gof.is_floating_point() or gof.dtype == torch.bool or tuple(gof.shape) != (Np,):
+            raise ValueError(f"geometry_of must be integer [{Np}], got {gof.dtype} {tuple(gof.shape)}")
+        geom_id = gof.long().numpy()
+        if Np and (geom_id.min() < 0 or geom_id.max() >= G):
+            raise ValueError(f"geometry_of must lie in [0, {G})")
+    packed["verts"] = np.ascontiguousarray(packed["verts"][:, ::-1])
+    return packed, geom_id
+
+
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
-                   blink=None, alphas=None):
+                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp"):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -749,7 +777,18 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     values or a (mean, var) pair (_draw_alphas; a pair is drawn from `generator` right after D).  The sub-position steps are
     then fractional_gaussian_noise(z) * sqrt(2 D / nPosPerFrame^alpha) with z = randn(Np, T, 2) drawn where the Brownian steps
     are, so the MSD per axis after k frames is 2 D k^alpha; on a GPU generator T = F * nPosPerFrame <= ops.FGN_MAX_T.  truth
-    gains alpha [Np] float64.  alphas = ones gives the movie and truth of alphas = None bit for bit."""
+    gains alpha [Np] float64.  alphas = ones gives the movie and truth of alphas = None bit for bit.
+
+    geometry (default None: free motion in the plane, the code path without it): a helpers/geometry.Geometry or a sequence of
+    G of them, filaments the particles are confined to; geometry_of [Np] integers names each particle's (default
+    arange(Np) % G); boundary "clamp" (the reference's Geometry.map_displacements) or "reflect" is what happens at a filament's
+    two ends.  Vertices are (x, y) and must lie in [margin, W - 1 - margin] x [margin, H - 1 - margin].  In place of the start
+    positions one torch.rand(Np) is drawn, times the filament's total length the start arc; then z = randn(Np, T, 1), and
+    the steps z * sqrt(2 D / nPosPerFrame) (with alphas: the fractional noise as above, one axis) go through
+    geometry.map_displacements (csrc/confine.hip on a GPU generator).  D is the 1-D coefficient ALONG the filament:
+    <ds^2> = 2 D k^alpha after k frames.  truth gains arc [Np, T] float64, edge [Np, T] int32 (within the particle's geometry)
+    and geometry_id [Np] int64; truth["pos"] is the mapped position in float32.  truth["y"] and truth["x"] remain the means of
+    a frame's sub-positions: where a frame's sub-positions go round a corner the mean lies off the filament."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -786,22 +825,42 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     gdev = generator.device if generator is not None else dev
     if gdev != dev and not (gdev.type == dev.type and dev.index is None):
         raise ValueError(f"the generator lives on {gdev}, the movie on {dev}")
+    packed = None
+    if geometry is None:
+        if geometry_of is not None or boundary != "clamp":
+            raise ValueError("geometry_of and boundary need a geometry")
+    else:
+        packed, geom_id = _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin)
     D = _draw_diffusion_coefficients(Np, Ds, generator, gdev)
     alpha = None if alphas is None else _draw_alphas(Np, alphas, generator, gdev)
     T = F_ * npos
-    span = torch.tensor([H - 1 - 2 * margin, W - 1 - 2 * margin], device=gdev)
-    start = margin + torch.rand(Np, 2, generator=generator, device=gdev) * span
-    if alpha is None:
-        steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
+    if packed is not None:
+        from . import geometry as _geometry
+        start = torch.rand(Np, generator=generator, device=gdev).double() * torch.from_numpy(packed["totals"][geom_id]).to(gdev)
+        z = torch.randn(Np, T, 1, generator=generator, device=gdev)
+        if alpha is None:
+            steps = z * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
+        else:
+            rescale = torch.from_numpy(np.power(float(npos), 1.0 - alpha.numpy())).to(gdev).float()
+            steps = fractional_gaussian_noise(z.double(), alpha).float() * torch.sqrt(2.0 * D.to(gdev).float() / npos * rescale).view(Np, 1, 1)
+        if T:
+            steps[:, 0] = 0.0
+        pos64, arc, edge = _geometry.map_displacements(steps.view(Np, T).double(), start, packed, geom_id, boundary, True)
+        pos = pos64.float().to(dev)
     else:
-        # variance 2 D / npos^alpha per sub-step, so that a frame of npos sub-steps keeps the MSD 2 D: written as the Brownian
-        # variance times npos^(1 - alpha), a factor taken on the host in float64 that is exactly 1 at alpha = 1
-        rescale = torch.from_numpy(np.power(float(npos), 1.0 - alpha.numpy())).to(gdev).float()
-        z = torch.randn(Np, T, 2, generator=generator, device=gdev)
-        steps = fractional_gaussian_noise(z.double(), alpha).float() * torch.sqrt(2.0 * D.to(gdev).float() / npos * rescale).view(Np, 1, 1)
-    if T:
-        steps[:, 0] = 0.0
-    pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
+        span = torch.tensor([H - 1 - 2 * margin, W - 1 - 2 * margin], device=gdev)
+        start = margin + torch.rand(Np, 2, generator=generator, device=gdev) * span
+        if alpha is None:
+            steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
+        else:
+            # variance 2 D / npos^alpha per sub-step, so that a frame of npos sub-steps keeps the MSD 2 D: written as the
+            # Brownian variance times npos^(1 - alpha), a factor taken on the host in float64 that is exactly 1 at alpha = 1
+            rescale = torch.from_numpy(np.power(float(npos), 1.0 - alpha.numpy())).to(gdev).float()
+            z = torch.randn(Np, T, 2, generator=generator, device=gdev)
+            steps = fractional_gaussian_noise(z.double(), alpha).float() * torch.sqrt(2.0 * D.to(gdev).float() / npos * rescale).view(Np, 1, 1)
+        if T:
+            steps[:, 0] = 0.0
+        pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
     pm, ps = props["particle_intensity"]
     bm, bs = props["background_intensity"]
     if pm > 1e-4 and ps > 1e-4:
@@ -830,4 +889,6 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         truth["visible"] = ~dark[pid, frame]
     if alpha is not None:
         truth["alpha"] = alpha.to(dev)
+    if packed is not None:
+        truth["arc"], truth["edge"], truth["geometry_id"] = arc.to(dev), edge.to(dev), torch.from_numpy(geom_id).to(dev)
     return vid.float(), truth

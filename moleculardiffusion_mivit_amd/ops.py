@@ -826,6 +826,66 @@ def fgn(z: torch.Tensor, gamma: torch.Tensor, gamma_row: torch.Tensor) -> torch.
     return out
 
 
+GEOM_CHUNK_T = 2048          # csrc/confine.hip: steps per pass through LDS (no limit on T)
+GEOM_MAX_EDGES = 512         # edges of one polyline, staged in LDS
+GEOM_MODES = {"clamp": 0, "reflect": 1}
+
+
+def map_displacements(disp: torch.Tensor, s0: torch.Tensor, geom_of: torch.Tensor, verts: torch.Tensor, lengths: torch.Tensor,
+                      vert_offsets: torch.Tensor, totals: torch.Tensor, mode):
+    """Displacements along polylines -> positions (csrc/confine.hip, mivit_map_displacements): disp [N, T] float64, s0 [N]
+    float64 start arcs, geom_of [N] int32 in [0, G); the packed geometries of helpers/geometry.pack_geometries: verts [V, 2]
+    float64, lengths [V] float64, vert_offsets [G + 1] int32, totals [G] float64, all on the GPU; mode "clamp" / 0 (the
+    reference: the arc is clamped to [0, total] after every step) or "reflect" / 1 (folded back at both ends) -> (pos [N, T, 2]
+    float64, arc [N, T] float64, edge [N, T] int32).  No limit on T; a geometry has at most GEOM_MAX_EDGES edges.  See
+    include/mivit_hip.h for the arithmetic and helpers/geometry.map_displacements for the front end."""
+    disp = _dev_tensor(disp, torch.float64, 2, "map_displacements", "disp [N, T]")
+    s0 = _dev_tensor(s0, torch.float64, 1, "map_displacements", "s0 [N]")
+    geom_of = _dev_tensor(geom_of, torch.int32, 1, "map_displacements", "geom_of [N]")
+    verts = _dev_tensor(verts, torch.float64, 2, "map_displacements", "verts [V, 2]")
+    lengths = _dev_tensor(lengths, torch.float64, 1, "map_displacements", "lengths [V]")
+    vert_offsets = _dev_tensor(vert_offsets, torch.int32, 1, "map_displacements", "vert_offsets [G + 1]")
+    totals = _dev_tensor(totals, torch.float64, 1, "map_displacements", "totals [G]")
+    if mode not in GEOM_MODES and not (isinstance(mode, int) and not isinstance(mode, bool) and mode in GEOM_MODES.values()):
+        raise ValueError(f"map_displacements: mode must be one of {sorted(GEOM_MODES)} (or 0 / 1), got {mode!r}")
+    mode = GEOM_MODES.get(mode, mode)
+    n, T = disp.shape
+    V, G = verts.shape[0], totals.numel()
+    if s0.numel() != n or geom_of.numel() != n:
+        raise ValueError(f"map_displacements: s0 and geom_of must be [{n}], got {tuple(s0.shape)} and {tuple(geom_of.shape)}")
+    if verts.shape[1] != 2 or lengths.numel() != V or vert_offsets.numel() != G + 1:
+        raise ValueError(f"map_displacements: need verts [V, 2], lengths [V], vert_offsets [G + 1] and totals [G], got "
+                         f"{tuple(verts.shape)}, {tuple(lengths.shape)}, {tuple(vert_offsets.shape)} and {tuple(totals.shape)}")
+    if n and T:
+        if G < 1:
+            raise ValueError(f"map_displacements: no geometry for {n} particles")
+        vo = vert_offsets.cpu()
+        nv = vo[1:] - vo[:-1]
+        if int(vo[0]) != 0 or int(vo[-1]) != V or int(nv.min()) < 2:
+            raise ValueError(f"map_displacements: vert_offsets must rise from 0 to V = {V} with at least two vertices per geometry")
+        if int(nv.max()) - 1 > GEOM_MAX_EDGES:
+            raise ValueError(f"map_displacements: a geometry has {int(nv.max()) - 1} edges, the kernel's limit is "
+                             f"{GEOM_MAX_EDGES} (GEOM_MAX_EDGES)")
+        if int(geom_of.min()) < 0 or int(geom_of.max()) >= G:
+            raise ValueError(f"map_displacements: geom_of must lie in [0, {G})")
+    return _map_displacements_checked(disp, s0, geom_of, verts, lengths, vert_offsets, totals, mode)
+
+
+def _map_displacements_checked(disp, s0, geom_of, verts, lengths, vert_offsets, totals, mode: int, out=None):
+    """map_displacements for contiguous GPU tensors of the right kinds and shapes whose vert_offsets and geom_of the caller has
+    already checked (helpers/geometry.map_displacements checks them on the host copies it packs from): allocation and launch,
+    nothing is read back.  out: (pos, arc, edge) to write into instead of allocating.  The kernel clamps every index it reads,
+    so an unchecked value can give a wrong position but cannot address out of bounds."""
+    n, T = disp.shape
+    pos, arc, edge = out if out is not None else (torch.empty(n, T, 2, dtype=torch.float64, device=disp.device),
+                                                  torch.empty(n, T, dtype=torch.float64, device=disp.device),
+                                                  torch.empty(n, T, dtype=torch.int32, device=disp.device))
+    N.check(N.lib.mivit_map_displacements(_p(disp), _p(s0), _p(geom_of), _p(verts), _p(lengths), _p(vert_offsets), _p(totals), n, T,
+                                          totals.numel(), verts.shape[0], mode, _p(pos), _p(arc), _p(edge), _s(disp)),
+            "mivit_map_displacements")
+    return pos, arc, edge
+
+
 MOVIE_MAX_RADIUS = 64        # csrc/movie.hip: limits of mivit_render_movie
 MOVIE_MAX_NPOS = 256
 MOVIE_MAX_UP = 64

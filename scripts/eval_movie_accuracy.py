@@ -8,11 +8,16 @@ included) and n_filled.  --blink P makes every particle dark with probability P 
 blink), --max-gap N closes and fills gaps of up to N missed frames (track_particles_tensors' max_gap).  --alpha A simulates
 fractional Brownian particles of that anomalous exponent (simulate_movie's alphas, csrc/fbm.hip) and adds, per track,
 alpha_true and alpha_msd = msd.estimate_alpha of the recovered track's MSD over the lags 1 .. --alpha-max-lag, its median
-over the tracks of at least 20 rows, and the same estimator's median on the truth table and on the truth without motion blur.  A tool, not a test: it asserts no accuracy.
+over the tracks of at least 20 rows, and the same estimator's median on the truth table and on the truth without motion blur.
+--cristae N SPACING DEPTH WIDTH confines every particle to one serpentine of N cristae (helpers/geometry.cristae_geometry,
+centred in the field; simulate_movie's geometry, csrc/confine.hip), --boundary clamp|reflect is what happens at its two ends;
+D is then the 1-D coefficient along the filament, and the output gains the filament's total length and the medians of D_true,
+D_msd and D_msd_weighted over the matched tracks.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
                                           [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10]
+                                          [--cristae 4 30 60 12] [--boundary reflect]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -49,6 +54,8 @@ def main():
     ap.add_argument("--max-gap", type=int, default=0)
     ap.add_argument("--alpha", type=float, default=None)
     ap.add_argument("--alpha-max-lag", type=int, default=10)
+    ap.add_argument("--cristae", type=float, nargs=4, default=None, metavar=("N", "SPACING", "DEPTH", "WIDTH"))
+    ap.add_argument("--boundary", choices=["clamp", "reflect"], default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
@@ -57,8 +64,17 @@ def main():
         props.update({"background_intensity": [props["background_intensity"][0], 0.0], "poisson_noise": -1})
     H, W = args.size
     g = torch.Generator(device="cuda").manual_seed(args.seed)
+    confine = {}
+    if args.cristae is not None:
+        from moleculardiffusion_mivit_amd.helpers import geometry as geo
+        n, spacing, depth, width = int(args.cristae[0]), *args.cristae[1:]
+        span = n * width + (n - 1) * spacing
+        confine = {"geometry": geo.cristae_geometry(n, spacing, depth, width, origin=((W - 1 - span) / 2, (H - 1 - depth) / 2)),
+                   "boundary": args.boundary or "clamp"}
+    elif args.boundary is not None:
+        raise SystemExit("--boundary needs --cristae")
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props,
-                                      generator=g, device="cuda", blink=args.blink, alphas=args.alpha)
+                                      generator=g, device="cuda", blink=args.blink, alphas=args.alpha, **confine)
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
@@ -85,6 +101,12 @@ def main():
                                                           score["particle_id"].tolist(), score["purity"].tolist(),
                                                           score["D_true"].tolist(), est["D_msd"].tolist(),
                                                           est["D_msd_weighted"].tolist(), est["D_model"].tolist())]}
+    if confine:
+        ok = score["particle_id"] >= 0
+        out["cristae"], out["boundary"] = args.cristae, confine["boundary"]
+        out["filament_length"] = float(confine["geometry"].total_length)
+        for key, col in (("D_true_median", score["D_true"]), ("D_msd_median", est["D_msd"]), ("D_msd_weighted_median", est["D_msd_weighted"])):
+            out[key] = float(col[ok].double().nanmedian()) if bool(ok.any()) else float("nan")
     if args.alpha is not None:
         a_msd = MSD.estimate_alpha(est["msd"], max_lag=args.alpha_max_lag)
         pid = score["particle_id"]
