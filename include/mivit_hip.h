@@ -424,6 +424,47 @@ int mivit_map_displacements(const double *disp, const double *s0, const int *geo
                             const int *vert_offsets, const double *totals, int N, int T, int G, int V, int mode, double *pos,
                             double *arc, int *edge, void *stream);
 
+/* Multi-state diffusion, csrc/segment.hip: tracks whose diffusion coefficient changes (andi_datasets' multi_state, from whose
+ * single_state the reference takes its trajectories; no counterpart in the reference itself).  All three in fp64 without
+ * contraction, no atomics, a track's / segment's / particle's result bitwise the same alone, in any batch and in every launch.
+ *
+ * mivit_segment_tracks: the optimal partition of every track into stretches of constant step variance, one wave per track.
+ * pos [N, 2] fp64 sorted by track and by frame, offsets [n_tracks + 1] int32 (CSR; entries are clamped to [0, N]: nothing is
+ * read out of bounds), max_len >= the rows of the longest track and <= 4096 (cs, F and prev live in LDS, 20 B a row; a larger
+ * value is an error, never a launch, and a track that is longer than max_len after all is cut to it).  A track of L rows has
+ * Linc = L - 1 increments, q_k = dy_k^2 + dx_k^2 between rows k and k + 1, cs[j] = q_0 + .. + q_{j-1} summed in ascending k
+ * (np.cumsum bit for bit), and with n = j - i, beta = penalty * log(Linc):
+ *   C(i, j) = (2 n) * log(max((cs[j] - cs[i]) / (2 n), min_var))        -2 log L of 2 n Gaussian samples, up to a constant
+ *   F(0) = -beta;  F(j) = min over i in {0} and [min_len, j - min_len] of (F(i) + C(i, j)) + beta,   j = min_len .. Linc
+ * prev[j] is the LOWEST i among equal minima; backtracking prev from Linc gives the changepoints.  Linc < 2 min_len leaves
+ * only i = 0: no changepoint; 1 <= Linc < min_len has no step of the recurrence and gets F(Linc) = (F(0) + C(0, Linc)) + beta.
+ * out: seg_start [N] int32, 1 on the first row of every segment (a track's first row included; a changepoint at increment c
+ * puts the shared row c into the later segment), 0 elsewhere on a track's rows; cost [n_tracks] fp64 = F(Linc), NaN where
+ * Linc < 1.  The only operation that may differ from the numpy restatement (helpers/msd._segment_numpy) is log.
+ * min_len >= 2, penalty >= 0, min_var > 0.  Arguments are validated before any HIP call; n_tracks = 0 is a no-op.
+ *
+ * mivit_segment_stats: one row of estimates per segment, one thread per segment.  seg_offsets [n_seg + 1] int32, the CSR of
+ * the segments over the same rows; seg_track_end [n_seg] int32, the row at which each segment's track ends (exclusive).  The
+ * increments of segment s run from row seg_offsets[s] to row min(seg_offsets[s + 1], seg_track_end[s] - 1): the increment that
+ * bridges to the next segment belongs to the earlier one; n is their number.  Sums in ascending index:
+ *   S2 = sum_k q_k;   S11 = sum_k (dy_k dy_{k+1} + dx_k dx_{k+1}) over the n - 1 neighbouring pairs inside the segment
+ *   D_mle  = S2 / ((4 n) dt)
+ *   D_cve  = D_mle + S11 / ((2 (n - 1)) dt)                             Vestergaard et al. 2014: localisation noise and
+ *   sigma2 = (R S2) / (2 n) + ((2 R - 1) S11) / (2 (n - 1))             motion blur (coefficient R in [0, 1/4]) cancel
+ * NaN where a divisor is below 1 (D_mle: n < 1; D_cve, sigma2: n < 2); n_increments [n_seg] int32.  No log: bitwise the numpy
+ * restatement (helpers/msd._segment_stats_numpy).  Rows are clamped to [0, N - 1].  dt > 0.  n_seg = 0 is a no-op.
+ *
+ * mivit_markov_states: the state path of every particle of a K-state Markov chain, one thread per particle.  u [N, T] fp64
+ * uniforms, p0 [K] and M [K, K] fp64 (rows summing to 1), 1 <= K <= 8.  state[n, 0] is the first k with u[n, 0] < p0[0] + ..
+ * + p0[k], the cumulative sum taken sequentially, and K - 1 if there is none (rounding); state[n, t] the same on row
+ * M[state[n, t - 1]].  out: state [N, T] int32.  Adds and compares only: bitwise the numpy restatement
+ * (helpers/generation._markov_host).  N = 0 or T = 0 is a no-op. */
+int mivit_segment_tracks(const double *pos, int N, const int *offsets, int n_tracks, int max_len, int min_len, double penalty,
+                         double min_var, int *seg_start, double *cost, void *stream);
+int mivit_segment_stats(const double *pos, int N, const int *seg_offsets, const int *seg_track_end, int n_seg, double dt,
+                        double R, double *d_cve, double *d_mle, double *sigma2, int *n_increments, void *stream);
+int mivit_markov_states(const double *u, const double *p0, const double *M, int N, int T, int K, int *state, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -148,6 +148,11 @@ SYMBOLS = {
                                       c_int, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p]),
     "mivit_fgn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_map_displacements": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p] * 4),
+    "mivit_segment_tracks": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p,
+                                     c_void_p, c_void_p]),
+    "mivit_segment_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mivit_markov_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes": (c_size_t, [c_int]),
     "mivit_attn_out_bwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "mivit_embed_small_supported": (c_int, [c_int, c_int, c_int]),

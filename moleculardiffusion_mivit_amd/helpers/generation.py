@@ -224,6 +224,98 @@ def fbm_single_state(N: int, T: int, Ds=(1.0, 0.0), alphas=1.0, dt: float = 1.0,
     return trajs, labels
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# Multi-state diffusion: a Markov chain of states with one diffusion coefficient each (csrc/segment.hip)
+# ------------------------------------------------------------------------------------------------------------------------
+def _markov_host(u: np.ndarray, p0: np.ndarray, M: np.ndarray) -> np.ndarray:
+    """The arithmetic of csrc/segment.hip::markov_kernel in numpy, vectorised over particles (include/mivit_hip.h,
+    mivit_markov_states): u [N, T], p0 [K], M [K, K] float64 -> state [N, T] int32, bitwise the kernel's."""
+    N, T = u.shape
+    K = len(p0)
+    rows = np.concatenate([p0.reshape(1, K), M.reshape(K, K)], axis=0)
+    state = np.zeros((N, T), np.int32)
+    row = np.zeros(N, np.int64)
+    for t in range(T):
+        pr = rows[row]                                                     # [N, K]
+        c = pr[:, 0].copy()
+        k = np.zeros(N, np.int64)
+        open_ = ~(u[:, t] < c)                                             # still searching (a NaN searches to the end)
+        for kk in range(1, K):
+            k = np.where(open_, kk, k)
+            c = np.where(open_, c + pr[:, kk], c)
+            open_ = open_ & ~(u[:, t] < c)
+        state[:, t] = k
+        row = 1 + k
+    return state
+
+
+def _markov_args(Ds, M, p0):
+    """(Ds [K], M [K, K], p0 [K]) as float64 arrays, checked; p0 = None is the stationary distribution of M."""
+    from .. import ops
+    Ds = np.asarray(torch.as_tensor(Ds).detach().cpu().numpy() if torch.is_tensor(Ds) else Ds, dtype=np.float64).reshape(-1)
+    M = np.asarray(torch.as_tensor(M).detach().cpu().numpy() if torch.is_tensor(M) else M, dtype=np.float64)
+    K = len(Ds)
+    if not 1 <= K <= ops.MARKOV_MAX_K:
+        raise ValueError(f"Ds holds {K} states, 1 .. {ops.MARKOV_MAX_K} (ops.MARKOV_MAX_K) are supported")
+    if not (np.isfinite(Ds).all() and (Ds >= 0).all()):
+        raise ValueError(f"Ds must be finite and >= 0, got {Ds.tolist()}")
+    if M.shape != (K, K):
+        raise ValueError(f"M must be [{K}, {K}], got {tuple(M.shape)}")
+    if not ((M >= 0).all() and np.allclose(M.sum(axis=1), 1.0, rtol=0, atol=1e-9)):
+        raise ValueError("every row of M must be a distribution: entries >= 0 that sum to 1")
+    if p0 is None:
+        # the left eigenvector of eigenvalue 1: (M^T - I) pi = 0 with sum(pi) = 1, by least squares
+        A = np.concatenate([M.T - np.eye(K), np.ones((1, K))], axis=0)
+        p0 = np.linalg.lstsq(A, np.concatenate([np.zeros(K), np.ones(1)]), rcond=None)[0]
+        p0 = np.clip(p0, 0.0, None)
+        p0 = p0 / p0.sum()
+    else:
+        p0 = np.asarray(torch.as_tensor(p0).detach().cpu().numpy() if torch.is_tensor(p0) else p0, dtype=np.float64).reshape(-1)
+        if p0.shape != (K,) or not ((p0 >= 0).all() and abs(p0.sum() - 1.0) <= 1e-9):
+            raise ValueError(f"p0 must be a distribution over the {K} states")
+    return Ds, np.ascontiguousarray(M), np.ascontiguousarray(p0)
+
+
+def markov_states(u, p0, M):
+    """State paths of a Markov chain from uniform numbers: u [N, T] in [0, 1), p0 [K] the distribution of the first state, M
+    [K, K] the transition matrix (row = from) -> state [N, T] int32 of u's kind.  state[n, 0] is the first k with u[n, 0] <
+    p0[0] + .. + p0[k], state[n, t] the same on row M[state[n, t - 1]]; the last state catches rounding.  CUDA tensors go to
+    the kernel (ops.markov_states, csrc/segment.hip), anything else to the numpy restatement, bitwise equal."""
+    is_t = torch.is_tensor(u)
+    if len(u.shape) != 2:
+        raise ValueError(f"u must be [N, T], got {tuple(u.shape)}")
+    host = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else v                                  # noqa: E731
+    p0h, Mh = np.asarray(host(p0), dtype=np.float64).reshape(-1), np.asarray(host(M), dtype=np.float64)
+    _markov_args(np.zeros(len(p0h)), Mh, p0h)
+    if is_t and u.device.type == "cuda":
+        from .. import ops
+        return ops.markov_states(u.detach().double().contiguous(), torch.from_numpy(p0h).to(u.device),
+                                 torch.from_numpy(np.ascontiguousarray(Mh)).to(u.device))
+    out = _markov_host(u.detach().double().numpy() if is_t else np.asarray(u, dtype=np.float64), p0h, Mh)
+    return torch.from_numpy(out) if is_t else out
+
+
+def multi_state(N: int, T: int, Ds, M, p0=None, dt: float = 1.0, generator: Optional[torch.Generator] = None, device="cpu",
+                return_states: bool = True):
+    """(T, N, 2) Brownian trajectories whose diffusion coefficient follows a Markov chain, in the layout of
+    brownian_single_state, and (with return_states) states [N, T] int64: stands in for
+    ``andi_datasets.models_phenom().multi_state(N, L=0, T, Ds, M)`` with alpha = 1 in every state.  Ds [K] the coefficient of
+    each state, M [K, K] the transition matrix per step, p0 [K] the distribution of the first state (default: the stationary
+    distribution of M).  Draws, in this order: torch.rand(N, T) for the states, torch.randn(T, N, 2) for the steps.  Step t
+    has variance 2 Ds[state[t]] dt per axis; position 0 is 0.  The state path comes from csrc/segment.hip on a GPU generator
+    and from its numpy restatement otherwise."""
+    Dsv, Mv, p0v = _markov_args(Ds, M, p0)
+    gdev = generator.device if generator is not None else torch.device(device)
+    u = torch.rand(N, T, generator=generator, device=gdev, dtype=torch.float64)
+    states = markov_states(u, p0v, Mv).long()
+    scale = torch.sqrt(2.0 * torch.from_numpy(Dsv).to(gdev) * dt).float()[states]                            # [N, T]
+    steps = torch.randn(T, N, 2, generator=generator, device=gdev) * scale.t().unsqueeze(-1)
+    if T:
+        steps[0] = 0.0
+    trajs = torch.cumsum(steps, dim=0).to(device)
+    return (trajs, states.to(device)) if return_states else trajs
+
+
 def psf_sigma_hr(props: dict) -> float:
     """Gaussian sigma on the upsampled grid (helpersGeneration.py: fwhm = wavelength / 2 * NA / psf_division_factor)."""
     fwhm = props["wavelength"] / 2 * props["NA"] / props.get("psf_division_factor", 1)
@@ -746,7 +838,7 @@ def _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin):
 
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
-                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp"):
+                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -788,7 +880,15 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     geometry.map_displacements (csrc/confine.hip on a GPU generator).  D is the 1-D coefficient ALONG the filament:
     <ds^2> = 2 D k^alpha after k frames.  truth gains arc [Np, T] float64, edge [Np, T] int32 (within the particle's geometry)
     and geometry_id [Np] int64; truth["pos"] is the mapped position in float32.  truth["y"] and truth["x"] remain the means of
-    a frame's sub-positions: where a frame's sub-positions go round a corner the mean lies off the filament."""
+    a frame's sub-positions: where a frame's sub-positions go round a corner the mean lies off the filament.
+
+    states (default None: one D per particle, the code path without it): a dict {"Ds": [K], "M": [K, K], "p0": optional [K],
+    "path": optional} of a multi-state particle (multi_state, _markov_args); the argument Ds must then be None.  u = rand(Np,
+    F) is drawn where D is drawn otherwise and markov_states(u, p0, M) is the state of every particle in every frame (csrc/
+    segment.hip on a GPU generator); "path", integer [Np, F] in [0, K), plants the states instead and nothing is drawn for
+    them.  The state is constant over the sub-positions of a frame: sub-step t of frame f has variance 2 Ds[state[p, f]] /
+    nPosPerFrame.  truth gains state (int64 per row) and D_row (float64 per row); truth["D"] is the mean of D_row over the
+    lifetime, so score_tracking keeps working.  Not together with alphas; with a geometry the steps run along the filament."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -831,14 +931,40 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError("geometry_of and boundary need a geometry")
     else:
         packed, geom_id = _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin)
-    D = _draw_diffusion_coefficients(Np, Ds, generator, gdev)
+    state = None
+    if states is None:
+        D = _draw_diffusion_coefficients(Np, Ds, generator, gdev)
+    else:
+        if alphas is not None:
+            raise ValueError("states and alphas cannot be combined: an exponent per state is not supported")
+        if Ds is not None:
+            raise ValueError("with states the coefficients are states['Ds']: Ds must be None")
+        if not isinstance(states, dict) or "Ds" not in states or "M" not in states or set(states) - {"Ds", "M", "p0", "path"}:
+            raise ValueError("states must be a dict with the keys Ds and M and optionally p0 and path")
+        state_Ds, state_M, state_p0 = _markov_args(states["Ds"], states["M"], states.get("p0"))
+        if states.get("path") is not None:
+            path = torch.as_tensor(states["path"]).detach().cpu()
+            if path.is_floating_point() or path.dtype == torch.bool or tuple(path.shape) != (Np, F_):
+                raise ValueError(f"states['path'] must be integer [{Np}, {F_}], got {path.dtype} {tuple(path.shape)}")
+            if path.numel() and (int(path.min()) < 0 or int(path.max()) >= len(state_Ds)):
+                raise ValueError(f"states['path'] must lie in [0, {len(state_Ds)})")
+            state = path.long().to(gdev)
+        else:
+            state = markov_states(torch.rand(Np, F_, generator=generator, device=gdev, dtype=torch.float64), state_p0,
+                                  state_M).long()
+        D_frame = torch.from_numpy(state_Ds).to(gdev)[state]                                                 # [Np, F] float64
     alpha = None if alphas is None else _draw_alphas(Np, alphas, generator, gdev)
     T = F_ * npos
+    if state is not None:
+        # one factor per sub-step in place of the one per particle: sqrt(2 D / npos) in float32, as without states
+        step_scale = torch.sqrt(2.0 * D_frame.float() / npos).repeat_interleave(npos, dim=1).view(Np, T, 1)
     if packed is not None:
         from . import geometry as _geometry
         start = torch.rand(Np, generator=generator, device=gdev).double() * torch.from_numpy(packed["totals"][geom_id]).to(gdev)
         z = torch.randn(Np, T, 1, generator=generator, device=gdev)
-        if alpha is None:
+        if state is not None:
+            steps = z * step_scale
+        elif alpha is None:
             steps = z * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
         else:
             rescale = torch.from_numpy(np.power(float(npos), 1.0 - alpha.numpy())).to(gdev).float()
@@ -850,7 +976,9 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     else:
         span = torch.tensor([H - 1 - 2 * margin, W - 1 - 2 * margin], device=gdev)
         start = margin + torch.rand(Np, 2, generator=generator, device=gdev) * span
-        if alpha is None:
+        if state is not None:
+            steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * step_scale
+        elif alpha is None:
             steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
         else:
             # variance 2 D / npos^alpha per sub-step, so that a frame of npos sub-steps keeps the MSD 2 D: written as the
@@ -883,8 +1011,14 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     pid, frame = ((first.view(Np, 1) <= fr) & (fr <= last.view(Np, 1))).nonzero(as_tuple=True)
     mean_pos = pos.double().view(Np, F_, npos, 2).mean(dim=2)
     offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(last - first + 1, 0)])
+    if state is not None:
+        state, D_frame = state.to(dev), D_frame.to(dev)
+        D_row = D_frame[pid, frame]
+        D = torch.zeros(Np, dtype=torch.float64, device=dev).index_add_(0, pid, D_row) / (last - first + 1).double()
     truth = {"frame": frame, "y": mean_pos[pid, frame, 0], "x": mean_pos[pid, frame, 1], "particle_id": pid, "offsets": offsets,
              "D": D.to(dev), "pos": pos, "amp": amp, "first": first, "last": last}
+    if state is not None:
+        truth["state"], truth["D_row"] = state[pid, frame], D_row
     if blink is not None:
         truth["visible"] = ~dark[pid, frame]
     if alpha is not None:

@@ -161,3 +161,152 @@ def track_msd(positions, offsets, dt=1.0, max_lag=None):
                                int(max_lag))
         return tuple(torch.from_numpy(a) for a in out)
     return _track_msd_numpy(np.asarray(positions, dtype=np.float64), offsets.astype(np.int64), float(dt), int(max_lag))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# multi-state tracks: changepoints of the step variance and one row of estimates per segment (csrc/segment.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _segment_numpy(pos, offsets, min_len, penalty, min_var, return_margin=False):
+    """The arithmetic of csrc/segment.hip::seg_tracks_kernel in its order (include/mivit_hip.h, mivit_segment_tracks):
+    np.cumsum is the sequential prefix sum, np.argmin returns the lowest index among equal minima.  pos [N, 2] float64,
+    offsets [n_tracks + 1] int64 -> (seg_start [N] int32, cost [n_tracks] float64).  Differs from the kernel in log alone.
+    return_margin: also margin [n_tracks], the smallest gap between the chosen candidate and the runner-up over the steps j
+    on the backtracked path (inf where no such step had two candidates): how far rounding is from changing the partition."""
+    n_tracks = len(offsets) - 1
+    seg_start = np.zeros(len(pos), np.int32)
+    cost = np.full(n_tracks, np.nan)
+    margin = np.full(n_tracks, np.inf)
+    for k in range(n_tracks):
+        a, b = int(offsets[k]), int(offsets[k + 1])
+        L = b - a
+        if L >= 1:
+            seg_start[a] = 1
+        Linc = L - 1
+        if Linc < 1:
+            continue
+        p = pos[a:b]
+        dy, dx = p[1:, 0] - p[:-1, 0], p[1:, 1] - p[:-1, 1]
+        cs = np.concatenate([np.zeros(1), np.cumsum(dy * dy + dx * dx)])
+        beta = penalty * np.log(float(Linc))
+
+        def step(j, cand):
+            tn = 2.0 * (j - cand).astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return (F[cand] + tn * np.log(np.maximum((cs[j] - cs[cand]) / tn, min_var))) + beta
+
+        F = np.full(Linc + 1, np.nan)
+        F[0] = -beta
+        if Linc < min_len:
+            cost[k] = step(Linc, np.zeros(1, np.int64))[0]
+            continue
+        prev = np.zeros(Linc + 1, np.int64)
+        gap = np.full(Linc + 1, np.inf)
+        for j in range(min_len, Linc + 1):
+            cand = np.concatenate([np.zeros(1, np.int64), np.arange(min_len, j - min_len + 1, dtype=np.int64)])
+            v = step(j, cand)
+            m = int(np.argmin(v)) if not np.isnan(v).all() else 0
+            F[j], prev[j] = v[m], cand[m]
+            if return_margin and len(v) > 1:
+                gap[j] = np.partition(v, 1)[1] - v[m]
+        cost[k] = F[Linc]
+        j = Linc
+        while j > 0:
+            margin[k] = min(margin[k], gap[j])
+            i = int(prev[j])
+            if i > 0:
+                seg_start[a + i] = 1
+            j = i
+    return (seg_start, cost, margin) if return_margin else (seg_start, cost)
+
+
+def _segment_stats_numpy(pos, seg_offsets, seg_track_end, dt, blur):
+    """The arithmetic of csrc/segment.hip::seg_stats_kernel in its order: np.cumsum(...)[-1] is a sequential sum.  -> (D_cve,
+    D_mle, sigma2 [n_seg] float64, n_increments [n_seg] int32), bitwise the kernel's."""
+    n_seg = len(seg_track_end)
+    d_cve, d_mle, sigma2 = np.full(n_seg, np.nan), np.full(n_seg, np.nan), np.full(n_seg, np.nan)
+    n_inc = np.zeros(n_seg, np.int32)
+    R = float(blur)
+    for s in range(n_seg):
+        r0 = int(seg_offsets[s])
+        r1 = min(int(seg_offsets[s + 1]), int(seg_track_end[s]) - 1, len(pos) - 1)
+        n = max(r1 - r0, 0)
+        n_inc[s] = n
+        if n < 1:
+            continue
+        p = pos[r0:r1 + 1]
+        dy, dx = p[1:, 0] - p[:-1, 0], p[1:, 1] - p[:-1, 1]
+        S2 = np.cumsum(dy * dy + dx * dx)[-1]
+        d_mle[s] = S2 / ((4.0 * float(n)) * dt)
+        if n >= 2:
+            S11 = np.cumsum(dy[:-1] * dy[1:] + dx[:-1] * dx[1:])[-1]
+            m1 = 2.0 * float(n - 1)
+            d_cve[s] = d_mle[s] + S11 / (m1 * dt)
+            sigma2[s] = (R * S2) / (2.0 * float(n)) + ((2.0 * R - 1.0) * S11) / m1
+    return d_cve, d_mle, sigma2, n_inc
+
+
+def segment_tracks(positions, offsets, dt=1.0, min_len=4, penalty=3.0, min_var=1e-12, blur=0.0):
+    """Tracks whose diffusion coefficient changes: the optimal partition of every track into stretches of constant step
+    variance, and the estimates of each stretch.  positions [N, 2] (y, x) sorted by track and by frame, offsets [n_tracks + 1]
+    (CSR), as track_msd takes them (gap-free rows) -> dict:
+        seg_offsets [n_seg + 1] int64   CSR of the segments over the same rows: track_msd, tracking.plan_sequences and
+                                        tracking.track_sequences accept it in place of offsets
+        seg_track   [n_seg] int64       the track of each segment
+        D_cve, D_mle, sigma2 [n_seg] float64, n_increments [n_seg] int64
+        cost        [n_tracks] float64  the penalised cost of the partition, NaN for a track without an increment
+    Penalised likelihood (optimal partitioning): the increments of a stretch are Gaussian with one variance, a stretch has at
+    least min_len increments, and every changepoint costs beta = penalty * log(increments of the track); a variance below
+    min_var counts as min_var (a track that does not move).  The changepoint at increment c puts row c into the later
+    segment; the increment that bridges two segments is counted in the earlier one's estimates.  D_mle = <q> / (4 dt) is the
+    maximum-likelihood estimate without localisation noise, which adds sigma^2 / dt to it; D_cve (Vestergaard et al. 2014)
+    adds the covariance of neighbouring increments, in which localisation noise and motion blur cancel, and sigma2 is the
+    localisation variance that goes with it, with blur the motion-blur coefficient R (0: instantaneous exposure, 1/6: the
+    whole frame).  D_cve and sigma2 are NaN for a segment of fewer than 2 increments.  include/mivit_hip.h has the
+    arithmetic.  CUDA tensors go to the kernels (csrc/segment.hip: two launches; a track has at most ops.SEG_MAX_LEN rows),
+    numpy arrays and CPU tensors to the numpy restatements; the output is of the input's kind."""
+    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
+        raise ValueError(f"min_len must be an integer >= 2, got {min_len}")
+    if not float(penalty) >= 0.0:
+        raise ValueError(f"penalty must be >= 0, got {penalty}")
+    if not 0.0 < float(min_var) < float("inf"):
+        raise ValueError(f"min_var must be positive and finite, got {min_var}")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    if torch.is_tensor(positions) != torch.is_tensor(offsets):
+        raise ValueError("positions and offsets must both be tensors or both be arrays")
+    if torch.is_tensor(positions) and positions.device != offsets.device:
+        raise ValueError(f"positions on {positions.device}, offsets on {offsets.device}")
+    offsets = offsets if torch.is_tensor(offsets) else np.asarray(offsets)
+    _check_offsets(offsets, positions.shape[0])
+    min_len, penalty, min_var, dt, blur = int(min_len), float(penalty), float(min_var), float(dt), float(blur)
+    is_t = torch.is_tensor(positions)
+    if is_t and positions.device.type == "cuda":
+        from .. import ops
+        lengths = offsets[1:] - offsets[:-1]
+        if len(lengths) and int(lengths.max()) > ops.SEG_MAX_LEN:
+            raise ValueError(f"a track of {int(lengths.max())} rows on the GPU, the kernel's limit is {ops.SEG_MAX_LEN} "
+                             f"(ops.SEG_MAX_LEN)")
+        pos = positions.detach().double().contiguous()
+        seg_start, cost = ops.segment_tracks(pos, offsets.int().contiguous(), min_len, penalty, min_var)
+        first = torch.nonzero(seg_start, as_tuple=True)[0]
+        seg_offsets = torch.cat([first, torch.full((1,), pos.shape[0], dtype=torch.int64, device=pos.device)])
+        seg_track = torch.searchsorted(offsets.long().contiguous(), first, right=True) - 1
+        # an empty track shares its offset with the next one: the LAST track that starts at or before the row owns it
+        track_end = offsets.long()[seg_track + 1]
+        d_cve, d_mle, sigma2, n_inc = ops.segment_stats(pos, seg_offsets.int(), track_end.int(), dt, blur)
+        return {"seg_offsets": seg_offsets, "seg_track": seg_track, "D_cve": d_cve, "D_mle": d_mle, "sigma2": sigma2,
+                "n_increments": n_inc.long(), "cost": cost}
+    pos = positions.detach().double().numpy() if is_t else np.asarray(positions, dtype=np.float64)
+    off = (offsets.detach().numpy() if is_t else offsets).astype(np.int64)
+    seg_start, cost = _segment_numpy(pos, off, min_len, penalty, min_var)
+    first = np.nonzero(seg_start)[0].astype(np.int64)
+    seg_offsets = np.concatenate([first, np.full(1, len(pos), np.int64)])
+    seg_track = np.searchsorted(off, first, side="right").astype(np.int64) - 1
+    d_cve, d_mle, sigma2, n_inc = _segment_stats_numpy(pos, seg_offsets, off[seg_track + 1], dt, blur)
+    out = {"seg_offsets": seg_offsets, "seg_track": seg_track, "D_cve": d_cve, "D_mle": d_mle, "sigma2": sigma2,
+           "n_increments": n_inc.astype(np.int64), "cost": cost}
+    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out

@@ -1127,7 +1127,7 @@ def refine_localizations_tensors(patches, ys, xs):
 
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
-                             batch_size=4096, **tracking_kwargs):
+                             batch_size=4096, segment=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1138,9 +1138,17 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     msd [n_tracks, longest track].  D_model is the model's output in the units it was trained in: no scale factor is applied
     here.  With max_gap > 0 among the tracking arguments the tracks are gap-closed and filled: length counts rows, the filled
     ones included, the result gains n_filled (int64 [n_tracks], the filled rows of each track), and with refine the filled
-    rows are fitted on their patch like any other row (a failed fit falls back to the interpolated position)."""
+    rows are fitted on their patch like any other row (a failed fit falls back to the interpolated position).
+
+    segment (default None: one number per track, the code path without it): a dict of helpers/msd.segment_tracks arguments
+    (min_len, penalty, min_var, blur; {} for the defaults; dt is this function's).  The result gains "segments": the
+    segment_tracks dict computed on the positions the MSD is taken on (csrc/segment.hip), plus D_model [n_seg], the mean of
+    the model's output over the windows of plan_sequences(seg_offsets, seq_len, tail), so that no window straddles a
+    changepoint (NaN for a segment shorter than seq_len), and n_sequences [n_seg].  The per-track entries are unchanged."""
     if not _is_cuda(movie):
         raise ValueError("estimate_track_diffusion needs a CUDA movie; move it to the GPU (movie.cuda())")
+    if segment is not None and (not isinstance(segment, dict) or set(segment) - {"min_len", "penalty", "min_var", "blur"}):
+        raise ValueError("segment must be None or a dict with keys among min_len, penalty, min_var and blur")
     _check_sequence_args(seq_len, tail, patch_size)
     if int(batch_size) != batch_size or batch_size < 1:
         raise ValueError(f"batch_size must be an integer >= 1, got {batch_size}")
@@ -1161,20 +1169,34 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
     n_sequences = torch.bincount(seq_track, minlength=n_tracks)
     model.eval()
-    outs = []
-    with torch.no_grad():
-        for b0 in range(0, len(seq), int(batch_size)):
-            out = model(seq[b0:b0 + int(batch_size)])
-            outs.append(out.reshape(len(out), -1)[:, 0].double())
-    per_seq = torch.cat(outs) if outs else torch.zeros(0, dtype=torch.float64, device=movie.device)
-    d_model = torch.full((n_tracks,), float("nan"), dtype=torch.float64, device=movie.device)
-    if len(per_seq):
-        d_model = torch.where(n_sequences > 0, torch.segment_reduce(per_seq, "mean", lengths=n_sequences), d_model)
+
+    def mean_per_group(seq, counts):
+        outs = []
+        with torch.no_grad():
+            for b0 in range(0, len(seq), int(batch_size)):
+                out = model(seq[b0:b0 + int(batch_size)])
+                outs.append(out.reshape(len(out), -1)[:, 0].double())
+        per_seq = torch.cat(outs) if outs else torch.zeros(0, dtype=torch.float64, device=movie.device)
+        d_model = torch.full((len(counts),), float("nan"), dtype=torch.float64, device=movie.device)
+        if len(per_seq):
+            d_model = torch.where(counts > 0, torch.segment_reduce(per_seq, "mean", lengths=counts), d_model)
+        return d_model
+
+    d_model = mean_per_group(seq, n_sequences)
+    segments = None
+    if segment is not None:
+        from . import msd as _msd
+        segments = _msd.segment_tracks(pos, offsets, dt=dt, **segment)
+        seg_seq, seg_of_seq, _ = track_sequences(movie, fr, y, x, segments["seg_offsets"], seq_len, patch_size, norm, tail)
+        segments["n_sequences"] = torch.bincount(seg_of_seq, minlength=len(segments["seg_track"]))
+        segments["D_model"] = mean_per_group(seg_seq, segments["n_sequences"])
     res = {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
            "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}
     if len(by_track) > 5:
         row_track = torch.repeat_interleave(torch.arange(n_tracks, device=movie.device), lengths)
         res["n_filled"] = torch.bincount(row_track[by_track[5]], minlength=n_tracks)
+    if segments is not None:
+        res["segments"] = segments
     return res
 
 

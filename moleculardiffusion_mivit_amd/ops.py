@@ -886,6 +886,94 @@ def _map_displacements_checked(disp, s0, geom_of, verts, lengths, vert_offsets, 
     return pos, arc, edge
 
 
+SEG_MAX_LEN = 4096           # csrc/segment.hip: rows of a track whose recurrence state (20 B a row) fits in LDS
+MARKOV_MAX_K = 8             # csrc/segment.hip: states of mivit_markov_states
+
+
+def _seg_tensor(t, dtype, ndim, name, what):
+    """_dev_tensor that takes no copy: a non-contiguous tensor is an error (the helpers pass contiguous ones)."""
+    if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype or t.dim() != ndim or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous {ndim}-D {str(dtype).replace('torch.', '')} GPU tensor")
+    return t
+
+
+def segment_tracks(pos: torch.Tensor, offsets: torch.Tensor, min_len: int = 4, penalty: float = 3.0, min_var: float = 1e-12):
+    """The optimal partition of every track into stretches of constant step variance (csrc/segment.hip,
+    mivit_segment_tracks): pos [N, 2] float64 on the GPU, sorted by track and by frame; offsets [n_tracks + 1] int32 (CSR, from
+    0 to N) -> (seg_start [N] int32, 1 on the first row of every segment; cost [n_tracks] float64, NaN for a track without an
+    increment).  A track has at most SEG_MAX_LEN rows.  The longest track is read back (one number) to size the kernel's LDS.
+    See include/mivit_hip.h for the recurrence and helpers/msd.segment_tracks for the front end."""
+    pos = _seg_tensor(pos, torch.float64, 2, "segment_tracks", "pos [N, 2]")
+    offsets = _seg_tensor(offsets, torch.int32, 1, "segment_tracks", "offsets [n_tracks + 1]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"segment_tracks: pos must be [N, 2], got {tuple(pos.shape)}")
+    if offsets.numel() < 1:
+        raise ValueError("segment_tracks: offsets must have n_tracks + 1 entries")
+    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
+        raise ValueError(f"segment_tracks: min_len must be an integer >= 2, got {min_len}")
+    if not float(penalty) >= 0.0:
+        raise ValueError(f"segment_tracks: penalty must be >= 0, got {penalty}")
+    if not 0.0 < float(min_var) < float("inf"):
+        raise ValueError(f"segment_tracks: min_var must be positive and finite, got {min_var}")
+    n, n_tracks = pos.shape[0], offsets.numel() - 1
+    seg_start = torch.zeros(n, dtype=torch.int32, device=pos.device)
+    cost = torch.empty(n_tracks, dtype=torch.float64, device=pos.device)
+    if n_tracks == 0:
+        return seg_start, cost
+    off = offsets.cpu()
+    if int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"segment_tracks: offsets must rise from 0 to the number of rows {n}")
+    max_len = int((off[1:] - off[:-1]).max())
+    if max_len > SEG_MAX_LEN:
+        raise ValueError(f"segment_tracks: a track of {max_len} rows, the kernel's limit is {SEG_MAX_LEN} (SEG_MAX_LEN)")
+    N.check(N.lib.mivit_segment_tracks(_p(pos), n, _p(offsets), n_tracks, max_len, int(min_len), float(penalty), float(min_var),
+                                       _p(seg_start), _p(cost), _s(pos)), "mivit_segment_tracks")
+    return seg_start, cost
+
+
+def segment_stats(pos: torch.Tensor, seg_offsets: torch.Tensor, seg_track_end: torch.Tensor, dt: float = 1.0, blur: float = 0.0):
+    """One row of estimates per segment (csrc/segment.hip, mivit_segment_stats): pos [N, 2] float64 on the GPU, seg_offsets
+    [n_seg + 1] int32 (the CSR of the segments over the rows), seg_track_end [n_seg] int32 (the row at which each segment's
+    track ends), blur the motion-blur coefficient R in [0, 1/4] -> (D_cve, D_mle, sigma2 [n_seg] float64, n_increments [n_seg]
+    int32).  See include/mivit_hip.h for the arithmetic."""
+    pos = _seg_tensor(pos, torch.float64, 2, "segment_stats", "pos [N, 2]")
+    seg_offsets = _seg_tensor(seg_offsets, torch.int32, 1, "segment_stats", "seg_offsets [n_seg + 1]")
+    seg_track_end = _seg_tensor(seg_track_end, torch.int32, 1, "segment_stats", "seg_track_end [n_seg]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"segment_stats: pos must be [N, 2], got {tuple(pos.shape)}")
+    if seg_offsets.numel() != seg_track_end.numel() + 1:
+        raise ValueError(f"segment_stats: seg_offsets must have one entry more than seg_track_end, got {seg_offsets.numel()} and "
+                         f"{seg_track_end.numel()}")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"segment_stats: dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"segment_stats: the blur coefficient must lie in [0, 1/4], got {blur}")
+    n_seg = seg_track_end.numel()
+    d_cve, d_mle, sigma2 = (torch.empty(n_seg, dtype=torch.float64, device=pos.device) for _ in range(3))
+    n_inc = torch.empty(n_seg, dtype=torch.int32, device=pos.device)
+    N.check(N.lib.mivit_segment_stats(_p(pos), pos.shape[0], _p(seg_offsets), _p(seg_track_end), n_seg, float(dt), float(blur),
+                                      _p(d_cve), _p(d_mle), _p(sigma2), _p(n_inc), _s(pos)), "mivit_segment_stats")
+    return d_cve, d_mle, sigma2, n_inc
+
+
+def markov_states(u: torch.Tensor, p0: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
+    """The state paths of a Markov chain from uniform numbers (csrc/segment.hip, mivit_markov_states): u [N, T], p0 [K] and M
+    [K, K] float64 on the GPU, 1 <= K <= MARKOV_MAX_K -> state [N, T] int32.  See include/mivit_hip.h and
+    helpers/generation.markov_states for the front end, which checks that p0 and the rows of M are distributions."""
+    u = _seg_tensor(u, torch.float64, 2, "markov_states", "u [N, T]")
+    p0 = _seg_tensor(p0, torch.float64, 1, "markov_states", "p0 [K]")
+    M = _seg_tensor(M, torch.float64, 2, "markov_states", "M [K, K]")
+    K = p0.numel()
+    if not 1 <= K <= MARKOV_MAX_K:
+        raise ValueError(f"markov_states: {K} states, 1 .. {MARKOV_MAX_K} (MARKOV_MAX_K) are supported")
+    if tuple(M.shape) != (K, K):
+        raise ValueError(f"markov_states: M must be [{K}, {K}], got {tuple(M.shape)}")
+    n, T = u.shape
+    state = torch.empty(n, T, dtype=torch.int32, device=u.device)
+    N.check(N.lib.mivit_markov_states(_p(u), _p(p0), _p(M), n, T, K, _p(state), _s(u)), "mivit_markov_states")
+    return state
+
+
 MOVIE_MAX_RADIUS = 64        # csrc/movie.hip: limits of mivit_render_movie
 MOVIE_MAX_NPOS = 256
 MOVIE_MAX_UP = 64

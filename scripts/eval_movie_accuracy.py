@@ -12,12 +12,19 @@ over the tracks of at least 20 rows, and the same estimator's median on the trut
 --cristae N SPACING DEPTH WIDTH confines every particle to one serpentine of N cristae (helpers/geometry.cristae_geometry,
 centred in the field; simulate_movie's geometry, csrc/confine.hip), --boundary clamp|reflect is what happens at its two ends;
 D is then the 1-D coefficient along the filament, and the output gains the filament's total length and the medians of D_true,
-D_msd and D_msd_weighted over the matched tracks.  A tool, not a test: it asserts no accuracy.
+D_msd and D_msd_weighted over the matched tracks.  --states D1 D2 P_STAY simulates two-state particles (simulate_movie's
+states: coefficients D1 and D2, probability P_STAY per frame of keeping the state; --D is then not used), runs
+estimate_track_diffusion(..., segment={"penalty": p}) (helpers/msd.segment_tracks, csrc/segment.hip) for every p of
+--penalties and adds "segmentation": per penalty, over the tracks matched to a particle, the recall and precision of the
+changepoints (a found one counts when it lies within 5 frames of a true one of that particle inside the track's frames,
+every true one once) and the mean absolute error per row against truth["D_row"] of D_cve and D_mle of the row's segment and
+of D_msd of its track.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
                                           [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10]
                                           [--cristae 4 30 60 12] [--boundary reflect]
+                                          [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -56,6 +63,8 @@ def main():
     ap.add_argument("--alpha-max-lag", type=int, default=10)
     ap.add_argument("--cristae", type=float, nargs=4, default=None, metavar=("N", "SPACING", "DEPTH", "WIDTH"))
     ap.add_argument("--boundary", choices=["clamp", "reflect"], default=None)
+    ap.add_argument("--states", type=float, nargs=3, default=None, metavar=("D1", "D2", "P_STAY"))
+    ap.add_argument("--penalties", type=float, nargs="+", default=[1.0, 2.0, 3.0, 4.0, 6.0, 8.0])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
@@ -73,8 +82,13 @@ def main():
                    "boundary": args.boundary or "clamp"}
     elif args.boundary is not None:
         raise SystemExit("--boundary needs --cristae")
-    movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props,
-                                      generator=g, device="cuda", blink=args.blink, alphas=args.alpha, **confine)
+    states = None
+    if args.states is not None:
+        d1, d2, stay = args.states
+        states = {"Ds": [d1, d2], "M": [[stay, 1.0 - stay], [1.0 - stay, stay]]}
+    movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, None if states else tuple(args.D), args.npos,
+                                      image_props=props, generator=g, device="cuda", blink=args.blink, alphas=args.alpha,
+                                      states=states, **confine)
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
@@ -125,7 +139,57 @@ def main():
         sharp = truth["pos"][:, ::args.npos].double()
         s_msd = MSD.mean_square_displacements(sharp)
         out["alpha_msd_truth_unblurred_median"] = float(MSD.estimate_alpha(s_msd, max_lag=args.alpha_max_lag).nanmedian())
+    if states is not None:
+        out["states"] = args.states
+        out["segmentation"] = [segmentation_scores(movie, model, args, norm, truth, score, fr, float(p)) for p in args.penalties]
     print(json.dumps(out))
+
+
+def segmentation_scores(movie, model, args, norm, truth, score, fr, penalty, tol=5):
+    """changepoint recall / precision and the per-row errors of one penalty (see the module's docstring)"""
+    est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
+                                       segment={"penalty": penalty})
+    seg = est["segments"]
+    Np, F_ = args.particles, args.frames
+    nan = float("nan")
+    d_true = torch.full((Np, F_), nan, dtype=torch.float64, device=movie.device)
+    d_true[truth["particle_id"], truth["frame"]] = truth["D_row"]
+    state = torch.full((Np, F_), -1, dtype=torch.int64, device=movie.device)
+    state[truth["particle_id"], truth["frame"]] = truth["state"]
+    n_rows = len(fr)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=movie.device), torch.cumsum(est["length"], 0)])
+    row_track = torch.repeat_interleave(torch.arange(len(est["length"]), device=movie.device), est["length"])
+    seg_len = seg["seg_offsets"][1:] - seg["seg_offsets"][:-1]
+    row_seg = torch.repeat_interleave(torch.arange(len(seg_len), device=movie.device), seg_len)
+    pid = score["particle_id"][row_track]
+    ok = pid >= 0
+    want = d_true[pid.clamp_min(0), fr.clamp(0, F_ - 1)]
+    ok = ok & ~torch.isnan(want)
+    mae = lambda col: float((col[ok] - want[ok]).abs().nanmean()) if bool(ok.any()) else nan                   # noqa: E731
+    n_true = n_found = n_hit = 0
+    off, so, st, frames = offsets.tolist(), seg["seg_offsets"].tolist(), seg["seg_track"].tolist(), fr.tolist()
+    starts = {}
+    for s, k in enumerate(st):
+        starts.setdefault(k, []).append(so[s])
+    state_h = state.cpu()
+    for k, p in enumerate(score["particle_id"].tolist()):
+        if p < 0 or off[k + 1] <= off[k]:
+            continue
+        f0, f1 = frames[off[k]], frames[off[k + 1] - 1]
+        path = state_h[p, f0:f1 + 1]
+        true_cp = [f0 + 1 + int(i) for i in torch.nonzero((path[1:] != path[:-1]) & (path[1:] >= 0) & (path[:-1] >= 0)).view(-1)]
+        found = [frames[r] for r in starts.get(k, [])[1:]]
+        n_true, n_found = n_true + len(true_cp), n_found + len(found)
+        free = set(true_cp)
+        for f in found:
+            near = [t for t in free if abs(t - f) <= tol]
+            if near:
+                free.discard(min(near, key=lambda t: abs(t - f)))
+                n_hit += 1
+    return {"penalty": penalty, "n_segments": len(seg_len), "n_true_changepoints": n_true, "n_found_changepoints": n_found,
+            "changepoint_recall": n_hit / n_true if n_true else nan, "changepoint_precision": n_hit / n_found if n_found else nan,
+            "mae_D_cve": mae(seg["D_cve"][row_seg]), "mae_D_mle": mae(seg["D_mle"][row_seg]), "mae_D_msd": mae(est["D_msd"][row_track]),
+            "rows_scored": int(ok.sum()), "rows": n_rows}
 
 
 if __name__ == "__main__":
