@@ -394,11 +394,8 @@ int launch_wgrad_small_f16(const void *dy, int64_t lddy, const void *x, int64_t 
 // small elementwise / reduction helpers (misc.hip)
 // out[n] (+)= sum_p part[p*n_stride + n]   (deterministic slab reduce)
 int launch_slab_reduce(const float *part, int nparts, int64_t n, float *out, int accumulate, hipStream_t s);
+// (queued, not launched, while a SlabDefer scope of slab_defer.h is active on the calling thread)
 int launch_slab_reduce_strided(const float *part, int nparts, int64_t stride, int64_t n, float *out, hipStream_t s);
-// queue the strided reductions issued from here on (their slabs must stay untouched) / run the queue as one launch
-void slab_defer_begin();
-void slab_defer_cancel();
-int slab_defer_flush(hipStream_t s);
 // up to three (slab, output) pairs of the same shape in one launch; pass null outputs from the end
 int launch_slab_reduce3(const float *p0, float *o0, const float *p1, float *o1, const float *p2, float *o2, int nparts,
                         int n, int accumulate, hipStream_t s);
@@ -430,6 +427,11 @@ struct ProfScope {
     hipStream_t s; bool on;
     explicit ProfScope(hipStream_t st) : s(st), on(prof_begin(st)) {}
     ~ProfScope() { if (on) prof_end(s); }
+};
+struct ProfPin {          // prof_pin_tag for a lifetime (set() re-pins)
+    explicit ProfPin(int tag) { prof_pin_tag(tag); }
+    ~ProfPin() { prof_pin_tag(-1); }
+    void set(int tag) { prof_pin_tag(tag); }
 };
 
 // hipGraph replay of launch-bound call sequences (misc.hip).  `key` must hold every value the body's launches depend on

@@ -4,6 +4,7 @@
 // the kernels in gemm.hip / norm.hip / attention.hip / misc.hip.  The engine owns no device memory: the caller
 // passes the parameter arena, the gradient arena and one workspace whose layout is computed here.
 #include "common.h"
+#include "slab_defer.h"
 #include <atomic>
 #include <algorithm>
 
@@ -457,7 +458,6 @@ extern "C" mivit_plan *mivit_plan_create(const mivit_config *cfg) {
     p->arena = (p->arena + 7) / 8 * 8;
     p->stages.push_back({b0, p->arena});
     // q/k/v must be contiguous (E*E and E are multiples of 4 whenever E is): verify
-    for (const LayerParams &lp : p->layers) (void)lp;
     if ((int64_t)E * E % 4 != 0 || E % 4 != 0) {
         mivit_set_error("plan_create: embed_dim must be a multiple of 4 (got %d)", E);
         delete p;
@@ -490,351 +490,315 @@ extern "C" size_t mivit_plan_workspace_bytes(const mivit_plan *plan, int B, int 
     return make_ws(plan, B, T, need_backward != 0).total;
 }
 
-// ------------------------------------------------------------------------------------------------
-// forward
-// ------------------------------------------------------------------------------------------------
-static int forward_impl(const mivit_plan *plan, const float *params, const float *x, const float *features, int B,
-                             int T, void *workspace, size_t workspace_bytes, int need_backward, float *out,
-                             void *stream) {
-    RC(check_call(plan, B, T, workspace_bytes, need_backward != 0, "mivit_forward"));
-    MIVIT_CHECK(params && x && workspace && out, "mivit_forward: null pointer");
-    const mivit_config &c = plan->c;
-    MIVIT_CHECK(c.fusion == MIVIT_FUSION_NONE || features, "Global features required for %s fusion",
-                c.fusion == MIVIT_FUSION_EARLY ? "early" : "late");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int dt = c.dtype, E = c.embed_dim, F = c.hidden_dim, H = c.num_heads, Dh = E / H;
-    const int off = c.use_regression_token ? 1 : 0, S = T + off, M = B * S, Mt = B * T;
-    const Ws w = make_ws(plan, B, T, need_backward != 0);
-    void *ws = workspace;
-    const float *P = params;
-    // bf16 mode: one conversion of the whole fp32 arena per step; every GEMM then stages bf16 weights
-    if (dt != MIVIT_F32) RC(launch_convert(1, P, plan->arena, 0, at(ws, w.wsh), plan->arena, 1, (int)plan->arena, 0, s, dt));
-    auto WT = [&](int64_t off) -> const void * {
-        return dt != MIVIT_F32 ? static_cast<const void *>(static_cast<const bf16 *>(at(ws, w.wsh)) + off)
-                                : static_cast<const void *>(P + off);
-    };
+namespace {
 
-    // 1. frame embedding: one token per whole frame (models.py:146-199), [B*T, P*P] x [E, P*P]^T
-    if (c.embedding == MIVIT_EMBED_EXTERNAL) {
-        RC(launch_convert(1, x, E, dt == MIVIT_F32, at(ws, w.emb), E, Mt, E, 0, s, dt));
-    } else {
-        const int K = c.patch_size * c.patch_size;
-        const StreamOps *so = stream_ops(dt);
-        if (so && so->embed_ok(dt, Mt, K, E)) {
-            prof_set_tag(MIVIT_PROF_EMBED_FWD);
-            RC(so->embed_fwd(x, WT(plan->emb_w), P + plan->emb_b, at(ws, w.emb), Mt, K, E, s));
-        } else {
-            RC(lin_fwd(dt, x, 1, K, WT(plan->emb_w), P + plan->emb_b, Mt, E, K, MIVIT_ACT_NONE, nullptr, 0, at(ws, w.emb), E,
-                       nullptr, 0, s));
-        }
+// One forward / backward call, built once after check_call: the plan, the sizes derived from it and the caller's buffers.
+struct Call {
+    const mivit_plan *plan; const mivit_config &cfg;
+    const int dt, E, F, H, Dh, L, B, T, off, S, M, Mt, f32;      // off: token row of a sequence's first frame; M / Mt: token / frame rows
+    const bool bwd;               // the workspace is laid out for (and the forward keeps what) a backward needs
+    const bool fused;             // the encoder layers run as fused blocks (fused_fwd.hip / fused_bwd.hip) ...
+    const FusedOps *fo;           // ... of this table (null: per-operator layers)
+    const Ws w;
+    void *ws; const float *P; float *G; hipStream_t s;      // workspace base, parameter arena, gradient arena (null in a forward)
+    Call(const mivit_plan *p, int B_, int T_, bool bwd_, void *workspace, const float *params, float *grads, void *stream)
+        : plan(p), cfg(p->c), dt(cfg.dtype), E(cfg.embed_dim), F(cfg.hidden_dim), H(cfg.num_heads), Dh(E / H), L(cfg.num_layers),
+          B(B_), T(T_), off(cfg.use_regression_token ? 1 : 0), S(T + off), M(B * S), Mt(B * T), f32(dt == MIVIT_F32), bwd(bwd_),
+          fused(L > 0 && fused_ok(dt, E, F, H, S)), fo(fused ? fused_ops(dt, E) : nullptr), w(make_ws(p, B, T, bwd)),
+          ws(workspace), P(params), G(grads), s(static_cast<hipStream_t>(stream)) {}
+    void *buf(size_t o) const { return at(ws, o); }                                   // workspace region at a Ws offset
+    float *fbuf(size_t o) const { return static_cast<float *>(at(ws, o)); }
+    const float *p(int64_t o) const { return P + o; }                                 // fp32 parameter (bias, LayerNorm affine, table)
+    float *g(int64_t o) const { return G + o; }                                       // its gradient
+    // GEMM weight operand: the 16-bit shadow of the arena (refreshed by every forward) in the 16-bit modes, the arena in fp32
+    const void *W(int64_t o) const { return f32 ? (const void *)(P + o) : (const void *)(static_cast<const bf16 *>(buf(w.wsh)) + o); }
+    const void *trunk_out() const { return L == 0 ? buf(w.x0) : (fused ? buf(w.xL) : buf(w.layer[L - 1].x2)); }      // = input of the final norm
+};
+
+// ---- forward ----------------------------------------------------------------------------------
+// 1. frame embedding: one token per whole frame (models.py:146-199), [B*T, P*P] x [E, P*P]^T
+int embed_fwd(const Call &c, const float *x) {
+    const mivit_plan *p = c.plan;
+    if (c.cfg.embedding == MIVIT_EMBED_EXTERNAL) return launch_convert(1, x, c.E, c.f32, c.buf(c.w.emb), c.E, c.Mt, c.E, 0, c.s, c.dt);
+    const int K = c.cfg.patch_size * c.cfg.patch_size; const StreamOps *so = stream_ops(c.dt);
+    if (so && so->embed_ok(c.dt, c.Mt, K, c.E)) {
+        prof_set_tag(MIVIT_PROF_EMBED_FWD);
+        return so->embed_fwd(x, c.W(p->emb_w), c.p(p->emb_b), c.buf(c.w.emb), c.Mt, K, c.E, c.s);
     }
-    // 2. LayerNorm of the tokens, written behind the regression-token row, + positional table (models.py:334,347,138)
-    {
-        LayerNormFwdArgs a = {};
-        a.dtype = dt; a.z = at(ws, w.emb); a.ldz = E; a.gamma = P + plan->n0_w; a.beta = P + plan->n0_b; a.M = Mt; a.E = E;
-        a.y = at(ws, w.x0); a.ldy = E; a.rows_per_seq = T; a.out_seq_stride = S; a.out_row_off = off;
-        a.pos = c.use_pos_encoding ? P + plan->pos : nullptr;
-        a.mean = static_cast<float *>(at(ws, w.mean0)); a.rstd = static_cast<float *>(at(ws, w.rstd0));
-        prof_set_tag(MIVIT_PROF_LN_FWD); RC(launch_layernorm_fwd(a, s));
+    return lin_fwd(c.dt, x, 1, K, c.W(p->emb_w), c.p(p->emb_b), c.Mt, c.E, K, MIVIT_ACT_NONE, nullptr, 0, c.buf(c.w.emb), c.E, nullptr, 0, c.s);
+}
+
+// 2. token assembly: LayerNorm of the tokens, written behind the regression-token row, + positional table (models.py:334,347,138);
+//    feature projector (models.py:316-320): Linear(Fg,E) -> ReLU -> Linear(E,E); regression token row (models.py:339-347)
+int tokens_fwd(const Call &c, const float *features) {
+    const mivit_plan *p = c.plan; const mivit_config &cfg = c.cfg; const Ws &w = c.w;
+    const int dt = c.dt, E = c.E, B = c.B;
+    LayerNormFwdArgs a = {};
+    a.dtype = dt; a.z = c.buf(w.emb); a.ldz = E; a.gamma = c.p(p->n0_w); a.beta = c.p(p->n0_b); a.M = c.Mt; a.E = E;
+    a.y = c.buf(w.x0); a.ldy = E; a.rows_per_seq = c.T; a.out_seq_stride = c.S; a.out_row_off = c.off;
+    a.pos = cfg.use_pos_encoding ? c.p(p->pos) : nullptr; a.mean = c.fbuf(w.mean0); a.rstd = c.fbuf(w.rstd0);
+    prof_set_tag(MIVIT_PROF_LN_FWD); RC(launch_layernorm_fwd(a, c.s));
+    if (cfg.fusion != MIVIT_FUSION_NONE) {
+        const int Fg = cfg.global_feature_dim;
+        RC(lin_fwd(dt, features, 1, Fg, c.W(p->fp0_w), c.p(p->fp0_b), B, E, Fg, MIVIT_ACT_RELU, nullptr, 0, c.buf(w.fp_h), E, nullptr, 0, c.s));
+        RC(lin_fwd(dt, c.buf(w.fp_h), 0, E, c.W(p->fp2_w), c.p(p->fp2_b), B, E, E, MIVIT_ACT_NONE, nullptr, 0, c.buf(w.fp_out), E, nullptr, 0, c.s));
     }
-    // feature projector (models.py:316-320): Linear(Fg,E) -> ReLU -> Linear(E,E)
-    if (c.fusion != MIVIT_FUSION_NONE) {
-        const int G = c.global_feature_dim;
-        RC(lin_fwd(dt, features, 1, G, WT(plan->fp0_w), P + plan->fp0_b, B, E, G, MIVIT_ACT_RELU, nullptr, 0,
-                   at(ws, w.fp_h), E, nullptr, 0, s));
-        RC(lin_fwd(dt, at(ws, w.fp_h), 0, E, WT(plan->fp2_w), P + plan->fp2_b, B, E, E, MIVIT_ACT_NONE, nullptr, 0,
-                   at(ws, w.fp_out), E, nullptr, 0, s));
-    }
-    // 3. regression token row (models.py:339-347)
-    if (c.use_regression_token)
-        RC(launch_reg_token_fill(dt, at(ws, w.x0), B, S, E, P + plan->reg,
-                                 c.fusion == MIVIT_FUSION_EARLY ? at(ws, w.fp_out) : nullptr,
-                                 c.use_pos_encoding ? P + plan->pos : nullptr, s));
-    // 4. encoder layers (post-norm, models.py:97-108)
-    const void *xin = at(ws, w.x0);
-    const bool fused = c.num_layers > 0 && fused_ok(dt, E, F, H, S);
-    if (fused) {
-        // fused layer blocks (fused_fwd.hip): the layers hand each other NORMALISED tokens, the consumer applies the producing
-        // LayerNorm's affine (folded into its weights); training keeps q|k|v and h for the backward kernels, inference
-        // nothing; only the last block materialises x for the final norm
-        const float *gin = nullptr, *bin = nullptr;
-        const void *nin = xin;
-        for (int l = 0; l < c.num_layers; ++l) {
-            const LayerParams &lp = plan->layers[l];
-            const Ws::L &b = w.layer[l];
-            const bool last = l + 1 == c.num_layers;
-            prof_set_tag(MIVIT_PROF_ATTN_BLOCK_FWD);
-            RC(fused_ops(dt, E)->attn_fwd(nin, gin, bin, WT(lp.qkv_w), P + lp.qkv_b, WT(lp.out_w), P + lp.out_b, P + lp.n1_w,
-                                     P + lp.n1_b, B, S, at(ws, b.ctx), at(ws, b.z1), static_cast<float *>(at(ws, b.rstd1)),
-                                     nullptr, nullptr, nullptr, need_backward ? at(ws, b.qkv) : nullptr, s));
-            prof_set_tag(MIVIT_PROF_MLP_BLOCK_FWD);
-            RC(fused_ops(dt, E)->mlp_fwd(at(ws, b.z1), P + lp.n1_w, P + lp.n1_b, WT(lp.fc1_w), P + lp.fc1_b, WT(lp.fc2_w), P + lp.fc2_b,
-                                    P + lp.n2_w, P + lp.n2_b, M, c.activation, at(ws, b.z2), static_cast<float *>(at(ws, b.rstd2)),
-                                    last ? at(ws, w.xL) : nullptr, nullptr, nullptr, nullptr, nullptr, s));      // (h is recomputed by the fused backward)
-            nin = at(ws, b.z2); gin = P + lp.n2_w; bin = P + lp.n2_b;
-        }
-        xin = at(ws, w.xL);
-    } else
-    for (int l = 0; l < c.num_layers; ++l) {
-        const LayerParams &lp = plan->layers[l];
-        const Ws::L &b = w.layer[l];
-        RC(lin_fwd(dt, xin, 0, E, WT(lp.qkv_w), P + lp.qkv_b, M, 3 * E, E, MIVIT_ACT_NONE, nullptr, 0, at(ws, b.qkv),
-                   3 * E, nullptr, 0, s));
-        prof_set_tag(MIVIT_PROF_ATTN_FWD); RC(launch_attention_fwd(dt, at(ws, b.qkv), B, S, H, Dh, at(ws, b.ctx), s));
-        RC(lin_res_ln(dt, at(ws, b.ctx), E, WT(lp.out_w), P + lp.out_b, M, E, E, xin, at(ws, b.z1), P + lp.n1_w, P + lp.n1_b,
-                      at(ws, b.x1), static_cast<float *>(at(ws, b.mean1)), static_cast<float *>(at(ws, b.rstd1)), s));
-        RC(lin_fwd(dt, at(ws, b.x1), 0, E, WT(lp.fc1_w), P + lp.fc1_b, M, F, E, c.activation, nullptr, 0, at(ws, b.h), F,
-                   c.activation == MIVIT_ACT_GELU ? at(ws, b.u) : nullptr, 0, s));
-        RC(lin_res_ln(dt, at(ws, b.h), F, WT(lp.fc2_w), P + lp.fc2_b, M, E, F, at(ws, b.x1), at(ws, b.z2), P + lp.n2_w, P + lp.n2_b,
-                      at(ws, b.x2), static_cast<float *>(at(ws, b.mean2)), static_cast<float *>(at(ws, b.rstd2)), s));
-        xin = at(ws, b.x2);
-    }
-    // 5. final LayerNorm + readout (models.py:141, :351-354).  Only the regression-token row is normalised when it
-    //    is the readout: the other rows of the final norm never reach the head.
-    {
-        LayerNormFwdArgs a = {};
-        a.dtype = dt; a.z = xin; a.ldz = E; a.gamma = P + plan->tn_w; a.beta = P + plan->tn_b; a.E = E; a.ldy = E;
-        a.mean = static_cast<float *>(at(ws, w.meanF)); a.rstd = static_cast<float *>(at(ws, w.rstdF));
-        if (c.use_regression_token) {
-            a.M = B; a.y = at(ws, w.pooled); a.in_rows = 1; a.in_stride = S; a.in_off = 0;
-            prof_set_tag(MIVIT_PROF_LN_FWD); RC(launch_layernorm_fwd(a, s));
-        } else {
-            a.M = M; a.y = at(ws, w.xF);
-            prof_set_tag(MIVIT_PROF_LN_FWD); RC(launch_layernorm_fwd(a, s));
-            RC(launch_mean_pool_fwd(dt, at(ws, w.xF), B, S, E, at(ws, w.pooled), s));
-        }
-    }
-    // 6. late fusion concat (models.py:356-359) and the MLP head (models.py:268-276)
-    const void *head_in = at(ws, w.pooled);
-    if (c.fusion == MIVIT_FUSION_LATE) {
-        const int f32 = dt == MIVIT_F32;
-        RC(launch_convert(f32, at(ws, w.pooled), E, f32, at(ws, w.head_in), 2 * E, B, E, 0, s, dt));
-        RC(launch_convert(f32, at(ws, w.fp_out), E, f32, col_ptr(at(ws, w.head_in), E, dt), 2 * E, B, E, 0, s, dt));
-        head_in = at(ws, w.head_in);
-    }
-    RC(lin_fwd(dt, head_in, 0, plan->head_in, WT(plan->h0_w), P + plan->h0_b, B, c.head_hidden, plan->head_in,
-               MIVIT_ACT_RELU, nullptr, 0, at(ws, w.hh), c.head_hidden, nullptr, 0, s));
-    RC(lin_fwd(dt, at(ws, w.hh), 0, c.head_hidden, WT(plan->h3_w), P + plan->h3_b, B, c.output_dim, c.head_hidden,
-               MIVIT_ACT_NONE, nullptr, 0, out, c.output_dim, nullptr, 1, s));
+    if (cfg.use_regression_token)
+        RC(launch_reg_token_fill(dt, c.buf(w.x0), B, c.S, E, c.p(p->reg), cfg.fusion == MIVIT_FUSION_EARLY ? c.buf(w.fp_out) : nullptr, a.pos, c.s));
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// backward
-// ------------------------------------------------------------------------------------------------
-namespace {
+// 3a. encoder layers as fused blocks (fused_fwd.hip): the layers hand each other NORMALISED tokens, the consumer applies the
+//     producing LayerNorm's affine (folded into its weights); training keeps q|k|v for the backward kernels (h is recomputed
+//     there), inference nothing; only the last block materialises x for the final norm
+int layers_fwd_fused(const Call &c) {
+    const float *gin = nullptr, *bin = nullptr;
+    const void *nin = c.buf(c.w.x0);
+    for (int l = 0; l < c.L; ++l) {
+        const LayerParams &lp = c.plan->layers[l]; const Ws::L &b = c.w.layer[l];
+        prof_set_tag(MIVIT_PROF_ATTN_BLOCK_FWD);
+        RC(c.fo->attn_fwd(nin, gin, bin, c.W(lp.qkv_w), c.p(lp.qkv_b), c.W(lp.out_w), c.p(lp.out_b), c.p(lp.n1_w), c.p(lp.n1_b), c.B, c.S,
+                          c.buf(b.ctx), c.buf(b.z1), c.fbuf(b.rstd1), nullptr, nullptr, nullptr, c.bwd ? c.buf(b.qkv) : nullptr, c.s));
+        prof_set_tag(MIVIT_PROF_MLP_BLOCK_FWD);
+        RC(c.fo->mlp_fwd(c.buf(b.z1), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w), c.p(lp.fc1_b), c.W(lp.fc2_w), c.p(lp.fc2_b), c.p(lp.n2_w),
+                         c.p(lp.n2_b), c.M, c.cfg.activation, c.buf(b.z2), c.fbuf(b.rstd2), l + 1 == c.L ? c.buf(c.w.xL) : nullptr,
+                         nullptr, nullptr, nullptr, nullptr, c.s));
+        nin = c.buf(b.z2); gin = c.p(lp.n2_w); bin = c.p(lp.n2_b);
+    }
+    return 0;
+}
 
+// 3b. encoder layers operator by operator (post-norm, models.py:97-108)
+int layers_fwd_general(const Call &c) {
+    const int dt = c.dt, E = c.E, F = c.F, M = c.M, act = c.cfg.activation;
+    const void *xin = c.buf(c.w.x0);
+    for (int l = 0; l < c.L; ++l) {
+        const LayerParams &lp = c.plan->layers[l]; const Ws::L &b = c.w.layer[l];
+        RC(lin_fwd(dt, xin, 0, E, c.W(lp.qkv_w), c.p(lp.qkv_b), M, 3 * E, E, MIVIT_ACT_NONE, nullptr, 0, c.buf(b.qkv), 3 * E, nullptr, 0, c.s));
+        prof_set_tag(MIVIT_PROF_ATTN_FWD); RC(launch_attention_fwd(dt, c.buf(b.qkv), c.B, c.S, c.H, c.Dh, c.buf(b.ctx), c.s));
+        RC(lin_res_ln(dt, c.buf(b.ctx), E, c.W(lp.out_w), c.p(lp.out_b), M, E, E, xin, c.buf(b.z1), c.p(lp.n1_w), c.p(lp.n1_b),
+                      c.buf(b.x1), c.fbuf(b.mean1), c.fbuf(b.rstd1), c.s));
+        RC(lin_fwd(dt, c.buf(b.x1), 0, E, c.W(lp.fc1_w), c.p(lp.fc1_b), M, F, E, act, nullptr, 0, c.buf(b.h), F,
+                   act == MIVIT_ACT_GELU ? c.buf(b.u) : nullptr, 0, c.s));
+        RC(lin_res_ln(dt, c.buf(b.h), F, c.W(lp.fc2_w), c.p(lp.fc2_b), M, E, F, c.buf(b.x1), c.buf(b.z2), c.p(lp.n2_w), c.p(lp.n2_b),
+                      c.buf(b.x2), c.fbuf(b.mean2), c.fbuf(b.rstd2), c.s));
+        xin = c.buf(b.x2);
+    }
+    return 0;
+}
+
+// 4. final LayerNorm + readout (models.py:141, :351-354).  Only the regression-token row is normalised when it is the
+//    readout: the other rows of the final norm never reach the head.
+int readout_fwd(const Call &c) {
+    const Ws &w = c.w; LayerNormFwdArgs a = {};
+    a.dtype = c.dt; a.z = c.trunk_out(); a.ldz = c.E; a.gamma = c.p(c.plan->tn_w); a.beta = c.p(c.plan->tn_b); a.E = c.E; a.ldy = c.E;
+    a.mean = c.fbuf(w.meanF); a.rstd = c.fbuf(w.rstdF);
+    prof_set_tag(MIVIT_PROF_LN_FWD);
+    if (c.cfg.use_regression_token) {
+        a.M = c.B; a.y = c.buf(w.pooled); a.in_rows = 1; a.in_stride = c.S; a.in_off = 0;
+        return launch_layernorm_fwd(a, c.s);
+    }
+    a.M = c.M; a.y = c.buf(w.xF); RC(launch_layernorm_fwd(a, c.s));
+    return launch_mean_pool_fwd(c.dt, c.buf(w.xF), c.B, c.S, c.E, c.buf(w.pooled), c.s);
+}
+
+// 5. late fusion concat (models.py:356-359) and the MLP head (models.py:268-276)
+int head_fwd(const Call &c, float *out) {
+    const mivit_plan *p = c.plan; const Ws &w = c.w;
+    const int dt = c.dt, E = c.E, B = c.B, Hh = c.cfg.head_hidden, Hin = p->head_in, O = c.cfg.output_dim;
+    const void *head_in = c.buf(w.pooled);
+    if (c.cfg.fusion == MIVIT_FUSION_LATE) {
+        RC(launch_convert(c.f32, c.buf(w.pooled), E, c.f32, c.buf(w.head_in), 2 * E, B, E, 0, c.s, dt));
+        RC(launch_convert(c.f32, c.buf(w.fp_out), E, c.f32, col_ptr(c.buf(w.head_in), E, dt), 2 * E, B, E, 0, c.s, dt));
+        head_in = c.buf(w.head_in);
+    }
+    RC(lin_fwd(dt, head_in, 0, Hin, c.W(p->h0_w), c.p(p->h0_b), B, Hh, Hin, MIVIT_ACT_RELU, nullptr, 0, c.buf(w.hh), Hh, nullptr, 0, c.s));
+    return lin_fwd(dt, c.buf(w.hh), 0, Hh, c.W(p->h3_w), c.p(p->h3_b), B, O, Hh, MIVIT_ACT_NONE, nullptr, 0, out, O, nullptr, 1, c.s);
+}
+
+int forward_impl(const mivit_plan *plan, const float *params, const float *x, const float *features, int B, int T,
+                        void *workspace, size_t workspace_bytes, int need_backward, float *out, void *stream) {
+    RC(check_call(plan, B, T, workspace_bytes, need_backward != 0, "mivit_forward"));
+    MIVIT_CHECK(params && x && workspace && out, "mivit_forward: null pointer");
+    MIVIT_CHECK(plan->c.fusion == MIVIT_FUSION_NONE || features, "Global features required for %s fusion",
+                plan->c.fusion == MIVIT_FUSION_EARLY ? "early" : "late");
+    const Call c(plan, B, T, need_backward != 0, workspace, params, nullptr, stream);
+    // 16-bit modes: one conversion of the whole fp32 arena per step; every GEMM then stages 16-bit weights
+    if (!c.f32) RC(launch_convert(1, c.P, plan->arena, 0, c.buf(c.w.wsh), plan->arena, 1, (int)plan->arena, 0, c.s, c.dt));
+    RC(embed_fwd(c, x));
+    RC(tokens_fwd(c, features));
+    RC(c.fused ? layers_fwd_fused(c) : layers_fwd_general(c));
+    RC(readout_fwd(c));
+    return head_fwd(c, out);
+}
+
+// ---- backward: one function per stage (mivit_plan::stages) and, for the encoder layers, per path.  dxa holds the gradient of
+// ---- a stage's output on entry and of its input on exit ----------------------------------------
 // backward of the feature projector given d(fp_out) (rows of `dy`, leading dim lddy)
-int feature_projector_bwd(const mivit_plan *plan, const Ws &w, void *ws, const float *P, float *G, const float *features,
-                          int B, const void *dy, int64_t lddy, float *dfeatures, hipStream_t s) {
-    const mivit_config &c = plan->c;
-    const int dt = c.dtype, E = c.embed_dim, Fg = c.global_feature_dim;
-    auto WT = [&](int64_t off) -> const void * {
-        return dt != MIVIT_F32 ? static_cast<const void *>(static_cast<const bf16 *>(at(ws, w.wsh)) + off)
-                                : static_cast<const void *>(P + off);
-    };
-    RC(lin_wgrad(dt, dy, lddy, at(ws, w.fp_h), 0, E, B, E, E, G + plan->fp2_w, G + plan->fp2_b, at(ws, w.wgrad),
-                 w.wgrad_bytes, s));
-    RC(lin_dgrad(dt, dy, lddy, WT(plan->fp2_w), B, E, E, MIVIT_ACT_RELU, at(ws, w.fp_h), E, nullptr, 0, at(ws, w.d_fp_h),
-                 E, 0, s));
-    RC(lin_wgrad(dt, at(ws, w.d_fp_h), E, features, 1, Fg, B, E, Fg, G + plan->fp0_w, G + plan->fp0_b, at(ws, w.wgrad),
-                 w.wgrad_bytes, s));
-    if (dfeatures)
-        RC(lin_dgrad(dt, at(ws, w.d_fp_h), E, WT(plan->fp0_w), B, E, Fg, MIVIT_ACT_NONE, nullptr, 0, nullptr, 0, dfeatures,
-                     Fg, 1, s));
+int feature_projector_bwd(const Call &c, const float *features, const void *dy, int64_t lddy, float *dfeatures) {
+    const mivit_plan *p = c.plan; const Ws &w = c.w;
+    const int dt = c.dt, E = c.E, B = c.B, Fg = c.cfg.global_feature_dim;
+    RC(lin_wgrad(dt, dy, lddy, c.buf(w.fp_h), 0, E, B, E, E, c.g(p->fp2_w), c.g(p->fp2_b), c.buf(w.wgrad), w.wgrad_bytes, c.s));
+    RC(lin_dgrad(dt, dy, lddy, c.W(p->fp2_w), B, E, E, MIVIT_ACT_RELU, c.buf(w.fp_h), E, nullptr, 0, c.buf(w.d_fp_h), E, 0, c.s));
+    RC(lin_wgrad(dt, c.buf(w.d_fp_h), E, features, 1, Fg, B, E, Fg, c.g(p->fp0_w), c.g(p->fp0_b), c.buf(w.wgrad), w.wgrad_bytes, c.s));
+    if (dfeatures) RC(lin_dgrad(dt, c.buf(w.d_fp_h), E, c.W(p->fp0_w), B, E, Fg, MIVIT_ACT_NONE, nullptr, 0, nullptr, 0, dfeatures, Fg, 1, c.s));
+    return 0;
+}
+
+// stage 0: head + (late fusion) feature projector + final norm
+int head_bwd(const Call &c, const float *dout, const float *features, float *dfeatures) {
+    const mivit_plan *p = c.plan; const Ws &w = c.w;
+    const int dt = c.dt, E = c.E, B = c.B, Hh = c.cfg.head_hidden, Hin = p->head_in, O = c.cfg.output_dim;
+    void *wg = c.buf(w.wgrad); const size_t wgb = w.wgrad_bytes;
+    const void *head_in = c.cfg.fusion == MIVIT_FUSION_LATE ? c.buf(w.head_in) : c.buf(w.pooled), *dy = dout;
+    if (!c.f32) { RC(launch_convert(1, dout, O, 0, c.buf(w.dout_t), O, B, O, 0, c.s, dt)); dy = c.buf(w.dout_t); }
+    RC(lin_wgrad(dt, dy, O, c.buf(w.hh), 0, Hh, B, O, Hh, c.g(p->h3_w), c.g(p->h3_b), wg, wgb, c.s));
+    RC(lin_dgrad(dt, dy, O, c.W(p->h3_w), B, O, Hh, MIVIT_ACT_RELU, c.buf(w.hh), Hh, nullptr, 0, c.buf(w.d_hh), Hh, 0, c.s));
+    RC(lin_wgrad(dt, c.buf(w.d_hh), Hh, head_in, 0, Hin, B, Hh, Hin, c.g(p->h0_w), c.g(p->h0_b), wg, wgb, c.s));
+    RC(lin_dgrad(dt, c.buf(w.d_hh), Hh, c.W(p->h0_w), B, Hh, Hin, MIVIT_ACT_NONE, nullptr, 0, nullptr, 0, c.buf(w.d_head_in), Hin, 0, c.s));
+    if (c.cfg.fusion == MIVIT_FUSION_LATE) RC(feature_projector_bwd(c, features, col_ptr(c.buf(w.d_head_in), E, dt), Hin, dfeatures));
+    LayerNormBwdArgs a = {};
+    a.dtype = dt; a.z = c.trunk_out(); a.ldz = E; a.gamma = c.p(p->tn_w); a.mean = c.fbuf(w.meanF); a.rstd = c.fbuf(w.rstdF);
+    a.E = E; a.dz = c.buf(w.dxa); a.lddz = E; a.dgamma = c.g(p->tn_w); a.dbeta = c.g(p->tn_b); a.ws = c.buf(w.ln); a.ws_bytes = w.ln_bytes;
+    if (c.cfg.use_regression_token) {
+        RC(launch_fill_zero(c.buf(w.dxa), (size_t)c.M * E * dtype_size(dt), c.s));
+        a.dy = c.buf(w.d_head_in); a.lddy = Hin; a.M = B; a.z_rows = 1; a.z_stride = c.S; a.z_off = 0;
+    } else {
+        const void *dp = c.buf(w.d_head_in);
+        if (Hin != E) {
+            RC(launch_convert(c.f32, c.buf(w.d_head_in), Hin, c.f32, c.buf(w.d_pool_c), E, B, E, 0, c.s, dt));
+            dp = c.buf(w.d_pool_c);
+        }
+        RC(launch_mean_pool_bwd(dt, dp, B, c.S, E, c.buf(w.dxb), c.s));
+        a.dy = c.buf(w.dxb); a.lddy = E; a.M = c.M;
+    }
+    prof_set_tag(MIVIT_PROF_LN_BWD);
+    return launch_layernorm_bwd(a, c.s);
+}
+
+// The weight-gradient workspace as the fused backward blocks of one layer get it.  Deferred slab reductions (slab_defer.h) need
+// the three blocks' slabs to coexist: one region each, back to back.  Otherwise every block has the whole workspace.
+struct FusedBwdWs { bool defer; struct Region { void *ptr; size_t bytes; } mlp, attn_out, qkv; };
+FusedBwdWs fused_bwd_ws(const Call &c, bool want_defer) {
+    uint8_t *wg = static_cast<uint8_t *>(c.buf(c.w.wgrad));
+    const size_t wgb = c.w.wgrad_bytes, n_mlp = c.fo->mlp_bwd_ws(c.M), n_ao = c.fo->attn_out_bwd_ws(c.M);
+    if (!want_defer || wgb < n_mlp + n_ao + c.fo->qkv_bwd_ws(c.M)) return {false, {wg, wgb}, {wg, wgb}, {wg, wgb}};
+    return {true, {wg, wgb}, {wg + n_mlp, wgb - n_mlp}, {wg + n_mlp + n_ao, wgb - n_mlp - n_ao}};
+}
+
+// stages 1..L, fused blocks (fused_bwd.hip): z1 / z2 hold xhat (no means), the Linear inputs x1 / x_in exist only as xhat of the
+// producing norm: their weight gradients are taken against xhat and corrected by the affine fix-up.  Four launches + ONE slab reduction.
+int layer_bwd_fused(const Call &c, int l) {
+    static const bool qkv_split = getenv("MIVIT_NO_QKV_BWD") != nullptr;                        // A/B: the two launches qkv_bwd replaces
+    static const bool no_defer = getenv("MIVIT_NO_SLAB_DEFER") != nullptr || qkv_split;         // A/B: one reduction behind every block
+    const Ws &w = c.w; const Ws::L &b = w.layer[l]; const LayerParams &lp = c.plan->layers[l];
+    const int dt = c.dt, E = c.E, M = c.M;
+    // x_in of layers l > 0 is the normalised output of the layer below, to be read through that layer's LayerNorm-2 affine
+    const void *xin = l > 0 ? c.buf(w.layer[l - 1].z2) : c.buf(w.x0);
+    const float *gin = l > 0 ? c.p(c.plan->layers[l - 1].n2_w) : nullptr, *bin = l > 0 ? c.p(c.plan->layers[l - 1].n2_b) : nullptr;
+    void *dx1 = c.buf(w.dxb), *dz1 = c.buf(w.dF);      // where d(x1) arrives / where LayerNorm-1's backward puts d(z1)
+    const FusedBwdWs r = fused_bwd_ws(c, !no_defer);
+    SlabDefer slabs(r.defer);
+    prof_set_tag(MIVIT_PROF_MLP_BLOCK_BWD);          // feed-forward block: d(x2) -> d(x1), all six parameter gradients
+    RC(c.fo->mlp_bwd(c.buf(w.dxa), c.buf(b.z2), c.fbuf(b.rstd2), c.p(lp.n2_w), c.buf(b.z1), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w),
+                     c.p(lp.fc1_b), c.W(lp.fc2_w), M, c.cfg.activation, dx1, c.g(lp.fc1_w), c.g(lp.fc1_b), c.g(lp.fc2_w), c.g(lp.fc2_b),
+                     c.g(lp.n2_w), c.g(lp.n2_b), r.mlp.ptr, r.mlp.bytes, c.s));
+    prof_set_tag(MIVIT_PROF_ATTN_OUT_BWD);           // LayerNorm-1 backward + out-projection weight / data gradient
+    RC(c.fo->attn_out_bwd(dx1, c.buf(b.z1), c.fbuf(b.rstd1), c.p(lp.n1_w), c.buf(b.ctx), c.W(lp.out_w), M, dz1, c.buf(w.dctx),
+                          c.g(lp.out_w), c.g(lp.out_b), c.g(lp.n1_w), c.g(lp.n1_b), r.attn_out.ptr, r.attn_out.bytes, c.s));
+    prof_set_tag(MIVIT_PROF_ATTN_CORE_BWD);
+    RC(launch_attention_bwd(dt, c.buf(b.qkv), c.buf(w.dctx), c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+    if (!qkv_split) {
+        // q|k|v projection: weight, bias and data gradient (+ the residual branch's d(z1)) in ONE pass over dqkv; the affine fix-up
+        // of the weight gradient, dW diag(gamma) + db (x) beta, rides on the kernel's slab writes
+        ProfPin pin(MIVIT_PROF_QKV_BWD);
+        RC(c.fo->qkv_bwd(c.buf(w.dqkv), xin, c.W(lp.qkv_w), dz1, M, c.buf(w.dxa), c.g(lp.qkv_w), c.g(lp.qkv_b), gin, bin, r.qkv.ptr, r.qkv.bytes, c.s));
+        return slabs.flush(c.s);
+    }
+    ProfPin pin(MIVIT_PROF_QKV_WGRAD);
+    RC(lin_wgrad(dt, c.buf(w.dqkv), 3 * E, xin, 0, E, M, 3 * E, E, c.g(lp.qkv_w), c.g(lp.qkv_b), r.qkv.ptr, r.qkv.bytes, c.s));
+    if (l > 0) RC(launch_affine_fixup(c.g(lp.qkv_w), c.g(lp.qkv_b), gin, bin, 3 * E, E, c.s));
+    pin.set(MIVIT_PROF_QKV_DGRAD);
+    return lin_dgrad(dt, c.buf(w.dqkv), 3 * E, c.W(lp.qkv_w), M, 3 * E, E, MIVIT_ACT_NONE, nullptr, 0, dz1, E, c.buf(w.dxa), E, 0, c.s);
+}
+
+// stages 1..L, operator by operator
+int layer_bwd_general(const Call &c, int l) {
+    const Ws &w = c.w; const Ws::L &b = w.layer[l]; const LayerParams &lp = c.plan->layers[l];
+    const int dt = c.dt, E = c.E, F = c.F, M = c.M, act = c.cfg.activation;
+    const void *xin = l > 0 ? c.buf(w.layer[l - 1].x2) : c.buf(w.x0);
+    void *wg = c.buf(w.wgrad), *dxa = c.buf(w.dxa), *dxb = c.buf(w.dxb); const size_t wgb = w.wgrad_bytes;
+    bool cs = false; LayerNormBwdArgs n2 = {};
+    n2.dtype = dt; n2.dy = dxa; n2.lddy = E; n2.z = c.buf(b.z2); n2.ldz = E; n2.gamma = c.p(lp.n2_w); n2.mean = c.fbuf(b.mean2);
+    n2.rstd = c.fbuf(b.rstd2); n2.M = M; n2.E = E; n2.dz = dxb; n2.lddz = E; n2.dgamma = c.g(lp.n2_w); n2.dbeta = c.g(lp.n2_b);
+    n2.ws = c.buf(w.ln); n2.ws_bytes = w.ln_bytes;
+    RC(ln_bwd_bias(n2, c.g(lp.fc2_b), &cs, c.s));                                             // dxb = d(z2), fc2.bias grad
+    RC(lin_wgrad(dt, dxb, E, c.buf(b.h), 0, F, M, E, F, c.g(lp.fc2_w), cs ? c.g(lp.fc2_b) : nullptr, wg, wgb, c.s));
+    RC(lin_dgrad(dt, dxb, E, c.W(lp.fc2_w), M, E, F, act, act == MIVIT_ACT_GELU ? c.buf(b.u) : c.buf(b.h), F, nullptr, 0, c.buf(w.dF), F, 0, c.s));
+    RC(lin_wgrad(dt, c.buf(w.dF), F, c.buf(b.x1), 0, E, M, F, E, c.g(lp.fc1_w), c.g(lp.fc1_b), wg, wgb, c.s));
+    RC(lin_dgrad(dt, c.buf(w.dF), F, c.W(lp.fc1_w), M, F, E, MIVIT_ACT_NONE, nullptr, 0, dxb, E, dxa, E, 0, c.s));      // dxa = d(x1)
+    LayerNormBwdArgs n1 = n2;
+    n1.dy = dxa; n1.z = c.buf(b.z1); n1.gamma = c.p(lp.n1_w); n1.mean = c.fbuf(b.mean1); n1.rstd = c.fbuf(b.rstd1);
+    n1.dz = dxb; n1.dgamma = c.g(lp.n1_w); n1.dbeta = c.g(lp.n1_b);
+    RC(ln_bwd_bias(n1, c.g(lp.out_b), &cs, c.s));                                             // dxb = d(z1), out_proj.bias grad
+    RC(lin_wgrad(dt, dxb, E, c.buf(b.ctx), 0, E, M, E, E, c.g(lp.out_w), cs ? c.g(lp.out_b) : nullptr, wg, wgb, c.s));
+    RC(lin_dgrad(dt, dxb, E, c.W(lp.out_w), M, E, E, MIVIT_ACT_NONE, nullptr, 0, nullptr, 0, c.buf(w.dctx), E, 0, c.s));
+    prof_set_tag(MIVIT_PROF_ATTN_BWD);
+    RC(launch_attention_bwd(dt, c.buf(b.qkv), c.buf(w.dctx), c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+    RC(lin_wgrad(dt, c.buf(w.dqkv), 3 * E, xin, 0, E, M, 3 * E, E, c.g(lp.qkv_w), c.g(lp.qkv_b), wg, wgb, c.s));
+    return lin_dgrad(dt, c.buf(w.dqkv), 3 * E, c.W(lp.qkv_w), M, 3 * E, E, MIVIT_ACT_NONE, nullptr, 0, dxb, E, dxa, E, 0, c.s);      // dxa = d(x_in)
+}
+
+// last stage: token assembly + embedding; dxa holds d(x0) [B,S,E]
+int embed_bwd(const Call &c, const float *x, const float *features, float *dfeatures, float *dx_tokens) {
+    const mivit_plan *p = c.plan; const mivit_config &cfg = c.cfg; const Ws &w = c.w;
+    const int dt = c.dt, E = c.E, B = c.B, S = c.S, Mt = c.Mt;
+    void *wg = c.buf(w.wgrad); const size_t wgb = w.wgrad_bytes;
+    if (cfg.use_pos_encoding) {
+        RC(launch_fill_zero(c.g(p->pos), (size_t)MAX_TOKENS * E * sizeof(float), c.s));
+        RC(launch_batch_colsum(dt, c.buf(w.dxa), B, S, E, 0, S, c.g(p->pos), c.buf(w.colsum), w.colsum_bytes, c.s));
+    }
+    if (cfg.use_regression_token) RC(launch_batch_colsum(dt, c.buf(w.dxa), B, S, E, 0, 1, c.g(p->reg), c.buf(w.colsum), w.colsum_bytes, c.s));
+    if (cfg.fusion == MIVIT_FUSION_EARLY) RC(feature_projector_bwd(c, features, c.buf(w.dxa), (int64_t)S * E, dfeatures));
+    LayerNormBwdArgs a = {};
+    a.dtype = dt; a.dy = c.buf(w.dxa); a.lddy = E; a.z = c.buf(w.emb); a.ldz = E; a.gamma = c.p(p->n0_w); a.mean = c.fbuf(w.mean0);
+    a.rstd = c.fbuf(w.rstd0); a.M = Mt; a.E = E; a.rows_per_seq = c.T; a.in_seq_stride = S; a.in_row_off = c.off;
+    a.dz = c.buf(w.dxb); a.lddz = E; a.dgamma = c.g(p->n0_w); a.dbeta = c.g(p->n0_b); a.ws = c.buf(w.ln); a.ws_bytes = w.ln_bytes;
+    if (cfg.embedding == MIVIT_EMBED_EXTERNAL) {
+        prof_set_tag(MIVIT_PROF_LN_BWD); RC(launch_layernorm_bwd(a, c.s));                        // dxb = d(tokens)
+        if (dx_tokens) RC(launch_convert(c.f32, c.buf(w.dxb), E, 1, dx_tokens, E, Mt, E, 0, c.s, dt));
+        return 0;
+    }
+    bool cs = false;
+    RC(ln_bwd_bias(a, c.g(p->emb_b), &cs, c.s));                                                  // dxb = d(embedding out)
+    const int K = cfg.patch_size * cfg.patch_size; const StreamOps *so = stream_ops(dt);
+    if (so && so->embed_ok(dt, Mt, K, E)) {
+        prof_set_tag(MIVIT_PROF_EMBED_WGRAD);
+        RC(so->embed_wgrad(c.buf(w.dxb), x, c.g(p->emb_w), Mt, K, E, wg, wgb, c.s));
+        if (cs) RC(lin_wgrad(dt, c.buf(w.dxb), E, x, 1, K, Mt, E, K, nullptr, c.g(p->emb_b), wg, wgb, c.s));
+        return 0;
+    }
+    return lin_wgrad(dt, c.buf(w.dxb), E, x, 1, K, Mt, E, K, c.g(p->emb_w), cs ? c.g(p->emb_b) : nullptr, wg, wgb, c.s);
+}
+
+int backward_impl(const mivit_plan *plan, const float *params, const float *x, const float *features, int B, int T,
+                         void *workspace, size_t workspace_bytes, const float *dout, float *grads, float *dfeatures,
+                         float *dx_tokens, int stage_begin, int stage_end, void *stream) {
+    RC(check_call(plan, B, T, workspace_bytes, true, "mivit_backward"));
+    MIVIT_CHECK(params && x && workspace && dout && grads, "mivit_backward: null pointer");
+    MIVIT_CHECK(stage_begin >= 0 && stage_begin <= stage_end && stage_end <= (int)plan->stages.size(),
+                "mivit_backward: bad stage range [%d,%d)", stage_begin, stage_end);
+    MIVIT_CHECK(plan->c.fusion == MIVIT_FUSION_NONE || features, "mivit_backward: features required");
+    const Call c(plan, B, T, true, workspace, params, grads, stream);
+    for (int st = stage_begin; st < stage_end; ++st) {
+        if (st == 0) RC(head_bwd(c, dout, features, dfeatures));
+        else if (st <= c.L) RC(c.fused ? layer_bwd_fused(c, c.L - st) : layer_bwd_general(c, c.L - st));      // layers L-1 .. 0
+        else RC(embed_bwd(c, x, features, dfeatures, dx_tokens));
+    }
     return 0;
 }
 
 }  // namespace
-
-static int backward_impl(const mivit_plan *plan, const float *params, const float *x, const float *features, int B,
-                              int T, void *workspace, size_t workspace_bytes, const float *dout, float *grads,
-                              float *dfeatures, float *dx_tokens, int stage_begin, int stage_end, void *stream) {
-    RC(check_call(plan, B, T, workspace_bytes, true, "mivit_backward"));
-    MIVIT_CHECK(params && x && workspace && dout && grads, "mivit_backward: null pointer");
-    const mivit_config &c = plan->c;
-    const int nst = (int)plan->stages.size();
-    MIVIT_CHECK(stage_begin >= 0 && stage_begin <= stage_end && stage_end <= nst, "mivit_backward: bad stage range [%d,%d)",
-                stage_begin, stage_end);
-    MIVIT_CHECK(c.fusion == MIVIT_FUSION_NONE || features, "mivit_backward: features required");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int dt = c.dtype, E = c.embed_dim, F = c.hidden_dim, H = c.num_heads, Dh = E / H, L = c.num_layers;
-    const int off = c.use_regression_token ? 1 : 0, S = T + off, M = B * S, Mt = B * T;
-    const int f32 = dt == MIVIT_F32;
-    const Ws w = make_ws(plan, B, T, true);
-    void *ws = workspace;
-    const float *P = params;
-    float *G = grads;
-    void *wg = at(ws, w.wgrad);
-    const size_t wgb = w.wgrad_bytes;
-    auto WT = [&](int64_t off) -> const void * {
-        return dt != MIVIT_F32 ? static_cast<const void *>(static_cast<const bf16 *>(at(ws, w.wsh)) + off)
-                                : static_cast<const void *>(P + off);
-    };
-
-    slab_defer_cancel();          // (a queue left behind by a call that failed mid-layer)
-    for (int st = stage_begin; st < stage_end; ++st) {
-        if (st == 0) {
-            // ---- head + final norm ----
-            const int Hh = c.head_hidden, Hin = plan->head_in, O = c.output_dim;
-            const bool fusedL = L > 0 && fused_ok(dt, E, F, H, S);
-            const void *xL = L > 0 ? (fusedL ? at(ws, w.xL) : at(ws, w.layer[L - 1].x2)) : at(ws, w.x0);
-            const void *head_in = c.fusion == MIVIT_FUSION_LATE ? at(ws, w.head_in) : at(ws, w.pooled);
-            const void *dy = dout;
-            if (!f32) { RC(launch_convert(1, dout, O, 0, at(ws, w.dout_t), O, B, O, 0, s, dt)); dy = at(ws, w.dout_t); }
-            RC(lin_wgrad(dt, dy, O, at(ws, w.hh), 0, Hh, B, O, Hh, G + plan->h3_w, G + plan->h3_b, wg, wgb, s));
-            RC(lin_dgrad(dt, dy, O, WT(plan->h3_w), B, O, Hh, MIVIT_ACT_RELU, at(ws, w.hh), Hh, nullptr, 0, at(ws, w.d_hh),
-                         Hh, 0, s));
-            RC(lin_wgrad(dt, at(ws, w.d_hh), Hh, head_in, 0, Hin, B, Hh, Hin, G + plan->h0_w, G + plan->h0_b, wg, wgb, s));
-            RC(lin_dgrad(dt, at(ws, w.d_hh), Hh, WT(plan->h0_w), B, Hh, Hin, MIVIT_ACT_NONE, nullptr, 0, nullptr, 0,
-                         at(ws, w.d_head_in), Hin, 0, s));
-            if (c.fusion == MIVIT_FUSION_LATE)
-                RC(feature_projector_bwd(plan, w, ws, P, G, features, B, col_ptr(at(ws, w.d_head_in), E, dt), Hin,
-                                         dfeatures, s));
-            LayerNormBwdArgs a = {};
-            a.dtype = dt; a.z = xL; a.ldz = E; a.gamma = P + plan->tn_w;
-            a.mean = static_cast<const float *>(at(ws, w.meanF)); a.rstd = static_cast<const float *>(at(ws, w.rstdF));
-            a.E = E; a.dz = at(ws, w.dxa); a.lddz = E; a.dgamma = G + plan->tn_w; a.dbeta = G + plan->tn_b;
-            a.ws = at(ws, w.ln); a.ws_bytes = w.ln_bytes;
-            if (c.use_regression_token) {
-                RC(launch_fill_zero(at(ws, w.dxa), (size_t)M * E * dtype_size(dt), s));
-                a.dy = at(ws, w.d_head_in); a.lddy = Hin; a.M = B; a.z_rows = 1; a.z_stride = S; a.z_off = 0;
-                prof_set_tag(MIVIT_PROF_LN_BWD); RC(launch_layernorm_bwd(a, s));
-            } else {
-                const void *dp = at(ws, w.d_head_in);
-                if (Hin != E) {
-                    RC(launch_convert(f32, at(ws, w.d_head_in), Hin, f32, at(ws, w.d_pool_c), E, B, E, 0, s, dt));
-                    dp = at(ws, w.d_pool_c);
-                }
-                RC(launch_mean_pool_bwd(dt, dp, B, S, E, at(ws, w.dxb), s));
-                a.dy = at(ws, w.dxb); a.lddy = E; a.M = M;
-                prof_set_tag(MIVIT_PROF_LN_BWD); RC(launch_layernorm_bwd(a, s));
-            }
-        } else if (st <= L) {
-            // ---- encoder layer l = L - st; dxa holds d(x2) on entry and d(x_in) on exit ----
-            const int l = L - st;
-            const LayerParams &lp = plan->layers[l];
-            const Ws::L &b = w.layer[l];
-            // fused layer blocks: z1 / z2 hold xhat (no means), the Linear inputs x1 / x_in exist only as xhat of the
-            // producing norm: their weight gradients are taken against xhat and corrected by launch_affine_fixup
-            const bool fz = fused_ok(dt, E, F, H, S);
-            const void *xin = l > 0 ? (fz ? at(ws, w.layer[l - 1].z2) : at(ws, w.layer[l - 1].x2)) : at(ws, w.x0);
-            LayerNormBwdArgs n2 = {};
-            n2.dtype = dt; n2.dy = at(ws, w.dxa); n2.lddy = E; n2.z = at(ws, b.z2); n2.ldz = E; n2.gamma = P + lp.n2_w;
-            n2.mean = fz ? nullptr : static_cast<const float *>(at(ws, b.mean2)); n2.rstd = static_cast<const float *>(at(ws, b.rstd2));
-            n2.M = M; n2.E = E; n2.dz = at(ws, w.dxb); n2.lddz = E; n2.dgamma = G + lp.n2_w; n2.dbeta = G + lp.n2_b;
-            n2.ws = at(ws, w.ln); n2.ws_bytes = w.ln_bytes;
-            bool cs = false;
-            void *dx1 = at(ws, w.dxa), *dz1 = at(ws, w.dxb);      // where d(x1) arrives / where LayerNorm-1's backward puts d(z1)
-            // fused path: the three blocks' slab reductions run as ONE launch at the end of the layer (misc.hip: slab_defer_*);
-            // each block then needs its own slab region.  MIVIT_NO_SLAB_DEFER=1: one reduction behind every block (A/B runs)
-            static const bool no_defer = getenv("MIVIT_NO_SLAB_DEFER") != nullptr || getenv("MIVIT_NO_QKV_BWD") != nullptr;
-            size_t ws_mlp = 0, ws_ao = 0;
-            bool defer = false;
-            if (fz) {
-                const FusedOps *fo = fused_ops(dt, E);
-                ws_mlp = fo->mlp_bwd_ws(M); ws_ao = fo->attn_out_bwd_ws(M);
-                defer = !no_defer && wgb >= ws_mlp + ws_ao + fo->qkv_bwd_ws(M);
-            }
-            uint8_t *wg_ao = defer ? static_cast<uint8_t *>(wg) + ws_mlp : static_cast<uint8_t *>(wg);
-            uint8_t *wg_qkv = defer ? wg_ao + ws_ao : static_cast<uint8_t *>(wg);
-            const size_t wgb_ao = defer ? wgb - ws_mlp : wgb, wgb_qkv = defer ? wgb - ws_mlp - ws_ao : wgb;
-            if (defer) slab_defer_begin();
-            if (fz) {
-                // feed-forward block in one launch (fused_bwd.hip): d(x2) -> d(x1), all six parameter gradients
-                dx1 = at(ws, w.dxb); dz1 = at(ws, w.dF);
-                prof_set_tag(MIVIT_PROF_MLP_BLOCK_BWD);
-                RC(fused_ops(dt, E)->mlp_bwd(at(ws, w.dxa), at(ws, b.z2), static_cast<const float *>(at(ws, b.rstd2)), P + lp.n2_w,
-                                        at(ws, b.z1), P + lp.n1_w, P + lp.n1_b, WT(lp.fc1_w), P + lp.fc1_b, WT(lp.fc2_w), M,
-                                        c.activation, dx1, G + lp.fc1_w, G + lp.fc1_b, G + lp.fc2_w, G + lp.fc2_b, G + lp.n2_w,
-                                        G + lp.n2_b, wg, wgb, s));
-            } else {
-            RC(ln_bwd_bias(n2, G + lp.fc2_b, &cs, s));                                            // dxb = d(z2), fc2.bias grad
-            RC(lin_wgrad(dt, at(ws, w.dxb), E, at(ws, b.h), 0, F, M, E, F, G + lp.fc2_w, cs ? G + lp.fc2_b : nullptr, wg, wgb, s));
-            RC(lin_dgrad(dt, at(ws, w.dxb), E, WT(lp.fc2_w), M, E, F, c.activation,
-                         c.activation == MIVIT_ACT_GELU ? at(ws, b.u) : at(ws, b.h), F, nullptr, 0, at(ws, w.dF), F, 0, s));
-            RC(lin_wgrad(dt, at(ws, w.dF), F, at(ws, b.x1), 0, E, M, F, E, G + lp.fc1_w, G + lp.fc1_b, wg, wgb, s));
-            RC(lin_dgrad(dt, at(ws, w.dF), F, WT(lp.fc1_w), M, F, E, MIVIT_ACT_NONE, nullptr, 0, at(ws, w.dxb), E,
-                         at(ws, w.dxa), E, 0, s));                                                // dxa = d(x1)
-            }
-            if (fz) {
-                // LayerNorm-1 backward + out-projection weight / data gradient in one launch (fused_bwd.hip)
-                prof_set_tag(MIVIT_PROF_ATTN_OUT_BWD);
-                RC(fused_ops(dt, E)->attn_out_bwd(dx1, at(ws, b.z1), static_cast<const float *>(at(ws, b.rstd1)), P + lp.n1_w, at(ws, b.ctx),
-                                       WT(lp.out_w), M, dz1, at(ws, w.dctx), G + lp.out_w, G + lp.out_b, G + lp.n1_w, G + lp.n1_b,
-                                       wg_ao, wgb_ao, s));
-            } else {
-            LayerNormBwdArgs n1 = n2;
-            n1.dy = dx1; n1.z = at(ws, b.z1); n1.gamma = P + lp.n1_w;
-            n1.mean = fz ? nullptr : static_cast<const float *>(at(ws, b.mean1)); n1.rstd = static_cast<const float *>(at(ws, b.rstd1));
-            n1.dz = dz1; n1.dgamma = G + lp.n1_w; n1.dbeta = G + lp.n1_b;
-            RC(ln_bwd_bias(n1, G + lp.out_b, &cs, s));                                            // dxb = d(z1), out_proj.bias grad
-            RC(lin_wgrad(dt, dz1, E, at(ws, b.ctx), 0, E, M, E, E, G + lp.out_w, cs ? G + lp.out_b : nullptr, wg, wgb, s));
-            RC(lin_dgrad(dt, dz1, E, WT(lp.out_w), M, E, E, MIVIT_ACT_NONE, nullptr, 0, nullptr, 0,
-                         at(ws, w.dctx), E, 0, s));
-            }
-            prof_set_tag(fz ? MIVIT_PROF_ATTN_CORE_BWD : MIVIT_PROF_ATTN_BWD);
-            RC(launch_attention_bwd(dt, at(ws, b.qkv), at(ws, w.dctx), B, S, H, Dh, at(ws, w.dqkv), s));
-            // q|k|v projection backward.  Fused path: weight, bias and data gradient (+ the residual branch's d(z1)) in ONE pass
-            // over dqkv (fused_bwd.hip::qkv_bwd_kernel); MIVIT_NO_QKV_BWD=1 keeps the two launches it replaces (A/B runs)
-            static const bool qkv_split = getenv("MIVIT_NO_QKV_BWD") != nullptr;
-            int rc_q = 0;
-            if (fz && !qkv_split) {
-                prof_pin_tag(MIVIT_PROF_QKV_BWD);
-                // (x_in of layers l > 0 is the normalised output of the layer below: the affine fix-up of the weight gradient,
-                //  dW diag(gamma) + db (x) beta, rides on the kernel's slab writes)
-                rc_q = fused_ops(dt, E)->qkv_bwd(at(ws, w.dqkv), xin, WT(lp.qkv_w), dz1, M, at(ws, w.dxa), G + lp.qkv_w, G + lp.qkv_b,
-                                                 l > 0 ? P + plan->layers[l - 1].n2_w : nullptr, l > 0 ? P + plan->layers[l - 1].n2_b : nullptr,
-                                                 wg_qkv, wgb_qkv, s);
-                if (defer) { const int rc_f = slab_defer_flush(s); if (!rc_q) rc_q = rc_f; }
-            } else {
-                if (fz) prof_pin_tag(MIVIT_PROF_QKV_WGRAD);
-                rc_q = lin_wgrad(dt, at(ws, w.dqkv), 3 * E, xin, 0, E, M, 3 * E, E, G + lp.qkv_w, G + lp.qkv_b, wg, wgb, s);
-                if (!rc_q && fz && l > 0)
-                    rc_q = launch_affine_fixup(G + lp.qkv_w, G + lp.qkv_b, P + plan->layers[l - 1].n2_w, P + plan->layers[l - 1].n2_b, 3 * E, E, s);
-                if (fz) prof_pin_tag(MIVIT_PROF_QKV_DGRAD);
-                if (!rc_q)
-                    rc_q = lin_dgrad(dt, at(ws, w.dqkv), 3 * E, WT(lp.qkv_w), M, 3 * E, E, MIVIT_ACT_NONE, nullptr, 0, dz1,
-                                     E, at(ws, w.dxa), E, 0, s);                                  // dxa = d(x_in)
-            }
-            prof_pin_tag(-1);
-            RC(rc_q);
-        } else {
-            // ---- token assembly + embedding; dxa holds d(x0) [B,S,E] ----
-            if (c.use_pos_encoding) {
-                RC(launch_fill_zero(G + plan->pos, (size_t)MAX_TOKENS * E * sizeof(float), s));
-                RC(launch_batch_colsum(dt, at(ws, w.dxa), B, S, E, 0, S, G + plan->pos, at(ws, w.colsum), w.colsum_bytes, s));
-            }
-            if (c.use_regression_token)
-                RC(launch_batch_colsum(dt, at(ws, w.dxa), B, S, E, 0, 1, G + plan->reg, at(ws, w.colsum), w.colsum_bytes, s));
-            if (c.fusion == MIVIT_FUSION_EARLY)
-                RC(feature_projector_bwd(plan, w, ws, P, G, features, B, at(ws, w.dxa), (int64_t)S * E, dfeatures, s));
-            LayerNormBwdArgs a = {};
-            a.dtype = dt; a.dy = at(ws, w.dxa); a.lddy = E; a.z = at(ws, w.emb); a.ldz = E; a.gamma = P + plan->n0_w;
-            a.mean = static_cast<const float *>(at(ws, w.mean0)); a.rstd = static_cast<const float *>(at(ws, w.rstd0));
-            a.M = Mt; a.E = E; a.rows_per_seq = T; a.in_seq_stride = S; a.in_row_off = off;
-            a.dz = at(ws, w.dxb); a.lddz = E; a.dgamma = G + plan->n0_w; a.dbeta = G + plan->n0_b;
-            a.ws = at(ws, w.ln); a.ws_bytes = w.ln_bytes;
-            if (c.embedding == MIVIT_EMBED_EXTERNAL) {
-                prof_set_tag(MIVIT_PROF_LN_BWD); RC(launch_layernorm_bwd(a, s));                  // dxb = d(tokens)
-                if (dx_tokens) RC(launch_convert(f32, at(ws, w.dxb), E, 1, dx_tokens, E, Mt, E, 0, s, dt));
-            } else {
-                bool cs = false;
-                RC(ln_bwd_bias(a, G + plan->emb_b, &cs, s));                                      // dxb = d(embedding out)
-                const int K = c.patch_size * c.patch_size;
-                const StreamOps *so = stream_ops(dt);
-                if (so && so->embed_ok(dt, Mt, K, E)) {
-                    prof_set_tag(MIVIT_PROF_EMBED_WGRAD);
-                    RC(so->embed_wgrad(at(ws, w.dxb), x, G + plan->emb_w, Mt, K, E, wg, wgb, s));
-                    if (cs) RC(lin_wgrad(dt, at(ws, w.dxb), E, x, 1, K, Mt, E, K, nullptr, G + plan->emb_b, wg, wgb, s));
-                } else {
-                    RC(lin_wgrad(dt, at(ws, w.dxb), E, x, 1, K, Mt, E, K, G + plan->emb_w, cs ? G + plan->emb_b : nullptr, wg, wgb, s));
-                }
-            }
-        }
-    }
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------------------
 // C-ABI entry points.  Small problems are launch-bound (~100 short kernels per call): a call whose arguments were seen
@@ -847,31 +811,29 @@ static bool graph_sized(const mivit_plan *plan, int B, int T) {
     return plan && (int64_t)B * (T + 1) * plan->c.embed_dim <= 65536LL * 128;
 }
 
-extern "C" int mivit_forward(const mivit_plan *plan, const float *params, const float *x, const float *features, int B,
-                             int T, void *workspace, size_t workspace_bytes, int need_backward, float *out,
-                             void *stream) {
+extern "C" int mivit_forward(const mivit_plan *plan, const float *params, const float *x, const float *features, int B, int T,
+                             void *workspace, size_t workspace_bytes, int need_backward, float *out, void *stream) {
+    const auto body = [&](hipStream_t cs) {
+        return forward_impl(plan, params, x, features, B, T, workspace, workspace_bytes, need_backward, out, cs);
+    };
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!graph_sized(plan, B, T))
-        return forward_impl(plan, params, x, features, B, T, workspace, workspace_bytes, need_backward, out, s);
+    if (!graph_sized(plan, B, T)) return body(s);
     const uint64_t key[] = {1, plan->uid, (uint64_t)params, (uint64_t)x, (uint64_t)features, (uint64_t)B, (uint64_t)T,
                             (uint64_t)workspace, (uint64_t)workspace_bytes, (uint64_t)need_backward, (uint64_t)out};
-    return graph_run(key, (int)(sizeof(key) / sizeof(key[0])), s, [&](hipStream_t cs) {
-        return forward_impl(plan, params, x, features, B, T, workspace, workspace_bytes, need_backward, out, cs);
-    });
+    return graph_run(key, (int)(sizeof(key) / sizeof(key[0])), s, body);
 }
 
 extern "C" int mivit_backward(const mivit_plan *plan, const float *params, const float *x, const float *features, int B,
                               int T, void *workspace, size_t workspace_bytes, const float *dout, float *grads,
                               float *dfeatures, float *dx_tokens, int stage_begin, int stage_end, void *stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!graph_sized(plan, B, T))
+    const auto body = [&](hipStream_t cs) {
         return backward_impl(plan, params, x, features, B, T, workspace, workspace_bytes, dout, grads, dfeatures, dx_tokens,
-                             stage_begin, stage_end, s);
+                             stage_begin, stage_end, cs);
+    };
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!graph_sized(plan, B, T)) return body(s);
     const uint64_t key[] = {2, plan->uid, (uint64_t)params, (uint64_t)x, (uint64_t)features, (uint64_t)B, (uint64_t)T,
                             (uint64_t)workspace, (uint64_t)workspace_bytes, (uint64_t)dout, (uint64_t)grads,
                             (uint64_t)dfeatures, (uint64_t)dx_tokens, (uint64_t)stage_begin, (uint64_t)stage_end};
-    return graph_run(key, (int)(sizeof(key) / sizeof(key[0])), s, [&](hipStream_t cs) {
-        return backward_impl(plan, params, x, features, B, T, workspace, workspace_bytes, dout, grads, dfeatures, dx_tokens,
-                             stage_begin, stage_end, cs);
-    });
+    return graph_run(key, (int)(sizeof(key) / sizeof(key[0])), s, body);
 }

@@ -1,5 +1,6 @@
 // Error plumbing, small elementwise / reduction kernels and library-level C-ABI entry points.
 #include "common.h"
+#include "slab_defer.h"
 #include <stdarg.h>
 #include <algorithm>
 
@@ -158,14 +159,10 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float *part, int
                                                           int accumulate, int vec_ok) {
     slab_reduce_block(part, nparts, n, ps, out, accumulate, vec_ok, blockIdx.x);
 }
-// several queued reductions in ONE launch (slab_defer_begin / slab_defer_flush below): block b belongs to the job whose block
-// range contains it; the arithmetic of a job is slab_reduce_kernel's
-constexpr int MAX_SLAB_JOBS = 8;
-struct SlabJobs {
-    const float *part[MAX_SLAB_JOBS]; float *out[MAX_SLAB_JOBS];
-    int nparts[MAX_SLAB_JOBS], n[MAX_SLAB_JOBS], stride[MAX_SLAB_JOBS], vec_ok[MAX_SLAB_JOBS], blk_end[MAX_SLAB_JOBS];
-    int njobs;
-};
+// several queued reductions in ONE launch (SlabDefer::flush below): block b belongs to the job whose block range contains it;
+// the arithmetic of a job is slab_reduce_kernel's.  (The argument type keeps its own internal-linkage name, which is part of the
+// kernel's symbol; its fields are slab_defer.h's.)
+struct SlabJobs : SlabQueue {};
 __global__ __launch_bounds__(256) void slab_reduce_multi_kernel(const SlabJobs j) {
     int k = 0;
     while (k + 1 < j.njobs && (int)blockIdx.x >= j.blk_end[k]) ++k;          // (uniform per block)
@@ -398,37 +395,20 @@ int launch_slab_reduce(const float *part, int nparts, int64_t n, float *out, int
     MIVIT_LAUNCH_CHECK();
     return 0;
 }
-// Deferred reductions: the fused backward blocks of one encoder layer (mlp_block_bwd, attn_out_bwd, qkv_bwd) each end in a slab
-// reduction whose result nothing in the layer's backward reads -- three dependent 5-7 us launches per layer on the critical path
-// (24 of the ~85 launches of a 64-wide model's step).  Between slab_defer_begin() and slab_defer_flush(s) the strided
-// reductions are queued (their slabs must stay untouched until the flush: the engine gives each block its own workspace region)
-// and run as ONE launch.
-static thread_local bool t_slab_defer = false;
-static thread_local SlabJobs t_slab_jobs = {};
-void slab_defer_begin() { t_slab_defer = true; t_slab_jobs.njobs = 0; }
-void slab_defer_cancel() { t_slab_defer = false; t_slab_jobs.njobs = 0; }          // (a call that failed between begin and flush)
-int slab_defer_flush(hipStream_t s) {
-    t_slab_defer = false;
-    const int nj = t_slab_jobs.njobs;
-    t_slab_jobs.njobs = 0;
-    if (nj == 0) return 0;
-    SlabJobs j = t_slab_jobs;
-    j.njobs = nj;
-    hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(j.blk_end[nj - 1]), dim3(256), 0, s, j);
+// the queue of a SlabDefer scope (slab_defer.h) as ONE launch
+int SlabDefer::flush(void *stream) {
+    SlabJobs j = {take()};
+    if (j.njobs == 0) return 0;
+    hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(j.blk_end[j.njobs - 1]), dim3(256), 0, static_cast<hipStream_t>(stream), j);
     MIVIT_LAUNCH_CHECK();
     return 0;
 }
-// the same for parts that are `stride` floats apart (one field of a per-workgroup record)
+// the same for parts that are `stride` floats apart (one field of a per-workgroup record); queued instead of launched while a
+// SlabDefer scope is active on this thread
 int launch_slab_reduce_strided(const float *part, int nparts, int64_t stride, int64_t n, float *out, hipStream_t s) {
     const int blocks = (int)((n + 127) / 128);
     const int vec_ok = (n % 4 == 0) && (stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(part) & 15) == 0);
-    if (t_slab_defer && t_slab_jobs.njobs < MAX_SLAB_JOBS && n < (1ll << 31) && stride < (1ll << 31)) {
-        SlabJobs &q = t_slab_jobs;
-        const int k = q.njobs++;
-        q.part[k] = part; q.out[k] = out; q.nparts[k] = nparts; q.n[k] = (int)n; q.stride[k] = (int)stride; q.vec_ok[k] = vec_ok;
-        q.blk_end[k] = (k ? q.blk_end[k - 1] : 0) + blocks;
-        return 0;
-    }
+    if (SlabDefer::push(part, nparts, stride, n, out, vec_ok)) return 0;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, part, nparts, n, stride, out, 0, vec_ok);
     MIVIT_LAUNCH_CHECK();
     return 0;
