@@ -673,6 +673,13 @@ int mivit_attention_fwd(int dtype, const void *qkv, int B, int S, int H, int Dh,
 /* dqkv: T [B*S, 3E] from dctx T [B*S,E]; probabilities are recomputed from q,k (nothing saved). */
 int mivit_attention_bwd(int dtype, const void *qkv, const void *dctx, int B, int S, int H, int Dh,
                         void *dqkv, void *stream);
+/* The same when only the first q_rows query rows of every sequence carry a gradient: dctx holds q_rows rows of E per
+ * sequence, dctx_seq_stride elements (a multiple of 8, >= q_rows * E) between sequences; the rows behind them are zero by
+ * contract and never read.  All of dqkv [B*S, 3E] is written (dq of the other query rows as zeros) and equals what
+ * mivit_attention_bwd makes of the zero-padded dctx.  16-bit dtypes, S <= 128, head dim 16 / 32 / 64 (the short-sequence
+ * kernel); an error elsewhere and under MIVIT_ATTN_BWD=1. */
+int mivit_attention_bwd_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S,
+                             int H, int Dh, void *dqkv, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Model level: GeneralTransformer.forward / its autograd (models.py:278-361, :111-141, :81-108).
@@ -737,6 +744,17 @@ int mivit_backward(const mivit_plan *plan, const float *params, const float *x, 
  * capture their kernel sequence into a hipGraph the second time they see the same arguments and replay it afterwards
  * (MIVIT_GRAPHS=0 disables; off while mivit_profile_enable is active). */
 void mivit_graph_stats(uint64_t *replays, uint64_t *captures, int *failures);
+
+/* Readout-row pruning of the last encoder layer (fused 16-bit layers with the regression-token readout, more than one token):
+ * the head reads B of its B * S output rows.
+ *   1 (default): the last feed-forward block's forward runs on those B rows and the attention core's backward on the one query
+ *      row per sequence that carries a gradient.  Every result is what it was: no sum changes its terms or their order.
+ *   2 (MIVIT_READOUT_ROWS=2): the feed-forward block's and LayerNorm-1 / out-projection's backward run on B rows too.  Same out
+ *      and loss; the last layer's fc1 / fc2 / norm2 / out_proj / norm1 gradients sum the same fp32 terms in another order, which
+ *      a training run amplifies like any other rounding difference.
+ *   0 (MIVIT_NO_READOUT_ROWS): every row.
+ * Returns the previous value.  A forward and the backward that follows it must run under the same value. */
+int mivit_set_readout_rows(int mode);
 
 /* ------------------------------------------------------------------------------------------------
  * In-library kernel timing (used by bench.py for the roofline line): when a tag's bit is set in `tag_mask`, the

@@ -102,6 +102,8 @@ SYMBOLS = {
     "mivit_attention_max_seq": (c_int, [c_int, c_int]),
     "mivit_attention_fwd": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_attention_bwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mivit_attention_bwd_rows": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mivit_set_readout_rows": (c_int, [c_int]),
     "mivit_plan_create": (c_void_p, [POINTER(MivitConfig)]),
     "mivit_plan_destroy": (None, [c_void_p]),
     "mivit_plan_num_params": (c_int, [c_void_p]),

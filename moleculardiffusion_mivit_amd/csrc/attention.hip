@@ -450,6 +450,21 @@ int launch_attention_bwd(int dtype, const void *qkv, const void *dctx, int B, in
          : dtype == MIVIT_BF16 ? attn_bwd_t<bf16>(qkv, dctx, B, S, H, Dh, dqkv, s) : attn_bwd_t<f16>(qkv, dctx, B, S, H, Dh, dqkv, s);
 }
 
+// dctx rows >= q_rows of every sequence are zero by contract: only the short-sequence 16-bit kernel (its 16-deep version) takes
+// the row count, nothing else stands in for it
+bool attention_bwd_rows_ok(int dtype, int S, int Dh) {
+    return attention_bwd_rows_supported(dtype, S, Dh) || attention_bwd_rows_supported_f16(dtype, S, Dh);
+}
+int launch_attention_bwd_q_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H,
+                                int Dh, void *dqkv, hipStream_t s) {
+    MIVIT_CHECK(B > 0 && S > 0 && H > 0 && Dh > 0, "attention_bwd_rows: empty problem");
+    if (attention_bwd_rows_supported(dtype, S, Dh)) return launch_attention_bwd_rows(qkv, dctx, dctx_seq_stride, q_rows, B, S, H, Dh, dqkv, s);
+    if (attention_bwd_rows_supported_f16(dtype, S, Dh))
+        return launch_attention_bwd_rows_f16(qkv, dctx, dctx_seq_stride, q_rows, B, S, H, Dh, dqkv, s);
+    MIVIT_FAIL("attention_bwd_rows: no kernel for dtype %d, S = %d, head dim %d (16-bit, S <= 128, head dim 16 / 32 / 64, MIVIT_ATTN_BWD unset or 2)",
+               dtype, S, Dh);
+}
+
 extern "C" int mivit_attention_max_seq(int dtype, int Dh) { return attention_max_seq(dtype, Dh); }
 extern "C" int mivit_attention_fwd(int dtype, const void *qkv, int B, int S, int H, int Dh, void *ctx, void *stream) {
     MIVIT_CHECK(dtype == MIVIT_F32 || dtype == MIVIT_BF16 || dtype == MIVIT_F16, "bad dtype %d", dtype);
@@ -461,4 +476,10 @@ extern "C" int mivit_attention_bwd(int dtype, const void *qkv, const void *dctx,
     MIVIT_CHECK(dtype == MIVIT_F32 || dtype == MIVIT_BF16 || dtype == MIVIT_F16, "bad dtype %d", dtype);
     MIVIT_CHECK(qkv && dctx && dqkv, "attention_bwd: null pointer");
     return launch_attention_bwd(dtype, qkv, dctx, B, S, H, Dh, dqkv, static_cast<hipStream_t>(stream));
+}
+extern "C" int mivit_attention_bwd_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S,
+                                        int H, int Dh, void *dqkv, void *stream) {
+    MIVIT_CHECK(dtype == MIVIT_F32 || dtype == MIVIT_BF16 || dtype == MIVIT_F16, "bad dtype %d", dtype);
+    MIVIT_CHECK(qkv && dctx && dqkv, "attention_bwd_rows: null pointer");
+    return launch_attention_bwd_q_rows(dtype, qkv, dctx, dctx_seq_stride, q_rows, B, S, H, Dh, dqkv, static_cast<hipStream_t>(stream));
 }

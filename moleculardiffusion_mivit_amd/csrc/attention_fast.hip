@@ -101,6 +101,10 @@ struct FastDims {
     int B, S, H, Dh, E;
     int ld;          // LDS image row length (elements)
     int img;         // elements per image (NTP * 16 * ld)
+    // attn_bwd_fast2<.., ROWS = true> only: dctx holds the first q_rows query rows of every sequence, do_stride elements apart;
+    // the rows behind them are zero by contract and never read (0: the full problem)
+    int q_rows;
+    int64_t do_stride;
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -389,7 +393,9 @@ __device__ __forceinline__ f32x4 mma16(k16_t a, k16_t b, f32x4 c) {
     return ELEM_MFMA_16x16x16(a, b, c);
 }
 
-template <int NT, int ND>
+// ROWS: only the first d.q_rows query rows of a sequence carry a gradient (dctx holds those rows, d.do_stride elements between
+// sequences).  The full problem (ROWS = false: q_rows = S, stride S * E) compiles to the code it always had.
+template <int NT, int ND, bool ROWS>
 __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(const bf16 *qkv, const bf16 *dctx, bf16 *dqkv, const FastDims d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int KD = (ND + 1) / 2;
@@ -403,7 +409,16 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
     bf16 *Kimg = Qimg + d.img, *Oimg = Kimg + d.img, *Simg = Oimg + d.img;     // Simg: dS of the current row tile, [key][16 queries]
     const int64_t ld3 = 3 * (int64_t)d.E;
     const bf16 *q = qkv + (int64_t)b * d.S * ld3 + h * d.Dh, *k = q + d.E, *v = q + 2 * d.E;
-    const bf16 *dO = dctx + (int64_t)b * d.S * d.E + h * d.Dh;
+    const int q_rows = ROWS ? d.q_rows : d.S;
+    const bf16 *dO = dctx + (ROWS ? (int64_t)b * d.do_stride : (int64_t)b * d.S * d.E) + h * d.Dh;
+    // row tiles behind the last query row that carries a gradient have dS = 0: they add nothing to dK / dV and their dQ is 0,
+    // stored here, 16 bytes per lane, while no accumulator is live (no trip when q_rows reaches the last tile)
+    const int nit = ROWS ? min(NT, (q_rows + 15) >> 4) : NT;
+    if (ROWS) {
+        bf16 *dq0 = dqkv + ((int64_t)b * d.S + nit * 16) * ld3 + h * d.Dh;
+        for (int u = lane; u < (d.S - nit * 16) * (ND * 2); u += 64)
+            *reinterpret_cast<uint4 *>(dq0 + (int64_t)(u / (ND * 2)) * ld3 + (u % (ND * 2)) * 8) = make_uint4(0u, 0u, 0u, 0u);
+    }
     // Every global load of the prologue is issued before the first wait.  (The staging helper's loop has a run-time trip
     // count: left as three calls it compiled to load -> s_waitcnt vmcnt(0) -> ds_write per 64 chunks, i.e. NINE serialised
     // memory round trips at the start of every wave, and the per-row-tile q / dO fragment loads added three more.)
@@ -412,12 +427,12 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
     bf16x8 kf[NT][KD], vf[NT][KD];
     if (BATCH) {
         uint4 sq[NIT], sk[NIT], so[NIT];
-        auto ld_nat = [&](const bf16 *src, int64_t sld, uint4 (&v)[NIT]) {
+        auto ld_nat = [&](const bf16 *src, int64_t sld, int rows, uint4 (&v)[NIT]) {
 #pragma unroll
             for (int i = 0; i < NIT; ++i) {
                 const int u = lane + 64 * i, r = u / CPR, dd = (u % CPR) * 8;
                 v[i] = make_uint4(0u, 0u, 0u, 0u);
-                if (u < NCH && r < d.S && dd + 8 <= d.Dh) v[i] = *reinterpret_cast<const uint4 *>(src + (int64_t)r * sld + dd);
+                if (u < NCH && r < rows && dd + 8 <= d.Dh) v[i] = *reinterpret_cast<const uint4 *>(src + (int64_t)r * sld + dd);
             }
         };
         auto st_nat = [&](bf16 *img, const uint4 (&v)[NIT]) {
@@ -427,7 +442,7 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
                 if (u < NCH) *reinterpret_cast<uint4 *>(img + r * d.ld + (SWZ ? (dd ^ (((r >> 2) & 1) << 4)) : dd)) = v[i];
             }
         };
-        ld_nat(q, ld3, sq); ld_nat(k, ld3, sk); ld_nat(dO, d.E, so);
+        ld_nat(q, ld3, d.S, sq); ld_nat(k, ld3, d.S, sk); ld_nat(dO, d.E, q_rows, so);
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -439,7 +454,7 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
     } else {
         stage_nat<SWZ>(Qimg, d.ld, q, ld3, d.S, NT * 16, d.Dh, lane);
         stage_nat<SWZ>(Kimg, d.ld, k, ld3, d.S, NT * 16, d.Dh, lane);
-        stage_nat<SWZ>(Oimg, d.ld, dO, d.E, d.S, NT * 16, d.Dh, lane);
+        stage_nat<SWZ>(Oimg, d.ld, dO, d.E, q_rows, NT * 16, d.Dh, lane);
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -470,14 +485,14 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
         for (int jd = 0; jd < ND; ++jd) { dv[j][jd] = zero; dk[j][jd] = zero; }
 
 #pragma unroll 1
-    for (int it = 0; it < NT; ++it) {
+    for (int it = 0; it < nit; ++it) {
         bf16x8 qf[KD], of[KD];
 #pragma unroll
         for (int kd = 0; kd < KD; ++kd) {
             if (SWZ) { qf[kd] = lfrag(Qimg, it * 16); of[kd] = lfrag(Oimg, it * 16); }
             else {
                 qf[kd] = gfrag(q, ld3, it * 16, d.S, kd * 32, d.Dh, lane);
-                of[kd] = gfrag(dO, d.E, it * 16, d.S, kd * 32, d.Dh, lane);
+                of[kd] = gfrag(dO, d.E, it * 16, q_rows, kd * 32, d.Dh, lane);
             }
         }
         f32x4 dS[NT];        // dS of this row tile: lane = key j*16 + cq, registers = queries it*16 + 4g + r
@@ -578,6 +593,7 @@ FastDims make_fast(int B, int S, int H, int Dh) {
     const int NT = (S + 15) / 16, NP = (NT + 1) / 2;
     d.ld = Dh + 8;
     d.img = NP * 32 * d.ld;
+    d.q_rows = 0; d.do_stride = 0;
     return d;
 }
 
@@ -599,12 +615,16 @@ int fwd_launch(const bf16 *qkv, bf16 *ctx, const FastDims &d, hipStream_t s) {
     MIVIT_LAUNCH_CHECK();
     return 0;
 }
+static int bwd_version() {          // MIVIT_ATTN_BWD: 1 = first (pair-tiled) version
+    static const int version = getenv("MIVIT_ATTN_BWD") ? atoi(getenv("MIVIT_ATTN_BWD")) : 2;
+    return version;
+}
 template <int NT, int ND>
 int bwd_launch(const bf16 *qkv, const bf16 *dctx, bf16 *dqkv, const FastDims &d, hipStream_t s) {
     const size_t per_wave = (size_t)3 * d.img * sizeof(bf16);
     const int wpb = waves_per_block(per_wave);
-    static const int version = getenv("MIVIT_ATTN_BWD") ? atoi(getenv("MIVIT_ATTN_BWD")) : 2;     // 1 = first (pair-tiled) version
-    auto kern = version == 2 ? attn_bwd_fast2<NT, ND> : attn_bwd_fast<NT, ND>;
+    const int version = bwd_version();
+    auto kern = version != 2 ? attn_bwd_fast<NT, ND> : (d.q_rows > 0 ? attn_bwd_fast2<NT, ND, true> : attn_bwd_fast2<NT, ND, false>);
     if (version == 2) {        // the 16-deep version needs NT * 16 image rows, not the pair-padded NP * 32: more waves fit a CU
         FastDims d2 = d;
         if (ND == 2) d2.ld = 32;             // unpadded rows + half-row exchange (conflict-free transposing reads)
@@ -674,6 +694,19 @@ int launch_attention_fwd_fast(const void *qkv, int B, int S, int H, int Dh, void
 
 int launch_attention_bwd_fast(const void *qkv, const void *dctx, int B, int S, int H, int Dh, void *dqkv, hipStream_t s) {
     const FastDims d = make_fast(B, S, H, Dh);
+    const int NT = (S + 15) / 16, ND = Dh / 16;
+    FAST_DISPATCH(bwd_launch, static_cast<const bf16 *>(qkv), static_cast<const bf16 *>(dctx), static_cast<bf16 *>(dqkv), d, s)
+}
+
+// The same backward for a dctx of which only the first q_rows query rows of every sequence exist (q_rows x E elements,
+// dctx_seq_stride elements apart); the other rows are zero by contract.  Only the 16-deep kernel knows the row count.
+bool attention_bwd_rows_supported(int dtype, int S, int Dh) { return attention_fast_supported(dtype, S, Dh) && bwd_version() == 2; }
+int launch_attention_bwd_rows(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H, int Dh,
+                              void *dqkv, hipStream_t s) {
+    MIVIT_CHECK(q_rows >= 1 && q_rows <= S && dctx_seq_stride >= (int64_t)q_rows * H * Dh && dctx_seq_stride % 8 == 0,
+                "attention_bwd_rows: %d rows of %d at stride %lld", q_rows, S, (long long)dctx_seq_stride);
+    FastDims d = make_fast(B, S, H, Dh);
+    d.q_rows = q_rows; d.do_stride = dctx_seq_stride;
     const int NT = (S + 15) / 16, ND = Dh / 16;
     FAST_DISPATCH(bwd_launch, static_cast<const bf16 *>(qkv), static_cast<const bf16 *>(dctx), static_cast<bf16 *>(dqkv), d, s)
 }

@@ -36,6 +36,8 @@
 #define attention_fast_supported attention_fast_supported_f16
 #define launch_attention_fwd_fast launch_attention_fwd_fast_f16
 #define launch_attention_bwd_fast launch_attention_bwd_fast_f16
+#define attention_bwd_rows_supported attention_bwd_rows_supported_f16
+#define launch_attention_bwd_rows launch_attention_bwd_rows_f16
 #define embed_dma_supported embed_dma_supported_f16
 #define launch_embed_fwd_dma launch_embed_fwd_dma_f16
 #define embed_wgrad_dma_ws_bytes embed_wgrad_dma_ws_bytes_f16

@@ -65,6 +65,15 @@ static const FusedOps *fused_ops(int dtype, int E) {
     if (dtype == MIVIT_F16 && !f16_off) return E == 64 ? &kFusedF16W64 : &kFusedF16;
     return nullptr;
 }
+// Readout-row pruning: under the regression-token readout the head reads B rows of the last layer's output.
+//   1 (default)  what leaves every result as it was: the last feed-forward block's forward on those B rows, the attention core's
+//                backward on the one query row per sequence that carries a gradient; every weight-gradient sum as before
+//   2            also the feed-forward block's and LayerNorm-1 / out-projection's backward on B rows: the last layer's fc1 /
+//                fc2 / norm2 / out_proj / norm1 gradients then sum the same fp32 terms in another order (MIVIT_READOUT_ROWS=2)
+//   0            every row (MIVIT_NO_READOUT_ROWS, mivit_set_readout_rows(0): A/B measurements, parity tests)
+static int g_readout_rows = getenv("MIVIT_NO_READOUT_ROWS") ? 0 : (getenv("MIVIT_READOUT_ROWS") ? atoi(getenv("MIVIT_READOUT_ROWS")) : 1);
+extern "C" int mivit_set_readout_rows(int on) { const int old = g_readout_rows; g_readout_rows = on; return old; }
+
 static bool fused_ok(int dtype, int E, int F, int H, int S) {
     const FusedOps *f = fused_ops(dtype, E);
     return f && f->ok(dtype, E, F, H, S);
@@ -121,6 +130,11 @@ struct Ws {
     std::vector<L> layer;
     size_t xF, meanF, rstdF, pooled, fp_h, fp_out, head_in, hh;
     size_t xL;           // fused layer blocks: x = gamma * xhat + beta of the LAST layer (input of the final norm)
+    // readout rows (fused blocks, regression token, S > 1): row b * S of the last layer's z1 gathered to [B,E]; that layer's
+    // compact z2 / rstd2 / xL use the first B rows of the full regions.  Backward: the same gather of rstd1 and ctx, compact
+    // d(z1) and d(ctx)
+    size_t z1c, rstd1c, ctxc, dz1c, dctxc;
+    size_t z2c, rstd2c, xLc;          // mode 1: the compact block's outputs before they are scattered to rows b * S of the full regions
     // backward temporaries
     size_t dout_t, d_hh, d_head_in, d_pool_c, d_fp_h, dxa, dxb, dF, dctx, dqkv, wgrad, ln, colsum;
     size_t wgrad_bytes, ln_bytes, colsum_bytes;
@@ -159,6 +173,9 @@ Ws make_ws(const mivit_plan *p, int B, int T, bool bwd) {
     }
     for (int l = nsets; l < L; ++l) w.layer.push_back(w.layer[0]);
     w.xL = fused ? take(M * E * ts) : 0;
+    const bool rows = fused && c.use_regression_token && S > 1;
+    w.z1c = rows ? take((size_t)B * E * ts) : 0;
+    if (rows) { w.z2c = take((size_t)B * E * ts); w.rstd2c = take((size_t)B * 4); w.xLc = take((size_t)B * E * ts); }
     w.xF = c.use_regression_token ? 0 : take(M * E * ts);
     w.meanF = take(M * 4); w.rstdF = take(M * 4);
     w.pooled = take((size_t)B * E * ts);
@@ -173,6 +190,10 @@ Ws make_ws(const mivit_plan *p, int B, int T, bool bwd) {
         w.d_fp_h = take((size_t)B * E * ts);
         w.dxa = take(M * E * ts); w.dxb = take(M * E * ts);
         w.dF = take(M * F * ts); w.dctx = take(M * E * ts); w.dqkv = take(M * 3 * E * ts);
+        if (rows) {
+            w.rstd1c = take((size_t)B * 4); w.ctxc = take((size_t)B * E * ts);
+            w.dz1c = take((size_t)B * E * ts); w.dctxc = take((size_t)B * E * ts);
+        }
         size_t wg = 0;
         auto mx = [&](int m, int n, int k) {
             size_t b = linear_wgrad_ws_bytes(m, n, k);
@@ -499,12 +520,16 @@ struct Call {
     const bool bwd;               // the workspace is laid out for (and the forward keeps what) a backward needs
     const bool fused;             // the encoder layers run as fused blocks (fused_fwd.hip / fused_bwd.hip) ...
     const FusedOps *fo;           // ... of this table (null: per-operator layers)
+    const bool rows;              // ... and the last layer's row-wise blocks on the B regression-token rows only (mode 2)
+    const bool rows_exact;        // ... or only what leaves every sum as it was (mode 1)
     const Ws w;
     void *ws; const float *P; float *G; hipStream_t s;      // workspace base, parameter arena, gradient arena (null in a forward)
     Call(const mivit_plan *p, int B_, int T_, bool bwd_, void *workspace, const float *params, float *grads, void *stream)
         : plan(p), cfg(p->c), dt(cfg.dtype), E(cfg.embed_dim), F(cfg.hidden_dim), H(cfg.num_heads), Dh(E / H), L(cfg.num_layers),
           B(B_), T(T_), off(cfg.use_regression_token ? 1 : 0), S(T + off), M(B * S), Mt(B * T), f32(dt == MIVIT_F32), bwd(bwd_),
-          fused(L > 0 && fused_ok(dt, E, F, H, S)), fo(fused ? fused_ops(dt, E) : nullptr), w(make_ws(p, B, T, bwd)),
+          fused(L > 0 && fused_ok(dt, E, F, H, S)), fo(fused ? fused_ops(dt, E) : nullptr),
+          rows(fused && cfg.use_regression_token && S > 1 && g_readout_rows == 2),
+          rows_exact(fused && cfg.use_regression_token && S > 1 && g_readout_rows != 0 && g_readout_rows != 2), w(make_ws(p, B, T, bwd)),
           ws(workspace), P(params), G(grads), s(static_cast<hipStream_t>(stream)) {}
     void *buf(size_t o) const { return at(ws, o); }                                   // workspace region at a Ws offset
     float *fbuf(size_t o) const { return static_cast<float *>(at(ws, o)); }
@@ -559,6 +584,34 @@ int layers_fwd_fused(const Call &c) {
         prof_set_tag(MIVIT_PROF_ATTN_BLOCK_FWD);
         RC(c.fo->attn_fwd(nin, gin, bin, c.W(lp.qkv_w), c.p(lp.qkv_b), c.W(lp.out_w), c.p(lp.out_b), c.p(lp.n1_w), c.p(lp.n1_b), c.B, c.S,
                           c.buf(b.ctx), c.buf(b.z1), c.fbuf(b.rstd1), nullptr, nullptr, nullptr, c.bwd ? c.buf(b.qkv) : nullptr, c.s));
+        if (c.rows_exact && l + 1 == c.L) {
+            // mode 1: the same B-row launch; its outputs go to rows b * S of the full regions, where the final norm and the
+            // unchanged backward look for them.  The backward reads every row of z2 / rstd2: the rows nobody computed are
+            // zeroed (their d(x2) is 0, so any finite value gives the exact zeros the computed rows gave)
+            const Ws &w = c.w; const size_t ts = dtype_size(c.dt); const int64_t SE = (int64_t)c.S * c.E;
+            RC(launch_convert(0, c.buf(b.z1), SE, 0, c.buf(w.z1c), c.E, c.B, c.E, 0, c.s, c.dt));
+            prof_set_tag(MIVIT_PROF_MLP_BLOCK_FWD);
+            RC(c.fo->mlp_fwd(c.buf(w.z1c), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w), c.p(lp.fc1_b), c.W(lp.fc2_w), c.p(lp.fc2_b),
+                             c.p(lp.n2_w), c.p(lp.n2_b), c.B, c.cfg.activation, c.buf(w.z2c), c.fbuf(w.rstd2c), c.buf(w.xLc), nullptr,
+                             nullptr, nullptr, nullptr, c.s));
+            RC(launch_convert(0, c.buf(w.xLc), c.E, 0, c.buf(w.xL), SE, c.B, c.E, 0, c.s, c.dt));
+            if (c.bwd) {
+                RC(launch_fill_zero(c.buf(b.z2), (size_t)c.M * c.E * ts, c.s));
+                RC(launch_fill_zero(c.buf(b.rstd2), (size_t)c.M * 4, c.s));
+                RC(launch_convert(0, c.buf(w.z2c), c.E, 0, c.buf(b.z2), SE, c.B, c.E, 0, c.s, c.dt));
+                RC(launch_convert(1, c.fbuf(w.rstd2c), 1, 1, c.fbuf(b.rstd2), c.S, c.B, 1, 0, c.s, c.dt));
+            }
+            return 0;
+        }
+        if (c.rows && l + 1 == c.L) {
+            // the head reads the regression-token row only: the feed-forward block of the last layer runs on those B rows, its
+            // z2 / rstd2 / xL compact at the start of the full regions (the attention block above needs every row: K and V)
+            RC(launch_convert(0, c.buf(b.z1), (int64_t)c.S * c.E, 0, c.buf(c.w.z1c), c.E, c.B, c.E, 0, c.s, c.dt));
+            prof_set_tag(MIVIT_PROF_MLP_BLOCK_FWD);
+            return c.fo->mlp_fwd(c.buf(c.w.z1c), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w), c.p(lp.fc1_b), c.W(lp.fc2_w), c.p(lp.fc2_b),
+                                 c.p(lp.n2_w), c.p(lp.n2_b), c.B, c.cfg.activation, c.buf(b.z2), c.fbuf(b.rstd2), c.buf(c.w.xL), nullptr,
+                                 nullptr, nullptr, nullptr, c.s);
+        }
         prof_set_tag(MIVIT_PROF_MLP_BLOCK_FWD);
         RC(c.fo->mlp_fwd(c.buf(b.z1), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w), c.p(lp.fc1_b), c.W(lp.fc2_w), c.p(lp.fc2_b), c.p(lp.n2_w),
                          c.p(lp.n2_b), c.M, c.cfg.activation, c.buf(b.z2), c.fbuf(b.rstd2), l + 1 == c.L ? c.buf(c.w.xL) : nullptr,
@@ -595,7 +648,8 @@ int readout_fwd(const Call &c) {
     a.mean = c.fbuf(w.meanF); a.rstd = c.fbuf(w.rstdF);
     prof_set_tag(MIVIT_PROF_LN_FWD);
     if (c.cfg.use_regression_token) {
-        a.M = c.B; a.y = c.buf(w.pooled); a.in_rows = 1; a.in_stride = c.S; a.in_off = 0;
+        a.M = c.B; a.y = c.buf(w.pooled);
+        if (!c.rows) { a.in_rows = 1; a.in_stride = c.S; a.in_off = 0; }          // (readout rows: the trunk's output is compact)
         return launch_layernorm_fwd(a, c.s);
     }
     a.M = c.M; a.y = c.buf(w.xF); RC(launch_layernorm_fwd(a, c.s));
@@ -661,8 +715,13 @@ int head_bwd(const Call &c, const float *dout, const float *features, float *dfe
     a.dtype = dt; a.z = c.trunk_out(); a.ldz = E; a.gamma = c.p(p->tn_w); a.mean = c.fbuf(w.meanF); a.rstd = c.fbuf(w.rstdF);
     a.E = E; a.dz = c.buf(w.dxa); a.lddz = E; a.dgamma = c.g(p->tn_w); a.dbeta = c.g(p->tn_b); a.ws = c.buf(w.ln); a.ws_bytes = w.ln_bytes;
     if (c.cfg.use_regression_token) {
-        RC(launch_fill_zero(c.buf(w.dxa), (size_t)c.M * E * dtype_size(dt), c.s));
-        a.dy = c.buf(w.d_head_in); a.lddy = Hin; a.M = B; a.z_rows = 1; a.z_stride = c.S; a.z_off = 0;
+        // d(trunk output) is non-zero in the regression-token rows only: [B,E] compact for the readout-row backward of the last
+        // layer, otherwise those rows of a zeroed [M,E]
+        a.dy = c.buf(w.d_head_in); a.lddy = Hin; a.M = B;
+        if (!c.rows) {
+            RC(launch_fill_zero(c.buf(w.dxa), (size_t)c.M * E * dtype_size(dt), c.s));
+            a.z_rows = 1; a.z_stride = c.S; a.z_off = 0;
+        }
     } else {
         const void *dp = c.buf(w.d_head_in);
         if (Hin != E) {
@@ -707,10 +766,60 @@ int layer_bwd_fused(const Call &c, int l) {
     RC(c.fo->attn_out_bwd(dx1, c.buf(b.z1), c.fbuf(b.rstd1), c.p(lp.n1_w), c.buf(b.ctx), c.W(lp.out_w), M, dz1, c.buf(w.dctx),
                           c.g(lp.out_w), c.g(lp.out_b), c.g(lp.n1_w), c.g(lp.n1_b), r.attn_out.ptr, r.attn_out.bytes, c.s));
     prof_set_tag(MIVIT_PROF_ATTN_CORE_BWD);
-    RC(launch_attention_bwd(dt, c.buf(b.qkv), c.buf(w.dctx), c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+    if (c.rows_exact && l + 1 == c.L && attention_bwd_rows_ok(dt, c.S, c.Dh))       // d(ctx) is zero behind row 0 of every sequence
+        RC(launch_attention_bwd_q_rows(dt, c.buf(b.qkv), c.buf(w.dctx), (int64_t)c.S * E, 1, c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+    else
+        RC(launch_attention_bwd(dt, c.buf(b.qkv), c.buf(w.dctx), c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
     if (!qkv_split) {
         // q|k|v projection: weight, bias and data gradient (+ the residual branch's d(z1)) in ONE pass over dqkv; the affine fix-up
         // of the weight gradient, dW diag(gamma) + db (x) beta, rides on the kernel's slab writes
+        ProfPin pin(MIVIT_PROF_QKV_BWD);
+        RC(c.fo->qkv_bwd(c.buf(w.dqkv), xin, c.W(lp.qkv_w), dz1, M, c.buf(w.dxa), c.g(lp.qkv_w), c.g(lp.qkv_b), gin, bin, r.qkv.ptr, r.qkv.bytes, c.s));
+        return slabs.flush(c.s);
+    }
+    ProfPin pin(MIVIT_PROF_QKV_WGRAD);
+    RC(lin_wgrad(dt, c.buf(w.dqkv), 3 * E, xin, 0, E, M, 3 * E, E, c.g(lp.qkv_w), c.g(lp.qkv_b), r.qkv.ptr, r.qkv.bytes, c.s));
+    if (l > 0) RC(launch_affine_fixup(c.g(lp.qkv_w), c.g(lp.qkv_b), gin, bin, 3 * E, E, c.s));
+    pin.set(MIVIT_PROF_QKV_DGRAD);
+    return lin_dgrad(dt, c.buf(w.dqkv), 3 * E, c.W(lp.qkv_w), M, 3 * E, E, MIVIT_ACT_NONE, nullptr, 0, dz1, E, c.buf(w.dxa), E, 0, c.s);
+}
+
+// stage 1 under the readout-row pruning: d(x2) of the last layer arrives as the B regression-token rows (every other row is
+// an exact zero, and with it d(z2), d(x1), d(z1) and d(ctx) of that row).  The same four kernels: the feed-forward block and
+// LayerNorm-1 / out-projection on gathered [B, .] operands, the attention core told that one query row per sequence carries a
+// gradient (d(k), d(v) are dense), the q|k|v projection on all rows with the compact d(z1) scattered into a zeroed residual.
+int last_layer_bwd_rows(const Call &c) {
+    static const bool qkv_split = getenv("MIVIT_NO_QKV_BWD") != nullptr;
+    static const bool no_defer = getenv("MIVIT_NO_SLAB_DEFER") != nullptr || qkv_split;
+    const int l = c.L - 1;
+    const Ws &w = c.w; const Ws::L &b = w.layer[l]; const LayerParams &lp = c.plan->layers[l];
+    const int dt = c.dt, E = c.E, M = c.M, B = c.B; const int64_t SE = (int64_t)c.S * E;
+    const void *xin = l > 0 ? c.buf(w.layer[l - 1].z2) : c.buf(w.x0);
+    const float *gin = l > 0 ? c.p(c.plan->layers[l - 1].n2_w) : nullptr, *bin = l > 0 ? c.p(c.plan->layers[l - 1].n2_b) : nullptr;
+    void *dx1 = c.buf(w.dxb), *dz1 = c.buf(w.dF);          // compact d(x1) / full d(z1)
+    const FusedBwdWs r = fused_bwd_ws(c, !no_defer);
+    SlabDefer slabs(r.defer);
+    RC(launch_convert(1, c.fbuf(b.rstd1), c.S, 1, c.fbuf(w.rstd1c), 1, B, 1, 0, c.s, dt));
+    RC(launch_convert(0, c.buf(b.ctx), SE, 0, c.buf(w.ctxc), E, B, E, 0, c.s, dt));
+    prof_set_tag(MIVIT_PROF_MLP_BLOCK_BWD);
+    RC(c.fo->mlp_bwd(c.buf(w.dxa), c.buf(b.z2), c.fbuf(b.rstd2), c.p(lp.n2_w), c.buf(w.z1c), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w),
+                     c.p(lp.fc1_b), c.W(lp.fc2_w), B, c.cfg.activation, dx1, c.g(lp.fc1_w), c.g(lp.fc1_b), c.g(lp.fc2_w), c.g(lp.fc2_b),
+                     c.g(lp.n2_w), c.g(lp.n2_b), r.mlp.ptr, r.mlp.bytes, c.s));
+    prof_set_tag(MIVIT_PROF_ATTN_OUT_BWD);
+    RC(c.fo->attn_out_bwd(dx1, c.buf(w.z1c), c.fbuf(w.rstd1c), c.p(lp.n1_w), c.buf(w.ctxc), c.W(lp.out_w), B, c.buf(w.dz1c), c.buf(w.dctxc),
+                          c.g(lp.out_w), c.g(lp.out_b), c.g(lp.n1_w), c.g(lp.n1_b), r.attn_out.ptr, r.attn_out.bytes, c.s));
+    if (attention_bwd_rows_ok(dt, c.S, c.Dh)) {
+        prof_set_tag(MIVIT_PROF_ATTN_CORE_BWD);
+        RC(launch_attention_bwd_q_rows(dt, c.buf(b.qkv), c.buf(w.dctxc), E, 1, B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+    } else {          // (MIVIT_ATTN_BWD=1: the first attention kernel reads every row of d(ctx))
+        RC(launch_fill_zero(c.buf(w.dctx), (size_t)M * E * dtype_size(dt), c.s));
+        RC(launch_convert(0, c.buf(w.dctxc), E, 0, c.buf(w.dctx), SE, B, E, 0, c.s, dt));
+        prof_set_tag(MIVIT_PROF_ATTN_CORE_BWD);
+        RC(launch_attention_bwd(dt, c.buf(b.qkv), c.buf(w.dctx), B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+    }
+    RC(launch_fill_zero(dz1, (size_t)M * E * dtype_size(dt), c.s));
+    RC(launch_convert(0, c.buf(w.dz1c), E, 0, dz1, SE, B, E, 0, c.s, dt));
+    if (!qkv_split) {
         ProfPin pin(MIVIT_PROF_QKV_BWD);
         RC(c.fo->qkv_bwd(c.buf(w.dqkv), xin, c.W(lp.qkv_w), dz1, M, c.buf(w.dxa), c.g(lp.qkv_w), c.g(lp.qkv_b), gin, bin, r.qkv.ptr, r.qkv.bytes, c.s));
         return slabs.flush(c.s);
@@ -792,6 +901,7 @@ int backward_impl(const mivit_plan *plan, const float *params, const float *x, c
     const Call c(plan, B, T, true, workspace, params, grads, stream);
     for (int st = stage_begin; st < stage_end; ++st) {
         if (st == 0) RC(head_bwd(c, dout, features, dfeatures));
+        else if (st == 1 && c.rows) RC(last_layer_bwd_rows(c));
         else if (st <= c.L) RC(c.fused ? layer_bwd_fused(c, c.L - st) : layer_bwd_general(c, c.L - st));      // layers L-1 .. 0
         else RC(embed_bwd(c, x, features, dfeatures, dx_tokens));
     }
@@ -819,7 +929,8 @@ extern "C" int mivit_forward(const mivit_plan *plan, const float *params, const 
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!graph_sized(plan, B, T)) return body(s);
     const uint64_t key[] = {1, plan->uid, (uint64_t)params, (uint64_t)x, (uint64_t)features, (uint64_t)B, (uint64_t)T,
-                            (uint64_t)workspace, (uint64_t)workspace_bytes, (uint64_t)need_backward, (uint64_t)out};
+                            (uint64_t)workspace, (uint64_t)workspace_bytes, (uint64_t)need_backward, (uint64_t)out,
+                            (uint64_t)g_readout_rows};          // (the switch changes the launch sequence)
     return graph_run(key, (int)(sizeof(key) / sizeof(key[0])), s, body);
 }
 
@@ -834,6 +945,7 @@ extern "C" int mivit_backward(const mivit_plan *plan, const float *params, const
     if (!graph_sized(plan, B, T)) return body(s);
     const uint64_t key[] = {2, plan->uid, (uint64_t)params, (uint64_t)x, (uint64_t)features, (uint64_t)B, (uint64_t)T,
                             (uint64_t)workspace, (uint64_t)workspace_bytes, (uint64_t)dout, (uint64_t)grads,
-                            (uint64_t)dfeatures, (uint64_t)dx_tokens, (uint64_t)stage_begin, (uint64_t)stage_end};
+                            (uint64_t)dfeatures, (uint64_t)dx_tokens, (uint64_t)stage_begin, (uint64_t)stage_end,
+                            (uint64_t)g_readout_rows};
     return graph_run(key, (int)(sizeof(key) / sizeof(key[0])), s, body);
 }
