@@ -465,6 +465,52 @@ int mivit_segment_stats(const double *pos, int N, const int *seg_offsets, const 
                         double R, double *d_cve, double *d_mle, double *sigma2, int *n_increments, void *stream);
 int mivit_markov_states(const double *u, const double *p0, const double *M, int N, int T, int K, int *state, void *stream);
 
+/* Diffusion states shared across tracks, csrc/hmm.hip: a hidden Markov model over the increments of ALL tracks of a movie, the
+ * inverse of multi_state above (K variances and K x K transition probabilities pooled over every row; the maximum-likelihood
+ * form of vbSPT; no counterpart in the reference).  fp64 without contraction, no LDS, no atomics; a group of 8 lanes owns a
+ * track and lane j is state j (a 64-thread workgroup holds 8 tracks); a track's outputs are bitwise the same alone, anywhere
+ * in a batch and in every launch.  A track has NO maximum length: the recurrence's state lives in global memory.
+ *
+ * pos [N, 2] fp64 sorted by track and by frame, offsets [n_tracks + 1] int32 (CSR; entries are clamped to [0, N]: nothing is
+ * read or written out of bounds whatever they hold).  A track of L rows at rows a .. a + L - 1 has T = L - 1 increments,
+ * q_t = dy_t^2 + dx_t^2 between rows t and t + 1.  1 <= K <= 8 states; state j has the per-axis increment variance v[j]
+ * (= 2 D_j dt + 2 sigma2 for the caller; the correlation that localisation noise puts between neighbouring increments is
+ * ignored), A [K, K] the transition probabilities, pi [K] the initial distribution.  With v_max = max_j v[j]:
+ *   m_t = q_t / (2 v_max);   b_j(q_t) = exp(-(q_t / (2 v_j) - m_t)) / v_j       exponent <= 0, the widest state has exp(0)
+ * (the density of the increment is b_j exp(-m_t) / (2 pi)).
+ *
+ * mivit_hmm_estep: the scaled forward-backward pass.  Every sum over a state index starts at 0 and runs in ascending index;
+ * t ascends in the forward pass and descends in the backward pass (the statistics are summed in descending t):
+ *   x_0 = pi * b(q_0);   x_t[j] = (sum_i alpha_{t-1}[i] * A[i][j]) * b_j(q_t);   c_t = sum_j x_t[j];   alpha_t = x_t / c_t
+ *   beta_{T-1} = 1;   w_{t+1}[j] = (b_j(q_{t+1}) / c_{t+1}) * beta_{t+1}[j];   beta_t[i] = sum_j A[i][j] * w_{t+1}[j]
+ *   gamma_t = alpha_t * beta_t;   xi_t[i][j] = (alpha_t[i] * A[i][j]) * w_{t+1}[j]      (t = 0 .. T - 2)
+ * out, per track: xi [n_tracks, K, K] = sum_t xi_t; g_sum [n_tracks, K] = sum_t gamma_t; gq_sum [n_tracks, K] = sum_t gamma_t
+ * * q_t; g_first [n_tracks, K] = gamma_0; loglik [n_tracks] = (sum_t log c_t - sum_t m_t) - T * log(2 pi), the two sums in
+ * ascending t.  out, per row: gamma [N, K], row a + t holds increment t and the last row of a track repeats the row before it;
+ * state [N] int32, the LOWEST index among the largest gamma.  A track with T < 1 has NaN statistics and loglik (a one-row
+ * track NaN in its gamma row and state -1).  The first c_t that is not in (0, inf) ends a track: loglik = -inf where that
+ * c_t is 0 (the likelihood underflowed under these parameters), NaN otherwise (a NaN or infinite position), and all its
+ * statistics and gamma rows are NaN, its states -1; no other track is touched.  workspace: [N, K] fp64 (b / c_t).  alpha_t is
+ * kept in gamma on the way forward; a lane reads back only what it wrote itself.  The only operations that may differ from
+ * the numpy restatement (helpers/msd._hmm_estep_numpy) are exp and log.
+ *
+ * mivit_hmm_viterbi: the most probable state path, in the log domain with every logarithm taken by the caller: logv [K] =
+ * log v, logA [K, K] = log A, logpi [K] = log pi (-inf where the probability is 0).
+ *   lb_j(q) = -(q / (2 v_j)) - logv_j;   delta_0[j] = logpi[j] + lb_j(q_0)
+ *   delta_t[j] = max_i (delta_{t-1}[i] + logA[i][j]) + lb_j(q_t),   the LOWEST i among equal maxima is the back-pointer
+ * (a candidate replaces the running maximum only where it compares greater, so NaN candidates never do); the path ends in the
+ * lowest j among the largest delta_{T-1} and follows the back-pointers.  out: state [N] int32 (row a + t = increment t, the
+ * last row repeats, -1 for a one-row track), logp [n_tracks] fp64 = max_j delta_{T-1}[j] (NaN where T < 1).  workspace:
+ * [N, 8] bytes, the back-pointers.  Adds, one division and compares only: bitwise the numpy restatement
+ * (helpers/msd._hmm_viterbi_numpy).
+ *
+ * Both: arguments are validated before any HIP call (sizes, K, null pointers); n_tracks = 0 is a no-op. */
+int mivit_hmm_estep(const double *pos, int N, const int *offsets, int n_tracks, int K, const double *v, const double *A,
+                    const double *pi, double *gamma, int *state, double *xi, double *g_sum, double *gq_sum, double *g_first,
+                    double *loglik, double *workspace, void *stream);
+int mivit_hmm_viterbi(const double *pos, int N, const int *offsets, int n_tracks, int K, const double *v, const double *logv,
+                      const double *logA, const double *logpi, int *state, double *logp, unsigned char *workspace, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

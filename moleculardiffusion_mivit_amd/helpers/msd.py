@@ -310,3 +310,356 @@ def segment_tracks(positions, offsets, dt=1.0, min_len=4, penalty=3.0, min_var=1
     out = {"seg_offsets": seg_offsets, "seg_track": seg_track, "D_cve": d_cve, "D_mle": d_mle, "sigma2": sigma2,
            "n_increments": n_inc.astype(np.int64), "cost": cost}
     return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# diffusion states shared across tracks: a hidden Markov model over the increments of all tracks (csrc/hmm.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+_LOG_2PI = float(np.log(2.0 * np.pi))
+
+
+def _hmm_layout(pos, offsets):
+    """What both restatements share: the first row a and the increments T of every track, the tracks in descending T (so the
+    tracks still running at step t are a prefix), and q of every row (the increment to the next row, track ends included:
+    those are never read)."""
+    a = offsets[:-1].astype(np.int64)
+    T = np.diff(offsets).astype(np.int64) - 1
+    order = np.argsort(-T, kind="stable")
+    Ts = T[order]
+    with np.errstate(over="ignore", invalid="ignore"):
+        dy, dx = pos[1:, 0] - pos[:-1, 0], pos[1:, 1] - pos[:-1, 1]
+        q = np.concatenate([dy * dy + dx * dx, np.zeros(1)])
+    return a[order], Ts, order, q
+
+
+def _hmm_estep_numpy(pos, offsets, v, A, pi):
+    """The arithmetic of csrc/hmm.hip::hmm_estep_kernel in its order (include/mivit_hip.h, mivit_hmm_estep): every sum over a
+    state index is an explicit loop in ascending index that starts at 0, the statistics are summed in descending t.  All
+    tracks advance together, one step t at a time (elementwise, so each track's numbers are those of the kernel's lanes).
+    pos [N, 2] float64, offsets [n_tracks + 1] int64, v [K], A [K, K], pi [K] -> (gamma [N, K], state [N] int32, xi [n_tracks,
+    K, K], g_sum, gq_sum, g_first [n_tracks, K], loglik [n_tracks]).  Differs from the kernel in exp and log alone."""
+    n_tracks, K, n_rows = len(offsets) - 1, len(v), len(pos)
+    a, Ts, order, q_all = _hmm_layout(pos, offsets)
+    gamma, ws = np.full((n_rows, K), np.nan), np.zeros((n_rows, K))
+    state = np.full(n_rows, -1, np.int32)
+    xi = np.zeros((n_tracks, K, K))
+    gs, gqs, gfirst = np.zeros((n_tracks, K)), np.zeros((n_tracks, K)), np.zeros((n_tracks, K))
+    slc, sm = np.zeros(n_tracks), np.zeros(n_tracks)
+    dead, cbad = np.zeros(n_tracks, bool), np.ones(n_tracks)
+    alpha = np.zeros((n_tracks, K))
+    vmax = v[0]
+    for i in range(1, K):
+        vmax = v[i] if v[i] > vmax else vmax
+    tvmax, tv = 2.0 * vmax, 2.0 * v
+    Tmax = int(Ts[0]) if n_tracks else 0
+    nact = [int(np.searchsorted(-Ts, -t, side="left")) for t in range(Tmax + 1)]          # tracks with T > t
+    with np.errstate(all="ignore"):
+        for t in range(Tmax):
+            n = nact[t]
+            rows = a[:n] + t
+            q = q_all[rows]
+            m = q / tvmax
+            b = np.exp(-(q[:, None] / tv[None, :] - m[:, None])) / v[None, :]
+            if t == 0:
+                x = pi[None, :] * b
+            else:
+                s = np.zeros((n, K))
+                for i in range(K):
+                    s = s + alpha[:n, i:i + 1] * A[i][None, :]
+                x = s * b
+            c = np.zeros(n)
+            for j in range(K):
+                c = c + x[:, j]
+            bad = ~((c > 0.0) & (c < np.inf))
+            new = bad & ~dead[:n]
+            cbad[:n][new] = c[new]
+            dead[:n] |= bad
+            alpha[:n] = x / c[:, None]
+            slc[:n] = slc[:n] + np.log(c)
+            sm[:n] = sm[:n] + m
+            gamma[rows] = alpha[:n]
+            ws[rows] = b / c[:, None]
+        beta = np.ones((n_tracks, K))
+        for t in range(Tmax - 1, -1, -1):
+            n, n2 = nact[t], nact[t + 1]                                                   # n2: the tracks with t < T - 1
+            rows = a[:n] + t
+            al = gamma[rows]
+            if n2:
+                w = ws[rows[:n2] + 1] * beta[:n2]
+                nb = np.zeros((n2, K))
+                for i in range(K):
+                    nb = nb + A[:, i][None, :] * w[:, i:i + 1]
+                    xi[:n2, i, :] = xi[:n2, i, :] + (al[:n2, i:i + 1] * A[i][None, :]) * w
+                beta[:n2] = nb
+            gam = al * beta[:n]
+            gs[:n] = gs[:n] + gam
+            gqs[:n] = gqs[:n] + gam * q_all[rows][:, None]
+            bg, best = gam[:, 0].copy(), np.zeros(n, np.int32)
+            for i in range(1, K):
+                up = gam[:, i] > bg
+                bg = np.where(up, gam[:, i], bg)
+                best = np.where(up, np.int32(i), best)
+            gamma[rows] = gam
+            state[rows] = best
+            gamma[rows[n2:] + 1] = gam[n2:]                                                # the last row repeats
+            state[rows[n2:] + 1] = best[n2:]
+            if t == 0:
+                gfirst[:n] = gam
+        loglik = (slc - sm) - Ts.astype(np.float64) * _LOG_2PI
+    none = Ts < 1
+    for arr in (xi, gs, gqs, gfirst, loglik):
+        arr[none | dead] = np.nan
+    loglik[dead & (cbad == 0.0)] = -np.inf
+    for k in np.nonzero(dead)[0]:
+        gamma[a[k]:a[k] + Ts[k] + 1] = np.nan
+        state[a[k]:a[k] + Ts[k] + 1] = -1
+    inv = np.empty(n_tracks, np.int64)
+    inv[order] = np.arange(n_tracks)
+    return gamma, state, xi[inv], gs[inv], gqs[inv], gfirst[inv], loglik[inv]
+
+
+def _hmm_viterbi_numpy(pos, offsets, v, logv, logA, logpi):
+    """The arithmetic of csrc/hmm.hip::hmm_viterbi_kernel in its order (mivit_hmm_viterbi): a candidate replaces the running
+    maximum only where it compares greater, in ascending index, so the lowest index wins among equal maxima and a NaN never
+    does (np.argmax would pick it).  The logarithms are inputs.  -> (state [N] int32, logp [n_tracks]), bitwise the kernel's."""
+    n_tracks, K, n_rows = len(offsets) - 1, len(v), len(pos)
+    a, Ts, order, q_all = _hmm_layout(pos, offsets)
+    state = np.full(n_rows, -1, np.int32)
+    logp = np.full(n_tracks, np.nan)
+    bp = np.zeros((n_rows, K), np.int32)
+    end = np.zeros(n_tracks, np.int32)
+    delta = np.zeros((n_tracks, K))
+    tv = 2.0 * v
+    Tmax = int(Ts[0]) if n_tracks else 0
+    nact = [int(np.searchsorted(-Ts, -t, side="left")) for t in range(Tmax + 1)]
+    with np.errstate(all="ignore"):
+        for t in range(Tmax):
+            n, n2 = nact[t], nact[t + 1]
+            rows = a[:n] + t
+            lb = -(q_all[rows][:, None] / tv[None, :]) - logv[None, :]
+            if t == 0:
+                delta[:n] = logpi[None, :] + lb
+            else:
+                bv, bi = delta[:n, 0:1] + logA[0][None, :], np.zeros((n, K), np.int32)
+                for i in range(1, K):
+                    cand = delta[:n, i:i + 1] + logA[i][None, :]
+                    up = cand > bv
+                    bv = np.where(up, cand, bv)
+                    bi = np.where(up, np.int32(i), bi)
+                delta[:n] = bv + lb
+                bp[rows] = bi
+            if n > n2:                                                                     # the tracks that end here
+                d = delta[n2:n]
+                bv, s = d[:, 0].copy(), np.zeros(n - n2, np.int32)
+                for i in range(1, K):
+                    up = d[:, i] > bv
+                    bv = np.where(up, d[:, i], bv)
+                    s = np.where(up, np.int32(i), s)
+                logp[n2:n], end[n2:n] = bv, s
+        s = end.copy()
+        for t in range(Tmax - 1, -1, -1):
+            n, n2 = nact[t], nact[t + 1]
+            rows = a[:n] + t
+            state[rows] = s[:n]
+            state[rows[n2:] + 1] = s[n2:n]                                                 # the last row repeats
+            if t > 0:
+                s[:n] = bp[rows, s[:n]]
+    inv = np.empty(n_tracks, np.int64)
+    inv[order] = np.arange(n_tracks)
+    return state, logp[inv]
+
+
+def _hmm_inputs(positions, offsets):
+    """The checks of track_msd / segment_tracks -> (pos, off, kind): kind "cuda" (float64 / int32 tensors on the GPU), "cpu" or
+    "numpy" (float64 / int64 arrays)."""
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    if torch.is_tensor(positions) != torch.is_tensor(offsets):
+        raise ValueError("positions and offsets must both be tensors or both be arrays")
+    if torch.is_tensor(positions) and positions.device != offsets.device:
+        raise ValueError(f"positions on {positions.device}, offsets on {offsets.device}")
+    offsets = offsets if torch.is_tensor(offsets) else np.asarray(offsets)
+    _check_offsets(offsets, positions.shape[0])
+    if torch.is_tensor(positions) and positions.device.type == "cuda":
+        return positions.detach().double().contiguous(), offsets.int().contiguous(), "cuda"
+    if torch.is_tensor(positions):
+        return positions.detach().double().numpy(), offsets.detach().numpy().astype(np.int64), "cpu"
+    return np.asarray(positions, dtype=np.float64), offsets.astype(np.int64), "numpy"
+
+
+def _hmm_estep_any(pos, off, kind, v, A, pi):
+    """One E-step on the input's device, float64 torch tensors in and out: the kernel on the GPU, the restatement elsewhere."""
+    if kind == "cuda":
+        from .. import ops
+        return ops.hmm_estep(pos, off, v.contiguous(), A.contiguous(), pi.contiguous())
+    out = _hmm_estep_numpy(pos, off, v.numpy(), A.numpy(), pi.numpy())
+    return tuple(torch.from_numpy(np.ascontiguousarray(o)) for o in out)
+
+
+def _hmm_viterbi_any(pos, off, kind, v, A, pi):
+    if kind == "cuda":
+        from .. import ops
+        return ops.hmm_viterbi(pos, off, v.contiguous(), A.contiguous(), pi.contiguous())
+    with np.errstate(divide="ignore"):
+        out = _hmm_viterbi_numpy(pos, off, v.numpy(), np.log(v.numpy()), np.log(A.numpy()), np.log(pi.numpy()))
+    return tuple(torch.from_numpy(np.ascontiguousarray(o)) for o in out)
+
+
+def _hmm_out(d, kind):
+    if kind != "numpy":
+        return d
+    return {k: (x.cpu().numpy() if torch.is_tensor(x) else x) for k, x in d.items()}
+
+
+def _hmm_scalars(dt, sigma2):
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(sigma2) < float("inf"):
+        raise ValueError(f"sigma2 must be finite and >= 0, got {sigma2}")
+    return float(dt), float(sigma2)
+
+
+def hmm_posteriors(positions, offsets, Ds, M, p0=None, dt=1.0, sigma2=0.0):
+    """The posterior of the hidden state of every row under GIVEN parameters: one E-step and the Viterbi path of the hidden
+    Markov model that fit_diffusion_states fits.  positions [N, 2] and offsets [n_tracks + 1] as segment_tracks takes them; Ds
+    [K], M [K, K] and p0 [K] as generation.multi_state takes them (p0 = None: the stationary distribution of M) -> dict of the
+    input's kind: gamma [N, K], state_posterior [N] (the largest gamma), state [N] (Viterbi), loglik [n_tracks] (the track's
+    log-likelihood, -inf where it underflows, NaN without an increment or with a NaN position), logp [n_tracks] (the Viterbi
+    path's log-probability up to -T log(2 pi)), and the E-step's statistics xi, g_sum, gq_sum, g_first.  A row holds the
+    increment that starts at it; a track's last row repeats the row before it, a one-row track has NaN and -1.  State j has
+    the per-axis increment variance 2 Ds[j] dt + 2 sigma2, sigma2 the localisation variance; the correlation that
+    localisation noise puts between neighbouring increments is ignored.  include/mivit_hip.h has the arithmetic.  CUDA
+    tensors go to the kernels (csrc/hmm.hip, two launches, no limit on a track's length), anything else to the restatements."""
+    from .generation import _markov_args
+    dt, sigma2 = _hmm_scalars(dt, sigma2)
+    Ds, M, p0 = _markov_args(Ds, M, p0)
+    pos, off, kind = _hmm_inputs(positions, offsets)
+    dev = pos.device if kind == "cuda" else "cpu"
+    v = torch.from_numpy(2.0 * Ds * dt + 2.0 * sigma2).to(dev)
+    if not bool((v > 0).all()):
+        raise ValueError("every state needs a positive increment variance 2 D dt + 2 sigma2")
+    A, pi = torch.from_numpy(M).to(dev), torch.from_numpy(p0).to(dev)
+    gamma, sp, xi, g_sum, gq_sum, g_first, loglik = _hmm_estep_any(pos, off, kind, v, A, pi)
+    state, logp = _hmm_viterbi_any(pos, off, kind, v, A, pi)
+    return _hmm_out({"gamma": gamma, "state_posterior": sp.long(), "state": state.long(), "loglik": loglik, "logp": logp,
+                     "xi": xi, "g_sum": g_sum, "gq_sum": gq_sum, "g_first": g_first}, kind)
+
+
+def fit_diffusion_states(positions, offsets, K, dt=1.0, sigma2=0.0, max_iter=200, tol=1e-8, min_var=1e-12, init=None):
+    """Diffusion states shared by all tracks of a movie: K diffusion coefficients, their K x K transition probabilities and the
+    state of every row, by maximum likelihood (EM) on a hidden Markov model over the increments of ALL tracks -- the inverse
+    of generation.multi_state(N, T, Ds, M).  Where segment_tracks cuts each track on its own, this pools: a stretch of a few
+    rows is recognised because its state is known from every other track.  positions, offsets as segment_tracks takes them
+    (gap-free rows) -> dict of the input's kind, states sorted by ascending D:
+        Ds [K], M [K, K], p0 [K]        the fitted parameters (p0: the distribution of a track's first state)
+        loglik, n_iter, converged       total log-likelihood of the used tracks, E-steps taken, whether tol was met
+        loglik_trace [n_iter]           the log-likelihood of every E-step
+        bic                             -2 loglik + (K^2 + K - 1) log(n_increments): compare fits of different K
+        n_tracks_used, n_increments     the tracks with a finite log-likelihood and their increments
+        gamma [N, K]                    posterior of the state of the increment that starts at each row
+        state [N], state_posterior [N]  the Viterbi path under the fitted parameters / the largest gamma; -1 where undefined
+        occupancy [K]                   the share of increments in each state
+    State j has the per-axis increment variance v_j = 2 D_j dt + 2 sigma2, sigma2 the (given) localisation variance; the
+    correlation that localisation noise puts between neighbouring increments is ignored, and D_j = (v_j - 2 sigma2) / (2 dt)
+    may come out negative where sigma2 is overstated.  The default start: v at the K quantile mid-points of q / 2 over all
+    increments, spread by factors from 0.5 to 2; M with 0.9 on the diagonal and the rest shared equally; p0 uniform.  init = {
+    "Ds", "M", "p0"} replaces any of them.  An iteration is an E-step (csrc/hmm.hip on CUDA tensors, its numpy restatement
+    elsewhere) and an M-step over the tracks with a finite log-likelihood (a few float64 torch ops on the input's device):
+        M[i][j] = Xi[i][j] / sum_j Xi[i][j];  v_j = max(GQ_j / (2 G_j), min_var);  p0 = G_first / sum(G_first)
+    (a state nothing was assigned to keeps its row and variance) until loglik - previous < tol * |loglik| or max_iter E-steps;
+    only the scalar loglik is read back per iteration.  A track without an increment, with a NaN position or whose likelihood
+    underflows contributes nothing."""
+    if isinstance(K, bool) or int(K) != K or K < 1:
+        raise ValueError(f"K must be an integer >= 1, got {K}")
+    K = int(K)
+    from .. import ops
+    if K > ops.MARKOV_MAX_K:
+        raise ValueError(f"K = {K} states, 1 .. {ops.MARKOV_MAX_K} (ops.MARKOV_MAX_K) are supported")
+    dt, sigma2 = _hmm_scalars(dt, sigma2)
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"max_iter must be an integer >= 1, got {max_iter}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"tol must be >= 0, got {tol}")
+    if not 0.0 < float(min_var) < float("inf"):
+        raise ValueError(f"min_var must be positive and finite, got {min_var}")
+    init = {} if init is None else dict(init)
+    if set(init) - {"Ds", "M", "p0"}:
+        raise ValueError(f"init: unknown keys {sorted(set(init) - {'Ds', 'M', 'p0'})}")
+    pos, off, kind = _hmm_inputs(positions, offsets)
+    dev = pos.device if kind == "cuda" else torch.device("cpu")
+    tpos = pos if kind == "cuda" else torch.from_numpy(pos if pos.flags.writeable else pos.copy())
+    toff = off.long() if kind == "cuda" else torch.from_numpy(off if off.flags.writeable else off.copy())
+    n_rows, n_tracks = tpos.shape[0], toff.numel() - 1
+    f64 = dict(dtype=torch.float64, device=dev)
+    host = lambda x: np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64)    # noqa: E731
+
+    if "Ds" in init:
+        d0 = host(init["Ds"]).reshape(-1)
+        if d0.shape != (K,) or not np.isfinite(d0).all():
+            raise ValueError(f"init['Ds'] must hold {K} finite values")
+        v = torch.from_numpy(2.0 * d0 * dt + 2.0 * sigma2).to(dev)
+        if not bool((v > 0).all()):
+            raise ValueError("init['Ds']: every state needs a positive increment variance 2 D dt + 2 sigma2")
+    else:
+        # q / 2 of every increment inside a track (E[q] = 2 v), sorted: order statistics, the same on every device
+        inside = torch.ones(n_rows, dtype=torch.bool, device=dev)
+        inside[toff[1:][toff[1:] > toff[:-1]] - 1] = False
+        d = tpos[1:] - tpos[:-1]
+        h = ((d * d).sum(dim=1) / 2.0)[inside[:-1]] if n_rows > 1 else torch.zeros(0, **f64)
+        h = torch.sort(h[torch.isfinite(h)])[0]
+        if h.numel() == 0:
+            raise ValueError("no track has a finite increment")
+        at = ((torch.arange(K, **f64) + 0.5) / K * h.numel()).long().clamp(max=h.numel() - 1)
+        spread = torch.from_numpy(np.geomspace(0.5, 2.0, K) if K > 1 else np.ones(1)).to(dev)
+        v = torch.clamp(h[at] * spread, min=float(min_var))
+    if "M" in init:
+        m0 = host(init["M"])
+        if m0.shape != (K, K) or not ((m0 >= 0).all() and np.allclose(m0.sum(axis=1), 1.0, rtol=0, atol=1e-9)):
+            raise ValueError(f"init['M'] must be [{K}, {K}] with rows that are distributions")
+        A = torch.from_numpy(np.ascontiguousarray(m0)).to(dev)
+    else:
+        A = torch.full((K, K), 0.1 / (K - 1) if K > 1 else 0.0, **f64)
+        A.fill_diagonal_(0.9 if K > 1 else 1.0)
+    if "p0" in init:
+        q0 = host(init["p0"]).reshape(-1)
+        if q0.shape != (K,) or not ((q0 >= 0).all() and abs(q0.sum() - 1.0) <= 1e-9):
+            raise ValueError(f"init['p0'] must be a distribution over the {K} states")
+        pi = torch.from_numpy(q0).to(dev)
+    else:
+        pi = torch.full((K,), 1.0 / K, **f64)
+
+    trace, converged, prev = [], False, None
+    zero = torch.zeros((), **f64)
+    for it in range(int(max_iter)):
+        gamma, sp, xi, g_sum, gq_sum, g_first, loglik = _hmm_estep_any(pos, off, kind, v, A, pi)
+        ok = torch.isfinite(loglik)
+        ll = float(torch.where(ok, loglik, zero).sum())                                    # the one read-back
+        trace.append(ll)
+        if prev is not None and ll - prev < float(tol) * abs(ll):
+            converged = True
+            break
+        prev = ll
+        if it == int(max_iter) - 1:
+            break
+        Xi = torch.where(ok[:, None, None], xi, zero).sum(dim=0)
+        G = torch.where(ok[:, None], g_sum, zero).sum(dim=0)
+        GQ = torch.where(ok[:, None], gq_sum, zero).sum(dim=0)
+        GF = torch.where(ok[:, None], g_first, zero).sum(dim=0)
+        rs = Xi.sum(dim=1, keepdim=True)
+        A = torch.where(rs > 0, Xi / rs, A)
+        v = torch.where(G > 0, torch.clamp(GQ / (2.0 * G), min=float(min_var)), v)
+        pi = torch.where(GF.sum() > 0, GF / GF.sum(), pi)
+    Ds = (v - 2.0 * sigma2) / (2.0 * dt)
+    perm = torch.argsort(Ds, stable=True)
+    Ds, v, pi, A = Ds[perm], v[perm].contiguous(), pi[perm].contiguous(), A[perm][:, perm].contiguous()
+    rank = torch.empty_like(perm)
+    rank[perm] = torch.arange(K, device=dev)
+    sp = sp.long()
+    sp = torch.where(sp >= 0, rank[sp.clamp(min=0)], sp)
+    state, _ = _hmm_viterbi_any(pos, off, kind, v, A, pi)
+    G = torch.where(ok[:, None], g_sum, zero).sum(dim=0)[perm]
+    n_inc = int(torch.where(ok, (toff[1:] - toff[:-1] - 1).to(dev), torch.zeros((), dtype=torch.int64, device=dev)).sum())
+    return _hmm_out({"Ds": Ds, "M": A, "p0": pi, "loglik": trace[-1], "n_iter": len(trace), "converged": converged,
+                     "loglik_trace": np.asarray(trace), "bic": -2.0 * trace[-1] + (K * K + K - 1) * float(np.log(max(n_inc, 1))),
+                     "n_tracks_used": int(ok.sum()), "n_increments": n_inc, "gamma": gamma[:, perm], "state": state.long(),
+                     "state_posterior": sp, "occupancy": G / G.sum()}, kind)

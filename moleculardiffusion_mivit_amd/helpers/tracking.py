@@ -1127,7 +1127,7 @@ def refine_localizations_tensors(patches, ys, xs):
 
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
-                             batch_size=4096, segment=None, **tracking_kwargs):
+                             batch_size=4096, segment=None, states=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1144,7 +1144,20 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     (min_len, penalty, min_var, blur; {} for the defaults; dt is this function's).  The result gains "segments": the
     segment_tracks dict computed on the positions the MSD is taken on (csrc/segment.hip), plus D_model [n_seg], the mean of
     the model's output over the windows of plan_sequences(seg_offsets, seq_len, tail), so that no window straddles a
-    changepoint (NaN for a segment shorter than seq_len), and n_sequences [n_seg].  The per-track entries are unchanged."""
+    changepoint (NaN for a segment shorter than seq_len), and n_sequences [n_seg].  The per-track entries are unchanged.
+
+    states (default None: off): a dict of helpers/msd.fit_diffusion_states arguments (K, required; sigma2, max_iter, tol,
+    min_var, init; dt is this function's).  The result gains "states": the fit_diffusion_states dict computed on the same
+    positions (csrc/hmm.hip: diffusion states SHARED by all tracks, where segment cuts each track on its own), plus
+    run_offsets [n_runs + 1], the CSR of the maximal runs of constant Viterbi state over the same rows (it refines offsets),
+    run_track and run_state [n_runs] (-1 for a one-row track), and D_model, n_sequences [n_runs] from the windows of
+    plan_sequences(run_offsets, seq_len, tail) exactly as for segment, so that no window straddles a switch.  The per-track
+    entries and those of segment are unchanged; both may be given."""
+    if states is not None:
+        if not isinstance(states, dict) or set(states) - {"K", "sigma2", "max_iter", "tol", "min_var", "init"}:
+            raise ValueError("states must be None or a dict with keys among K, sigma2, max_iter, tol, min_var and init")
+        if "K" not in states:
+            raise ValueError("states needs the number of states K")
     if not _is_cuda(movie):
         raise ValueError("estimate_track_diffusion needs a CUDA movie; move it to the GPU (movie.cuda())")
     if segment is not None and (not isinstance(segment, dict) or set(segment) - {"min_len", "penalty", "min_var", "blur"}):
@@ -1190,6 +1203,21 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         seg_seq, seg_of_seq, _ = track_sequences(movie, fr, y, x, segments["seg_offsets"], seq_len, patch_size, norm, tail)
         segments["n_sequences"] = torch.bincount(seg_of_seq, minlength=len(segments["seg_track"]))
         segments["D_model"] = mean_per_group(seg_seq, segments["n_sequences"])
+    fitted = None
+    if states is not None:
+        from . import msd as _msd
+        fitted = _msd.fit_diffusion_states(pos, offsets, dt=dt, **states)
+        st = fitted["state"]
+        first = torch.zeros(len(st), dtype=torch.bool, device=movie.device)
+        first[1:] = st[1:] != st[:-1]
+        first[offsets[:-1][lengths > 0]] = True                            # a track's first row always starts a run
+        first = torch.nonzero(first, as_tuple=True)[0]
+        fitted["run_offsets"] = torch.cat([first, torch.full((1,), len(st), dtype=torch.int64, device=movie.device)])
+        fitted["run_track"] = torch.searchsorted(offsets.long().contiguous(), first, right=True) - 1
+        fitted["run_state"] = st[first]
+        run_seq, run_of_seq, _ = track_sequences(movie, fr, y, x, fitted["run_offsets"], seq_len, patch_size, norm, tail)
+        fitted["n_sequences"] = torch.bincount(run_of_seq, minlength=len(first))
+        fitted["D_model"] = mean_per_group(run_seq, fitted["n_sequences"])
     res = {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
            "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}
     if len(by_track) > 5:
@@ -1197,6 +1225,8 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["n_filled"] = torch.bincount(row_track[by_track[5]], minlength=n_tracks)
     if segments is not None:
         res["segments"] = segments
+    if fitted is not None:
+        res["states"] = fitted
     return res
 
 

@@ -887,7 +887,7 @@ def _map_displacements_checked(disp, s0, geom_of, verts, lengths, vert_offsets, 
 
 
 SEG_MAX_LEN = 4096           # csrc/segment.hip: rows of a track whose recurrence state (20 B a row) fits in LDS
-MARKOV_MAX_K = 8             # csrc/segment.hip: states of mivit_markov_states
+MARKOV_MAX_K = 8             # csrc/segment.hip: states of mivit_markov_states; csrc/hmm.hip: of mivit_hmm_estep / _viterbi
 
 
 def _seg_tensor(t, dtype, ndim, name, what):
@@ -972,6 +972,70 @@ def markov_states(u: torch.Tensor, p0: torch.Tensor, M: torch.Tensor) -> torch.T
     state = torch.empty(n, T, dtype=torch.int32, device=u.device)
     N.check(N.lib.mivit_markov_states(_p(u), _p(p0), _p(M), n, T, K, _p(state), _s(u)), "mivit_markov_states")
     return state
+
+
+def _hmm_args(name, pos, offsets, v, A, pi):
+    """The checks both hidden-Markov wrappers share -> (n, n_tracks, K); every rejection is a ValueError before any launch."""
+    pos = _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
+    offsets = _seg_tensor(offsets, torch.int32, 1, name, "offsets [n_tracks + 1]")
+    v = _seg_tensor(v, torch.float64, 1, name, "v [K]")
+    A = _seg_tensor(A, torch.float64, 2, name, "A [K, K]")
+    pi = _seg_tensor(pi, torch.float64, 1, name, "pi [K]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"{name}: pos must be [N, 2], got {tuple(pos.shape)}")
+    if offsets.numel() < 1:
+        raise ValueError(f"{name}: offsets must have n_tracks + 1 entries")
+    K = v.numel()
+    if not 1 <= K <= MARKOV_MAX_K:
+        raise ValueError(f"{name}: {K} states, 1 .. {MARKOV_MAX_K} (MARKOV_MAX_K) are supported")
+    if tuple(A.shape) != (K, K):
+        raise ValueError(f"{name}: A must be [{K}, {K}], got {tuple(A.shape)}")
+    if pi.numel() != K:
+        raise ValueError(f"{name}: pi must be [{K}], got {tuple(pi.shape)}")
+    if len({t.device for t in (pos, offsets, v, A, pi)}) != 1:
+        raise ValueError(f"{name}: all tensors must be on one device")
+    n, n_tracks = pos.shape[0], offsets.numel() - 1
+    if n_tracks:
+        off = offsets.cpu()
+        if int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+            raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n}")
+    elif n:
+        raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n}")
+    return n, n_tracks, K
+
+
+def hmm_estep(pos: torch.Tensor, offsets: torch.Tensor, v: torch.Tensor, A: torch.Tensor, pi: torch.Tensor):
+    """One E-step of the hidden Markov model over the increments of all tracks (csrc/hmm.hip, mivit_hmm_estep): pos [N, 2]
+    float64 on the GPU, sorted by track and by frame; offsets [n_tracks + 1] int32 (CSR, from 0 to N); v [K] the per-axis
+    increment variance of every state, A [K, K] the transition probabilities, pi [K] the initial distribution, float64, 1 <=
+    K <= MARKOV_MAX_K -> (gamma [N, K], state [N] int32, xi [n_tracks, K, K], g_sum, gq_sum, g_first [n_tracks, K], loglik
+    [n_tracks]).  A track has no maximum length.  See include/mivit_hip.h for the arithmetic and helpers/msd.
+    fit_diffusion_states for the front end."""
+    n, n_tracks, K = _hmm_args("hmm_estep", pos, offsets, v, A, pi)
+    f64 = dict(dtype=torch.float64, device=pos.device)
+    gamma, ws = torch.empty(n, K, **f64), torch.empty(n, K, **f64)
+    state = torch.empty(n, dtype=torch.int32, device=pos.device)
+    xi = torch.empty(n_tracks, K, K, **f64)
+    g_sum, gq_sum, g_first = (torch.empty(n_tracks, K, **f64) for _ in range(3))
+    loglik = torch.empty(n_tracks, **f64)
+    N.check(N.lib.mivit_hmm_estep(_p(pos), n, _p(offsets), n_tracks, K, _p(v), _p(A), _p(pi), _p(gamma), _p(state), _p(xi),
+                                  _p(g_sum), _p(gq_sum), _p(g_first), _p(loglik), _p(ws), _s(pos)), "mivit_hmm_estep")
+    return gamma, state, xi, g_sum, gq_sum, g_first, loglik
+
+
+def hmm_viterbi(pos: torch.Tensor, offsets: torch.Tensor, v: torch.Tensor, A: torch.Tensor, pi: torch.Tensor):
+    """The most probable state path of every track under the same model (csrc/hmm.hip, mivit_hmm_viterbi); arguments as
+    hmm_estep -> (state [N] int32, -1 on a one-row track; logp [n_tracks] float64, the path's log-probability up to the
+    constant -T log(2 pi), NaN for a track without an increment).  The logarithms of v, A and pi are taken here, in torch: the
+    kernel adds and compares only.  See include/mivit_hip.h."""
+    n, n_tracks, K = _hmm_args("hmm_viterbi", pos, offsets, v, A, pi)
+    state = torch.empty(n, dtype=torch.int32, device=pos.device)
+    logp = torch.empty(n_tracks, dtype=torch.float64, device=pos.device)
+    bp = torch.empty(n, 8, dtype=torch.uint8, device=pos.device)
+    logv, logA, logpi = torch.log(v), torch.log(A), torch.log(pi)
+    N.check(N.lib.mivit_hmm_viterbi(_p(pos), n, _p(offsets), n_tracks, K, _p(v), _p(logv), _p(logA), _p(logpi), _p(state),
+                                    _p(logp), _p(bp), _s(pos)), "mivit_hmm_viterbi")
+    return state, logp
 
 
 MOVIE_MAX_RADIUS = 64        # csrc/movie.hip: limits of mivit_render_movie

@@ -18,13 +18,17 @@ estimate_track_diffusion(..., segment={"penalty": p}) (helpers/msd.segment_track
 --penalties and adds "segmentation": per penalty, over the tracks matched to a particle, the recall and precision of the
 changepoints (a found one counts when it lies within 5 frames of a true one of that particle inside the track's frames,
 every true one once) and the mean absolute error per row against truth["D_row"] of D_cve and D_mle of the row's segment and
-of D_msd of its track.  A tool, not a test: it asserts no accuracy.
+of D_msd of its track.  --hmm K (with --states) also runs estimate_track_diffusion(..., states={"K": k})
+(helpers/msd.fit_diffusion_states, csrc/hmm.hip) for k = 1, 2, 3 and K and adds "hmm": the fitted Ds and M of K next to the
+planted ones (states sorted by ascending D), over the rows of matched tracks the mean absolute error of Ds[state] (the
+Viterbi state) against truth["D_row"] and the share of rows whose state is the planted one, the BIC of every k and the k it
+picks.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
                                           [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10]
                                           [--cristae 4 30 60 12] [--boundary reflect]
-                                          [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8]
+                                          [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -65,6 +69,7 @@ def main():
     ap.add_argument("--boundary", choices=["clamp", "reflect"], default=None)
     ap.add_argument("--states", type=float, nargs=3, default=None, metavar=("D1", "D2", "P_STAY"))
     ap.add_argument("--penalties", type=float, nargs="+", default=[1.0, 2.0, 3.0, 4.0, 6.0, 8.0])
+    ap.add_argument("--hmm", type=int, default=None, metavar="K")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
@@ -82,6 +87,8 @@ def main():
                    "boundary": args.boundary or "clamp"}
     elif args.boundary is not None:
         raise SystemExit("--boundary needs --cristae")
+    if args.hmm is not None and args.states is None:
+        raise SystemExit("--hmm needs --states")
     states = None
     if args.states is not None:
         d1, d2, stay = args.states
@@ -142,7 +149,40 @@ def main():
     if states is not None:
         out["states"] = args.states
         out["segmentation"] = [segmentation_scores(movie, model, args, norm, truth, score, fr, float(p)) for p in args.penalties]
+        if args.hmm is not None:
+            out["hmm"] = hmm_scores(movie, model, args, norm, truth, score, fr, states)
     print(json.dumps(out))
+
+
+def hmm_scores(movie, model, args, norm, truth, score, fr, planted):
+    """the pooled fit of --hmm K against the planted states (see the module's docstring)"""
+    fits = {}
+    for k in sorted({1, 2, 3, args.hmm}):
+        fits[k] = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
+                                               states={"K": k})
+    est, st = fits[args.hmm], fits[args.hmm]["states"]
+    Np, F_ = args.particles, args.frames
+    nan = float("nan")
+    d_true = torch.full((Np, F_), nan, dtype=torch.float64, device=movie.device)
+    d_true[truth["particle_id"], truth["frame"]] = truth["D_row"]
+    order = sorted(range(len(planted["Ds"])), key=lambda i: planted["Ds"][i])              # planted states by ascending D
+    rank = torch.empty(len(order), dtype=torch.int64, device=movie.device)
+    rank[torch.tensor(order, device=movie.device)] = torch.arange(len(order), device=movie.device)
+    s_true = torch.full((Np, F_), -1, dtype=torch.int64, device=movie.device)
+    s_true[truth["particle_id"], truth["frame"]] = rank[truth["state"].long()]
+    row_track = torch.repeat_interleave(torch.arange(len(est["length"]), device=movie.device), est["length"])
+    pid = score["particle_id"][row_track]
+    f = fr.clamp(0, F_ - 1)
+    want, want_s = d_true[pid.clamp_min(0), f], s_true[pid.clamp_min(0), f]
+    ok = (pid >= 0) & ~torch.isnan(want) & (st["state"] >= 0)
+    got = st["Ds"][st["state"].clamp_min(0)]
+    bic = {k: float(v["states"]["bic"]) for k, v in fits.items()}
+    return {"K": args.hmm, "Ds": st["Ds"].tolist(), "M": st["M"].tolist(), "p0": st["p0"].tolist(),
+            "planted_Ds": [planted["Ds"][i] for i in order], "planted_M": [[planted["M"][i][j] for j in order] for i in order],
+            "n_iter": st["n_iter"], "converged": st["converged"], "n_tracks_used": st["n_tracks_used"],
+            "mae_D_hmm": float((got[ok] - want[ok]).abs().mean()) if bool(ok.any()) else nan,
+            "state_accuracy": float((st["state"][ok] == want_s[ok]).double().mean()) if bool(ok.any()) and args.hmm == len(order) else nan,
+            "rows_scored": int(ok.sum()), "n_runs": int(len(st["run_track"])), "bic": bic, "bic_picks": min(bic, key=bic.get)}
 
 
 def segmentation_scores(movie, model, args, norm, truth, score, fr, penalty, tol=5):
