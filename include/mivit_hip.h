@@ -619,6 +619,43 @@ int mivit_qkv_bwd_affine_w64_f16(const void *dqkv, const void *x, const void *Wq
                                  float *db, const float *fix_gamma, const float *fix_beta, void *workspace, size_t workspace_bytes,
                                  void *stream);
 
+/* The last encoder layer under the regression-token readout (csrc/engine.hip, mivit_set_readout_rows(1)): the head reads row 0
+ * of every S-token sequence, so in that layer's backward d(x1), d(z1), d(ctx) and dq are exact zeros in every other row.  Two
+ * variants of the operators above that neither compute, read nor write what is zero or never read; what they do produce is
+ * bitwise what the full operator produces from the same buffers.  Same arguments, layouts and workspaces unless stated.
+ *   mivit_attn_block_fwd_q1  : k and v (and their rows of qkv_out) for every row; the query side -- q, attention, out-projection,
+ *       residual, LayerNorm -- for the first min(S, 16) rows of a sequence only.  Rows behind them: q, ctx, rstd (x_out, z_out,
+ *       mean) are NOT written; n_out is written as zeros when qkv_out is given (a backward follows, and mivit_mlp_block_bwd
+ *       reads every row of it) and not written otherwise.  S <= 16: mivit_attn_block_fwd.
+ *   mivit_attn_out_bwd_rows  : dy is zero outside the rows r % S == 0 by contract.  Only those rows of dy / n1 / rstd1 / ctx are
+ *       read and only those rows of dctx are written; dz1 is written in every row (zeros in the others: mivit_qkv_bwd reads
+ *       them all); dWo, dbo, dgamma1, dbeta1 sum the same terms in the same order.
+ * Suffixes as above: _w64 (E = 64), _f16, _w64_f16. */
+int mivit_attn_block_fwd_q1(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv_bf16,
+        const float *bqkv, const void *Wo_bf16, const float *bo, const float *gamma_out, const float *beta_out, int B, int S,
+        void *ctx, void *n_out, float *rstd, void *x_out, void *z_out, float *mean, void *qkv_out, void *stream);
+int mivit_attn_out_bwd_rows(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+        const void *Wo_bf16, int M, int S, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1, float *dbeta1,
+        void *workspace, size_t workspace_bytes, void *stream);
+int mivit_attn_block_fwd_q1_w64(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv_bf16,
+        const float *bqkv, const void *Wo_bf16, const float *bo, const float *gamma_out, const float *beta_out, int B, int S,
+        void *ctx, void *n_out, float *rstd, void *x_out, void *z_out, float *mean, void *qkv_out, void *stream);
+int mivit_attn_out_bwd_rows_w64(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+        const void *Wo_bf16, int M, int S, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1, float *dbeta1,
+        void *workspace, size_t workspace_bytes, void *stream);
+int mivit_attn_block_fwd_q1_f16(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv,
+        const float *bqkv, const void *Wo, const float *bo, const float *gamma_out, const float *beta_out, int B, int S,
+        void *ctx, void *n_out, float *rstd, void *x_out, void *z_out, float *mean, void *qkv_out, void *stream);
+int mivit_attn_out_bwd_rows_f16(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+        const void *Wo, int M, int S, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1, float *dbeta1,
+        void *workspace, size_t workspace_bytes, void *stream);
+int mivit_attn_block_fwd_q1_w64_f16(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv,
+        const float *bqkv, const void *Wo, const float *bo, const float *gamma_out, const float *beta_out, int B, int S,
+        void *ctx, void *n_out, float *rstd, void *x_out, void *z_out, float *mean, void *qkv_out, void *stream);
+int mivit_attn_out_bwd_rows_w64_f16(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+        const void *Wo, int M, int S, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1, float *dbeta1,
+        void *workspace, size_t workspace_bytes, void *stream);
+
 /* DeepResNetEmbedding in inference mode (helpers/models.py:230-257; ResidualBlock :202-228): conv3x3(1->32)+BN+ReLU,
  * ResidualBlock(32->64), ResidualBlock(64->128), global average pool, Linear(128->E), fused in one kernel that keeps F
  * whole frames in LDS.  Eval-mode BatchNorm is folded by the caller: conv weights are pre-scaled by
@@ -726,6 +763,10 @@ int mivit_attention_bwd(int dtype, const void *qkv, const void *dctx, int B, int
  * kernel); an error elsewhere and under MIVIT_ATTN_BWD=1. */
 int mivit_attention_bwd_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S,
                              int H, int Dh, void *dqkv, void *stream);
+/* The same reading less: of q only the first q_rows rows of a sequence are read (every other query row has dS = 0 whatever its
+ * scores are: zeros stand in for it).  dqkv is bitwise that of mivit_attention_bwd_rows. */
+int mivit_attention_bwd_rows_lean(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S,
+                                  int H, int Dh, void *dqkv, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Model level: GeneralTransformer.forward / its autograd (models.py:278-361, :111-141, :81-108).
@@ -794,7 +835,10 @@ void mivit_graph_stats(uint64_t *replays, uint64_t *captures, int *failures);
 /* Readout-row pruning of the last encoder layer (fused 16-bit layers with the regression-token readout, more than one token):
  * the head reads B of its B * S output rows.
  *   1 (default): the last feed-forward block's forward runs on those B rows and the attention core's backward on the one query
- *      row per sequence that carries a gradient.  Every result is what it was: no sum changes its terms or their order.
+ *      row per sequence that carries a gradient; the last attention block computes its query side for the first row tile only,
+ *      and its LayerNorm-1 / out-projection and attention-core backward do not read the rows in which d(x1) is an exact zero
+ *      or whose q only ever multiplies one.  Every result is what it was: no sum changes its terms or their order.
+ *   3: mode 1 without the second sentence (the launches mode 1 made before the readout query; A/B runs and tests).
  *   2 (MIVIT_READOUT_ROWS=2): the feed-forward block's and LayerNorm-1 / out-projection's backward run on B rows too.  Same out
  *      and loss; the last layer's fc1 / fc2 / norm2 / out_proj / norm1 gradients sum the same fp32 terms in another order, which
  *      a training run amplifies like any other rounding difference.

@@ -103,6 +103,8 @@ SYMBOLS = {
     "mivit_attention_fwd": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_attention_bwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_attention_bwd_rows": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mivit_attention_bwd_rows_lean": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_void_p]),
     "mivit_set_readout_rows": (c_int, [c_int]),
     "mivit_plan_create": (c_void_p, [POINTER(MivitConfig)]),
     "mivit_plan_destroy": (None, [c_void_p]),
@@ -177,13 +179,18 @@ SYMBOLS = {
     "mivit_qkv_bwd_affine": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "mivit_qkv_bwd_affine_w64": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "mivit_mlp_block_bwd_set_waves_f16": (c_int, [c_int]),
+    "mivit_attn_block_fwd_q1": (c_int, [c_void_p] * 9 + [c_int, c_int] + [c_void_p] * 8),
+    "mivit_attn_out_bwd_rows": (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "mivit_profile_enable": (c_int, [ctypes.c_uint64]),
     "mivit_profile_collect": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(c_int)]),
     "mivit_profile_tag_name": (c_char_p, [c_int]),
 }
 # the fp16 builds of the fused blocks export the same operator set as the bf16 width-128 build, suffixed _f16 / _w64_f16
+for _name in ("mivit_attn_block_fwd_q1", "mivit_attn_out_bwd_rows"):
+    SYMBOLS[_name + "_w64"] = SYMBOLS[_name]
 for _sfx in ("_f16", "_w64_f16"):
-    for _name in ("mivit_fused_layer_supported", "mivit_attn_block_fwd", "mivit_mlp_block_fwd", "mivit_mlp_block_bwd_workspace_bytes",
+    for _name in ("mivit_attn_block_fwd_q1", "mivit_attn_out_bwd_rows",
+                  "mivit_fused_layer_supported", "mivit_attn_block_fwd", "mivit_mlp_block_fwd", "mivit_mlp_block_bwd_workspace_bytes",
                   "mivit_mlp_block_bwd", "mivit_attn_out_bwd_workspace_bytes", "mivit_attn_out_bwd", "mivit_qkv_bwd_workspace_bytes",
                   "mivit_qkv_bwd", "mivit_qkv_bwd_affine"):
         SYMBOLS[_name + _sfx] = SYMBOLS[_name]

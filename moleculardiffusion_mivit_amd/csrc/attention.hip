@@ -455,12 +455,12 @@ int launch_attention_bwd(int dtype, const void *qkv, const void *dctx, int B, in
 bool attention_bwd_rows_ok(int dtype, int S, int Dh) {
     return attention_bwd_rows_supported(dtype, S, Dh) || attention_bwd_rows_supported_f16(dtype, S, Dh);
 }
-int launch_attention_bwd_q_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H,
-                                int Dh, void *dqkv, hipStream_t s) {
+int launch_attention_bwd_q_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, bool q_lean, int B,
+                                int S, int H, int Dh, void *dqkv, hipStream_t s) {
     MIVIT_CHECK(B > 0 && S > 0 && H > 0 && Dh > 0, "attention_bwd_rows: empty problem");
-    if (attention_bwd_rows_supported(dtype, S, Dh)) return launch_attention_bwd_rows(qkv, dctx, dctx_seq_stride, q_rows, B, S, H, Dh, dqkv, s);
+    if (attention_bwd_rows_supported(dtype, S, Dh)) return launch_attention_bwd_rows(qkv, dctx, dctx_seq_stride, q_rows, q_lean, B, S, H, Dh, dqkv, s);
     if (attention_bwd_rows_supported_f16(dtype, S, Dh))
-        return launch_attention_bwd_rows_f16(qkv, dctx, dctx_seq_stride, q_rows, B, S, H, Dh, dqkv, s);
+        return launch_attention_bwd_rows_f16(qkv, dctx, dctx_seq_stride, q_rows, q_lean, B, S, H, Dh, dqkv, s);
     MIVIT_FAIL("attention_bwd_rows: no kernel for dtype %d, S = %d, head dim %d (16-bit, S <= 128, head dim 16 / 32 / 64, MIVIT_ATTN_BWD unset or 2)",
                dtype, S, Dh);
 }
@@ -481,5 +481,12 @@ extern "C" int mivit_attention_bwd_rows(int dtype, const void *qkv, const void *
                                         int H, int Dh, void *dqkv, void *stream) {
     MIVIT_CHECK(dtype == MIVIT_F32 || dtype == MIVIT_BF16 || dtype == MIVIT_F16, "bad dtype %d", dtype);
     MIVIT_CHECK(qkv && dctx && dqkv, "attention_bwd_rows: null pointer");
-    return launch_attention_bwd_q_rows(dtype, qkv, dctx, dctx_seq_stride, q_rows, B, S, H, Dh, dqkv, static_cast<hipStream_t>(stream));
+    return launch_attention_bwd_q_rows(dtype, qkv, dctx, dctx_seq_stride, q_rows, false, B, S, H, Dh, dqkv, static_cast<hipStream_t>(stream));
+}
+extern "C" int mivit_attention_bwd_rows_lean(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows,
+                                             int B, int S, int H, int Dh, void *dqkv, void *stream) {
+    MIVIT_CHECK(dtype == MIVIT_F32 || dtype == MIVIT_BF16 || dtype == MIVIT_F16, "bad dtype %d", dtype);
+    MIVIT_CHECK(qkv && dctx && dqkv, "attention_bwd_rows_lean: null pointer");
+    return launch_attention_bwd_q_rows(dtype, qkv, dctx, dctx_seq_stride, q_rows, true, B, S, H, Dh, dqkv,
+                                       static_cast<hipStream_t>(stream));
 }

@@ -105,6 +105,9 @@ struct FastDims {
     // the rows behind them are zero by contract and never read (0: the full problem)
     int q_rows;
     int64_t do_stride;
+    // ... and, ROWS = true only: stage the first q_rows q rows and zeros for the rest of the image (every other query row has
+    // dO = 0, hence dP = 0 and dS = P (dP - delta) = 0 whatever its scores are: its q only ever multiplies an exact zero)
+    int q_lean;
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -414,6 +417,7 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
     // row tiles behind the last query row that carries a gradient have dS = 0: they add nothing to dK / dV and their dQ is 0,
     // stored here, 16 bytes per lane, while no accumulator is live (no trip when q_rows reaches the last tile)
     const int nit = ROWS ? min(NT, (q_rows + 15) >> 4) : NT;
+    const int q_stage = ROWS && d.q_lean ? q_rows : d.S;          // q rows that reach the image
     if (ROWS) {
         bf16 *dq0 = dqkv + ((int64_t)b * d.S + nit * 16) * ld3 + h * d.Dh;
         for (int u = lane; u < (d.S - nit * 16) * (ND * 2); u += 64)
@@ -442,7 +446,7 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
                 if (u < NCH) *reinterpret_cast<uint4 *>(img + r * d.ld + (SWZ ? (dd ^ (((r >> 2) & 1) << 4)) : dd)) = v[i];
             }
         };
-        ld_nat(q, ld3, d.S, sq); ld_nat(k, ld3, d.S, sk); ld_nat(dO, d.E, q_rows, so);
+        ld_nat(q, ld3, q_stage, sq); ld_nat(k, ld3, d.S, sk); ld_nat(dO, d.E, q_rows, so);
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -452,7 +456,7 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
             }
         st_nat(Qimg, sq); st_nat(Kimg, sk); st_nat(Oimg, so);
     } else {
-        stage_nat<SWZ>(Qimg, d.ld, q, ld3, d.S, NT * 16, d.Dh, lane);
+        stage_nat<SWZ>(Qimg, d.ld, q, ld3, q_stage, NT * 16, d.Dh, lane);
         stage_nat<SWZ>(Kimg, d.ld, k, ld3, d.S, NT * 16, d.Dh, lane);
         stage_nat<SWZ>(Oimg, d.ld, dO, d.E, q_rows, NT * 16, d.Dh, lane);
 #pragma unroll
@@ -491,7 +495,7 @@ __global__ __launch_bounds__(256, (NT * ND <= 6 ? 3 : 1)) void attn_bwd_fast2(co
         for (int kd = 0; kd < KD; ++kd) {
             if (SWZ) { qf[kd] = lfrag(Qimg, it * 16); of[kd] = lfrag(Oimg, it * 16); }
             else {
-                qf[kd] = gfrag(q, ld3, it * 16, d.S, kd * 32, d.Dh, lane);
+                qf[kd] = gfrag(q, ld3, it * 16, q_stage, kd * 32, d.Dh, lane);
                 of[kd] = gfrag(dO, d.E, it * 16, q_rows, kd * 32, d.Dh, lane);
             }
         }
@@ -593,7 +597,7 @@ FastDims make_fast(int B, int S, int H, int Dh) {
     const int NT = (S + 15) / 16, NP = (NT + 1) / 2;
     d.ld = Dh + 8;
     d.img = NP * 32 * d.ld;
-    d.q_rows = 0; d.do_stride = 0;
+    d.q_rows = 0; d.do_stride = 0; d.q_lean = 0;
     return d;
 }
 
@@ -701,12 +705,13 @@ int launch_attention_bwd_fast(const void *qkv, const void *dctx, int B, int S, i
 // The same backward for a dctx of which only the first q_rows query rows of every sequence exist (q_rows x E elements,
 // dctx_seq_stride elements apart); the other rows are zero by contract.  Only the 16-deep kernel knows the row count.
 bool attention_bwd_rows_supported(int dtype, int S, int Dh) { return attention_fast_supported(dtype, S, Dh) && bwd_version() == 2; }
-int launch_attention_bwd_rows(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H, int Dh,
-                              void *dqkv, hipStream_t s) {
+// q_lean: FastDims::q_lean (false: every q row staged)
+int launch_attention_bwd_rows(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, bool q_lean, int B, int S, int H,
+                              int Dh, void *dqkv, hipStream_t s) {
     MIVIT_CHECK(q_rows >= 1 && q_rows <= S && dctx_seq_stride >= (int64_t)q_rows * H * Dh && dctx_seq_stride % 8 == 0,
                 "attention_bwd_rows: %d rows of %d at stride %lld", q_rows, S, (long long)dctx_seq_stride);
     FastDims d = make_fast(B, S, H, Dh);
-    d.q_rows = q_rows; d.do_stride = dctx_seq_stride;
+    d.q_rows = q_rows; d.do_stride = dctx_seq_stride; d.q_lean = q_lean ? 1 : 0;
     const int NT = (S + 15) / 16, ND = Dh / 16;
     FAST_DISPATCH(bwd_launch, static_cast<const bf16 *>(qkv), static_cast<const bf16 *>(dctx), static_cast<bf16 *>(dqkv), d, s)
 }

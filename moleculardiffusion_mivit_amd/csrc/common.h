@@ -303,8 +303,8 @@ int launch_attention_bwd(int dtype, const void *qkv, const void *dctx, int B, in
 // the same for a dctx that holds the first q_rows query rows of every sequence, dctx_seq_stride elements apart (the other rows are
 // zero by contract and never read); ..._ok: a kernel exists, otherwise the launch is an error
 bool attention_bwd_rows_ok(int dtype, int S, int Dh);
-int launch_attention_bwd_q_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H,
-                                int Dh, void *dqkv, hipStream_t s);
+int launch_attention_bwd_q_rows(int dtype, const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, bool q_lean, int B,
+                                int S, int H, int Dh, void *dqkv, hipStream_t s);
 int attention_max_seq(int dtype, int Dh);
 // bf16 short-sequence fast path (attention_fast.hip)
 bool attention_fast_supported(int dtype, int S, int Dh);
@@ -312,8 +312,8 @@ int launch_attention_fwd_fast(const void *qkv, int B, int S, int H, int Dh, void
 int launch_attention_bwd_fast(const void *qkv, const void *dctx, int B, int S, int H, int Dh, void *dqkv, hipStream_t s);
 // ... for a dctx whose sequences hold their first q_rows query rows only (the rest is zero by contract and never read)
 bool attention_bwd_rows_supported(int dtype, int S, int Dh);
-int launch_attention_bwd_rows(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H, int Dh,
-                              void *dqkv, hipStream_t s);
+int launch_attention_bwd_rows(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, bool q_lean, int B, int S, int H,
+                              int Dh, void *dqkv, hipStream_t s);
 
 // LDS-DMA streaming kernels of the frame embedding, bf16 mode (embed.hip)
 bool embed_dma_supported(int dtype, int M, int K, int E);
@@ -377,8 +377,8 @@ bool attention_fast_supported_f16(int dtype, int S, int Dh);
 int launch_attention_fwd_fast_f16(const void *qkv, int B, int S, int H, int Dh, void *ctx, hipStream_t s);
 int launch_attention_bwd_fast_f16(const void *qkv, const void *dctx, int B, int S, int H, int Dh, void *dqkv, hipStream_t s);
 bool attention_bwd_rows_supported_f16(int dtype, int S, int Dh);
-int launch_attention_bwd_rows_f16(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, int B, int S, int H, int Dh,
-                                  void *dqkv, hipStream_t s);
+int launch_attention_bwd_rows_f16(const void *qkv, const void *dctx, int64_t dctx_seq_stride, int q_rows, bool q_lean, int B, int S,
+                                  int H, int Dh, void *dqkv, hipStream_t s);
 bool embed_dma_supported_f16(int dtype, int M, int K, int E);
 int launch_embed_fwd_dma_f16(const float *X, const void *W_bf16, const float *bias, void *Y, int M, int K, int E, hipStream_t s);
 size_t embed_wgrad_dma_ws_bytes_f16(int M, int K, int E);

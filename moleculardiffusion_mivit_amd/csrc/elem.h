@@ -110,4 +110,6 @@ __device__ __forceinline__ float elem_hi(uint32_t w) { return __uint_as_float(w 
 #define mivit_qkv_bwd_workspace_bytes MIVIT_FUSED_NAME(mivit_qkv_bwd_workspace_bytes)
 #define mivit_qkv_bwd MIVIT_FUSED_NAME(mivit_qkv_bwd)
 #define mivit_qkv_bwd_affine MIVIT_FUSED_NAME(mivit_qkv_bwd_affine)
+#define mivit_attn_block_fwd_q1 MIVIT_FUSED_NAME(mivit_attn_block_fwd_q1)
+#define mivit_attn_out_bwd_rows MIVIT_FUSED_NAME(mivit_attn_out_bwd_rows)
 #endif

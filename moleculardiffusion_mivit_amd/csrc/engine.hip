@@ -17,7 +17,8 @@
     bool fused_layer_supported##SFX(int dtype, int E, int F, int H, int S);                                                        \
     int launch_attn_block_fwd##SFX(const void *nin, const float *gin, const float *bin, const void *Wqkv, const float *bqkv,       \
                                    const void *Wo, const float *bo, const float *gout, const float *bout, int B, int S, void *ctx, \
-                                   void *nout, float *rstd, void *xout, void *zout, float *mean, void *qkvout, hipStream_t s);     \
+                                   void *nout, float *rstd, void *xout, void *zout, float *mean, void *qkvout, bool q1,            \
+                                   hipStream_t s);                                                                                 \
     int launch_mlp_block_fwd##SFX(const void *nin, const float *gin, const float *bin, const void *W1, const float *b1,            \
                                   const void *W2, const float *b2, const float *gout, const float *bout, int M, int act,           \
                                   void *nout, float *rstd, void *xout, void *zout, float *mean, void *hout, void *uout,            \
@@ -25,8 +26,8 @@
     size_t mlp_block_bwd_ws_bytes##SFX(int M);                                                                                     \
     size_t attn_out_bwd_ws_bytes##SFX(int M);                                                                                      \
     int launch_attn_out_bwd##SFX(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,         \
-                                 const void *Wo, int M, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1,             \
-                                 float *dbeta1, void *ws, size_t ws_bytes, hipStream_t s);                                         \
+                                 const void *Wo, int M, int live_S, void *dz1, void *dctx, float *dWo, float *dbo,                 \
+                                 float *dgamma1, float *dbeta1, void *ws, size_t ws_bytes, hipStream_t s);                         \
     int launch_mlp_block_bwd##SFX(const void *dy, const void *n2, const float *rstd2, const float *gamma2, const void *n1,         \
                                   const float *gamma1, const float *beta1, const void *W1, const float *b1, const void *W2, int M, \
                                   int act, void *dx1, float *dW1, float *db1, float *dW2, float *db2, float *dgamma2,              \
@@ -67,12 +68,29 @@ static const FusedOps *fused_ops(int dtype, int E) {
 }
 // Readout-row pruning: under the regression-token readout the head reads B rows of the last layer's output.
 //   1 (default)  what leaves every result as it was: the last feed-forward block's forward on those B rows, the attention core's
-//                backward on the one query row per sequence that carries a gradient; every weight-gradient sum as before
+//                backward on the one query row per sequence that carries a gradient; every weight-gradient sum as before.  And
+//                the readout QUERY: the last attention block's query side for row tile 0 only, its LayerNorm-1 / out-projection
+//                and attention-core backward reading the readout rows only where every other row is an exact zero (rq_parts)
+//   3            mode 1 without the readout-query part: the launches mode 1 made before it (A/B measurements, tests)
 //   2            also the feed-forward block's and LayerNorm-1 / out-projection's backward on B rows: the last layer's fc1 /
 //                fc2 / norm2 / out_proj / norm1 gradients then sum the same fp32 terms in another order (MIVIT_READOUT_ROWS=2)
 //   0            every row (MIVIT_NO_READOUT_ROWS, mivit_set_readout_rows(0): A/B measurements, parity tests)
 static int g_readout_rows = getenv("MIVIT_NO_READOUT_ROWS") ? 0 : (getenv("MIVIT_READOUT_ROWS") ? atoi(getenv("MIVIT_READOUT_ROWS")) : 1);
 extern "C" int mivit_set_readout_rows(int on) { const int old = g_readout_rows; g_readout_rows = on; return old; }
+// The parts of mode 1's readout query, MIVIT_READOUT_QUERY_PARTS = their bit mask (read once; A/B measurements of single parts):
+//   1  attn_block_fwd: query side for row tile 0 only (fused_fwd.hip, Q1).  It leaves q, ctx and rstd1 behind tile 0 unwritten,
+//      so with it attn_bwd_fast2 reads of q only the rows that carry a gradient (q_lean), and it needs part 2
+//   2  attn_out_bwd: d(x1) / n1 / rstd1 / ctx read and d(ctx) written in the readout rows only
+// The q|k|v backward is unchanged and reads every row: d(z1) and dq keep their zero rows.
+static int rq_parts() {
+    static const int parts = [] {
+        const char *e = getenv("MIVIT_READOUT_QUERY_PARTS");
+        int m = e ? atoi(e) & 3 : 3;
+        if (!(m & 2)) m &= ~1;
+        return m;
+    }();
+    return parts;
+}
 
 static bool fused_ok(int dtype, int E, int F, int H, int S) {
     const FusedOps *f = fused_ops(dtype, E);
@@ -522,6 +540,7 @@ struct Call {
     const FusedOps *fo;           // ... of this table (null: per-operator layers)
     const bool rows;              // ... and the last layer's row-wise blocks on the B regression-token rows only (mode 2)
     const bool rows_exact;        // ... or only what leaves every sum as it was (mode 1)
+    const int rq;                 // ... with these parts of the readout query (rq_parts; 0 in mode 3)
     const Ws w;
     void *ws; const float *P; float *G; hipStream_t s;      // workspace base, parameter arena, gradient arena (null in a forward)
     Call(const mivit_plan *p, int B_, int T_, bool bwd_, void *workspace, const float *params, float *grads, void *stream)
@@ -529,7 +548,8 @@ struct Call {
           B(B_), T(T_), off(cfg.use_regression_token ? 1 : 0), S(T + off), M(B * S), Mt(B * T), f32(dt == MIVIT_F32), bwd(bwd_),
           fused(L > 0 && fused_ok(dt, E, F, H, S)), fo(fused ? fused_ops(dt, E) : nullptr),
           rows(fused && cfg.use_regression_token && S > 1 && g_readout_rows == 2),
-          rows_exact(fused && cfg.use_regression_token && S > 1 && g_readout_rows != 0 && g_readout_rows != 2), w(make_ws(p, B, T, bwd)),
+          rows_exact(fused && cfg.use_regression_token && S > 1 && g_readout_rows != 0 && g_readout_rows != 2),
+          rq(rows_exact && g_readout_rows != 3 && attention_bwd_rows_ok(dt, S, Dh) ? rq_parts() : 0), w(make_ws(p, B, T, bwd)),
           ws(workspace), P(params), G(grads), s(static_cast<hipStream_t>(stream)) {}
     void *buf(size_t o) const { return at(ws, o); }                                   // workspace region at a Ws offset
     float *fbuf(size_t o) const { return static_cast<float *>(at(ws, o)); }
@@ -583,7 +603,8 @@ int layers_fwd_fused(const Call &c) {
         const LayerParams &lp = c.plan->layers[l]; const Ws::L &b = c.w.layer[l];
         prof_set_tag(MIVIT_PROF_ATTN_BLOCK_FWD);
         RC(c.fo->attn_fwd(nin, gin, bin, c.W(lp.qkv_w), c.p(lp.qkv_b), c.W(lp.out_w), c.p(lp.out_b), c.p(lp.n1_w), c.p(lp.n1_b), c.B, c.S,
-                          c.buf(b.ctx), c.buf(b.z1), c.fbuf(b.rstd1), nullptr, nullptr, nullptr, c.bwd ? c.buf(b.qkv) : nullptr, c.s));
+                          c.buf(b.ctx), c.buf(b.z1), c.fbuf(b.rstd1), nullptr, nullptr, nullptr, c.bwd ? c.buf(b.qkv) : nullptr,
+                          (c.rq & 1) && l + 1 == c.L, c.s));
         if (c.rows_exact && l + 1 == c.L) {
             // mode 1: the same B-row launch; its outputs go to rows b * S of the full regions, where the final norm and the
             // unchanged backward look for them.  The backward reads every row of z2 / rstd2: the rows nobody computed are
@@ -758,16 +779,20 @@ int layer_bwd_fused(const Call &c, int l) {
     void *dx1 = c.buf(w.dxb), *dz1 = c.buf(w.dF);      // where d(x1) arrives / where LayerNorm-1's backward puts d(z1)
     const FusedBwdWs r = fused_bwd_ws(c, !no_defer);
     SlabDefer slabs(r.defer);
+    // readout query (mode 1, last layer): d(x1), d(z1), d(ctx) and dq are exact zeros outside row 0 of every sequence -- the
+    // kernels below neither read nor write those zeros
+    const int rq = l + 1 == c.L ? c.rq : 0;
     prof_set_tag(MIVIT_PROF_MLP_BLOCK_BWD);          // feed-forward block: d(x2) -> d(x1), all six parameter gradients
     RC(c.fo->mlp_bwd(c.buf(w.dxa), c.buf(b.z2), c.fbuf(b.rstd2), c.p(lp.n2_w), c.buf(b.z1), c.p(lp.n1_w), c.p(lp.n1_b), c.W(lp.fc1_w),
                      c.p(lp.fc1_b), c.W(lp.fc2_w), M, c.cfg.activation, dx1, c.g(lp.fc1_w), c.g(lp.fc1_b), c.g(lp.fc2_w), c.g(lp.fc2_b),
                      c.g(lp.n2_w), c.g(lp.n2_b), r.mlp.ptr, r.mlp.bytes, c.s));
     prof_set_tag(MIVIT_PROF_ATTN_OUT_BWD);           // LayerNorm-1 backward + out-projection weight / data gradient
-    RC(c.fo->attn_out_bwd(dx1, c.buf(b.z1), c.fbuf(b.rstd1), c.p(lp.n1_w), c.buf(b.ctx), c.W(lp.out_w), M, dz1, c.buf(w.dctx),
-                          c.g(lp.out_w), c.g(lp.out_b), c.g(lp.n1_w), c.g(lp.n1_b), r.attn_out.ptr, r.attn_out.bytes, c.s));
+    RC(c.fo->attn_out_bwd(dx1, c.buf(b.z1), c.fbuf(b.rstd1), c.p(lp.n1_w), c.buf(b.ctx), c.W(lp.out_w), M, (rq & 2) ? c.S : 0, dz1,
+                          c.buf(w.dctx), c.g(lp.out_w), c.g(lp.out_b), c.g(lp.n1_w), c.g(lp.n1_b), r.attn_out.ptr, r.attn_out.bytes, c.s));
     prof_set_tag(MIVIT_PROF_ATTN_CORE_BWD);
     if (c.rows_exact && l + 1 == c.L && attention_bwd_rows_ok(dt, c.S, c.Dh))       // d(ctx) is zero behind row 0 of every sequence
-        RC(launch_attention_bwd_q_rows(dt, c.buf(b.qkv), c.buf(w.dctx), (int64_t)c.S * E, 1, c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+        RC(launch_attention_bwd_q_rows(dt, c.buf(b.qkv), c.buf(w.dctx), (int64_t)c.S * E, 1, (rq & 1) != 0, c.B, c.S,
+                                       c.H, c.Dh, c.buf(w.dqkv), c.s));
     else
         RC(launch_attention_bwd(dt, c.buf(b.qkv), c.buf(w.dctx), c.B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
     if (!qkv_split) {
@@ -806,11 +831,11 @@ int last_layer_bwd_rows(const Call &c) {
                      c.p(lp.fc1_b), c.W(lp.fc2_w), B, c.cfg.activation, dx1, c.g(lp.fc1_w), c.g(lp.fc1_b), c.g(lp.fc2_w), c.g(lp.fc2_b),
                      c.g(lp.n2_w), c.g(lp.n2_b), r.mlp.ptr, r.mlp.bytes, c.s));
     prof_set_tag(MIVIT_PROF_ATTN_OUT_BWD);
-    RC(c.fo->attn_out_bwd(dx1, c.buf(w.z1c), c.fbuf(w.rstd1c), c.p(lp.n1_w), c.buf(w.ctxc), c.W(lp.out_w), B, c.buf(w.dz1c), c.buf(w.dctxc),
+    RC(c.fo->attn_out_bwd(dx1, c.buf(w.z1c), c.fbuf(w.rstd1c), c.p(lp.n1_w), c.buf(w.ctxc), c.W(lp.out_w), B, 0, c.buf(w.dz1c), c.buf(w.dctxc),
                           c.g(lp.out_w), c.g(lp.out_b), c.g(lp.n1_w), c.g(lp.n1_b), r.attn_out.ptr, r.attn_out.bytes, c.s));
     if (attention_bwd_rows_ok(dt, c.S, c.Dh)) {
         prof_set_tag(MIVIT_PROF_ATTN_CORE_BWD);
-        RC(launch_attention_bwd_q_rows(dt, c.buf(b.qkv), c.buf(w.dctxc), E, 1, B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
+        RC(launch_attention_bwd_q_rows(dt, c.buf(b.qkv), c.buf(w.dctxc), E, 1, false, B, c.S, c.H, c.Dh, c.buf(w.dqkv), c.s));
     } else {          // (MIVIT_ATTN_BWD=1: the first attention kernel reads every row of d(ctx))
         RC(launch_fill_zero(c.buf(w.dctx), (size_t)M * E * dtype_size(dt), c.s));
         RC(launch_convert(0, c.buf(w.dctxc), E, 0, c.buf(w.dctx), SE, B, E, 0, c.s, dt));

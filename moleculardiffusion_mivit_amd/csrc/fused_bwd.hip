@@ -766,8 +766,22 @@ struct AttnOutBwdArgs {
     int M;
     bf16 *dz1, *dctx;
     float *slabs;
+    int S;          // ROWS: rows r with r % S == 0 are live (the readout row of every S-token sequence)
 };
 
+// Readout-row launches: row r carries a gradient when r % S == 0.  No division in the tile loop: a thread's rows sit at fixed
+// places of a tile, so (place % S) is taken once, the tile's (first row % S) is carried from tile to tile, and the sum of the two
+// residues, x in [0, 2 S - 2], is a multiple of S exactly when it is 0 or S.
+__device__ __forceinline__ bool live_at(int x, int S) { return x == 0 || x == S; }
+__device__ __forceinline__ int rem_add(int rem, int step, int S) { const int r = rem + step; return r >= S ? r - S : r; }
+
+// ROWS: dy is an exact zero outside the live rows (r % S == 0), and with it dz1 and dctx: the pieces of the other rows are
+// not requested (their thread-private slots read as zero, n1 and rstd1 included) and their dctx rows are not stored (the attention
+// core reads the live rows only); dz1 is stored in every row, zeros in the dead ones: qkv_bwd reads them all.  The
+// LDS images, every MFMA and the column sums run as in the full kernel -- a dead row adds the exact zeros it always added.
+// A wave whose rows are all dead skips its requests and stores, so the queue is no longer the counted one: the tile wait of
+// this mode is vmcnt(0) (what is outstanding there is the handful of live-row stores of the last tile).
+template <bool ROWS>
 __global__ __launch_bounds__(NT, 2) void attn_out_bwd_kernel(const AttnOutBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16 *DZ = reinterpret_cast<bf16 *>(smem + AO_OFF_DZ), *CT = reinterpret_cast<bf16 *>(smem + AO_OFF_CT);
@@ -802,32 +816,44 @@ __global__ __launch_bounds__(NT, 2) void attn_out_bwd_kernel(const AttnOutBwdArg
 
     const int ntiles = (a.M + R - 1) / R;
     int tile = blockIdx.x;
-    auto prefetch = [&](int t) {
+    // ROWS: residues mod S of this thread's element-wise rows and dctx store rows within a tile, of the tile's first row, and of
+    // the grid's stride in rows
+    int lm[RPT], sm[2], rem = 0, rstep = 0;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) lm[i] = ROWS ? (r0 + RPP * i) % a.S : 0;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) sm[rt] = ROWS ? (16 * rt + cq) % a.S : 0;
+    if (ROWS) { rem = (int)(((int64_t)blockIdx.x * R) % a.S); rstep = (int)(((int64_t)gridDim.x * R) % a.S); }
+    auto prefetch = [&](int t, int trem) {
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
-            const int64_t row = min((int64_t)t * R + r0 + RPP * i, (int64_t)a.M - 1);
+            const int64_t rw = (int64_t)t * R + r0 + RPP * i, row = min(rw, (int64_t)a.M - 1);
             const int64_t o = row * E + 8 * c;
-            dma16_opaque(a.dy + o, stg + (3 * i + 0) * NT + wave * 64);
-            dma16_opaque(a.n1 + o, stg + (3 * i + 1) * NT + wave * 64);
-            dma16_opaque(a.ctx + o, stg + (3 * i + 2) * NT + wave * 64);
-            dma4_opaque(a.rstd1 + row, rst + i * NT + wave * 64);
+            if (!ROWS || (rw < a.M && live_at(trem + lm[i], a.S))) {
+                dma16_opaque(a.dy + o, stg + (3 * i + 0) * NT + wave * 64);
+                dma16_opaque(a.n1 + o, stg + (3 * i + 1) * NT + wave * 64);
+                dma16_opaque(a.ctx + o, stg + (3 * i + 2) * NT + wave * 64);
+                dma4_opaque(a.rstd1 + row, rst + i * NT + wave * 64);
+            }
         }
     };
-    if (tile < ntiles) prefetch(tile);
+    if (tile < ntiles) prefetch(tile, rem);
     bool first = true;
     for (; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = (int64_t)tile * R;
+        const int nrem = ROWS ? rem_add(rem, rstep, a.S) : 0;          // (the clamped re-read of the last round is never consumed)
         // ---- phase 0: LayerNorm backward, dz1 -> HBM + LDS image, ctx -> LDS image ----
         // the staged rows were requested one tile ago; younger than them are only the four dctx row stores of the last
         // phase 1 (every full tile issues them; the one partial tile is the last of the launch): do not wait for their acks
         // (width 64: NROWST = 2 of them)
-        if (first) wait_vm<0>(); else wait_vm<NROWST>();
+        if (first || ROWS) wait_vm<0>(); else wait_vm<NROWST>();
         first = false;
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
             float d[8], nh[8], gdy[8];
-            const bool ok = row0 + r0 + RPP * i < a.M;
-            const uint4 pdy = keep_if(stg[(3 * i + 0) * NT + tid], ok), pn = stg[(3 * i + 1) * NT + tid];
+            const bool ok = row0 + r0 + RPP * i < a.M && (!ROWS || live_at(rem + lm[i], a.S));
+            const uint4 pdy = keep_if(stg[(3 * i + 0) * NT + tid], ok);
+            const uint4 pn = ROWS ? keep_if(stg[(3 * i + 1) * NT + tid], ok) : stg[(3 * i + 1) * NT + tid];
             const uint4 pct = keep_if(stg[(3 * i + 2) * NT + tid], ok);
             unpack8(pdy, d); unpack8(pn, nh);
             float s1 = 0.f, s2 = 0.f;
@@ -843,11 +869,11 @@ __global__ __launch_bounds__(NT, 2) void attn_out_bwd_kernel(const AttnOutBwdArg
 #pragma unroll
             for (int e = 0; e < 8; ++e) { dz[e] = prs * (gdy[e] - s1 - nh[e] * s2); sz[e] += dz[e]; }
             store16(DZ + (r0 + RPP * i) * LDE + 8 * c, dz);
-            if (ok) store16(a.dz1 + (row0 + r0 + RPP * i) * E + 8 * c, dz);
+            if (ROWS ? row0 + r0 + RPP * i < a.M : ok) store16(a.dz1 + (row0 + r0 + RPP * i) * E + 8 * c, dz);
             *reinterpret_cast<uint4 *>(CT + (r0 + RPP * i) * LDE + 8 * c) = pct;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        prefetch(min(tile + (int)gridDim.x, ntiles - 1));
+        prefetch(min(tile + (int)gridDim.x, ntiles - 1), nrem);
         barrier();          // raw s_barrier (LDS drained): __syncthreads() also waits vmcnt(0), i.e. for the row prefetch just issued and for store acks
         // ---- phase 1: dctx^T for this wave's 32 context features; dWo rows 32 wave .. +31 ----
         f32x4 dc[KT2][2];
@@ -862,7 +888,7 @@ __global__ __launch_bounds__(NT, 2) void attn_out_bwd_kernel(const AttnOutBwdArg
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
             const int64_t row = row0 + 16 * rt + cq;
-            if (row < a.M) {
+            if (row < a.M && (!ROWS || live_at(rem + sm[rt], a.S))) {
 #pragma unroll
                 for (int ct = 0; ct < KT2; ++ct) {
                     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -881,6 +907,7 @@ __global__ __launch_bounds__(NT, 2) void attn_out_bwd_kernel(const AttnOutBwdArg
                 dWo[et][ct] = mma(za, cb, dWo[et][ct]);                 // [e][c] += dz1^T ctx
             }
         }
+        rem = nrem;
         barrier();          // raw s_barrier (LDS drained): __syncthreads() also waits vmcnt(0), i.e. for the row prefetch just issued and for store acks
     }
     // ---- partial gradients -> this workgroup's slab ----
@@ -1207,21 +1234,26 @@ extern "C" int mivit_mlp_block_bwd(const void *dy, const void *n2, const float *
 size_t attn_out_bwd_ws_bytes(int M) { return align_up((size_t)std::min(512, ceil_div(std::max(M, 1), R)) * AO_SL_TOTAL * sizeof(float), 256); }
 
 // dz1, dctx [M,E] bf16; dWo [E,E], dbo, dgamma1, dbeta1 [E] fp32 (overwritten)
+// live_S > 0: the readout-row mode of the kernel -- only the rows r % live_S == 0 of dy are non-zero (by contract), only those
+// rows of dy / n1 / rstd1 / ctx are read and only those rows of dctx written (dz1: every row, zeros in the others); the parameter
+// gradients are the full launch's
 int launch_attn_out_bwd(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx, const void *Wo, int M,
-                        void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1, float *dbeta1, void *ws, size_t ws_bytes,
-                        hipStream_t s) {
+                        int live_S, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1, float *dbeta1, void *ws,
+                        size_t ws_bytes, hipStream_t s) {
     MIVIT_CHECK(dy && n1 && rstd1 && gamma1 && ctx && Wo && dz1 && dctx && dWo && dbo && dgamma1 && dbeta1 && ws && M > 0,
                 "attn_out_bwd: null pointer / empty problem");
     MIVIT_CHECK(aligned16(dy) && aligned16(n1) && aligned16(ctx) && aligned16(Wo) && aligned16(dz1) && aligned16(dctx),
                 "attn_out_bwd: pointers must be 16-byte aligned");
     MIVIT_CHECK(ws_bytes >= attn_out_bwd_ws_bytes(M), "attn_out_bwd: workspace too small");
+    MIVIT_CHECK(live_S >= 0, "attn_out_bwd: live-row stride %d", live_S);
     AttnOutBwdArgs a{static_cast<const bf16 *>(dy), static_cast<const bf16 *>(n1), rstd1, gamma1, static_cast<const bf16 *>(ctx),
-                     static_cast<const bf16 *>(Wo), M, static_cast<bf16 *>(dz1), static_cast<bf16 *>(dctx), static_cast<float *>(ws)};
+                     static_cast<const bf16 *>(Wo), M, static_cast<bf16 *>(dz1), static_cast<bf16 *>(dctx), static_cast<float *>(ws), live_S};
     const int grid = std::min(512, ceil_div(M, R));            // two resident workgroups per CU
     {
         ProfScope prof(s);
-        MIVIT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(attn_out_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, AO_LDS));
-        hipLaunchKernelGGL(attn_out_bwd_kernel, dim3(grid), dim3(NT), AO_LDS, s, a);
+        auto kern = live_S > 0 ? attn_out_bwd_kernel<true> : attn_out_bwd_kernel<false>;
+        MIVIT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, AO_LDS));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), AO_LDS, s, a);
         MIVIT_LAUNCH_CHECK();
     }
     const float *sl = static_cast<const float *>(ws);
@@ -1250,6 +1282,14 @@ extern "C" int mivit_attn_out_bwd(const void *dy, const void *n1, const float *r
                                   const void *Wo_bf16, int M, void *dz1, void *dctx, float *dWo, float *dbo, float *dgamma1,
                                   float *dbeta1, void *workspace, size_t workspace_bytes, void *stream) {
     prof_set_tag(MIVIT_PROF_OP);
-    return launch_attn_out_bwd(dy, n1, rstd1, gamma1, ctx, Wo_bf16, M, dz1, dctx, dWo, dbo, dgamma1, dbeta1, workspace, workspace_bytes,
+    return launch_attn_out_bwd(dy, n1, rstd1, gamma1, ctx, Wo_bf16, M, 0, dz1, dctx, dWo, dbo, dgamma1, dbeta1, workspace, workspace_bytes,
+                               static_cast<hipStream_t>(stream));
+}
+extern "C" int mivit_attn_out_bwd_rows(const void *dy, const void *n1, const float *rstd1, const float *gamma1, const void *ctx,
+                                       const void *Wo_bf16, int M, int S, void *dz1, void *dctx, float *dWo, float *dbo,
+                                       float *dgamma1, float *dbeta1, void *workspace, size_t workspace_bytes, void *stream) {
+    prof_set_tag(MIVIT_PROF_OP);
+    MIVIT_CHECK(S >= 1, "attn_out_bwd_rows: sequence length %d", S);
+    return launch_attn_out_bwd(dy, n1, rstd1, gamma1, ctx, Wo_bf16, M, S, dz1, dctx, dWo, dbo, dgamma1, dbeta1, workspace, workspace_bytes,
                                static_cast<hipStream_t>(stream));
 }

@@ -435,10 +435,16 @@ static_assert(ATT_LDS <= 160 * 1024, "LDS budget");
 
 // NT row tiles per sequence (S <= 16 NT); EXTRAS: the optional q|k|v output is compiled in; NW waves per workgroup
 // (one workgroup per CU: 8 waves share the register file two per SIMD, 4 waves own a whole SIMD's 512 registers each)
-template <int NT, bool EXTRAS, int NW>
+// Q1: the QUERY side for row tile 0 only (the last layer under the regression-token readout: the head reads row 0 of a sequence).
+// k and v are projected and stored for every row; q, scores / softmax / P V, out-projection, residual and LayerNorm run for the
+// first 16 rows -- the same MFMAs on the same operands as in the full kernel, so those rows are bitwise the full kernel's.  Of the
+// rows behind them q, ctx, z and rstd are NOT written, the normalised output is written as ZEROS when the q|k|v store is on (a
+// backward follows, and its feed-forward block reads every row) and not at all otherwise.
+template <int NT, bool EXTRAS, int NW, bool Q1 = false>
 __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NP = (NT + 1) / 2;
+    constexpr int NQ = Q1 ? 1 : NT;                  // query row tiles
     bf16 *Wq = reinterpret_cast<bf16 *>(smem);
     bf16 *Wo = reinterpret_cast<bf16 *>(smem + ATT_LDS_WQKV);
     float *vec = reinterpret_cast<float *>(smem + ATT_LDS_WQKV + ATT_LDS_WO);
@@ -522,6 +528,7 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
                 // (head dim 16: the upper half of the 32-deep contraction is zero on both operands)
     #pragma unroll
                 for (int which = 0; which < 2; ++which) {
+                    const int nrt = Q1 && which == 0 ? 1 : NT;             // (constant once `which` is unrolled)
                     request_w(cur ^ 1, (which + 1) * E + h * DH);          // the next block: k after q, v after k
                     __builtin_amdgcn_sched_barrier(0);
                     f32x4 pa[DT][NT];
@@ -530,16 +537,19 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
     #pragma unroll
                         for (int dt = 0; dt < DT; ++dt)
     #pragma unroll
-                            for (int rt = 0; rt < NT; ++rt) pa[dt][rt] = mma(wb[cur][ks][dt], xf[rt][ks], ks == 0 ? zero : pa[dt][rt]);
+                            for (int rt = 0; rt < NT; ++rt)
+                                if (rt < nrt) pa[dt][rt] = mma(wb[cur][ks][dt], xf[rt][ks], ks == 0 ? zero : pa[dt][rt]);
                     cur ^= 1;
     #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) {
                         const f32x4 bb = ld4(bqkv + which * E + h * DH + 16 * dt + 4 * g);
     #pragma unroll
-                        for (int rt = 0; rt < NT; ++rt) pa[dt][rt] += bb;
+                        for (int rt = 0; rt < NT; ++rt)
+                            if (rt < nrt) pa[dt][rt] += bb;
                     }
     #pragma unroll
                     for (int rt = 0; rt < NT; ++rt) {
+                        if (rt >= nrt) continue;
                         if (which == 0) qf[rt] = pack8(pa[0][rt], DT == 2 ? pa[DT - 1][rt] : zero);
                         else kf[rt] = pack8(pa[0][rt], DT == 2 ? pa[DT - 1][rt] : zero);
                         if (EXTRAS) {          // (q leaves unscaled, as the reference's q_proj output)
@@ -595,12 +605,14 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
                 // (head dim 16: the upper half of the 32-deep contraction is zero on both operands)
     #pragma unroll
                 for (int which = 0; which < 2; ++which) {
+                    const int nrt = Q1 && which == 0 ? 1 : NT;             // (constant once `which` is unrolled)
                     f32x4 pa[DT][NT];
     #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) {
                         const f32x4 bb = ld4(bqkv + which * E + h * DH + 16 * dt + 4 * g);
     #pragma unroll
-                        for (int rt = 0; rt < NT; ++rt) pa[dt][rt] = bb;
+                        for (int rt = 0; rt < NT; ++rt)
+                            if (rt < nrt) pa[dt][rt] = bb;
                     }
     #pragma unroll
                     for (int ks = 0; ks < KS; ++ks)
@@ -608,10 +620,12 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
                         for (int dt = 0; dt < DT; ++dt) {
                             const bf16x8 w = lds_frag(Wq + (which * E + h * DH + 16 * dt + cq) * LDE + ks * 32 + 8 * g);
     #pragma unroll
-                            for (int rt = 0; rt < NT; ++rt) pa[dt][rt] = mma(w, xf[rt][ks], pa[dt][rt]);
+                            for (int rt = 0; rt < NT; ++rt)
+                                if (rt < nrt) pa[dt][rt] = mma(w, xf[rt][ks], pa[dt][rt]);
                         }
     #pragma unroll
                     for (int rt = 0; rt < NT; ++rt) {
+                        if (rt >= nrt) continue;
                         if (which == 0) qf[rt] = pack8(pa[0][rt], DT == 2 ? pa[DT - 1][rt] : zero);
                         else kf[rt] = pack8(pa[0][rt], DT == 2 ? pa[DT - 1][rt] : zero);
                         if (EXTRAS) {          // (q leaves unscaled, as the reference's q_proj output)
@@ -669,7 +683,7 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
             __builtin_amdgcn_sched_barrier(0);
             // ---- scores, softmax, P V per query tile ----
 #pragma unroll
-            for (int it = 0; it < NT; ++it) {
+            for (int it = 0; it < NQ; ++it) {
                 f32x4 st[NT];                        // S^T tile (log2 units): lane = query it*16 + cq, registers = keys 16 j + 4 g + r
                 float m = -INFINITY;
 #pragma unroll
@@ -728,7 +742,7 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
 #pragma unroll
             for (int nt = 0; nt < ET; ++nt)
 #pragma unroll
-                for (int rt = 0; rt < NT; ++rt) oa[nt][rt] = bvs[nt] + gvs[nt] * mma((nt & 1) ? id1 : id0, xf[rt][nt >> 1], zero);
+                for (int rt = 0; rt < NQ; ++rt) oa[nt][rt] = bvs[nt] + gvs[nt] * mma((nt & 1) ? id1 : id0, xf[rt][nt >> 1], zero);
 #pragma unroll
             for (int kb = 0; kb < KS; ++kb) {
                 if (kb + 1 < KS) request_wo((kb + 1) & 1, kb + 1);
@@ -736,14 +750,14 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
 #pragma unroll
                 for (int nt = 0; nt < ET; ++nt)
 #pragma unroll
-                    for (int rt = 0; rt < NT; ++rt) oa[nt][rt] = mma(wo[kb & 1][nt], cf[kb][rt], oa[nt][rt]);
+                    for (int rt = 0; rt < NQ; ++rt) oa[nt][rt] = mma(wo[kb & 1][nt], cf[kb][rt], oa[nt][rt]);
             }
         } else {
 #pragma unroll
             for (int nt = 0; nt < ET; ++nt) {
                 const f32x4 bv = ld4(bo + 16 * nt + 4 * g), gv = ld4(gin + 16 * nt + 4 * g);
 #pragma unroll
-                for (int rt = 0; rt < NT; ++rt) oa[nt][rt] = bv + gv * mma((nt & 1) ? id1 : id0, xf[rt][nt >> 1], zero);
+                for (int rt = 0; rt < NQ; ++rt) oa[nt][rt] = bv + gv * mma((nt & 1) ? id1 : id0, xf[rt][nt >> 1], zero);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -752,17 +766,25 @@ __global__ __launch_bounds__(NW * 64) void attn_block_fwd_kernel(const AttnFwdAr
                 for (int nt = 0; nt < ET; ++nt) {
                     const bf16x8 w = lds_frag(Wo + (16 * nt + cq) * LDE + kb * 32 + 8 * g);
 #pragma unroll
-                    for (int rt = 0; rt < NT; ++rt) oa[nt][rt] = mma(w, cf[kb][rt], oa[nt][rt]);
+                    for (int rt = 0; rt < NQ; ++rt) oa[nt][rt] = mma(w, cf[kb][rt], oa[nt][rt]);
                 }
                 __builtin_amdgcn_sched_barrier(0);      // keeps the weight-fragment reads of later heads from piling up
             }
         }
 #pragma unroll
-        for (int rt = 0; rt < NT; ++rt) {
+        for (int rt = 0; rt < NQ; ++rt) {
             f32x4 z[ET];
 #pragma unroll
             for (int nt = 0; nt < ET; ++nt) z[nt] = oa[nt][rt];
             ln_store(z, dst, vo_e[rt], vo_r[rt], gout, bout);
+        }
+        if constexpr (Q1) {
+            if (has_qkv) {          // the backward's feed-forward block reads every row of the normalised output: zeros behind tile 0
+#pragma unroll
+                for (int rt = 1; rt < NT; ++rt)
+#pragma unroll
+                    for (int i = 0; i < KS; ++i) __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{0u, 0u, 0u, 0u}, dst.n, vo_l[rt] + 64 * i, 0, 0);
+            }
         }
     }
 }
@@ -825,7 +847,7 @@ int launch_mlp_block_fwd(const void *nin, const float *gin, const float *bin, co
 
 int launch_attn_block_fwd(const void *nin, const float *gin, const float *bin, const void *Wqkv, const float *bqkv,
                           const void *Wo, const float *bo, const float *gout, const float *bout, int B, int S, void *ctx,
-                          void *nout, float *rstd, void *xout, void *zout, float *mean, void *qkvout, hipStream_t s) {
+                          void *nout, float *rstd, void *xout, void *zout, float *mean, void *qkvout, bool q1, hipStream_t s) {
     MIVIT_CHECK(nin && Wqkv && bqkv && Wo && bo && ctx && nout && rstd && B > 0, "attn_block_fwd: null pointer / empty problem");
     MIVIT_CHECK(S >= 1 && S <= 64, "attn_block_fwd: %d tokens per sequence (supported: 1..64)", S);
     MIVIT_CHECK((gin == nullptr) == (bin == nullptr), "attn_block_fwd: input affine needs both gamma and beta");
@@ -843,12 +865,15 @@ int launch_attn_block_fwd(const void *nin, const float *gin, const float *bin, c
     // waves per workgroup (measured, scripts/bench_fused.py): width 128 -- four (one per SIMD, 242-386 registers) for three and four
     // row tiles and for every training launch (with the q|k|v store, 31 tokens: 245 against 284 us; 16 tokens: 132 against 163),
     // eight for the lean forward of one or two tiles (151 against 169 us); width 64 -- eight throughout
+    // (the one-query-tile variant was measured at both counts too: three tiles with the q|k|v store, four waves 8.156 / 8.122 ms per
+    //  step against eight 8.187 / 8.135 -- the same rule)
     const int nw = nw_env == 8 || nw_env == 4 ? nw_env : (E == 128 && (nt >= 3 || qkvout) ? 4 : 8);
     const int grid = std::min(256, ceil_div(B, nw));
     ProfScope prof(s);
+    // q1: the query side for row tile 0 only (attn_block_fwd_kernel, Q1); one row tile: that is the whole sequence
 #define ATT_LAUNCH3(NT_, EX_, NW_)                                                               \
     do {                                                                                         \
-        auto kern = attn_block_fwd_kernel<NT_, EX_, NW_>;                                        \
+        auto kern = q1 && NT_ > 1 ? attn_block_fwd_kernel<NT_, EX_, NW_, (NT_ > 1)> : attn_block_fwd_kernel<NT_, EX_, NW_, false>; \
         RC(set_lds(kern, ATT_LDS));                                                              \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NW_ * 64), ATT_LDS, s, a);                     \
     } while (0)
@@ -887,5 +912,13 @@ extern "C" int mivit_attn_block_fwd(const void *n_in, const float *gamma_in, con
                                     void *z_out, float *mean, void *qkv_out, void *stream) {
     prof_set_tag(MIVIT_PROF_OP);
     return launch_attn_block_fwd(n_in, gamma_in, beta_in, Wqkv_bf16, bqkv, Wo_bf16, bo, gamma_out, beta_out, B, S, ctx, n_out,
-                                 rstd, x_out, z_out, mean, qkv_out, static_cast<hipStream_t>(stream));
+                                 rstd, x_out, z_out, mean, qkv_out, false, static_cast<hipStream_t>(stream));
+}
+extern "C" int mivit_attn_block_fwd_q1(const void *n_in, const float *gamma_in, const float *beta_in, const void *Wqkv_bf16,
+                                       const float *bqkv, const void *Wo_bf16, const float *bo, const float *gamma_out,
+                                       const float *beta_out, int B, int S, void *ctx, void *n_out, float *rstd, void *x_out,
+                                       void *z_out, float *mean, void *qkv_out, void *stream) {
+    prof_set_tag(MIVIT_PROF_OP);
+    return launch_attn_block_fwd(n_in, gamma_in, beta_in, Wqkv_bf16, bqkv, Wo_bf16, bo, gamma_out, beta_out, B, S, ctx, n_out,
+                                 rstd, x_out, z_out, mean, qkv_out, true, static_cast<hipStream_t>(stream));
 }
