@@ -511,6 +511,42 @@ int mivit_hmm_estep(const double *pos, int N, const int *offsets, int n_tracks, 
 int mivit_hmm_viterbi(const double *pos, int N, const int *offsets, int n_tracks, int K, const double *v, const double *logv,
                       const double *logA, const double *logpi, int *state, double *logp, unsigned char *workspace, void *stream);
 
+/* Stage drift, csrc/drift.hip: the motion all tracks of a movie share, from their frame-to-frame increments (trackpy's
+ * compute_drift; no counterpart in the reference, whose movies do not drift).  fp64 without contraction, no atomics; a frame's
+ * result is bitwise the same alone, in any batch and in every launch, and bitwise the numpy restatements' (helpers/msd.
+ * _drift_frames_numpy, _drift_integrate_numpy): adds, multiplications, divisions and compares only.
+ *
+ * mivit_drift_frames: one statistic of the increments per frame and axis, ONE WORKGROUP of 256 threads per frame.  pos [N, 2]
+ * fp64, the table sorted by track; pair_row [M] int32: increment m is pos[r] - pos[r - 1] with r = pair_row[m], gathered by
+ * the kernel (r is clamped to [1, N - 1]: nothing is read out of bounds; M > 0 needs N >= 2); frame_offsets [F + 1] int32, the
+ * CSR of pair_row over the frames (entries clamped to [0, M]); the increments of frame f are d_0 .. d_{n-1} in the order of
+ * pair_row.  out: stat [F, 2] fp64, 0 where n = 0.
+ *   mode 0, mean:   s_t = ((+0 + d_t) + d_{t+256}) + d_{t+512} + ..   for t = 0 .. 255 (+0 where the frame has no such entry);
+ *                   then for half = 128, 64, .. 1:  s_i = s_i + s_{i+half}, i < half;   stat = s_0 / n.
+ *                   The order depends on the position of an increment within its frame alone; n has no limit.
+ *   mode 1, median: per axis the exact median under the order of the values with -0 before +0: the middle value for odd n,
+ *                   (a + b) / 2 of the two middle values for even n; NaN if an increment of the axis is NaN.  The frame is
+ *                   sorted in LDS (a bitonic network over 64-bit keys, 8 B a pair, padded to a power of two), so n <= 4096
+ *                   (32 KiB: five workgroups a CU); max_pairs >= the pairs of the largest frame sizes the LDS of the launch, a
+ *                   value above 4096 is an error, never a launch, and a frame that is larger after all is cut to its first
+ *                   increments, as many as the LDS of the launch holds.  max_pairs is not used by mode 0.
+ *
+ * mivit_drift_integrate: stat [F, 2], n_pairs [F] int32 (the weights: the pairs of each frame, negative counts as 0),
+ * half_window h >= 0 -> velocity [F, 2], drift [F, 2] fp64.  With W(f) = [max(1, f - h), min(F - 1, f + h)]:
+ *   velocity[f] = (sum_{g in W(f)} n_g * stat_g) / (sum_{g in W(f)} n_g)   the numerator from +0 in ascending g, the product
+ *                 rounded before it is added, the denominator in integers; 0 where the denominator is 0
+ *   velocity[0] = 0;   h = 0: velocity[f] = stat[f] itself, bit for bit, for f >= 1
+ *   drift: the running sum of velocity in BLOCKS of 256 frames.  p[b][i] = v[256 b] + .. + v[256 b + i] sequentially
+ *          (np.cumsum of the block); T[b] = p[b][255]; O[b] = T[0] + .. + T[b - 1] sequentially (np.cumsum of the totals);
+ *          drift[256 b + i] = O[b] + p[b][i] for b >= 1 and p[0][i] for b = 0.  drift[f] depends on velocity[0 .. f] alone.
+ * One thread per (frame, axis) for velocity; one workgroup for drift (thread b sums block b, 65 536 frames a pass).
+ *
+ * Both: arguments are validated before any HIP call (sizes, mode, the median's limit, null pointers); F = 0 is a no-op. */
+int mivit_drift_frames(const double *pos, int N, const int *pair_row, int M, const int *frame_offsets, int F, int mode,
+                       int max_pairs, double *stat, void *stream);
+int mivit_drift_integrate(const double *stat, const int *n_pairs, int F, int half_window, double *velocity, double *drift,
+                          void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

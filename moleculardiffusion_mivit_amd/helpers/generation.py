@@ -838,7 +838,7 @@ def _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin):
 
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
-                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None):
+                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None, drift=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -888,7 +888,15 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     segment.hip on a GPU generator); "path", integer [Np, F] in [0, K), plants the states instead and nothing is drawn for
     them.  The state is constant over the sub-positions of a frame: sub-step t of frame f has variance 2 Ds[state[p, f]] /
     nPosPerFrame.  truth gains state (int64 per row) and D_row (float64 per row); truth["D"] is the mean of D_row over the
-    lifetime, so score_tracking keeps working.  Not together with alphas; with a geometry the steps run along the filament."""
+    lifetime, so score_tracking keeps working.  Not together with alphas; with a geometry the steps run along the filament.
+
+    drift (default None: a stage at rest, the code path without it): the offset of the stage in every frame, a finite real
+    [F, 2] array or tensor (y, x) in pixels, or a pair (vy, vx) in pixels per frame for drift[f] = f * (vy, vx).  Row f is added
+    to every sub-position of frame f of every particle once the trajectories are built (free, alphas, geometry and states
+    alike) and before rendering: truth["pos"] is float32(pos + drift[f]) with the float32 position pos of the stage at rest
+    and drift in float64, rounded once, and truth["y"], truth["x"] are the means of those: what was rendered and what a tracker
+    sees.  With a geometry truth["arc"] and truth["edge"] stay in the filament's own frame.  truth gains drift ([F, 2]
+    float64).  Nothing is drawn for it; a zero drift gives the movie and the positions of drift = None bit for bit."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -922,6 +930,20 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError(f"blink must be a probability in [0, 1) or a bool mask [{Np}, {F_}], got {blink!r}")
         else:
             blink_p = float(blink)
+    drift_f = None
+    if drift is not None:
+        what = f"drift must be a real [{F_}, 2] array or tensor of offsets (y, x) or a pair (vy, vx) in pixels per frame"
+        try:
+            drift_f = (drift if torch.is_tensor(drift) else torch.from_numpy(np.array(drift))).detach().cpu()     # floats: float64
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{what}, got {drift!r}") from None
+        if drift_f.dtype == torch.bool or drift_f.is_complex() or tuple(drift_f.shape) not in ((2,), (F_, 2)):
+            raise ValueError(f"{what}, got {drift_f.dtype} {tuple(drift_f.shape)}")
+        drift_f = drift_f.double()
+        if not bool(torch.isfinite(drift_f).all()):
+            raise ValueError("drift must be finite")
+        if drift_f.dim() == 1:
+            drift_f = torch.arange(F_, dtype=torch.float64).view(F_, 1) * drift_f.view(1, 2)
     gdev = generator.device if generator is not None else dev
     if gdev != dev and not (gdev.type == dev.type and dev.index is None):
         raise ValueError(f"the generator lives on {gdev}, the movie on {dev}")
@@ -989,6 +1011,9 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         if T:
             steps[:, 0] = 0.0
         pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
+    if drift_f is not None:
+        drift_f = drift_f.to(dev)
+        pos = (pos.double() + drift_f.repeat_interleave(npos, dim=0).view(1, T, 2)).float()     # rounded once
     pm, ps = props["particle_intensity"]
     bm, bs = props["background_intensity"]
     if pm > 1e-4 and ps > 1e-4:
@@ -1025,4 +1050,6 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         truth["alpha"] = alpha.to(dev)
     if packed is not None:
         truth["arc"], truth["edge"], truth["geometry_id"] = arc.to(dev), edge.to(dev), torch.from_numpy(geom_id).to(dev)
+    if drift_f is not None:
+        truth["drift"] = drift_f
     return vid.float(), truth

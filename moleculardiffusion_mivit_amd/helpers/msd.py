@@ -663,3 +663,232 @@ def fit_diffusion_states(positions, offsets, K, dt=1.0, sigma2=0.0, max_iter=200
                      "loglik_trace": np.asarray(trace), "bic": -2.0 * trace[-1] + (K * K + K - 1) * float(np.log(max(n_inc, 1))),
                      "n_tracks_used": int(ok.sum()), "n_increments": n_inc, "gamma": gamma[:, perm], "state": state.long(),
                      "state_posterior": sp, "occupancy": G / G.sum()}, kind)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# stage drift: the motion all tracks share, from their frame-to-frame increments (csrc/drift.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+_DRIFT_THREADS = 256           # csrc/drift.hip: partial sums of a frame's mean
+_DRIFT_SCAN_BLOCK = 256        # csrc/drift.hip: frames per block of the running sum
+_DRIFT_MODES = {"mean": 0, "median": 1}
+_SIGN64 = np.uint64(1 << 63)
+
+
+def _drift_keys(d):
+    """float64 -> uint64 keys whose unsigned order is the order of the values, -0 before +0 (csrc/drift.hip::drift_key)."""
+    u = np.ascontiguousarray(d, dtype=np.float64).view(np.uint64)
+    return np.where(u >= _SIGN64, ~u, u | _SIGN64)
+
+
+def _drift_unkeys(k):
+    return np.where(k >= _SIGN64, k & ~_SIGN64, ~k).view(np.float64)
+
+
+def _drift_frames_numpy(pos, pair_row, frame_offsets, mode):
+    """The arithmetic of csrc/drift.hip::drift_frames_kernel in its order (include/mivit_hip.h, mivit_drift_frames).  Mean: 256
+    partial sums, entry t over the increments t, t + 256, .. of the frame from +0 (np.cumsum over the rounds is sequential;
+    the zeros that pad the last round add nothing to a sum that started at +0), folded in halves.  Median: np.sort of the
+    keys that order -0 before +0.  pos [N, 2] float64, pair_row [M], frame_offsets [F + 1] integers -> stat [F, 2], bitwise
+    the kernel's."""
+    F, W = len(frame_offsets) - 1, _DRIFT_THREADS
+    stat = np.zeros((F, 2))
+    pair_row = np.asarray(pair_row, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        d = pos[pair_row] - pos[pair_row - 1] if len(pair_row) else np.zeros((0, 2))
+        for f in range(F):
+            a, b = int(frame_offsets[f]), int(frame_offsets[f + 1])
+            n = b - a
+            if n <= 0:
+                continue
+            x = d[a:b]
+            if mode == 0:
+                rounds = -(-n // W)
+                pad = np.zeros((rounds + 1, W, 2))                                          # round 0: the +0 the sums start from
+                pad[1:].reshape(-1, 2)[:n] = x
+                s = np.cumsum(pad, axis=0)[-1]
+                half = W // 2
+                while half > 0:
+                    s[:half] = s[:half] + s[half:2 * half]
+                    half //= 2
+                stat[f] = s[0] / float(n)
+            else:
+                for axis in range(2):
+                    col = x[:, axis]
+                    if np.isnan(col).any():
+                        stat[f, axis] = np.nan
+                        continue
+                    v = _drift_unkeys(np.sort(_drift_keys(col)))
+                    stat[f, axis] = v[n // 2] if n % 2 else (v[n // 2 - 1] + v[n // 2]) / 2.0
+    return stat
+
+
+def _drift_integrate_numpy(stat, n_pairs, half_window):
+    """The arithmetic of csrc/drift.hip::drift_velocity_kernel and drift_scan_kernel in their order (mivit_drift_integrate):
+    the window's numerator from +0 in ascending frame, each product rounded first; the running sum in blocks of 256 frames,
+    np.cumsum inside a block and over the block totals.  stat [F, 2] float64, n_pairs [F] integers -> (velocity, drift)
+    [F, 2], bitwise the kernels'."""
+    F, B = len(stat), _DRIFT_SCAN_BLOCK
+    vel = np.zeros((F, 2))
+    with np.errstate(all="ignore"):
+        if F > 1 and half_window == 0:
+            vel[1:] = stat[1:]
+        elif F > 1:
+            h = min(int(half_window), F)
+            c = np.maximum(np.asarray(n_pairs, dtype=np.int64), 0)
+            w = c.astype(np.float64)[:, None] * stat
+            num, den = np.zeros((F, 2)), np.zeros(F, np.int64)
+            f = np.arange(F)
+            for off in range(-h, h + 1):
+                g = f + off
+                ok = (g >= 1) & (g <= F - 1) & (f >= 1)
+                g = np.clip(g, 0, F - 1)
+                num = np.where(ok[:, None], num + w[g], num)
+                den = den + np.where(ok, c[g], 0)
+            vel = np.where((den > 0)[:, None], num / den.astype(np.float64)[:, None], 0.0)
+        nb = -(-F // B)
+        pad = np.zeros((nb * B, 2))
+        pad[:F] = vel
+        drift = np.cumsum(pad.reshape(nb, B, 2), axis=1)
+        if nb > 1:
+            drift[1:] = np.cumsum(drift[:-1, B - 1], axis=0)[:, None, :] + drift[1:]
+    return vel, drift.reshape(nb * B, 2)[:F].copy()
+
+
+def _drift_pairs(pos, fr, off, usable, F, min_pairs):
+    """The increments estimate_drift uses, as the kernel takes them: pos [N, 2] float64, fr [N] and off [n_tracks + 1] int64,
+    usable [N] bool or None, tensors on one device -> (pair_row [M] int64, the later row of every increment, grouped by its
+    frame and in ascending row within a frame; n_pairs [F] int64, after min_pairs; frame_offsets [F + 1] int64; n_rejected).
+    Torch ops on the device: no loop over frames or tracks."""
+    n, dev = pos.shape[0], pos.device
+    if n >= 2:
+        first = torch.zeros(n, dtype=torch.bool, device=dev)
+        first[off[:-1][off[1:] > off[:-1]]] = True
+        cand = ~first[1:] & (fr[1:] - fr[:-1] == 1)
+        if usable is not None:
+            cand &= usable[1:] & usable[:-1]
+        finite = torch.isfinite(pos).all(dim=1)
+        finite = finite[1:] & finite[:-1]
+        n_rejected = int((cand & ~finite).sum())
+        rows = torch.nonzero(cand & finite, as_tuple=True)[0] + 1
+    else:
+        n_rejected, rows = 0, torch.zeros(0, dtype=torch.int64, device=dev)
+    pf = fr[rows]
+    order = torch.argsort(pf, stable=True)                      # rows stay in ascending order within a frame
+    rows, pf = rows[order], pf[order]
+    counts = torch.bincount(pf, minlength=F)
+    enough = counts >= min_pairs
+    rows = rows[enough[pf]]
+    counts = torch.where(enough, counts, torch.zeros((), dtype=counts.dtype, device=dev))
+    frame_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)])
+    return rows, counts, frame_offsets, n_rejected
+
+
+def _check_frames(frames, n, what="frames"):
+    if len(frames.shape) != 1 or frames.shape[0] != n:
+        raise ValueError(f"{what} must be [N] with one entry per row, got {tuple(frames.shape)} for {n} rows")
+    kind = frames.dtype
+    if torch.is_tensor(frames):
+        integer = not (kind == torch.bool or kind.is_floating_point or kind.is_complex)
+    else:
+        integer = kind.kind in "iu"
+    if not integer:
+        raise ValueError(f"{what} must be integers, got {kind}")
+
+
+def estimate_drift(positions, frames, offsets, n_frames=None, estimator="mean", smoothing=0, min_pairs=1, use=None):
+    """The drift of the stage from the tracks themselves (trackpy's compute_drift): positions [N, 2] (y, x) and frames [N]
+    (integers >= 0) sorted by track and by frame within a track, offsets [n_tracks + 1] (CSR), as tracking.
+    tracks_table_by_track and simulate_movie's truth give them -> dict of the input's kind:
+        drift    [F, 2] float64   the stage offset of every frame relative to frame 0: subtract_drift takes it
+        velocity [F, 2] float64   its increment per frame, velocity[0] = 0
+        n_pairs  [F] int32        the increments each frame's estimate rests on (0 where there were fewer than min_pairs)
+        n_rejected                increments left out because a position was not finite
+    F = n_frames (default max(frames) + 1).  An increment pos[r] - pos[r - 1] is used when rows r - 1 and r are consecutive
+    rows of one track, their frames differ by exactly 1 (the increment across a gap is left out), both are usable (use [N]
+    bool, default all: pass ~filled for a gap-closed table) and both positions are finite; it belongs to the later frame.  Per
+    frame the estimator is the "mean" of its increments or their exact "median" per axis (robust against a few tracks that
+    jump), 0 where a frame has fewer than min_pairs.  smoothing = h > 0 replaces each frame's value by the mean over the
+    frames max(1, f - h) .. min(F - 1, f + h) weighted by n_pairs; h = 0 keeps it as it is.  drift is the running sum.
+    include/mivit_hip.h has the arithmetic and every summation order.
+
+    Subtracting the mean of n increments removes 1 / n of every particle's own motion with it: D of the corrected tracks
+    comes out near (1 - 1 / n) D, and smoothing over 2 h + 1 frames reduces the loss to about 1 / ((2 h + 1) n).
+
+    The pair list is a handful of torch ops on the input's device (a stable sort by frame, bincount, cumsum; no loop over
+    frames or tracks).  CUDA tensors go to the kernels (csrc/drift.hip, no atomics: the same bits in every run; the median
+    takes at most ops.DRIFT_MAX_PAIRS increments a frame), anything else to the numpy restatements, bitwise equal."""
+    if estimator not in _DRIFT_MODES:
+        raise ValueError(f"estimator must be 'mean' or 'median', got {estimator!r}")
+    if isinstance(smoothing, bool) or int(smoothing) != smoothing or smoothing < 0:
+        raise ValueError(f"smoothing must be an integer >= 0 (the half window in frames), got {smoothing}")
+    if isinstance(min_pairs, bool) or int(min_pairs) != min_pairs or min_pairs < 1:
+        raise ValueError(f"min_pairs must be an integer >= 1, got {min_pairs}")
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    is_t = torch.is_tensor(positions)
+    given = [frames, offsets] + ([] if use is None else [use])
+    if any(torch.is_tensor(g) != is_t for g in given):
+        raise ValueError("positions, frames, offsets and use must all be tensors or all be arrays")
+    if is_t and any(g.device != positions.device for g in given):
+        raise ValueError(f"positions on {positions.device}, the other arguments elsewhere")
+    if not is_t:
+        positions, frames, offsets = np.asarray(positions, dtype=np.float64), np.asarray(frames), np.asarray(offsets)
+        use = None if use is None else np.asarray(use)
+    n = positions.shape[0]
+    _check_frames(frames, n)
+    _check_offsets(offsets, n)
+    if use is not None and (tuple(use.shape) != (n,) or use.dtype != (torch.bool if is_t else np.bool_)):
+        raise ValueError(f"use must be bool [N], got {use.dtype} {tuple(use.shape)}")
+    if is_t:
+        as_t = lambda a: a.detach()                                                               # noqa: E731
+    else:
+        as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a) if a.flags.writeable else a.copy())     # noqa: E731
+    pos, fr, off = as_t(positions).double().contiguous(), as_t(frames).long(), as_t(offsets).long()
+    dev = pos.device
+    f_lo, f_hi = (int(fr.min()), int(fr.max())) if n else (0, -1)
+    if f_lo < 0:
+        raise ValueError(f"frames must be >= 0, got {f_lo}")
+    if n_frames is None:
+        F = f_hi + 1
+    else:
+        if isinstance(n_frames, bool) or int(n_frames) != n_frames or n_frames < 0:
+            raise ValueError(f"n_frames must be None or an integer >= 0, got {n_frames}")
+        F = int(n_frames)
+        if f_hi >= F:
+            raise ValueError(f"frame {f_hi} in a movie of n_frames = {F}")
+    usable = None if use is None else as_t(use)
+    rows, counts, frame_offsets, n_rejected = _drift_pairs(pos, fr, off, usable, F, int(min_pairs))
+    mode, h = _DRIFT_MODES[estimator], int(smoothing)
+    if dev.type == "cuda":
+        from .. import ops
+        n_pairs = counts.int()
+        stat = ops.drift_frames(pos, rows.int(), frame_offsets.int(), mode)
+        velocity, drift = ops.drift_integrate(stat, n_pairs, h)
+        return {"drift": drift, "velocity": velocity, "n_pairs": n_pairs, "n_rejected": n_rejected}
+    stat = _drift_frames_numpy(pos.numpy(), rows.numpy(), frame_offsets.numpy(), mode)
+    velocity, drift = _drift_integrate_numpy(stat, counts.numpy(), h)
+    out = {"drift": drift, "velocity": velocity, "n_pairs": counts.numpy().astype(np.int32)}
+    if is_t:
+        out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in out.items()}
+    out["n_rejected"] = n_rejected
+    return out
+
+
+def subtract_drift(positions, frames, drift):
+    """positions [N, 2] - drift[frames] (trackpy's subtract_drift): drift [F, 2] as estimate_drift returns it, frames [N]
+    integers in [0, F); arrays or tensors on one device, the result of the input's kind."""
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    if len(drift.shape) != 2 or drift.shape[1] != 2:
+        raise ValueError(f"drift must be [F, 2], got {tuple(drift.shape)}")
+    is_t = torch.is_tensor(positions)
+    if torch.is_tensor(frames) != is_t or torch.is_tensor(drift) != is_t:
+        raise ValueError("positions, frames and drift must all be tensors or all be arrays")
+    if not is_t:
+        positions, frames, drift = np.asarray(positions), np.asarray(frames), np.asarray(drift)
+    elif frames.device != positions.device or drift.device != positions.device:
+        raise ValueError(f"positions on {positions.device}, frames on {frames.device}, drift on {drift.device}")
+    _check_frames(frames, positions.shape[0])
+    if positions.shape[0] and (int(frames.min()) < 0 or int(frames.max()) >= drift.shape[0]):
+        raise ValueError(f"frames must lie in [0, {drift.shape[0]}), got {int(frames.min())} .. {int(frames.max())}")
+    return positions - drift[frames.long() if is_t else frames.astype(np.int64)]

@@ -1127,7 +1127,7 @@ def refine_localizations_tensors(patches, ys, xs):
 
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
-                             batch_size=4096, segment=None, states=None, **tracking_kwargs):
+                             batch_size=4096, segment=None, states=None, drift=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1152,7 +1152,17 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     run_offsets [n_runs + 1], the CSR of the maximal runs of constant Viterbi state over the same rows (it refines offsets),
     run_track and run_state [n_runs] (-1 for a one-row track), and D_model, n_sequences [n_runs] from the windows of
     plan_sequences(run_offsets, seq_len, tail) exactly as for segment, so that no window straddles a switch.  The per-track
-    entries and those of segment are unchanged; both may be given."""
+    entries and those of segment are unchanged; both may be given.
+
+    drift (default None: a stage at rest, the code path without it): a dict of helpers/msd.estimate_drift arguments (estimator,
+    smoothing, min_pairs; {} for the defaults).  The drift of the stage is estimated from the increments of all tracks on the
+    positions the MSD is taken on (refined or integer; the filled rows of gap-closed tracks are left out of the estimate
+    through use) and subtracted (csrc/drift.hip), and track_msd, segment and states run on the corrected positions.  The
+    result gains "drift": the estimate_drift dict plus positions, the corrected [N, 2].  D_model is unchanged by
+    construction: the patches are cut from the movie at the detected positions, and a patch does not know where the stage
+    is."""
+    if drift is not None and (not isinstance(drift, dict) or set(drift) - {"estimator", "smoothing", "min_pairs"}):
+        raise ValueError("drift must be None or a dict with keys among estimator, smoothing and min_pairs")
     if states is not None:
         if not isinstance(states, dict) or set(states) - {"K", "sigma2", "max_iter", "tol", "min_var", "init"}:
             raise ValueError("states must be None or a dict with keys among K, sigma2, max_iter, tol, min_var and init")
@@ -1178,6 +1188,13 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         pos = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1)
     else:
         pos = torch.stack([y, x], dim=1).double()
+    drifted = None
+    if drift is not None:
+        from . import msd as _msd
+        drifted = _msd.estimate_drift(pos, fr, offsets, n_frames=movie.shape[0],
+                                      use=~by_track[5] if len(by_track) > 5 else None, **drift)
+        pos = _msd.subtract_drift(pos, fr, drifted["drift"])
+        drifted["positions"] = pos
     msd, d_lstsq, d_weighted = ops.track_msd(pos, offsets.int(), float(dt), 0)
     seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
     n_sequences = torch.bincount(seq_track, minlength=n_tracks)
@@ -1227,6 +1244,8 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["segments"] = segments
     if fitted is not None:
         res["states"] = fitted
+    if drifted is not None:
+        res["drift"] = drifted
     return res
 
 

@@ -1038,6 +1038,64 @@ def hmm_viterbi(pos: torch.Tensor, offsets: torch.Tensor, v: torch.Tensor, A: to
     return state, logp
 
 
+DRIFT_MAX_PAIRS = 4096       # csrc/drift.hip: increments of one frame that the median sorts in LDS (8 B a pair, 32 KiB)
+DRIFT_MODES = {"mean": 0, "median": 1}
+
+
+def drift_frames(pos: torch.Tensor, pair_row: torch.Tensor, frame_offsets: torch.Tensor, mode="mean") -> torch.Tensor:
+    """The mean or the exact median of the increments of every frame (csrc/drift.hip, mivit_drift_frames): pos [N, 2] float64
+    on the GPU, the table sorted by track; pair_row [M] int32 in [1, N): increment m is pos[r] - pos[r - 1] with r =
+    pair_row[m]; frame_offsets [F + 1] int32, the CSR of pair_row over the frames (from 0 to M); mode "mean" (0) or "median"
+    (1) -> stat [F, 2] float64, 0 for a frame without a pair.  The median sorts a frame in LDS: at most DRIFT_MAX_PAIRS pairs a
+    frame.  frame_offsets and the range of pair_row are read back to be checked: every rejection is a ValueError before any
+    launch.  See include/mivit_hip.h for the summation order and helpers/msd.estimate_drift for the front end."""
+    pos = _seg_tensor(pos, torch.float64, 2, "drift_frames", "pos [N, 2]")
+    pair_row = _seg_tensor(pair_row, torch.int32, 1, "drift_frames", "pair_row [M]")
+    frame_offsets = _seg_tensor(frame_offsets, torch.int32, 1, "drift_frames", "frame_offsets [F + 1]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"drift_frames: pos must be [N, 2], got {tuple(pos.shape)}")
+    if frame_offsets.numel() < 1:
+        raise ValueError("drift_frames: frame_offsets must have F + 1 entries")
+    if isinstance(mode, bool) or mode not in DRIFT_MODES and mode not in DRIFT_MODES.values():
+        raise ValueError(f"drift_frames: mode must be 'mean' (0) or 'median' (1), got {mode!r}")
+    mode = DRIFT_MODES.get(mode, mode)
+    if len({t.device for t in (pos, pair_row, frame_offsets)}) != 1:
+        raise ValueError("drift_frames: all tensors must be on one device")
+    n, M, F = pos.shape[0], pair_row.numel(), frame_offsets.numel() - 1
+    off = frame_offsets.cpu()
+    if int(off[0]) != 0 or int(off[-1]) != M or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"drift_frames: frame_offsets must rise from 0 to the number of pairs {M}")
+    max_pairs = int((off[1:] - off[:-1]).max()) if F else 0
+    if mode == 1 and max_pairs > DRIFT_MAX_PAIRS:
+        raise ValueError(f"drift_frames: a frame of {max_pairs} pairs, the median's limit is {DRIFT_MAX_PAIRS} (DRIFT_MAX_PAIRS)")
+    if M and (int(pair_row.min()) < 1 or int(pair_row.max()) >= n):
+        raise ValueError(f"drift_frames: pair_row must lie in [1, {n}), the later row of an increment")
+    stat = torch.empty(F, 2, dtype=torch.float64, device=pos.device)
+    N.check(N.lib.mivit_drift_frames(_p(pos), n, _p(pair_row), M, _p(frame_offsets), F, mode, max_pairs, _p(stat), _s(pos)),
+            "mivit_drift_frames")
+    return stat
+
+
+def drift_integrate(stat: torch.Tensor, n_pairs: torch.Tensor, half_window: int = 0):
+    """The windowed velocity and its running sum (csrc/drift.hip, mivit_drift_integrate): stat [F, 2] float64 and n_pairs [F]
+    int32 on the GPU, half_window h >= 0 -> (velocity [F, 2], drift [F, 2]) float64.  velocity[f] is the mean of stat over the
+    frames max(1, f - h) .. min(F - 1, f + h) weighted by n_pairs (stat[f] itself for h = 0), velocity[0] = 0, and drift its
+    running sum in blocks of 256 frames.  See include/mivit_hip.h for the order."""
+    stat = _seg_tensor(stat, torch.float64, 2, "drift_integrate", "stat [F, 2]")
+    n_pairs = _seg_tensor(n_pairs, torch.int32, 1, "drift_integrate", "n_pairs [F]")
+    if stat.shape[1] != 2 or n_pairs.numel() != stat.shape[0]:
+        raise ValueError(f"drift_integrate: stat must be [F, 2] and n_pairs [F], got {tuple(stat.shape)} and {tuple(n_pairs.shape)}")
+    if stat.device != n_pairs.device:
+        raise ValueError("drift_integrate: all tensors must be on one device")
+    if isinstance(half_window, bool) or int(half_window) != half_window or half_window < 0:
+        raise ValueError(f"drift_integrate: half_window must be an integer >= 0, got {half_window}")
+    F = stat.shape[0]
+    velocity, drift = torch.empty_like(stat), torch.empty_like(stat)
+    N.check(N.lib.mivit_drift_integrate(_p(stat), _p(n_pairs), F, min(int(half_window), 2 ** 31 - 1), _p(velocity), _p(drift),
+                                        _s(stat)), "mivit_drift_integrate")
+    return velocity, drift
+
+
 MOVIE_MAX_RADIUS = 64        # csrc/movie.hip: limits of mivit_render_movie
 MOVIE_MAX_NPOS = 256
 MOVIE_MAX_UP = 64

@@ -22,13 +22,19 @@ of D_msd of its track.  --hmm K (with --states) also runs estimate_track_diffusi
 (helpers/msd.fit_diffusion_states, csrc/hmm.hip) for k = 1, 2, 3 and K and adds "hmm": the fitted Ds and M of K next to the
 planted ones (states sorted by ascending D), over the rows of matched tracks the mean absolute error of Ds[state] (the
 Viterbi state) against truth["D_row"] and the share of rows whose state is the planted one, the BIC of every k and the k it
-picks.  A tool, not a test: it asserts no accuracy.
+picks.  --drift VY,VX moves the stage by that many pixels per frame (simulate_movie's drift) and adds "drift": the planted
+velocity, the mean of the estimated one and the RMS error of the estimated drift (helpers/msd.estimate_drift with
+--drift-estimator mean|median and --drift-smoothing H, csrc/drift.hip, through estimate_track_diffusion(..., drift={...})),
+and over the matched tracks the medians of D_true and of D_msd and D_msd_weighted without and with the correction (the
+per-track columns gain D_msd_corrected and D_msd_weighted_corrected); with --states --hmm K also the fitted Ds of K without
+and with it.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
                                           [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10]
                                           [--cristae 4 30 60 12] [--boundary reflect]
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
+                                          [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -70,7 +76,18 @@ def main():
     ap.add_argument("--states", type=float, nargs=3, default=None, metavar=("D1", "D2", "P_STAY"))
     ap.add_argument("--penalties", type=float, nargs="+", default=[1.0, 2.0, 3.0, 4.0, 6.0, 8.0])
     ap.add_argument("--hmm", type=int, default=None, metavar="K")
+    ap.add_argument("--drift", default=None, metavar="VY,VX")
+    ap.add_argument("--drift-estimator", choices=["mean", "median"], default="mean")
+    ap.add_argument("--drift-smoothing", type=int, default=0, metavar="H")
     args = ap.parse_args()
+    drift = None
+    if args.drift is not None:
+        try:
+            drift = tuple(float(v) for v in args.drift.split(","))
+        except ValueError:
+            drift = ()
+        if len(drift) != 2:
+            raise SystemExit("--drift takes VY,VX in pixels per frame")
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
     props = dict(gen.DEFAULT_IMAGE_PROPS)
@@ -95,7 +112,7 @@ def main():
         states = {"Ds": [d1, d2], "M": [[stay, 1.0 - stay], [1.0 - stay, stay]]}
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, None if states else tuple(args.D), args.npos,
                                       image_props=props, generator=g, device="cuda", blink=args.blink, alphas=args.alpha,
-                                      states=states, **confine)
+                                      states=states, **confine, **({} if drift is None else {"drift": drift}))
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
@@ -146,12 +163,40 @@ def main():
         sharp = truth["pos"][:, ::args.npos].double()
         s_msd = MSD.mean_square_displacements(sharp)
         out["alpha_msd_truth_unblurred_median"] = float(MSD.estimate_alpha(s_msd, max_lag=args.alpha_max_lag).nanmedian())
+    if drift is not None:
+        out["drift"] = drift_scores(movie, model, args, norm, truth, score, est, out["tracks"], states)
     if states is not None:
         out["states"] = args.states
         out["segmentation"] = [segmentation_scores(movie, model, args, norm, truth, score, fr, float(p)) for p in args.penalties]
         if args.hmm is not None:
             out["hmm"] = hmm_scores(movie, model, args, norm, truth, score, fr, states)
     print(json.dumps(out))
+
+
+def drift_scores(movie, model, args, norm, truth, score, est, rows, states):
+    """D with and without the drift correction against the truth (see the module's docstring)"""
+    how = {"estimator": args.drift_estimator, "smoothing": args.drift_smoothing}
+    hmm = {"states": {"K": args.hmm}} if states is not None and args.hmm is not None else {}
+    cor = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap, drift=how,
+                                       **hmm)
+    assert torch.equal(cor["track_id"], est["track_id"])
+    for row, a, b in zip(rows, cor["D_msd"].tolist(), cor["D_msd_weighted"].tolist()):
+        row["D_msd_corrected"], row["D_msd_weighted_corrected"] = a, b
+    ok = score["particle_id"] >= 0
+    med = lambda col: float(col[ok].double().nanmedian()) if bool(ok.any()) else float("nan")              # noqa: E731
+    d = cor["drift"]
+    planted = truth["drift"] - truth["drift"][0]
+    out = {"planted_velocity": (truth["drift"][-1] - truth["drift"][0]).div(max(len(planted) - 1, 1)).tolist(),
+           "estimator": args.drift_estimator, "smoothing": args.drift_smoothing,
+           "velocity_mean": d["velocity"][1:].mean(dim=0).tolist(), "drift_rmse": float((d["drift"] - planted).pow(2).mean().sqrt()),
+           "n_pairs_median": float(d["n_pairs"][1:].double().median()), "n_rejected": d["n_rejected"],
+           "D_true_median": med(score["D_true"]), "D_msd_median": med(est["D_msd"]), "D_msd_corrected_median": med(cor["D_msd"]),
+           "D_msd_weighted_median": med(est["D_msd_weighted"]), "D_msd_weighted_corrected_median": med(cor["D_msd_weighted"])}
+    if hmm:
+        raw = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap, **hmm)
+        out["hmm_Ds"], out["hmm_Ds_corrected"] = raw["states"]["Ds"].tolist(), cor["states"]["Ds"].tolist()
+        out["planted_Ds"] = sorted(states["Ds"])
+    return out
 
 
 def hmm_scores(movie, model, args, norm, truth, score, fr, planted):
