@@ -309,6 +309,25 @@ int mivit_dog_peaks(const float *movie, int F, int H, int W, const double *w1, i
 int mivit_refine_gaussian(const float *patches, int N, int P, double xtol, double *params, float *peak, int *status,
                           void *stream);
 
+/* Poisson maximum-likelihood fit of every localisation with a Cramer-Rao bound per parameter (Smith et al., Nat. Methods 2010,
+ * in the Levenberg-Marquardt form of Laurence & Chromy 2010), csrc/localize.hip, one thread per patch.  patches [N, P, P] fp32,
+ * P odd, 3 .. 15, pixel centres at integers.  Data d = max((patch - offset) / gain, 0) + read_var (gain > 0 in ADU per photon,
+ * offset in ADU, read_var >= 0 the readout variance in photons^2, added to data and model as Huang et al. 2013 do).  Model
+ * mu = b + N E(ix; x0, s) E(iy; y0, s) + read_var with E the Gaussian integrated over the pixel, parameters (N photons, x0, y0,
+ * s, b); fit_sigma = 0 holds s at sigma0 (0.2 < sigma0 < P).  The damped loop of mivit_refine_gaussian (same lambda schedule,
+ * stopping rule on the undamped step with 0 < xtol <= 1.49012e-8, 100 iterations) on the Poisson deviance
+ * 2 sum(mu - d + d log(d / mu)) with the Fisher information sum dmu dmu^T / mu as its matrix; a step is accepted unless the
+ * deviance rises by more than 1e-13 of 2 sum(mu + d), the magnitude its rounding error scales with; a trial point with N <= 0,
+ * s outside (0.2, P) or a pixel with mu <= 0 is rejected like a cost increase.  Start: b = min(d) but at least 1e-3 max(d),
+ * N = max(sum(d - b), max(d)), the centre P / 2, sigma0.  out: params [N, 5] fp64; crlb [N, 5] fp64, the diagonal of the
+ * inverse Fisher matrix at the returned point (variances; NaN where status != 0 or the matrix is not positive definite; the s
+ * entry is 0 with fit_sigma = 0); deviance [N] fp64; status [N] int32: 0 converged, 1 damping exhausted (or a patch without a
+ * photon), 2 iteration cap, 3 non-finite patch (parameters NaN); iterations [N] int32.  Arguments are validated before any
+ * HIP call; N = 0 is a no-op. */
+int mivit_fit_spots_mle(const float *patches, int N, int P, double gain, double offset, double read_var, double sigma0,
+                        int fit_sigma, double xtol, double *params, double *crlb, double *deviance, int *status,
+                        int *iterations, void *stream);
+
 /* Linking of a whole movie: the reference's link_particles (helpers/helpersTracking.py:123-177, one
  * scipy.optimize.linear_sum_assignment per frame) for all F - 1 pairs of consecutive frames in one launch, csrc/linking.hip.
  * coords [F, cap, 2] int32 (y, x) and count [F] int32 as mivit_dog_peaks leaves them (device); movie_start [F] bytes or NULL:

@@ -140,6 +140,7 @@ SYMBOLS = {
     "mivit_dog_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mivit_refine_gaussian": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mivit_fit_spots_mle": (c_int, [c_void_p, c_int, c_int] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double] + [c_void_p] * 6),
     "mivit_link_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "mivit_chain_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mivit_close_gaps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p,

@@ -838,7 +838,7 @@ def _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin):
 
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
-                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None, drift=None):
+                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None, drift=None, camera=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -896,7 +896,16 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     alike) and before rendering: truth["pos"] is float32(pos + drift[f]) with the float32 position pos of the stage at rest
     and drift in float64, rounded once, and truth["y"], truth["x"] are the means of those: what was rendered and what a tracker
     sees.  With a geometry truth["arc"] and truth["edge"] stay in the filament's own frame.  truth gains drift ([F, 2]
-    float64).  Nothing is drawn for it; a zero drift gives the movie and the positions of drift = None bit for bit."""
+    float64).  Nothing is drawn for it; a zero drift gives the movie and the positions of drift = None bit for bit.
+
+    camera (default None: the training image model above, the code path without it): a photon-counting camera, a dict
+    {"background": photons per pixel, "gain": ADU per photon (default 1), "offset": ADU (default 0), "read_noise": ADU standard
+    deviation (default 0)}.  The movie is offset + gain * Poisson(render_movie(pos, amp) + background) + read_noise * randn,
+    drawn from `generator` after the amplitudes and the blink draws (randn only with read_noise > 0).  particle_intensity
+    keeps its meaning, the peak of the expected image, now in photons; background_intensity and poisson_noise of image_props
+    are neither used nor drawn.  truth gains camera (the dict with the defaults filled in) and photons (float64 per row): the
+    expected photons of the particle in that frame, amp.sum(-1) * 2 pi (psf_sigma_hr / upsampling_factor)^2.  What
+    tracking.fit_spots_mle takes as read_var is (read_noise / gain)^2."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -944,6 +953,18 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError("drift must be finite")
         if drift_f.dim() == 1:
             drift_f = torch.arange(F_, dtype=torch.float64).view(F_, 1) * drift_f.view(1, 2)
+    cam = None
+    if camera is not None:
+        if not isinstance(camera, dict) or "background" not in camera or set(camera) - {"background", "gain", "offset", "read_noise"}:
+            raise ValueError("camera must be None or a dict with the key background and optionally gain, offset and read_noise")
+        try:
+            cam = {k: float(camera.get(k, v)) for k, v in (("background", 0.0), ("gain", 1.0), ("offset", 0.0), ("read_noise", 0.0))}
+        except (TypeError, ValueError):
+            raise ValueError(f"camera values must be numbers, got {camera!r}") from None
+        if not all(math.isfinite(v) for v in cam.values()):
+            raise ValueError(f"camera values must be finite, got {camera!r}")
+        if cam["background"] < 0 or cam["gain"] <= 0 or cam["read_noise"] < 0:
+            raise ValueError(f"camera needs background >= 0, gain > 0 and read_noise >= 0, got {camera!r}")
     gdev = generator.device if generator is not None else dev
     if gdev != dev and not (gdev.type == dev.type and dev.index is None):
         raise ValueError(f"the generator lives on {gdev}, the movie on {dev}")
@@ -1027,10 +1048,15 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         dark = dark.to(dev)
         amp = torch.where(dark.unsqueeze(-1), torch.zeros((), dtype=amp.dtype, device=dev), amp)
     vid = render_movie(pos, amp, sigma, H, W, up, radius, first, last).to(dev)
-    vid = vid + clipped_background(vid.shape, bm, bs, generator, dev)
-    pn = props["poisson_noise"]
-    if pn != -1:
-        vid = vid * torch.poisson(torch.full(vid.shape, float(pn), device=dev), generator=generator) / pn
+    if cam is None:
+        vid = vid + clipped_background(vid.shape, bm, bs, generator, dev)
+        pn = props["poisson_noise"]
+        if pn != -1:
+            vid = vid * torch.poisson(torch.full(vid.shape, float(pn), device=dev), generator=generator) / pn
+    else:
+        vid = cam["offset"] + cam["gain"] * torch.poisson(vid.float() + cam["background"], generator=generator)
+        if cam["read_noise"] > 0:
+            vid = vid + cam["read_noise"] * torch.randn(vid.shape, generator=generator, device=dev)
     first, last = first.to(dev), last.to(dev)
     fr = torch.arange(F_, device=dev).view(1, F_)
     pid, frame = ((first.view(Np, 1) <= fr) & (fr <= last.view(Np, 1))).nonzero(as_tuple=True)
@@ -1052,4 +1078,7 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         truth["arc"], truth["edge"], truth["geometry_id"] = arc.to(dev), edge.to(dev), torch.from_numpy(geom_id).to(dev)
     if drift_f is not None:
         truth["drift"] = drift_f
+    if cam is not None:
+        truth["camera"] = cam
+        truth["photons"] = amp.double().sum(-1)[pid, frame] * (2.0 * math.pi * (sigma / up) ** 2)
     return vid.float(), truth

@@ -15,6 +15,7 @@ start of a later one across up to max_gap missed frames (close_gaps_movie) and t
 interpolated position (fill_gaps), so that every track stays contiguous in frames.  Movies are filtered as float32.  pandas and scipy are only
 imported by the functions that need them: detect_particles_movie, track_particles_flat, extract_patches_flat and
 refine_localizations need neither pandas nor (except for linking) scipy."""
+import math
 from typing import Dict, Sequence, Tuple
 
 import numpy as np
@@ -891,23 +892,263 @@ def refine_gaussian_patches(patches, xtol=FIT_XTOL):
     return _refine_numpy(patches, xtol)
 
 
-def refine_localizations(patches, ys, xs):
+# ----------------------------------------------------------------------------------------------------------------------
+# Poisson maximum-likelihood fit with Cramer-Rao bounds (csrc/localize.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+MLE_MIN_SIGMA = 0.2       # the fitted width stays in (MLE_MIN_SIGMA, P)
+MLE_COST_SLACK = 1e-13    # FIT_COST_SLACK - 1, of 2 sum(mu + d) instead of the cost
+_SQRT2, _SQRT_2PI = 1.4142135623730951, 2.5066282746310002
+_erf = np.frompyfunc(math.erf, 1, 1)
+
+
+def _mle_data(raw, gain, offset, read_var):
+    """Camera units -> photons: max((patch - offset) / gain, 0) + read_var, float64."""
+    with np.errstate(invalid="ignore"):
+        e = (raw.astype(np.float64) - offset) / gain
+        return np.where(e > 0.0, e, 0.0) + read_var
+
+
+def _mle_axis(P, c, s, fs):
+    """The three tables of one axis for centres c [n] and widths s [n] -> E, dE/dc, dE/ds, each [P, n] (ml_axis)."""
+    w, nc = _SQRT2 * s, 1.0 / (_SQRT_2PI * s)
+    ns = nc / s
+    t = [(float(k) - 0.5) - c for k in range(P + 1)]
+    u = [tk / w for tk in t]
+    e = [_erf(uk).astype(np.float64) for uk in u]
+    g = [np.exp(-(uk * uk)) for uk in u]
+    E = np.stack([0.5 * (e[k + 1] - e[k]) for k in range(P)])
+    dc = np.stack([(g[k] - g[k + 1]) * nc for k in range(P)])
+    ds = np.stack([(t[k] * g[k] - t[k + 1] * g[k + 1]) * ns for k in range(P)]) if fs else np.zeros_like(E)
+    return E, dc, ds
+
+
+def _mle_normal(d, p, read_var, fs):
+    """Deviance, gradient, Fisher matrix, the out-of-domain flag and 2 sum(mu + d), the magnitude the deviance's rounding
+    error scales with, of the model at p [n, 5] for data d [n, P, P] in photons (ml_eval of csrc/localize.hip: the same sums
+    in the same order, pixel by pixel)."""
+    n, P, _ = d.shape
+    cost, mag, g, A = np.zeros(n), np.zeros(n), np.zeros((n, 5)), np.zeros((n, 5, 5))
+    with np.errstate(all="ignore"):
+        bad = ~(p[:, 0] > 0.0) | ~(p[:, 3] > MLE_MIN_SIGMA) | ~(p[:, 3] < float(P))
+        ok = ~bad
+        q = np.where(ok[:, None], p, np.array([1.0, 0.0, 0.0, 1.0, 1.0]))        # placeholders: their rows are zeroed below
+        Ex, dEx, sEx = _mle_axis(P, q[:, 1], q[:, 3], fs)
+        Ey, dEy, sEy = _mle_axis(P, q[:, 2], q[:, 3], fs)
+        nonpos = np.zeros(n, bool)
+        one = np.ones(n)
+        for iy in range(P):
+            nEy, ndEy, nsEy = q[:, 0] * Ey[iy], q[:, 0] * dEy[iy], q[:, 0] * sEy[iy]
+            for ix in range(P):
+                mu = (q[:, 4] + nEy * Ex[ix]) + read_var
+                nonpos |= ~(mu > 0.0)
+                dd = d[:, iy, ix]
+                rm = 1.0 / mu
+                r = dd * rm
+                cost = cost + np.where(dd > 0.0, (mu - dd) + dd * np.log(np.where(dd > 0.0, r, 1.0)), mu)
+                mag = mag + (mu + dd)
+                J = (Ex[ix] * Ey[iy], nEy * dEx[ix], ndEy * Ex[ix], nEy * sEx[ix] + nsEy * Ex[ix], one)
+                w = 1.0 - r
+                for i in range(5):
+                    g[:, i] = g[:, i] + J[i] * w
+                    Jr = J[i] * rm
+                    for j in range(i + 1):
+                        A[:, i, j] = A[:, i, j] + Jr * J[j]
+        cost, mag = 2.0 * cost, 2.0 * mag
+        if not fs:
+            A[:, 3, 3] = 1.0
+        cost[bad], mag[bad], g[bad], A[bad] = 0.0, 0.0, 0.0, 0.0
+    return cost, g, A, bad | (ok & nonpos), mag
+
+
+def _mle_crlb(A):
+    """Diagonal of A^-1 through the Cholesky factor (ml_crlb) -> (variances [n, 5], ok [n])."""
+    n = len(A)
+    L = np.zeros((n, 5, 5))
+    ok = np.ones(n, bool)
+    v = np.zeros((n, 5))
+    with np.errstate(all="ignore"):
+        for i in range(5):
+            for j in range(i + 1):
+                s = A[:, i, j].copy()
+                for k in range(j):
+                    s = s - L[:, i, k] * L[:, j, k]
+                if i == j:
+                    ok &= (s > 0.0) & (s < 1e300)
+                    L[:, i, i] = np.sqrt(np.where(ok, s, 1.0))
+                else:
+                    L[:, i, j] = s / L[:, j, j]
+        for j in range(5):
+            X = np.zeros((n, 5))
+            X[:, j] = 1.0 / L[:, j, j]
+            acc = X[:, j] * X[:, j]
+            for i in range(j + 1, 5):
+                s = np.zeros(n)
+                for k in range(j, i):
+                    s = s - L[:, i, k] * X[:, k]
+                X[:, i] = s / L[:, i, i]
+                acc = acc + X[:, i] * X[:, i]
+            v[:, j] = acc
+    return v, ok
+
+
+def _check_mle_args(shape, gain, offset, read_var, sigma0, xtol):
+    if len(shape) != 3 or shape[1] != shape[2]:
+        raise ValueError(f"patches must be [N, P, P], got {tuple(shape)}")
+    P = shape[1]
+    if P % 2 != 1 or not 3 <= P <= 15:
+        raise ValueError(f"patch side must be odd and from 3 to 15, got {P}")
+    if not (gain > 0 and math.isfinite(gain)):
+        raise ValueError(f"gain must be finite and > 0, got {gain}")
+    if not math.isfinite(offset):
+        raise ValueError(f"offset must be finite, got {offset}")
+    if not (read_var >= 0 and math.isfinite(read_var)):
+        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    if not MLE_MIN_SIGMA < sigma0 < P:
+        raise ValueError(f"sigma0 must lie in ({MLE_MIN_SIGMA}, {P}), got {sigma0}")
+    if not 0 < xtol <= 1.49012e-8:
+        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
+
+
+def _fit_mle_numpy(patches, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_sigma=True, xtol=FIT_XTOL,
+                   max_iter=FIT_MAX_ITER):
+    """The fit of csrc/localize.hip::ml_kernel for patches [N, P, P] on the host, all patches side by side -> (params [N, 5]
+    float64 (photons, x0, y0, sigma, background), crlb [N, 5] float64, deviance [N] float64, status [N] int32, iterations
+    [N] int32).  Equal to the kernel apart from erf, exp and log."""
+    raw = np.asarray(patches)
+    N, P, _ = raw.shape
+    fs = bool(fit_sigma)
+    status, iters = np.full(N, 2, np.int32), np.zeros(N, np.int32)
+    crlb = np.full((N, 5), np.nan)
+    if N == 0:
+        return np.zeros((0, 5)), crlb, np.zeros(0), status, iters
+    d = _mle_data(raw, gain, offset, read_var)
+    flat = d.reshape(N, -1)
+    finite = np.isfinite(raw.reshape(N, -1)).all(axis=1)
+    mx, mn = flat.max(axis=1), flat.min(axis=1)
+    total = np.zeros(N)
+    for t in range(P * P):
+        total = total + flat[:, t]
+    with np.errstate(invalid="ignore"):
+        b0 = np.maximum(mn, 1e-3 * mx)
+        total = total - float(P * P) * b0
+    p = np.stack([np.maximum(total, mx), np.full(N, float(P // 2)), np.full(N, float(P // 2)), np.full(N, float(sigma0)), b0],
+                 axis=1)
+    p[~finite] = np.nan
+    cost, g, A, bad, mag = _mle_normal(d, p, read_var, fs)
+    status[bad] = 1
+    with np.errstate(invalid="ignore"):
+        status[~bad & ~(cost < 1e300)] = 3
+    status[~finite] = 3
+    cost[~finite] = np.nan
+    lam = np.full(N, 1e-3)
+    for _ in range(max_iter):
+        act = np.nonzero(status == 2)[0]
+        if len(act) == 0:
+            break
+        iters[act] += 1
+        dstep, ok = _fit_solve(A[act], g[act], lam[act])
+        fail = act[~ok]
+        lam[fail] *= 10.0
+        status[fail[lam[fail] > 1e10]] = 1
+        act, dstep = act[ok], dstep[ok]
+        if len(act) == 0:
+            continue
+        pa = p[act]
+        a0, a4 = np.abs(pa[:, 0]), np.abs(pa[:, 4])
+        scale = np.stack([a0, np.maximum(np.abs(pa[:, 1]), 1.0), np.maximum(np.abs(pa[:, 2]), 1.0), np.abs(pa[:, 3]),
+                          np.maximum(a4, a0)], axis=1)
+        d0, ok0 = _fit_solve(A[act], g[act], 0.0)
+        with np.errstate(invalid="ignore"):
+            small = ok0 & (np.abs(d0) <= xtol * scale).all(axis=1)
+        q = pa + dstep
+        cq, gq, Aq, badq, mq = _mle_normal(d[act], q, read_var, fs)
+        # the slack of the least-squares loop, taken of the magnitude of the summed terms: the deviance is a sum of differences
+        # far larger than itself, and its rounding error is relative to those (csrc/localize.hip::ml_kernel)
+        with np.errstate(invalid="ignore"):
+            better = ~badq & (cq <= cost[act] + MLE_COST_SLACK * mag[act])
+        up = act[better]
+        p[up], cost[up], mag[up], g[up], A[up] = q[better], cq[better], mq[better], gq[better], Aq[better]
+        lam[up] = np.maximum(lam[up] * 0.1, 1e-12)
+        down = act[~better]
+        lam[down] *= 10.0
+        status[down[lam[down] > 1e10]] = 1
+        status[act[small]] = 0
+    done = np.nonzero(status == 0)[0]
+    if len(done):
+        v, ok = _mle_crlb(A[done])
+        if not fs:
+            v[:, 3] = 0.0
+        crlb[done[ok]] = v[ok]
+    return p, crlb, cost, status, iters
+
+
+def fit_spots_mle(patches, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_sigma=True, xtol=FIT_XTOL):
+    """Poisson maximum-likelihood fit of patches [N, P, P] (P odd, 3 .. 15; camera units, photons = max((patch - offset) /
+    gain, 0), read_var the readout variance in photons^2) with the Cramer-Rao bound of every parameter: CUDA float tensors go
+    to the kernel (ops.fit_spots_mle), anything else to the host restatement -> (params [N, 5] float64 (photons, x0, y0,
+    sigma, background per pixel), crlb [N, 5] float64 (variances; NaN where status != 0), deviance [N] float64, status [N]
+    int32, iterations [N] int32) of the input's kind.  fit_sigma=False holds sigma at sigma0."""
+    gain, offset, read_var, sigma0, xtol = float(gain), float(offset), float(read_var), float(sigma0), float(xtol)
+    _check_mle_args(patches.shape, gain, offset, read_var, sigma0, xtol)
+    if _is_cuda(patches):
+        from .. import ops
+        return ops.fit_spots_mle(patches.float(), gain, offset, read_var, sigma0, bool(fit_sigma), xtol)
+    if torch.is_tensor(patches):
+        out = _fit_mle_numpy(patches.detach().numpy(), gain, offset, read_var, sigma0, fit_sigma, xtol)
+        return tuple(torch.from_numpy(np.ascontiguousarray(o)) for o in out)
+    return _fit_mle_numpy(patches, gain, offset, read_var, sigma0, fit_sigma, xtol)
+
+
+_CAMERA_KEYS = ("gain", "offset", "read_var", "sigma0", "fit_sigma")
+
+
+def _check_refine_method(method, camera):
+    if method not in ("lsq", "mle"):
+        raise ValueError(f"method must be 'lsq' or 'mle', got {method!r}")
+    if camera is not None and (not isinstance(camera, dict) or set(camera) - set(_CAMERA_KEYS)):
+        raise ValueError(f"camera must be None or a dict with keys among {', '.join(_CAMERA_KEYS)}")
+    if camera is not None and method != "mle":
+        raise ValueError("camera needs method='mle': the least-squares fit has no camera model")
+    return dict(camera or {})
+
+
+def refine_localizations(patches, ys, xs, method="lsq", camera=None):
     """Sub-pixel positions of N localisations without pandas: patches [N, P, P] (extract_patches_flat) around the integer
     positions ys / xs [N] -> dict of numpy arrays x_refined, y_refined, psf_size (float64), max_intensity (the patches' dtype)
     and status (int32).  Where the fit failed (status != 0) the reference's fallback applies: the integer position and
-    psf_size 10."""
-    params, peak, status = refine_gaussian_patches(patches)
-    if torch.is_tensor(params):
-        params, peak, status = params.cpu().numpy(), peak.cpu().numpy(), status.cpu().numpy()
+    psf_size 10.
+
+    method "lsq" (default: the reference's unweighted least-squares fit, the code path without the argument) or "mle": the
+    Poisson maximum-likelihood fit (fit_spots_mle) with the camera model `camera`, a dict with keys among gain, offset,
+    read_var, sigma0 and fit_sigma.  "mle" adds x_std, y_std (square roots of the Cramer-Rao bounds, pixels), photons,
+    background (photons per pixel) and deviance (float64); they are NaN where status != 0."""
+    camera = _check_refine_method(method, camera)
+    if method == "mle":
+        params, crlb, dev, status, _ = fit_spots_mle(patches, **camera)
+        flat = patches.reshape(len(patches), -1)
+        if torch.is_tensor(params):
+            params, crlb, dev, status = (t.cpu().numpy() for t in (params, crlb, dev, status))
+            flat = flat.cpu().numpy()
+        peak = flat.max(axis=1) if len(flat) else flat[:, 0]
+    else:
+        params, peak, status = refine_gaussian_patches(patches)
+        if torch.is_tensor(params):
+            params, peak, status = params.cpu().numpy(), peak.cpu().numpy(), status.cpu().numpy()
     half = patches.shape[1] // 2
     if _is_cuda(ys):
         ys, xs = ys.cpu(), xs.cpu()
     ys, xs = np.asarray(ys), np.asarray(xs)
     okf = status == 0
-    return {"x_refined": np.where(okf, xs - half + params[:, 1], xs.astype(np.float64)),
-            "y_refined": np.where(okf, ys - half + params[:, 2], ys.astype(np.float64)),
-            "psf_size": np.where(okf, params[:, 3], float(FALLBACK_PSF_SIZE)),
-            "max_intensity": peak, "status": status}
+    res = {"x_refined": np.where(okf, xs - half + params[:, 1], xs.astype(np.float64)),
+           "y_refined": np.where(okf, ys - half + params[:, 2], ys.astype(np.float64)),
+           "psf_size": np.where(okf, params[:, 3], float(FALLBACK_PSF_SIZE)),
+           "max_intensity": peak, "status": status}
+    if method == "mle":
+        with np.errstate(invalid="ignore"):
+            res.update({"x_std": np.sqrt(crlb[:, 1]), "y_std": np.sqrt(crlb[:, 2]),
+                        "photons": np.where(okf, params[:, 0], np.nan), "background": np.where(okf, params[:, 4], np.nan),
+                        "deviance": np.where(okf, dev, np.nan)})
+    return res
 
 
 def add_refined_localization_to_dataframe(df_tracks, tracks, patches, patch_size):
@@ -1108,26 +1349,39 @@ def track_sequences(movie, frames, ys, xs, offsets, seq_len, patch_size=7, norm=
     return seq, torch.from_numpy(seq_track), torch.from_numpy(seq_row)
 
 
-def refine_localizations_tensors(patches, ys, xs):
+def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None):
     """refine_localizations without the copy to the host: CUDA patches [N, P, P] (extract_patches_flat) around the integer
     positions ys / xs [N] -> dict of CUDA tensors x_refined, y_refined, psf_size (float64), max_intensity (float32) and status
-    (int32), with the same fallback where the fit failed (status != 0): the integer position and psf_size 10."""
+    (int32), with the same fallback where the fit failed (status != 0): the integer position and psf_size 10.  method and
+    camera as refine_localizations: "mle" adds x_std, y_std, photons, background and deviance (float64, NaN where status !=
+    0)."""
     if not _is_cuda(patches):
         raise ValueError("refine_localizations_tensors needs CUDA patches; use refine_localizations on the host")
-    params, peak, status = refine_gaussian_patches(patches)
+    camera = _check_refine_method(method, camera)
+    if method == "mle":
+        params, crlb, dev, status, _ = fit_spots_mle(patches, **camera)
+        peak = patches.float().reshape(len(patches), -1).amax(dim=1) if len(patches) else patches.float().reshape(0)
+    else:
+        params, peak, status = refine_gaussian_patches(patches)
     half = patches.shape[1] // 2
     ys, xs = torch.as_tensor(ys).to(patches.device), torch.as_tensor(xs).to(patches.device)
     if not (len(ys) == len(xs) == len(params)):
         raise ValueError("patches, ys and xs must have one entry per localisation")
     okf = status == 0
-    return {"x_refined": torch.where(okf, xs - half + params[:, 1], xs.double()),
-            "y_refined": torch.where(okf, ys - half + params[:, 2], ys.double()),
-            "psf_size": torch.where(okf, params[:, 3], torch.full_like(params[:, 3], float(FALLBACK_PSF_SIZE))),
-            "max_intensity": peak, "status": status}
+    res = {"x_refined": torch.where(okf, xs - half + params[:, 1], xs.double()),
+           "y_refined": torch.where(okf, ys - half + params[:, 2], ys.double()),
+           "psf_size": torch.where(okf, params[:, 3], torch.full_like(params[:, 3], float(FALLBACK_PSF_SIZE))),
+           "max_intensity": peak, "status": status}
+    if method == "mle":
+        nan = torch.full_like(dev, float("nan"))
+        res.update({"x_std": torch.sqrt(crlb[:, 1]), "y_std": torch.sqrt(crlb[:, 2]),
+                    "photons": torch.where(okf, params[:, 0], nan), "background": torch.where(okf, params[:, 4], nan),
+                    "deviance": torch.where(okf, dev, nan)})
+    return res
 
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
-                             batch_size=4096, segment=None, states=None, drift=None, **tracking_kwargs):
+                             batch_size=4096, segment=None, states=None, drift=None, localization=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1160,7 +1414,26 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     through use) and subtracted (csrc/drift.hip), and track_msd, segment and states run on the corrected positions.  The
     result gains "drift": the estimate_drift dict plus positions, the corrected [N, 2].  D_model is unchanged by
     construction: the patches are cut from the movie at the detected positions, and a patch does not know where the stage
-    is."""
+    is.
+
+    localization (default None: the least-squares refinement, the code path without it): a dict with keys among gain, offset,
+    read_var, sigma0 and fit_sigma ({} for the defaults), the camera model of fit_spots_mle; needs refine=True.  The
+    refinement is then the Poisson maximum-likelihood fit (csrc/localize.hip, refine_localizations_tensors(method="mle")), and
+    the result gains "localization", the per-row tensors y_std, x_std (pixels), photons, background, psf_size, deviance and
+    status in the row order of tracks_table_by_track, and sigma2_loc [n_tracks]: the mean of (y_std^2 + x_std^2) / 2 over a
+    track's rows with status 0 that are not filled, NaN where there is none.  states = {"sigma2": "crlb", ...} passes the mean
+    of that quantity over all such rows of the movie to fit_diffusion_states as its localisation variance and reports it as
+    states["sigma2"] (the key is there only then); it is a ValueError without localization."""
+    if localization is not None:
+        if not isinstance(localization, dict) or set(localization) - set(_CAMERA_KEYS):
+            raise ValueError(f"localization must be None or a dict with keys among {', '.join(_CAMERA_KEYS)}")
+        if not refine:
+            raise ValueError("localization needs refine=True: it is the refinement")
+    if isinstance(states, dict) and isinstance(states.get("sigma2"), str):
+        if states["sigma2"] != "crlb":
+            raise ValueError(f"states['sigma2'] must be a number or 'crlb', got {states['sigma2']!r}")
+        if localization is None:
+            raise ValueError("states['sigma2'] = 'crlb' needs localization: the least-squares fit returns no bound")
     if drift is not None and (not isinstance(drift, dict) or set(drift) - {"estimator", "smoothing", "min_pairs"}):
         raise ValueError("drift must be None or a dict with keys among estimator, smoothing and min_pairs")
     if states is not None:
@@ -1183,7 +1456,27 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     lengths = offsets[1:] - offsets[:-1]
     n_tracks = len(lengths)
     movie = movie.float()
-    if refine:
+    located, from_crlb = None, False
+    if refine and localization is not None:
+        fit = refine_localizations_tensors(extract_patches_flat(movie, fr, y, x, patch_size), y, x, method="mle",
+                                           camera=localization)
+        pos = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1)
+        located = {k: fit[k] for k in ("y_std", "x_std", "photons", "background", "psf_size", "deviance", "status")}
+        var_row = (fit["y_std"] * fit["y_std"] + fit["x_std"] * fit["x_std"]) / 2.0
+        good = fit["status"] == 0
+        if len(by_track) > 5:
+            good = good & ~by_track[5]
+        row_of = torch.repeat_interleave(torch.arange(n_tracks, device=movie.device), lengths)
+        zero = torch.zeros((), dtype=torch.float64, device=movie.device)
+        n_good = torch.bincount(row_of[good], minlength=n_tracks)
+        sigma2_loc = torch.zeros(n_tracks, dtype=torch.float64, device=movie.device).index_add_(
+            0, row_of, torch.where(good, var_row, zero)) / n_good
+        sigma2_loc = torch.where(n_good > 0, sigma2_loc, torch.full_like(sigma2_loc, float("nan")))
+        if states is not None and states.get("sigma2") == "crlb":
+            if not bool(good.any()):
+                raise ValueError("states['sigma2'] = 'crlb': no row of the movie has a converged fit")
+            states, from_crlb = dict(states, sigma2=float(var_row[good].mean())), True
+    elif refine:
         fit = refine_localizations_tensors(extract_patches_flat(movie, fr, y, x, patch_size), y, x)
         pos = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1)
     else:
@@ -1224,6 +1517,8 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     if states is not None:
         from . import msd as _msd
         fitted = _msd.fit_diffusion_states(pos, offsets, dt=dt, **states)
+        if from_crlb:
+            fitted["sigma2"] = float(states["sigma2"])
         st = fitted["state"]
         first = torch.zeros(len(st), dtype=torch.bool, device=movie.device)
         first[1:] = st[1:] != st[:-1]
@@ -1246,6 +1541,8 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["states"] = fitted
     if drifted is not None:
         res["drift"] = drifted
+    if located is not None:
+        res["localization"], res["sigma2_loc"] = located, sigma2_loc
     return res
 
 

@@ -622,6 +622,41 @@ def refine_gaussian(patches: torch.Tensor, xtol: float = 1e-11):
     return params, peak, status
 
 
+def fit_spots_mle(patches: torch.Tensor, gain: float = 1.0, offset: float = 0.0, read_var: float = 0.0, sigma0: float = 1.0,
+                  fit_sigma: bool = True, xtol: float = 1e-11):
+    """Poisson maximum-likelihood fit of every patch with its Cramer-Rao bound (csrc/localize.hip, mivit_fit_spots_mle):
+    patches [N, P, P] float32 on the GPU, P odd, 3 .. 15, in camera units; photons = max((patch - offset) / gain, 0), read_var
+    the readout variance in photons^2 -> (params [N, 5] float64 (photons, x0, y0, sigma, background per pixel), crlb [N, 5]
+    float64 (variances; NaN where status != 0), deviance [N] float64, status [N] int32 (0 where the fit converged),
+    iterations [N] int32).  fit_sigma=False holds sigma at sigma0."""
+    import math
+    patches = _frames_f32(patches, "fit_spots_mle")
+    if patches.dim() != 3 or patches.shape[1] != patches.shape[2]:
+        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    n, P, _ = patches.shape
+    gain, offset, read_var, sigma0, xtol = float(gain), float(offset), float(read_var), float(sigma0), float(xtol)
+    if not (gain > 0 and math.isfinite(gain)):
+        raise ValueError(f"gain must be finite and > 0, got {gain}")
+    if not math.isfinite(offset):
+        raise ValueError(f"offset must be finite, got {offset}")
+    if not (read_var >= 0 and math.isfinite(read_var)):
+        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    if not 0.2 < sigma0 < P:
+        raise ValueError(f"sigma0 must lie in (0.2, {P}), got {sigma0}")
+    if not 0 < xtol <= 1.49012e-8:
+        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
+    dev = patches.device
+    params = torch.zeros(n, 5, dtype=torch.float64, device=dev)
+    crlb = torch.zeros(n, 5, dtype=torch.float64, device=dev)
+    deviance = torch.zeros(n, dtype=torch.float64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    iterations = torch.zeros(n, dtype=torch.int32, device=dev)
+    N.check(N.lib.mivit_fit_spots_mle(_p(patches), n, P, gain, offset, read_var, sigma0, 1 if fit_sigma else 0, xtol,
+                                      _p(params), _p(crlb), _p(deviance), _p(status), _p(iterations), _s(patches)),
+            "mivit_fit_spots_mle")
+    return params, crlb, deviance, status, iterations
+
+
 LINK_MAX_DETECTIONS = 1024
 
 

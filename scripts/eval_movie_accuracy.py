@@ -27,7 +27,16 @@ velocity, the mean of the estimated one and the RMS error of the estimated drift
 --drift-estimator mean|median and --drift-smoothing H, csrc/drift.hip, through estimate_track_diffusion(..., drift={...})),
 and over the matched tracks the medians of D_true and of D_msd and D_msd_weighted without and with the correction (the
 per-track columns gain D_msd_corrected and D_msd_weighted_corrected); with --states --hmm K also the fitted Ds of K without
-and with it.  A tool, not a test: it asserts no accuracy.
+and with it.  --camera BG,GAIN,OFFSET[,READ] replaces the training image model by a photon-counting camera
+(simulate_movie's camera: BG photons per pixel, GAIN ADU per photon, OFFSET ADU, READ noise in ADU; particle_intensity is then
+the peak in photons) and adds "camera": for the least-squares refinement, and with --mle beside it for the Poisson
+maximum-likelihood one (csrc/localize.hip, estimate_track_diffusion(..., localization={...})), the RMS position error per
+axis over the rows of matched tracks that lie within --max-distance of their particle, the RMS of error / reported std (ML
+only), the medians of D_msd, D_msd_weighted and of D_cve over the matched tracks, the mean CRLB ((y_std^2 + x_std^2) / 2 over
+the converged rows) beside the median sigma2 that segment_tracks estimates from the covariances of neighbouring increments
+(which also contains the motion blur), the mean deviance per degree of freedom, and with --states --hmm K the fitted Ds with
+sigma2 = 0 and with sigma2 = "crlb".  --intensity PEAK sets the mean of particle_intensity (its spread scaled along), the peak
+of a spot in the movie's units: photons with --camera.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
@@ -35,6 +44,7 @@ and with it.  A tool, not a test: it asserts no accuracy.
                                           [--cristae 4 30 60 12] [--boundary reflect]
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
+                                          [--camera 10,2,100,1.5] [--mle] [--intensity 300]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -79,7 +89,21 @@ def main():
     ap.add_argument("--drift", default=None, metavar="VY,VX")
     ap.add_argument("--drift-estimator", choices=["mean", "median"], default="mean")
     ap.add_argument("--drift-smoothing", type=int, default=0, metavar="H")
+    ap.add_argument("--camera", default=None, metavar="BG,GAIN,OFFSET[,READ]")
+    ap.add_argument("--mle", action="store_true")
+    ap.add_argument("--intensity", type=float, default=None, metavar="PEAK")
     args = ap.parse_args()
+    camera = None
+    if args.camera is not None:
+        try:
+            v = [float(t) for t in args.camera.split(",")]
+        except ValueError:
+            v = []
+        if len(v) not in (3, 4):
+            raise SystemExit("--camera takes BG,GAIN,OFFSET[,READ]")
+        camera = {"background": v[0], "gain": v[1], "offset": v[2], "read_noise": v[3] if len(v) == 4 else 0.0}
+    elif args.mle:
+        raise SystemExit("--mle needs --camera: the maximum-likelihood fit assumes photon counts")
     drift = None
     if args.drift is not None:
         try:
@@ -91,6 +115,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("eval_movie_accuracy.py needs a GPU")
     props = dict(gen.DEFAULT_IMAGE_PROPS)
+    if args.intensity is not None:
+        props["particle_intensity"] = [args.intensity, props["particle_intensity"][1] * args.intensity / props["particle_intensity"][0]]
     if args.noise_free:
         props.update({"background_intensity": [props["background_intensity"][0], 0.0], "poisson_noise": -1})
     H, W = args.size
@@ -112,13 +138,17 @@ def main():
         states = {"Ds": [d1, d2], "M": [[stay, 1.0 - stay], [1.0 - stay, stay]]}
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, None if states else tuple(args.D), args.npos,
                                       image_props=props, generator=g, device="cuda", blink=args.blink, alphas=args.alpha,
-                                      states=states, **confine, **({} if drift is None else {"drift": drift}))
+                                      states=states, **confine, **({} if drift is None else {"drift": drift}),
+                                      **({} if camera is None else {"camera": camera}))
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location="cuda"))
     bm, bs = props["background_intensity"]
-    norm = (bm, bs, props["particle_intensity"][0] + bm)
+    if camera is not None:                                   # the same three numbers in camera units
+        bm = camera["offset"] + camera["gain"] * camera["background"]
+        bs = (camera["gain"] ** 2 * camera["background"] + camera["read_noise"] ** 2) ** 0.5
+    norm = (bm, bs, (camera["gain"] if camera else 1.0) * props["particle_intensity"][0] + bm)
     est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap)
     table, _ = trk.track_particles_tensors(movie, return_dog=False, max_gap=args.max_gap)
     fr, y, x, tid = trk.tracks_table_by_track(table)[:4]
@@ -165,6 +195,8 @@ def main():
         out["alpha_msd_truth_unblurred_median"] = float(MSD.estimate_alpha(s_msd, max_lag=args.alpha_max_lag).nanmedian())
     if drift is not None:
         out["drift"] = drift_scores(movie, model, args, norm, truth, score, est, out["tracks"], states)
+    if camera is not None:
+        out["camera"] = camera_scores(movie, model, args, norm, truth, score, props, camera, states)
     if states is not None:
         out["states"] = args.states
         out["segmentation"] = [segmentation_scores(movie, model, args, norm, truth, score, fr, float(p)) for p in args.penalties]
@@ -196,6 +228,61 @@ def drift_scores(movie, model, args, norm, truth, score, est, rows, states):
         raw = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap, **hmm)
         out["hmm_Ds"], out["hmm_Ds_corrected"] = raw["states"]["Ds"].tolist(), cor["states"]["Ds"].tolist()
         out["planted_Ds"] = sorted(states["Ds"])
+    return out
+
+
+def camera_scores(movie, model, args, norm, truth, score, props, camera, states):
+    """least-squares and maximum-likelihood localisation side by side (see the module's docstring)"""
+    loc = {"gain": camera["gain"], "offset": camera["offset"], "read_var": (camera["read_noise"] / camera["gain"]) ** 2,
+           "sigma0": gen.psf_sigma_hr(props) / props["upsampling_factor"]}
+    table, _ = trk.track_particles_tensors(movie, return_dog=False, max_gap=args.max_gap)
+    fr, y, x, _, offsets = trk.tracks_table_by_track(table)[:5]
+    lengths = offsets[1:] - offsets[:-1]
+    row_track = torch.repeat_interleave(torch.arange(len(lengths), device=movie.device), lengths)
+    pid = score["particle_id"][row_track]
+    nan = float("nan")
+    true = torch.full((args.particles, args.frames, 2), nan, dtype=torch.float64, device=movie.device)
+    true[truth["particle_id"], truth["frame"]] = torch.stack([truth["y"], truth["x"]], dim=1)
+    want = true[pid.clamp_min(0), fr.clamp(0, args.frames - 1)]
+    patches = trk.extract_patches_flat(movie.float(), fr, y, x, args.patch_size)
+    track_ok = score["particle_id"] >= 0
+    med = lambda col: float(col[track_ok].double().nanmedian()) if bool(track_ok.any()) else nan             # noqa: E731
+    hmm = states is not None and args.hmm is not None
+    out = {"camera": camera, "fit": loc, "peak_photons": props["particle_intensity"][0],
+           "photons_true_mean": float(truth["photons"].mean()) if len(truth["photons"]) else nan}
+    for method in ("lsq", "mle") if args.mle else ("lsq",):
+        how = {"method": "mle", "camera": loc} if method == "mle" else {}
+        fit = trk.refine_localizations_tensors(patches, y, x, **how)
+        err = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1) - want
+        ok = (pid >= 0) & (fit["status"] == 0) & (err.pow(2).sum(dim=1).sqrt() <= args.max_distance)
+        est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
+                                           segment={}, **({"localization": loc} if method == "mle" else {}))
+        seg = est["segments"]
+        col = {"rows_scored": int(ok.sum()), "rows": int(len(fr)), "converged": float((fit["status"] == 0).double().mean()),
+               "rmse_y": float(err[ok, 0].pow(2).mean().sqrt()), "rmse_x": float(err[ok, 1].pow(2).mean().sqrt()),
+               "D_true_median": med(score["D_true"]), "D_msd_median": med(est["D_msd"]),
+               "D_msd_weighted_median": med(est["D_msd_weighted"]), "D_cve_median": float(seg["D_cve"].nanmedian()),
+               "sigma2_from_covariances_median": float(seg["sigma2"].nanmedian())}
+        if method == "mle":
+            var = (fit["y_std"] ** 2 + fit["x_std"] ** 2) / 2.0
+            dof = args.patch_size ** 2 - 5
+            col.update({"rms_error_over_std_y": float((err[ok, 0] / fit["y_std"][ok]).pow(2).mean().sqrt()),
+                        "rms_error_over_std_x": float((err[ok, 1] / fit["x_std"][ok]).pow(2).mean().sqrt()),
+                        "crlb_mean": float(var[fit["status"] == 0].mean()), "sigma2_loc_median": float(est["sigma2_loc"].nanmedian()),
+                        "photons_fitted_mean": float(fit["photons"][ok].mean()), "background_fitted_mean": float(fit["background"][ok].mean()),
+                        "deviance_per_dof": float(fit["deviance"][ok].mean()) / dof})
+            if hmm:
+                kw = dict(norm=norm, max_gap=args.max_gap, localization=loc)
+                zero = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, states={"K": args.hmm}, **kw)
+                crlb = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size,
+                                                    states={"K": args.hmm, "sigma2": "crlb"}, **kw)
+                col.update({"hmm_Ds_sigma2_0": zero["states"]["Ds"].tolist(), "hmm_Ds_sigma2_crlb": crlb["states"]["Ds"].tolist(),
+                            "hmm_sigma2_used": crlb["states"]["sigma2"], "planted_Ds": sorted(states["Ds"])})
+        elif hmm:
+            zero = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
+                                                states={"K": args.hmm})
+            col.update({"hmm_Ds_sigma2_0": zero["states"]["Ds"].tolist(), "planted_Ds": sorted(states["Ds"])})
+        out[method] = col
     return out
 
 
