@@ -884,7 +884,9 @@ int mivit_backward(const mivit_plan *plan, const float *params, const float *x, 
 
 /* hipGraph replay statistics.  mivit_forward / mivit_backward / mivit_deepresnet_train_* on small (launch-bound) problems
  * capture their kernel sequence into a hipGraph the second time they see the same arguments and replay it afterwards
- * (MIVIT_GRAPHS=0 disables; off while mivit_profile_enable is active). */
+ * (MIVIT_GRAPHS=0 disables; off while mivit_profile_enable is active).  A replay reads the current contents of every buffer:
+ * only addresses, sizes and the launch sequence are frozen.  Changing any mivit_*_set_* switch starts the affected keys over
+ * (the next call runs directly, the one after is captured under the new value). */
 void mivit_graph_stats(uint64_t *replays, uint64_t *captures, int *failures);
 
 /* Readout-row pruning of the last encoder layer (fused 16-bit layers with the regression-token readout, more than one token):

@@ -449,5 +449,9 @@ struct ProfPin {          // prof_pin_tag for a lifetime (set() re-pins)
 // hipGraph replay of launch-bound call sequences (misc.hip).  `key` must hold every value the body's launches depend on
 // (pointers, sizes).  First sighting of a key: body(s) runs directly.  Second: body is captured on an internal stream,
 // instantiated and launched on s.  Later: replay.  Disabled by MIVIT_GRAPHS=0, while the in-library profiler is on, and
-// after repeated capture failures; small LRU.
+// after repeated capture failures; small LRU.  A replay reads the current contents of every buffer; only addresses, sizes
+// and the launch sequence are frozen.  graph_run appends the device and the switch epoch to every key: a run-time switch that
+// can change what a body launches (every mivit_*_set_*) calls graph_switch_changed() when its value changes, so that no call
+// site has to list the switches and a key captured under the old value is never replayed under the new one.
+void graph_switch_changed();
 int graph_run(const uint64_t *key, int nkey, hipStream_t s, const std::function<int(hipStream_t)> &body);

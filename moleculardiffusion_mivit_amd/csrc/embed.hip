@@ -730,7 +730,11 @@ int fwd_dma_launch(const EmbFwdArgs &a, hipStream_t s) {
 // forward tiling, selectable for A/B runs and so that the tests reach every launcher branch at small sizes:
 // MIVIT_EMBED_FWD_VARIANT / mivit_embed_set_variant (0 = by problem size)
 static int g_embed_variant = getenv("MIVIT_EMBED_FWD_VARIANT") ? atoi(getenv("MIVIT_EMBED_FWD_VARIANT")) : 0;
-extern "C" int mivit_embed_set_variant(int v) { const int old = g_embed_variant; g_embed_variant = v; return old; }
+extern "C" int mivit_embed_set_variant(int v) {
+    const int old = g_embed_variant; g_embed_variant = v;
+    if (v != old) graph_switch_changed();          // captured launch sequences made under the old value start over
+    return old;
+}
 
 bool embed_dma_supported(int dtype, int M, int K, int E) {
     return dtype == MIVIT_ELEM_DTYPE && E % 128 == 0 && K % 128 == 0 && K >= 256 && M >= 128;

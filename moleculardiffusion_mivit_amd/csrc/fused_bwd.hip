@@ -1126,6 +1126,7 @@ static int g_mlp_bwd_waves = [] { const char *e = getenv("MIVIT_MLP_BWD_WAVES");
 extern "C" int mivit_mlp_block_bwd_set_waves(int waves) {
     const int old = g_mlp_bwd_waves;
     if (waves == 4 || waves == 8) g_mlp_bwd_waves = waves;
+    if (g_mlp_bwd_waves != old) graph_switch_changed();      // captured launch sequences made under the old value start over
     return old;
 }
 #endif

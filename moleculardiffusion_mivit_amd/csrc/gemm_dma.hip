@@ -603,7 +603,11 @@ int launch_gemm_dma_dgrad(const void *dy, int64_t lddy, const void *W_bf16, int 
     return launch_variant<true>(a, s);
 }
 
-extern "C" int mivit_gemm_dma_set_variant(int v) { const int old = g_variant; g_variant = v; return old; }
+extern "C" int mivit_gemm_dma_set_variant(int v) {
+    const int old = g_variant; g_variant = v;
+    if (v != old) graph_switch_changed();          // captured launch sequences made under the old value start over
+    return old;
+}
 extern "C" int mivit_gemm_dma_supported(int M, int N, int K, int dgrad) {
     return dgrad ? gemm_dma_supported(M, K, N, true) : gemm_dma_supported(M, N, K, false);
 }

@@ -24,6 +24,7 @@ extern "C" int mivit_device_count(void) {
 // ------------------------------------------------------------------------------------------------
 // kernel timing
 // ------------------------------------------------------------------------------------------------
+#include <atomic>
 #include <mutex>
 #include <vector>
 namespace {
@@ -295,6 +296,7 @@ struct GraphEntry {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t last_use = 0;
+    int dev = 0;
 };
 struct GraphState {
     std::mutex mu;
@@ -305,14 +307,26 @@ struct GraphState {
     uint64_t replays = 0, captures = 0;
 };
 GraphState g_graph;
+std::atomic<uint64_t> g_switch_epoch{0};      // bumped by every run-time switch whose value changed; part of every key
 size_t graph_cap() { static const size_t c = [] { const char *e = getenv("MIVIT_GRAPH_CAP"); return e ? (size_t)atoi(e) : (size_t)32; }(); return c; }
 
-void graph_drop(GraphEntry &e) {
-    if (e.exec) (void)hipGraphExecDestroy(e.exec);
+// An evicted exec may still have its last launch in flight on a caller's stream.  HIP documents nothing about destroying an
+// exec that is executing (CUDA frees it asynchronously on completion; hipGraphExecDestroy promises only hipSuccess), so
+// the entry's device is drained first.  Evictions are rare (more than graph_cap() live keys) and an entry that was never
+// captured costs nothing.
+void graph_drop(GraphEntry &e, int cur_dev) {
+    if (e.exec) {
+        if (e.dev != cur_dev) (void)hipSetDevice(e.dev);
+        (void)hipDeviceSynchronize();
+        if (e.dev != cur_dev) (void)hipSetDevice(cur_dev);
+        (void)hipGraphExecDestroy(e.exec);
+    }
     if (e.graph) (void)hipGraphDestroy(e.graph);
     e.exec = nullptr; e.graph = nullptr;
 }
 }  // namespace
+
+void graph_switch_changed() { g_switch_epoch.fetch_add(1, std::memory_order_relaxed); }
 
 int graph_run(const uint64_t *key, int nkey, hipStream_t s, const std::function<int(hipStream_t)> &body) {
     GraphState &g = g_graph;
@@ -326,6 +340,7 @@ int graph_run(const uint64_t *key, int nkey, hipStream_t s, const std::function<
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { lk.unlock(); return body(s); }
     std::vector<uint64_t> k(key, key + nkey);
     k.push_back((uint64_t)dev);
+    k.push_back(g_switch_epoch.load(std::memory_order_relaxed));
     GraphEntry *hit = nullptr;
     for (auto &e : g.entries)
         if (e.key == k) { hit = &e; break; }
@@ -340,10 +355,10 @@ int graph_run(const uint64_t *key, int nkey, hipStream_t s, const std::function<
             size_t lru = 0;
             for (size_t i = 1; i < g.entries.size(); ++i)
                 if (g.entries[i].last_use < g.entries[lru].last_use) lru = i;
-            graph_drop(g.entries[lru]);
+            graph_drop(g.entries[lru], dev);
             g.entries.erase(g.entries.begin() + lru);
         }
-        GraphEntry e; e.key = k; e.last_use = g.tick;
+        GraphEntry e; e.key = k; e.last_use = g.tick; e.dev = dev;
         g.entries.push_back(e);
         lk.unlock();
         return body(s);

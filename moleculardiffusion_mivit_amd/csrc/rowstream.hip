@@ -362,8 +362,17 @@ int launch_rowstream(bool dgrad, const void *A, int64_t lda, const void *W_bf16,
 }
 
 // operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
-extern "C" int mivit_rowstream_set_wavestream(int mode) { const int old = g_use_ws; g_use_ws = mode; return old; }
-extern "C" int mivit_rowstream_set_wavestream_mask(int mask) { const int old = g_ws_mask; g_ws_mask = mask; return old; }
+// (a changed switch starts every captured launch sequence over: graph_switch_changed, misc.hip)
+extern "C" int mivit_rowstream_set_wavestream(int mode) {
+    const int old = g_use_ws; g_use_ws = mode;
+    if (mode != old) graph_switch_changed();
+    return old;
+}
+extern "C" int mivit_rowstream_set_wavestream_mask(int mask) {
+    const int old = g_ws_mask; g_ws_mask = mask;
+    if (mask != old) graph_switch_changed();
+    return old;
+}
 extern "C" int mivit_rowstream_fwd(const void *x, int64_t ldx, const void *W_bf16, const float *bias, int M, int N, int K,
                                    int act, const void *resid, int64_t ldr, void *y, int64_t ldy, void *y_preact,
                                    const float *ln_gamma, const float *ln_beta, void *ln_out, float *mean, float *rstd,

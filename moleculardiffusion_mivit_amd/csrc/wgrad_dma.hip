@@ -223,7 +223,11 @@ int launch_wgrad_dma(const void *dy, int64_t lddy, const void *x, int64_t ldx, i
 }
 
 // operator-level C-ABI (include/mivit_hip.h): the fp16 build exports the same entries suffixed _f16 (elem.h)
-extern "C" int mivit_wgrad_bf16_set_config(int cfg) { const int old = g_cfg; g_cfg = cfg; return old; }
+extern "C" int mivit_wgrad_bf16_set_config(int cfg) {
+    const int old = g_cfg; g_cfg = cfg;
+    if (cfg != old) graph_switch_changed();        // captured launch sequences made under the old value start over
+    return old;
+}
 extern "C" size_t mivit_wgrad_bf16_workspace_bytes(int M, int N, int K) {
     return (N % TILE == 0 && K % TILE == 0) ? wgrad_dma_ws_bytes(M, N, K) : 0;
 }

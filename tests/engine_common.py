@@ -1,6 +1,7 @@
 """Case table, fp64 reference, bf16-autocast yardstick and arena packing of the engine-dispatch suites
 (tests/test_engine_paths.py on the host, tests/test_engine_paths_gpu.py on the device).  Host only: nothing here imports the
-HIP library, so the table and both oracles are checked where no GPU exists.
+HIP library, so the table and both oracles are checked where no GPU exists.  At the end: `Rig` and `Guarded`, the device
+buffers of tests/test_engine_paths_gpu.py and tests/test_graph_replay_gpu.py; they load the library when one is made.
 
 A case is one point of the constructor surface chosen for the BRANCH of csrc/engine.hip it reaches (fused blocks or per-operator
 layers, the stage-0 readout variants, the zero-layer trunk, the external embedding), not for the experiment it mirrors; the
@@ -194,6 +195,19 @@ def pick_salt(case, B):
     return _pick_salt(case.name, B)
 
 
+def nth_salt(case, B, n, params=None):
+    """The n-th (from 0) input salt below 64 that is admissible in the sense of pick_salt under `params` (fp64, reference
+    keys; default: the closed-form set, so nth_salt(case, B, 0) == pick_salt(case, B)).  None: fewer than n + 1 such salts."""
+    p = orc.closed_form_params(case.cfg, dtype=torch.float64) if params is None else params
+    for salt in range(64):
+        frames, _, _, feats = _batch64(case.name, B, salt)
+        if orc.min_kink_margin(p, case.cfg, frames, feats) > KINK_MARGIN:
+            if n == 0:
+                return salt
+            n -= 1
+    return None
+
+
 # ---- error measures ---------------------------------------------------------------------------------------------------------
 def _tensors(r):
     """Gradient tensors of a result in one dict.  d(features) / d(tokens) live on another scale than the parameter gradients
@@ -265,3 +279,119 @@ def padding_mask(plan):
 
 def unpack_arena(plan, arena):
     return {name: arena[off:off + n] for name, off, n in zip(plan.param_names, plan.param_offsets, plan.param_numels)}
+
+
+# ---- device side: one plan with guarded buffers at fixed addresses -------------------------------------------------------------
+# (the HIP library is imported when a Rig is made, not when this module is: the table and the oracles stay host-only)
+def _native():
+    from moleculardiffusion_mivit_amd import _native as N
+    return N
+
+
+LOSS_SCALE = {"fp32": 1.0, "bf16": 1.0, "fp16": 4096.0}
+GUARD_BYTES = 4096
+
+
+class Guarded:
+    """`numel` elements of `dtype` inside a larger device allocation: 256 bytes in front of and 4 KiB behind the region hold
+    a byte pattern that must survive every call."""
+    PATTERN = 0xA5
+
+    def __init__(self, numel, dtype):
+        self.isz = torch.empty(0, dtype=dtype).element_size()
+        self.front, self.nbytes = 256, numel * self.isz
+        self.raw = torch.full((self.front + self.nbytes + GUARD_BYTES,), self.PATTERN, dtype=torch.uint8, device="cuda")
+        assert self.raw.data_ptr() % 256 == 0
+        self.t = self.raw[self.front:self.front + self.nbytes].view(dtype)
+
+    def intact(self):
+        return bool((self.raw[:self.front] == self.PATTERN).all()) and bool((self.raw[self.front + self.nbytes:] == self.PATTERN).all())
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def same(a, b):
+    """bitwise equality of two fp32 tensors (NaN payloads included)"""
+    return a.shape == b.shape and bool(torch.equal(bits(a), bits(b)))
+
+
+class Rig:
+    """One plan with its device buffers at fixed addresses."""
+
+    def __init__(self, case, precision, B, salt):
+        from moleculardiffusion_mivit_amd.engine import MivitPlan
+        N = _native()
+        cfg = case.cfg
+        self.case, self.precision, self.B, self.T = case, precision, B, case.T
+        self.scale = LOSS_SCALE[precision]
+        self.plan = plan = MivitPlan(
+            precision=precision, embedding={"linear": N.EMBED_LINEAR, "cnn": N.EMBED_CNN, "external": N.EMBED_EXTERNAL}[case.embedding],
+            patch_size=0 if case.embedding == "external" else cfg.patch_size, embed_dim=cfg.embed_dim, num_heads=cfg.num_heads,
+            hidden_dim=cfg.hidden_dim, num_layers=cfg.num_layers,
+            activation={"relu": N.ACT_RELU, "leaky_relu": N.ACT_LEAKY_RELU, "gelu": N.ACT_GELU}[cfg.activation],
+            use_pos_encoding=cfg.use_pos_encoding, use_regression_token=cfg.use_regression_token,
+            fusion={"none": N.FUSION_NONE, "early": N.FUSION_EARLY, "late": N.FUSION_LATE}[case.fusion],
+            global_feature_dim=cfg.global_feature_dim or 0, head_hidden=cfg.head_hidden, output_dim=cfg.output_dim)
+        assert sorted(plan.param_names) == sorted(param_names(case))
+        self.pad = padding_mask(plan).cuda()
+        self.arena = pack_arena(plan, orc.closed_form_params(cfg, dtype=torch.float64)).cuda()
+        x, labels, feats = batch(case, B, salt, torch.float32)
+        self.x, self.labels = x.contiguous().cuda(), labels.cuda()
+        self.feats = None if feats is None else feats.contiguous().cuda()
+        self.ws = Guarded(plan.workspace_bytes(B, case.T, True), torch.uint8)
+        self.out = Guarded(B * cfg.output_dim, torch.float32)
+        self.grads = Guarded(plan.arena_numel, torch.float32)
+        self.dfeat = Guarded(B * cfg.global_feature_dim, torch.float32) if case.dfeatures else None
+        self.dx = Guarded(B * case.T * cfg.embed_dim, torch.float32) if case.dx_tokens else None
+        self.dout = torch.zeros(B, cfg.output_dim, device="cuda")
+        self.guards = [g for g in (self.ws, self.out, self.grads, self.dfeat, self.dx) if g is not None]
+
+    def _poison(self):
+        for g in (self.out, self.grads, self.dfeat, self.dx):
+            if g is not None:
+                bits(g.t).fill_(SENTINEL)          # the NaN sentinel as a signed word
+
+    def forward(self, ws_fill=None):
+        self._poison()
+        if ws_fill is not None:
+            self.ws.t.fill_(ws_fill)
+        self.plan.forward(self.arena, self.x, self.feats, self.B, self.T, self.ws.t, True, self.out.t)
+        out = self.out.t.view(self.B, -1)
+        self.loss = F.mse_loss(out, self.labels)
+        self.dout.copy_((out - self.labels) * (2.0 * self.scale / out.numel()))
+
+    def backward(self, s0=0, s1=None, dfeat=True, dx=True):
+        self.plan.backward(self.arena, self.x, self.feats, self.B, self.T, self.ws.t, self.dout, self.grads.t,
+                           self.dfeat.t if (self.dfeat is not None and dfeat) else None,
+                           self.dx.t if (self.dx is not None and dx) else None, s0, self.plan.num_stages if s1 is None else s1)
+
+    def snapshot(self):
+        torch.cuda.synchronize()
+        assert all(g.intact() for g in self.guards), "a kernel wrote outside its buffer"
+        return SimpleNamespace(out=self.out.t.view(self.B, -1).clone(), loss=self.loss.clone(), arena=self.grads.t.clone(),
+                               dfeat=None if self.dfeat is None else self.dfeat.t.clone(),
+                               dx=None if self.dx is None else self.dx.t.clone())
+
+    def step(self, ws_fill=None, **kw):
+        self.forward(ws_fill)
+        self.backward(**kw)
+        return self.snapshot()
+
+    def result(self, snap):
+        """a snapshot in the oracle's terms: unscaled gradients by reference name"""
+        shapes = orc.param_shapes(self.case.cfg)
+        cfg = self.case.cfg
+        g = {k: (v / self.scale).reshape(shapes[k]) for k, v in unpack_arena(self.plan, snap.arena).items()}
+        return SimpleNamespace(out=snap.out, loss=snap.loss, grads=g,
+                               dfeatures=None if snap.dfeat is None else (snap.dfeat / self.scale).view(self.B, cfg.global_feature_dim),
+                               dx_tokens=None if snap.dx is None else (snap.dx / self.scale).view(self.B, self.T, cfg.embed_dim))
+
+
+def graph_stats():
+    """(replays, captures, failures) of the library's hipGraph cache"""
+    import ctypes
+    r, c, f = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+    _native().lib.mivit_graph_stats(ctypes.byref(r), ctypes.byref(c), ctypes.byref(f))
+    return r.value, c.value, f.value

@@ -8,124 +8,23 @@ fp16 runs its backward under a loss scale of 2**12 (what GradScaler does, as in 
 gradients are unscaled, exactly, before the comparison; bitwise comparisons are made on the scaled values."""
 import ctypes
 import functools
-from types import SimpleNamespace
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import engine_common as ec
-from oracle import mivit_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 NAMES = [c.name for c in ec.CASES]
 ALL = [(n, p) for n in NAMES for p in ec.PRECISIONS]
 IDS = [f"{n}-{p}" for n, p in ALL]
-LOSS_SCALE = {"fp32": 1.0, "bf16": 1.0, "fp16": 4096.0}
-GUARD_BYTES = 4096
+Guarded, Rig, _bits, _same = ec.Guarded, ec.Rig, ec.bits, ec.same          # (shared with tests/test_graph_replay_gpu.py)
 
 
 def _native():
     from moleculardiffusion_mivit_amd import _native as N
     return N
-
-
-class Guarded:
-    """`numel` elements of `dtype` inside a larger device allocation: 256 bytes in front of and 4 KiB behind the region hold
-    a byte pattern that must survive every call."""
-    PATTERN = 0xA5
-
-    def __init__(self, numel, dtype):
-        self.isz = torch.empty(0, dtype=dtype).element_size()
-        self.front, self.nbytes = 256, numel * self.isz
-        self.raw = torch.full((self.front + self.nbytes + GUARD_BYTES,), self.PATTERN, dtype=torch.uint8, device="cuda")
-        assert self.raw.data_ptr() % 256 == 0
-        self.t = self.raw[self.front:self.front + self.nbytes].view(dtype)
-
-    def intact(self):
-        return bool((self.raw[:self.front] == self.PATTERN).all()) and bool((self.raw[self.front + self.nbytes:] == self.PATTERN).all())
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    """bitwise equality of two fp32 tensors (NaN payloads included)"""
-    return a.shape == b.shape and bool(torch.equal(_bits(a), _bits(b)))
-
-
-class Rig:
-    """One plan with its device buffers at fixed addresses."""
-
-    def __init__(self, case, precision, B, salt):
-        from moleculardiffusion_mivit_amd.engine import MivitPlan
-        N = _native()
-        cfg = case.cfg
-        self.case, self.precision, self.B, self.T = case, precision, B, case.T
-        self.scale = LOSS_SCALE[precision]
-        self.plan = plan = MivitPlan(
-            precision=precision, embedding={"linear": N.EMBED_LINEAR, "cnn": N.EMBED_CNN, "external": N.EMBED_EXTERNAL}[case.embedding],
-            patch_size=0 if case.embedding == "external" else cfg.patch_size, embed_dim=cfg.embed_dim, num_heads=cfg.num_heads,
-            hidden_dim=cfg.hidden_dim, num_layers=cfg.num_layers,
-            activation={"relu": N.ACT_RELU, "leaky_relu": N.ACT_LEAKY_RELU, "gelu": N.ACT_GELU}[cfg.activation],
-            use_pos_encoding=cfg.use_pos_encoding, use_regression_token=cfg.use_regression_token,
-            fusion={"none": N.FUSION_NONE, "early": N.FUSION_EARLY, "late": N.FUSION_LATE}[case.fusion],
-            global_feature_dim=cfg.global_feature_dim or 0, head_hidden=cfg.head_hidden, output_dim=cfg.output_dim)
-        assert sorted(plan.param_names) == sorted(ec.param_names(case))
-        self.pad = ec.padding_mask(plan).cuda()
-        self.arena = ec.pack_arena(plan, orc.closed_form_params(cfg, dtype=torch.float64)).cuda()
-        x, labels, feats = ec.batch(case, B, salt, torch.float32)
-        self.x, self.labels = x.contiguous().cuda(), labels.cuda()
-        self.feats = None if feats is None else feats.contiguous().cuda()
-        self.ws = Guarded(plan.workspace_bytes(B, case.T, True), torch.uint8)
-        self.out = Guarded(B * cfg.output_dim, torch.float32)
-        self.grads = Guarded(plan.arena_numel, torch.float32)
-        self.dfeat = Guarded(B * cfg.global_feature_dim, torch.float32) if case.dfeatures else None
-        self.dx = Guarded(B * case.T * cfg.embed_dim, torch.float32) if case.dx_tokens else None
-        self.dout = torch.zeros(B, cfg.output_dim, device="cuda")
-        self.guards = [g for g in (self.ws, self.out, self.grads, self.dfeat, self.dx) if g is not None]
-
-    def _poison(self):
-        for g in (self.out, self.grads, self.dfeat, self.dx):
-            if g is not None:
-                _bits(g.t).fill_(ec.SENTINEL)          # the NaN sentinel as a signed word
-
-    def forward(self, ws_fill=None):
-        self._poison()
-        if ws_fill is not None:
-            self.ws.t.fill_(ws_fill)
-        self.plan.forward(self.arena, self.x, self.feats, self.B, self.T, self.ws.t, True, self.out.t)
-        out = self.out.t.view(self.B, -1)
-        self.loss = F.mse_loss(out, self.labels)
-        self.dout.copy_((out - self.labels) * (2.0 * self.scale / out.numel()))
-
-    def backward(self, s0=0, s1=None, dfeat=True, dx=True):
-        self.plan.backward(self.arena, self.x, self.feats, self.B, self.T, self.ws.t, self.dout, self.grads.t,
-                           self.dfeat.t if (self.dfeat is not None and dfeat) else None,
-                           self.dx.t if (self.dx is not None and dx) else None, s0, self.plan.num_stages if s1 is None else s1)
-
-    def snapshot(self):
-        torch.cuda.synchronize()
-        assert all(g.intact() for g in self.guards), "a kernel wrote outside its buffer"
-        return SimpleNamespace(out=self.out.t.view(self.B, -1).clone(), loss=self.loss.clone(), arena=self.grads.t.clone(),
-                               dfeat=None if self.dfeat is None else self.dfeat.t.clone(),
-                               dx=None if self.dx is None else self.dx.t.clone())
-
-    def step(self, ws_fill=None, **kw):
-        self.forward(ws_fill)
-        self.backward(**kw)
-        return self.snapshot()
-
-    def result(self, snap):
-        """a snapshot in the oracle's terms: unscaled gradients by reference name"""
-        shapes = orc.param_shapes(self.case.cfg)
-        cfg = self.case.cfg
-        g = {k: (v / self.scale).reshape(shapes[k]) for k, v in ec.unpack_arena(self.plan, snap.arena).items()}
-        return SimpleNamespace(out=snap.out, loss=snap.loss, grads=g,
-                               dfeatures=None if snap.dfeat is None else (snap.dfeat / self.scale).view(self.B, cfg.global_feature_dim),
-                               dx_tokens=None if snap.dx is None else (snap.dx / self.scale).view(self.B, self.T, cfg.embed_dim))
 
 
 @functools.lru_cache(maxsize=None)
@@ -147,10 +46,7 @@ def _rigs(name, precision):
     return [_rig(name, precision, B) for B in ec.CASE_BY_NAME[name].batches(precision)]
 
 
-def _graph_stats():
-    r, c, f = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
-    _native().lib.mivit_graph_stats(ctypes.byref(r), ctypes.byref(c), ctypes.byref(f))
-    return r.value, c.value, f.value
+_graph_stats = ec.graph_stats
 
 
 # ---- a. accuracy ------------------------------------------------------------------------------------------------------------
