@@ -328,6 +328,33 @@ int mivit_fit_spots_mle(const float *patches, int N, int P, double gain, double 
                         int fit_sigma, double xtol, double *params, double *crlb, double *deviance, int *status,
                         int *iterations, void *stream);
 
+/* Joint Poisson maximum-likelihood fit of a localisation and one neighbour inside its patch, csrc/localize2.hip, one wave per
+ * patch.  patches [N, P, P] fp32, camera scalars, sigma0, fit_sigma and xtol as mivit_fit_spots_mle.  count [N] int32: the
+ * emitters of each patch, 1 or 2; guess [N, 4] fp64: the starting centres x1, y1, x2, y2 in patch coordinates (the last two are
+ * not read where count = 1).  Model mu = b + sum_{e < count} N_e E(ix; x_e, s) E(iy; y_e, s) + read_var, one width and one
+ * background for both emitters, parameters (N1, x1, y1, N2, x2, y2, s, b).  Start: b and the photons above it as
+ * mivit_fit_spots_mle, split evenly between the emitters.  The loop is that of mivit_fit_spots_mle (lambda schedule, stopping
+ * rule, cost slack, Fisher information); a trial point with an N_e <= 0, s outside (0.2, P), a centre outside [-1, P] on either
+ * axis or a pixel with mu <= 0 is rejected like a cost increase.  out: params [N, 8] fp64; crlb [N, 8] fp64, the diagonal of
+ * the inverse Fisher matrix at the returned point (NaN where status != 0 or the matrix is not positive definite, as for two
+ * emitters that collapsed onto each other; the s entry is 0 with fit_sigma = 0); where count = 1 the fit is the five-parameter
+ * one and the three entries of emitter 2 are NaN in both; deviance [N] fp64; status [N] int32: 0 converged, 1 damping
+ * exhausted (or no photon, a starting centre outside [-1, P], or two starting centres on one point: singular by symmetry, no
+ * iteration), 2 iteration cap, 3 non-finite patch or guess, or a count
+ * that is neither 1 nor 2 (parameters NaN); iterations [N] int32.  Every sum is taken by one lane in pixel order: the result
+ * of a patch does not depend on the batch.  Arguments are validated before any HIP call; N = 0 is a no-op. */
+int mivit_fit_spots_mle2(const float *patches, const int *count, const double *guess, int N, int P, double gain, double offset,
+                         double read_var, double sigma0, int fit_sigma, double xtol, double *params, double *crlb,
+                         double *deviance, int *status, int *iterations, void *stream);
+
+/* The nearest other detection of the same frame for every row of a detections table sorted by frame, csrc/localize2.hip, one
+ * thread per row.  frame_offsets [F + 1] int32: rows frame_offsets[f] .. frame_offsets[f + 1] - 1 belong to frame f (clamped to
+ * 0 .. n); ys, xs [n] int32 the integer positions; reach >= 0.  out: neighbour [n] int32, the row of the same frame with
+ * max(|dy|, |dx|) <= reach that is nearest by squared Euclidean distance, ties to the lower row, -1 if there is none;
+ * n_neighbours [n] int32, the number of rows within reach.  Arguments are validated before any HIP call; n = 0 is a no-op. */
+int mivit_spot_neighbours(const int *frame_offsets, const int *ys, const int *xs, int F, int n, int reach, int *neighbour,
+                          int *n_neighbours, void *stream);
+
 /* Linking of a whole movie: the reference's link_particles (helpers/helpersTracking.py:123-177, one
  * scipy.optimize.linear_sum_assignment per frame) for all F - 1 pairs of consecutive frames in one launch, csrc/linking.hip.
  * coords [F, cap, 2] int32 (y, x) and count [F] int32 as mivit_dog_peaks leaves them (device); movie_start [F] bytes or NULL:

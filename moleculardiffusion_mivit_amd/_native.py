@@ -141,6 +141,9 @@ SYMBOLS = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mivit_refine_gaussian": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mivit_fit_spots_mle": (c_int, [c_void_p, c_int, c_int] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double] + [c_void_p] * 6),
+    "mivit_fit_spots_mle2": (c_int, [c_void_p] * 3 + [c_int, c_int] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double]
+                             + [c_void_p] * 6),
+    "mivit_spot_neighbours": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 3),
     "mivit_link_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "mivit_chain_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mivit_close_gaps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p,

@@ -1099,6 +1099,362 @@ def fit_spots_mle(patches, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_s
     return _fit_mle_numpy(patches, gain, offset, read_var, sigma0, fit_sigma, xtol)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# joint fit of a localisation and its nearest neighbour (csrc/localize2.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+_MLE2_ROW = np.array([i for i in range(8) for j in range(i + 1)])        # lower triangle row by row, as the kernel's lanes
+_MLE2_COL = np.array([j for i in range(8) for j in range(i + 1)])
+
+
+def _mle2_outside(p, P, two):
+    """m2_outside: an N_e <= 0, s outside (MLE_MIN_SIGMA, P) or a centre outside [-1, P], of the live emitters."""
+    with np.errstate(invalid="ignore"):
+        bad = ~(p[:, 0] > 0.0) | ~(p[:, 6] > MLE_MIN_SIGMA) | ~(p[:, 6] < float(P))
+        bad2 = ~(p[:, 3] > 0.0)
+        for k in (1, 2):
+            bad |= ~(p[:, k] >= -1.0) | ~(p[:, k] <= float(P))
+            bad2 |= ~(p[:, 3 + k] >= -1.0) | ~(p[:, 3 + k] <= float(P))
+    return bad | (two & bad2)
+
+
+def _mle2_normal(d, p, two, read_var, fs):
+    """Deviance, gradient [n, 8], Fisher matrix [n, 8, 8] (lower triangle), the out-of-domain flag and 2 sum(mu + d) of the
+    two-emitter model at p [n, 8] = (N1, x1, y1, N2, x2, y2, s, b) for data d [n, P, P] in photons; two [n]: the rows with a
+    second emitter (elsewhere N2 = x2 = y2 = 0 in p).  m2_eval of csrc/localize2.hip: the per-pixel quantities by the same
+    expressions, every sum over the pixels in pixel order."""
+    n, P, _ = d.shape
+    with np.errstate(all="ignore"):
+        bad = _mle2_outside(p, P, two)
+        ok = ~bad
+        q = np.where(ok[:, None], p, np.array([1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 1.0]))   # placeholders: zeroed below
+        Ex1, dEx1, sEx1 = (a.T[:, None, :] for a in _mle_axis(P, q[:, 1], q[:, 6], fs))     # [n, 1, P]
+        Ey1, dEy1, sEy1 = (a.T[:, :, None] for a in _mle_axis(P, q[:, 2], q[:, 6], fs))     # [n, P, 1]
+        Ex2, dEx2, sEx2 = (a.T[:, None, :] for a in _mle_axis(P, q[:, 4], q[:, 6], fs))
+        Ey2, dEy2, sEy2 = (a.T[:, :, None] for a in _mle_axis(P, q[:, 5], q[:, 6], fs))
+        N1, N2, t3 = q[:, 0, None, None], q[:, 3, None, None], two[:, None, None]
+        nEy1, ndEy1, nsEy1 = N1 * Ey1, N1 * dEy1, N1 * sEy1
+        nEy2, ndEy2, nsEy2 = N2 * Ey2, N2 * dEy2, N2 * sEy2
+        mu = q[:, 7, None, None] + nEy1 * Ex1
+        mu = np.where(t3, mu + nEy2 * Ex2, mu) + read_var
+        J6 = nEy1 * sEx1 + nsEy1 * Ex1
+        J6 = np.where(t3, J6 + (nEy2 * sEx2 + nsEy2 * Ex2), J6)
+        zero = np.zeros_like(mu)
+        J = np.stack([Ex1 * Ey1, nEy1 * dEx1, ndEy1 * Ex1, np.where(t3, Ex2 * Ey2, zero), np.where(t3, nEy2 * dEx2, zero),
+                      np.where(t3, ndEy2 * Ex2, zero), J6, np.ones_like(mu)]).reshape(8, n, P * P)
+        nonpos = (~(mu > 0.0)).reshape(n, -1).any(axis=1)
+        rm = (1.0 / mu).reshape(n, -1)
+        dd = d.reshape(n, -1)
+        mu = mu.reshape(n, -1)
+        r = dd * rm
+        term = np.where(dd > 0.0, (mu - dd) + dd * np.log(np.where(dd > 0.0, r, 1.0)), mu)
+        w = 1.0 - r
+        tri, g, cost, mag = np.zeros((36, n)), np.zeros((8, n)), np.zeros(n), np.zeros(n)
+        for t in range(P * P):                                                    # pixel order, one sum per entry
+            Jt = J[:, :, t]
+            tri = tri + (Jt[_MLE2_ROW] * rm[:, t]) * Jt[_MLE2_COL]
+            g = g + Jt * w[:, t]
+            cost = cost + term[:, t]
+            mag = mag + (mu[:, t] + dd[:, t])
+        cost, mag = 2.0 * cost, 2.0 * mag
+        A = np.zeros((n, 8, 8))
+        A[:, _MLE2_ROW, _MLE2_COL] = tri.T
+        if not fs:
+            A[:, 6, 6] = 1.0
+        for k in (3, 4, 5):
+            A[~two, k, k] = 1.0
+        g = np.ascontiguousarray(g.T)
+        cost[bad], mag[bad], g[bad], A[bad] = 0.0, 0.0, 0.0, 0.0
+    return cost, g, A, bad | (ok & nonpos), mag
+
+
+def _mle2_chol(A, lam):
+    """Cholesky factor of A + lam diag(A) for every patch (m2_chol) -> (L [n, 8, 8], ok [n])."""
+    n = len(A)
+    L = np.zeros((n, 8, 8))
+    ok = np.ones(n, bool)
+    for i in range(8):
+        for j in range(i + 1):
+            s = A[:, i, j].copy()
+            if i == j:
+                s = s + lam * s
+            for k in range(j):
+                s = s - L[:, i, k] * L[:, j, k]
+            if i == j:
+                ok &= (s > 0.0) & (s < 1e300)
+                L[:, i, i] = np.sqrt(np.where(ok, s, 1.0))
+            else:
+                L[:, i, j] = s / L[:, j, j]
+    return L, ok
+
+
+def _mle2_solve(A, g, lam):
+    """(A + lam diag(A)) d = -g by Cholesky for every patch (m2_solve) -> (d [n, 8], ok [n])."""
+    n = len(g)
+    with np.errstate(all="ignore"):
+        L, ok = _mle2_chol(A, lam)
+        z = np.zeros((n, 8))
+        for i in range(8):
+            s = -g[:, i]
+            for k in range(i):
+                s = s - L[:, i, k] * z[:, k]
+            z[:, i] = s / L[:, i, i]
+        d = np.zeros((n, 8))
+        for i in range(7, -1, -1):
+            s = z[:, i]
+            for k in range(i + 1, 8):
+                s = s - L[:, k, i] * d[:, k]
+            d[:, i] = s / L[:, i, i]
+    return d, ok
+
+
+def _mle2_crlb(A):
+    """Diagonal of A^-1 through the Cholesky factor (m2_crlb) -> (variances [n, 8], ok [n])."""
+    n = len(A)
+    v = np.zeros((n, 8))
+    with np.errstate(all="ignore"):
+        L, ok = _mle2_chol(A, 0.0)
+        for j in range(8):
+            X = np.zeros((n, 8))
+            X[:, j] = 1.0 / L[:, j, j]
+            acc = X[:, j] * X[:, j]
+            for i in range(j + 1, 8):
+                s = np.zeros(n)
+                for k in range(j, i):
+                    s = s - L[:, i, k] * X[:, k]
+                X[:, i] = s / L[:, i, i]
+                acc = acc + X[:, i] * X[:, i]
+            v[:, j] = acc
+    return v, ok
+
+
+def _fit_mle2_numpy(patches, count, guess, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_sigma=True, xtol=FIT_XTOL,
+                    max_iter=FIT_MAX_ITER):
+    """The fit of csrc/localize2.hip::ml2_kernel for patches [N, P, P], count [N] and guess [N, 4] on the host, all patches
+    side by side -> (params [N, 8] float64 (N1, x1, y1, N2, x2, y2, sigma, background), crlb [N, 8] float64, deviance [N]
+    float64, status [N] int32, iterations [N] int32); the entries of emitter 2 are NaN where count = 1.  Equal to the kernel
+    apart from erf, exp and log."""
+    raw = np.asarray(patches)
+    count, guess = np.asarray(count), np.asarray(guess, dtype=np.float64)
+    N, P, _ = raw.shape
+    fs = bool(fit_sigma)
+    status, iters = np.full(N, 2, np.int32), np.zeros(N, np.int32)
+    crlb = np.full((N, 8), np.nan)
+    if N == 0:
+        return np.zeros((0, 8)), crlb, np.zeros(0), status, iters
+    two = count == 2
+    d = _mle_data(raw, gain, offset, read_var)
+    flat = d.reshape(N, -1)
+    finite = np.isfinite(raw.reshape(N, -1)).all(axis=1) & (two | (count == 1))
+    finite &= np.isfinite(guess[:, :2]).all(axis=1) & (~two | np.isfinite(guess[:, 2:]).all(axis=1))
+    mx, mn = flat.max(axis=1), flat.min(axis=1)
+    total = np.zeros(N)
+    for t in range(P * P):
+        total = total + flat[:, t]
+    with np.errstate(invalid="ignore"):
+        b0 = np.maximum(mn, 1e-3 * mx)
+        total = total - float(P * P) * b0
+        n0 = np.maximum(total, mx)
+    zero = np.zeros(N)
+    p = np.stack([np.where(two, 0.5 * n0, n0), guess[:, 0], guess[:, 1], np.where(two, 0.5 * n0, zero),
+                  np.where(two, guess[:, 2], zero), np.where(two, guess[:, 3], zero), np.full(N, float(sigma0)), b0], axis=1)
+    p[~finite] = np.nan
+    cost, g, A, bad, mag = _mle2_normal(d, p, two, read_var, fs)
+    with np.errstate(invalid="ignore"):
+        same = two & ~_mle2_outside(p, P, two) & (p[:, 1] == p[:, 4]) & (p[:, 2] == p[:, 5])
+    cost[same] = 0.0                           # two guesses on one point: a singular start, not evaluated (ml2_kernel)
+    bad = bad | same
+    status[bad] = 1
+    with np.errstate(invalid="ignore"):
+        status[~bad & ~(cost < 1e300)] = 3
+    status[~finite] = 3
+    cost[~finite] = np.nan
+    lam = np.full(N, 1e-3)
+    for _ in range(max_iter):
+        act = np.nonzero(status == 2)[0]
+        if len(act) == 0:
+            break
+        iters[act] += 1
+        dstep, ok = _mle2_solve(A[act], g[act], lam[act])
+        fail = act[~ok]
+        lam[fail] *= 10.0
+        status[fail[lam[fail] > 1e10]] = 1
+        act, dstep = act[ok], dstep[ok]
+        if len(act) == 0:
+            continue
+        pa = np.abs(p[act])
+        a0 = np.maximum(pa[:, 0], pa[:, 3])
+        scale = np.stack([pa[:, 0], np.maximum(pa[:, 1], 1.0), np.maximum(pa[:, 2], 1.0), pa[:, 3], np.maximum(pa[:, 4], 1.0),
+                          np.maximum(pa[:, 5], 1.0), pa[:, 6], np.maximum(pa[:, 7], a0)], axis=1)
+        d0, ok0 = _mle2_solve(A[act], g[act], 0.0)
+        with np.errstate(invalid="ignore"):
+            small = ok0 & (np.abs(d0) <= xtol * scale).all(axis=1)
+        q = p[act] + dstep
+        cq, gq, Aq, badq, mq = _mle2_normal(d[act], q, two[act], read_var, fs)
+        with np.errstate(invalid="ignore"):
+            better = ~badq & (cq <= cost[act] + MLE_COST_SLACK * mag[act])
+        up = act[better]
+        p[up], cost[up], mag[up], g[up], A[up] = q[better], cq[better], mq[better], gq[better], Aq[better]
+        lam[up] = np.maximum(lam[up] * 0.1, 1e-12)
+        down = act[~better]
+        lam[down] *= 10.0
+        status[down[lam[down] > 1e10]] = 1
+        status[act[small]] = 0
+    done = np.nonzero(status == 0)[0]
+    if len(done):
+        v, ok = _mle2_crlb(A[done])
+        if not fs:
+            v[:, 6] = 0.0
+        crlb[done[ok]] = v[ok]
+    one = np.nonzero(~two)[0]
+    p[one[:, None], [3, 4, 5]] = np.nan
+    crlb[one[:, None], [3, 4, 5]] = np.nan
+    return p, crlb, cost, status, iters
+
+
+def fit_spots_mle2(patches, count, guess, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_sigma=True, xtol=FIT_XTOL):
+    """Joint Poisson maximum-likelihood fit of one or two emitters per patch with one width and one background: patches
+    [N, P, P] and the camera model as fit_spots_mle, count [N] (1 or 2 emitters), guess [N, 4] (the starting centres x1, y1,
+    x2, y2 in patch coordinates; the last two are ignored where count = 1).  CUDA float tensors go to the kernel
+    (ops.fit_spots_mle2, csrc/localize2.hip), anything else to the host restatement -> (params [N, 8] float64 (N1, x1, y1, N2,
+    x2, y2, sigma, background), crlb [N, 8] float64 (variances; NaN where status != 0), deviance [N] float64, status [N]
+    int32, iterations [N] int32) of the input's kind.  Where count = 1 the fit is the five-parameter one and the entries of
+    emitter 2 are NaN.  Two guesses on one point are a singular start (status 1, no iteration); two emitters that collapse
+    onto each other on the way end with a non-zero status when the factor fails."""
+    gain, offset, read_var, sigma0, xtol = float(gain), float(offset), float(read_var), float(sigma0), float(xtol)
+    _check_mle_args(patches.shape, gain, offset, read_var, sigma0, xtol)
+    n = patches.shape[0]
+    if tuple(count.shape) != (n,) or tuple(guess.shape) != (n, 4):
+        raise ValueError(f"count must be [{n}] and guess [{n}, 4], got {tuple(count.shape)} and {tuple(guess.shape)}")
+    cuda = _is_cuda(patches)
+    cnt = torch.as_tensor(count).to(patches.device) if cuda else torch.as_tensor(np.asarray(count))
+    gs = torch.as_tensor(guess).to(patches.device) if cuda else torch.as_tensor(np.asarray(guess))
+    if cnt.is_floating_point() or cnt.dtype == torch.bool or not bool(((cnt == 1) | (cnt == 2)).all()):
+        raise ValueError("count must hold integers 1 or 2")
+    gs = gs.double()
+    if not bool((torch.isfinite(gs[:, :2]).all(dim=1) & ((cnt == 1) | torch.isfinite(gs[:, 2:]).all(dim=1))).all()):
+        raise ValueError("guess must be finite (the last two columns where count = 2)")
+    if cuda:
+        from .. import ops
+        return ops.fit_spots_mle2(patches.float(), cnt.int(), gs, gain, offset, read_var, sigma0, bool(fit_sigma), xtol)
+    host = patches.detach().numpy() if torch.is_tensor(patches) else patches
+    out = _fit_mle2_numpy(host, cnt.numpy(), gs.numpy(), gain, offset, read_var, sigma0, fit_sigma, xtol)
+    if torch.is_tensor(patches):
+        return tuple(torch.from_numpy(np.ascontiguousarray(o)) for o in out)
+    return out
+
+
+def _spot_neighbours_numpy(frame_offsets, ys, xs, reach):
+    """nb_kernel of csrc/localize2.hip on the host: rows sorted by frame -> (neighbour [n], n_neighbours [n]) int32."""
+    off, ys, xs = np.asarray(frame_offsets, np.int64), np.asarray(ys, np.int64), np.asarray(xs, np.int64)
+    n = len(ys)
+    neighbour, within = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+    for f in range(len(off) - 1):
+        a, b = max(int(off[f]), 0), min(int(off[f + 1]), n)
+        if b - a < 2:
+            continue
+        dy, dx = np.abs(ys[a:b, None] - ys[None, a:b]), np.abs(xs[a:b, None] - xs[None, a:b])
+        ok = (dy <= reach) & (dx <= reach)
+        np.fill_diagonal(ok, False)
+        d2 = np.where(ok, dy * dy + dx * dx, np.iinfo(np.int64).max)
+        neighbour[a:b] = np.where(ok.any(axis=1), a + np.argmin(d2, axis=1), -1)       # argmin: the first, so the lower row
+        within[a:b] = ok.sum(axis=1)
+    return neighbour, within
+
+
+def spot_neighbours(frames, ys, xs, reach):
+    """For every localisation the nearest other one of its frame within a square reach: frames / ys / xs [n] in any order
+    (positions are rounded half-to-even, as extract_patches_flat cuts its patches) -> (neighbour [n] int64: the row, in the
+    caller's order, with max(|dy|, |dx|) <= reach that is nearest by squared Euclidean distance, ties to the lower row, -1 if
+    there is none; n_neighbours [n] int64: the rows within reach) of the input's kind.  CUDA tensors: a stable sort by frame
+    and the CSR over it with torch ops, then ops.spot_neighbours (csrc/localize2.hip); anything else the same on the host."""
+    if int(reach) != reach or reach < 0:
+        raise ValueError(f"reach must be an integer >= 0, got {reach}")
+    if not (len(frames) == len(ys) == len(xs)):
+        raise ValueError("frames, ys and xs must have one entry per localisation")
+    n = len(frames)
+    if _is_cuda(frames) and _is_cuda(ys) and _is_cuda(xs):
+        from .. import ops
+        dev = frames.device
+        fr = frames.long()
+        if n == 0:
+            return torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+        if int(fr.min()) < 0:
+            raise ValueError("frames must be >= 0")
+        fs, order = torch.sort(fr, stable=True)
+        offsets = torch.zeros(int(fs[-1]) + 2, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(torch.bincount(fs), 0)
+        yy, xx = torch.round(ys.double()).int()[order], torch.round(xs.double()).int()[order]
+        nb, within = ops.spot_neighbours(offsets.int(), yy.contiguous(), xx.contiguous(), int(reach))
+        neighbour = torch.empty(n, dtype=torch.int64, device=dev)
+        neighbour[order] = torch.where(nb >= 0, order[nb.long().clamp(min=0)], torch.full_like(order, -1))
+        count = torch.empty(n, dtype=torch.int64, device=dev)
+        count[order] = within.long()
+        return neighbour, count
+    is_t = torch.is_tensor(frames)
+    host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    fr = host(frames).astype(np.int64)
+    if n and fr.min() < 0:
+        raise ValueError("frames must be >= 0")
+    order = np.argsort(fr, kind="stable")
+    offsets = np.zeros(int(fr.max()) + 2 if n else 1, np.int64)
+    offsets[1:] = np.cumsum(np.bincount(fr)) if n else 0
+    yy = np.rint(host(ys).astype(np.float64)).astype(np.int64)[order]
+    xx = np.rint(host(xs).astype(np.float64)).astype(np.int64)[order]
+    nb, within = _spot_neighbours_numpy(offsets, yy, xx, int(reach))
+    neighbour, count = np.empty(n, np.int64), np.empty(n, np.int64)
+    neighbour[order] = np.where(nb >= 0, order[np.maximum(nb, 0)], -1)
+    count[order] = within
+    if is_t:
+        return torch.from_numpy(neighbour), torch.from_numpy(count)
+    return neighbour, count
+
+
+def _check_neighbours(neighbours, method, frames, P):
+    """neighbours: None, True or {"reach": r} -> the reach, or None"""
+    if neighbours is None or neighbours is False:
+        return None
+    if neighbours is not True and (not isinstance(neighbours, dict) or set(neighbours) - {"reach"}):
+        raise ValueError("neighbours must be None, True or a dict with the key reach")
+    if method != "mle":
+        raise ValueError("neighbours needs method='mle': the joint fit is a maximum-likelihood fit")
+    if frames is None:
+        raise ValueError("neighbours needs frames: a neighbour is a localisation of the same frame")
+    reach = P // 2 if neighbours is True else neighbours.get("reach", P // 2)
+    if int(reach) != reach or not 0 <= reach <= P // 2 + 1:                  # the fit keeps a centre within [-1, P]
+        raise ValueError(f"neighbours['reach'] must be an integer from 0 to P // 2 + 1 = {P // 2 + 1}, got {reach}")
+    return int(reach)
+
+
+def _fit_with_neighbours(patches, frames, ys, xs, reach, camera):
+    """The joint fit of every row with its nearest neighbour (count = 1 where it has none), guessed at the patch centre and
+    at the neighbour's offset from it -> (params [N, 8], crlb [N, 8], deviance, status, neighbour, n_neighbours): CUDA tensors
+    for CUDA patches, numpy arrays otherwise."""
+    half = patches.shape[1] // 2
+    if len(frames) != len(patches) or len(ys) != len(patches) or len(xs) != len(patches):
+        raise ValueError("patches, frames, ys and xs must have one entry per localisation")
+    if _is_cuda(patches):
+        dev = patches.device
+        fr, yy, xx = (torch.as_tensor(a).to(dev) for a in (frames, ys, xs))
+        yy, xx = torch.round(yy.double()), torch.round(xx.double())
+        nb, within = spot_neighbours(fr, yy, xx, reach)
+        has, j = nb >= 0, nb.clamp(min=0)
+        centre, zero = torch.full_like(yy, float(half)), torch.zeros_like(yy)
+        guess = torch.stack([centre, centre, torch.where(has, half + (xx[j] - xx), zero),
+                             torch.where(has, half + (yy[j] - yy), zero)], dim=1)
+        params, crlb, dev_, status, _ = fit_spots_mle2(patches, torch.where(has, 2, 1).int(), guess, **camera)
+        return params, crlb, dev_, status, nb, within
+    host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    yy, xx = np.rint(host(ys).astype(np.float64)), np.rint(host(xs).astype(np.float64))
+    nb, within = spot_neighbours(host(frames), yy, xx, reach)
+    has, j = nb >= 0, np.maximum(nb, 0)
+    centre, zero = np.full(len(yy), float(half)), np.zeros(len(yy))
+    guess = np.stack([centre, centre, np.where(has, half + (xx[j] - xx), zero), np.where(has, half + (yy[j] - yy), zero)],
+                     axis=1)
+    params, crlb, dev_, status, _ = fit_spots_mle2(host(patches), np.where(has, 2, 1).astype(np.int32), guess, **camera)
+    return params, crlb, dev_, status, nb, within
+
+
+_PRIMARY = [0, 1, 2, 6, 7]      # (N1, x1, y1, sigma, background) of the joint fit: the columns of the single-emitter fit
 _CAMERA_KEYS = ("gain", "offset", "read_var", "sigma0", "fit_sigma")
 
 
@@ -1112,7 +1468,7 @@ def _check_refine_method(method, camera):
     return dict(camera or {})
 
 
-def refine_localizations(patches, ys, xs, method="lsq", camera=None):
+def refine_localizations(patches, ys, xs, method="lsq", camera=None, frames=None, neighbours=None):
     """Sub-pixel positions of N localisations without pandas: patches [N, P, P] (extract_patches_flat) around the integer
     positions ys / xs [N] -> dict of numpy arrays x_refined, y_refined, psf_size (float64), max_intensity (the patches' dtype)
     and status (int32).  Where the fit failed (status != 0) the reference's fallback applies: the integer position and
@@ -1121,9 +1477,24 @@ def refine_localizations(patches, ys, xs, method="lsq", camera=None):
     method "lsq" (default: the reference's unweighted least-squares fit, the code path without the argument) or "mle": the
     Poisson maximum-likelihood fit (fit_spots_mle) with the camera model `camera`, a dict with keys among gain, offset,
     read_var, sigma0 and fit_sigma.  "mle" adds x_std, y_std (square roots of the Cramer-Rao bounds, pixels), photons,
-    background (photons per pixel) and deviance (float64); they are NaN where status != 0."""
+    background (photons per pixel) and deviance (float64); they are NaN where status != 0.
+
+    neighbours (default None: every localisation fitted alone, the code path without the argument): True or {"reach": r}, with
+    method "mle" and frames [N], the frame of every row.  Each row learns its nearest neighbour of the same frame inside its
+    patch (spot_neighbours; r from 0 to P // 2 + 1, the last pixel the fit lets a centre reach; default P // 2) and is fitted jointly with it (fit_spots_mle2, csrc/localize2.hip:
+    one width and one background for both, the row's own centre guessed at the patch centre, the neighbour's at its offset);
+    a row without one goes through the same fit with one emitter.  The keys above carry the row's own emitter; the result
+    gains n_neighbours (int64, the rows within reach: with more than one the fit is with the nearest), neighbour (int64,
+    its row or -1) and photons_neighbour (float64, NaN without a neighbour or where status != 0)."""
     camera = _check_refine_method(method, camera)
-    if method == "mle":
+    reach = _check_neighbours(neighbours, method, frames, patches.shape[1])
+    if reach is not None:
+        tonp = lambda t: t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        params8, crlb8, dev, status, nb, within = (tonp(t) for t in _fit_with_neighbours(patches, frames, ys, xs, reach, camera))
+        params, crlb = params8[:, _PRIMARY], crlb8[:, _PRIMARY]
+        flat = tonp(patches).reshape(len(patches), -1)
+        peak = flat.max(axis=1) if len(flat) else flat[:, 0]
+    elif method == "mle":
         params, crlb, dev, status, _ = fit_spots_mle(patches, **camera)
         flat = patches.reshape(len(patches), -1)
         if torch.is_tensor(params):
@@ -1148,6 +1519,8 @@ def refine_localizations(patches, ys, xs, method="lsq", camera=None):
             res.update({"x_std": np.sqrt(crlb[:, 1]), "y_std": np.sqrt(crlb[:, 2]),
                         "photons": np.where(okf, params[:, 0], np.nan), "background": np.where(okf, params[:, 4], np.nan),
                         "deviance": np.where(okf, dev, np.nan)})
+    if reach is not None:
+        res.update({"n_neighbours": within, "neighbour": nb, "photons_neighbour": np.where(okf, params8[:, 3], np.nan)})
     return res
 
 
@@ -1349,16 +1722,22 @@ def track_sequences(movie, frames, ys, xs, offsets, seq_len, patch_size=7, norm=
     return seq, torch.from_numpy(seq_track), torch.from_numpy(seq_row)
 
 
-def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None):
+def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None, frames=None, neighbours=None):
     """refine_localizations without the copy to the host: CUDA patches [N, P, P] (extract_patches_flat) around the integer
     positions ys / xs [N] -> dict of CUDA tensors x_refined, y_refined, psf_size (float64), max_intensity (float32) and status
     (int32), with the same fallback where the fit failed (status != 0): the integer position and psf_size 10.  method and
     camera as refine_localizations: "mle" adds x_std, y_std, photons, background and deviance (float64, NaN where status !=
-    0)."""
+    0).  frames and neighbours as refine_localizations: the joint fit with the nearest neighbour of the same frame, which adds
+    n_neighbours, neighbour (int64) and photons_neighbour (float64)."""
     if not _is_cuda(patches):
         raise ValueError("refine_localizations_tensors needs CUDA patches; use refine_localizations on the host")
     camera = _check_refine_method(method, camera)
-    if method == "mle":
+    reach = _check_neighbours(neighbours, method, frames, patches.shape[1])
+    if reach is not None:
+        params8, crlb8, dev, status, nb, within = _fit_with_neighbours(patches, frames, ys, xs, reach, camera)
+        params, crlb = params8[:, _PRIMARY], crlb8[:, _PRIMARY]
+        peak = patches.float().reshape(len(patches), -1).amax(dim=1) if len(patches) else patches.float().reshape(0)
+    elif method == "mle":
         params, crlb, dev, status, _ = fit_spots_mle(patches, **camera)
         peak = patches.float().reshape(len(patches), -1).amax(dim=1) if len(patches) else patches.float().reshape(0)
     else:
@@ -1377,6 +1756,8 @@ def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None):
         res.update({"x_std": torch.sqrt(crlb[:, 1]), "y_std": torch.sqrt(crlb[:, 2]),
                     "photons": torch.where(okf, params[:, 0], nan), "background": torch.where(okf, params[:, 4], nan),
                     "deviance": torch.where(okf, dev, nan)})
+    if reach is not None:
+        res.update({"n_neighbours": within, "neighbour": nb, "photons_neighbour": torch.where(okf, params8[:, 3], nan)})
     return res
 
 
@@ -1423,10 +1804,18 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     status in the row order of tracks_table_by_track, and sigma2_loc [n_tracks]: the mean of (y_std^2 + x_std^2) / 2 over a
     track's rows with status 0 that are not filled, NaN where there is none.  states = {"sigma2": "crlb", ...} passes the mean
     of that quantity over all such rows of the movie to fit_diffusion_states as its localisation variance and reports it as
-    states["sigma2"] (the key is there only then); it is a ValueError without localization."""
+    states["sigma2"] (the key is there only then); it is a ValueError without localization.  localization may also hold
+    "neighbours": True or {"reach": r} (refine_localizations_tensors): every row is fitted jointly with its nearest neighbour of
+    the same frame inside its patch (csrc/localize2.hip), the positions, "localization" and sigma2_loc come from the joint fit
+    and its bounds, and "localization" gains n_neighbours, neighbour (rows of tracks_table_by_track) and photons_neighbour."""
+    neighbours = None
     if localization is not None:
-        if not isinstance(localization, dict) or set(localization) - set(_CAMERA_KEYS):
-            raise ValueError(f"localization must be None or a dict with keys among {', '.join(_CAMERA_KEYS)}")
+        if not isinstance(localization, dict) or set(localization) - set(_CAMERA_KEYS) - {"neighbours"}:
+            raise ValueError(f"localization must be None or a dict with keys among {', '.join(_CAMERA_KEYS)} and neighbours")
+        neighbours = localization.get("neighbours")
+        localization = {k: v for k, v in localization.items() if k != "neighbours"}
+        if _check_neighbours(neighbours, "mle", (), patch_size) is None:
+            neighbours = None
         if not refine:
             raise ValueError("localization needs refine=True: it is the refinement")
     if isinstance(states, dict) and isinstance(states.get("sigma2"), str):
@@ -1459,9 +1848,10 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     located, from_crlb = None, False
     if refine and localization is not None:
         fit = refine_localizations_tensors(extract_patches_flat(movie, fr, y, x, patch_size), y, x, method="mle",
-                                           camera=localization)
+                                           camera=localization, **({"frames": fr, "neighbours": neighbours} if neighbours is not None else {}))
         pos = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1)
-        located = {k: fit[k] for k in ("y_std", "x_std", "photons", "background", "psf_size", "deviance", "status")}
+        located = {k: fit[k] for k in ("y_std", "x_std", "photons", "background", "psf_size", "deviance", "status")
+                   + (("n_neighbours", "neighbour", "photons_neighbour") if neighbours is not None else ())}
         var_row = (fit["y_std"] * fit["y_std"] + fit["x_std"] * fit["x_std"]) / 2.0
         good = fit["status"] == 0
         if len(by_track) > 5:

@@ -657,6 +657,71 @@ def fit_spots_mle(patches: torch.Tensor, gain: float = 1.0, offset: float = 0.0,
     return params, crlb, deviance, status, iterations
 
 
+def fit_spots_mle2(patches: torch.Tensor, count: torch.Tensor, guess: torch.Tensor, gain: float = 1.0, offset: float = 0.0,
+                   read_var: float = 0.0, sigma0: float = 1.0, fit_sigma: bool = True, xtol: float = 1e-11):
+    """Joint Poisson maximum-likelihood fit of one or two emitters per patch, one width and one background for both
+    (csrc/localize2.hip, mivit_fit_spots_mle2): patches [N, P, P] float32 on the GPU and the camera scalars as fit_spots_mle,
+    count [N] int32 (1 or 2 emitters; the caller guarantees it: another value ends with status 3), guess [N, 4] float64 (the
+    starting centres x1, y1, x2, y2 in patch coordinates; the last two are not read where count = 1) -> (params [N, 8] float64
+    (N1, x1, y1, N2, x2, y2, sigma, background), crlb [N, 8] float64 (variances; NaN where status != 0), deviance [N] float64,
+    status [N] int32, iterations [N] int32).  Where count = 1 the entries of emitter 2 are NaN."""
+    import math
+    patches = _frames_f32(patches, "fit_spots_mle2")
+    if patches.dim() != 3 or patches.shape[1] != patches.shape[2]:
+        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    n, P, _ = patches.shape
+    for t, name, dtype, shape in ((count, "count", torch.int32, (n,)), (guess, "guess", torch.float64, (n, 4))):
+        if not torch.is_tensor(t) or t.device != patches.device:
+            raise RuntimeError(f"fit_spots_mle2: {name} must be a GPU tensor on the patches' device")
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f"fit_spots_mle2: {name} must be {dtype} of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    count, guess = count.contiguous(), guess.contiguous()
+    gain, offset, read_var, sigma0, xtol = float(gain), float(offset), float(read_var), float(sigma0), float(xtol)
+    if not (gain > 0 and math.isfinite(gain)):
+        raise ValueError(f"gain must be finite and > 0, got {gain}")
+    if not math.isfinite(offset):
+        raise ValueError(f"offset must be finite, got {offset}")
+    if not (read_var >= 0 and math.isfinite(read_var)):
+        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    if not 0.2 < sigma0 < P:
+        raise ValueError(f"sigma0 must lie in (0.2, {P}), got {sigma0}")
+    if not 0 < xtol <= 1.49012e-8:
+        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
+    dev = patches.device
+    params = torch.zeros(n, 8, dtype=torch.float64, device=dev)
+    crlb = torch.zeros(n, 8, dtype=torch.float64, device=dev)
+    deviance = torch.zeros(n, dtype=torch.float64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    iterations = torch.zeros(n, dtype=torch.int32, device=dev)
+    N.check(N.lib.mivit_fit_spots_mle2(_p(patches), _p(count), _p(guess), n, P, gain, offset, read_var, sigma0,
+                                       1 if fit_sigma else 0, xtol, _p(params), _p(crlb), _p(deviance), _p(status),
+                                       _p(iterations), _s(patches)), "mivit_fit_spots_mle2")
+    return params, crlb, deviance, status, iterations
+
+
+def spot_neighbours(frame_offsets: torch.Tensor, ys: torch.Tensor, xs: torch.Tensor, reach: int):
+    """The nearest other detection of the same frame within a square reach (csrc/localize2.hip, mivit_spot_neighbours): rows
+    sorted by frame, frame_offsets [F + 1] int32 over ys, xs [n] int32 (the integer positions), all on the GPU -> (neighbour
+    [n] int32: the row with max(|dy|, |dx|) <= reach nearest by squared Euclidean distance, ties to the lower row, -1 if there
+    is none; n_neighbours [n] int32: the rows within reach)."""
+    for t, name in ((frame_offsets, "frame_offsets"), (ys, "ys"), (xs, "xs")):
+        if not torch.is_tensor(t) or t.device.type != "cuda":
+            raise RuntimeError(f"spot_neighbours: {name} must be a GPU tensor")
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise ValueError(f"spot_neighbours: {name} must be a 1-D int32 tensor")
+    if len(ys) != len(xs) or len(frame_offsets) < 1:
+        raise ValueError("spot_neighbours: ys and xs must have one entry per row and frame_offsets at least one entry")
+    if int(reach) != reach or reach < 0:
+        raise ValueError(f"reach must be an integer >= 0, got {reach}")
+    frame_offsets, ys, xs = frame_offsets.contiguous(), ys.contiguous(), xs.contiguous()
+    n = len(ys)
+    neighbour = torch.full((n,), -1, dtype=torch.int32, device=ys.device)
+    within = torch.zeros(n, dtype=torch.int32, device=ys.device)
+    N.check(N.lib.mivit_spot_neighbours(_p(frame_offsets), _p(ys), _p(xs), len(frame_offsets) - 1, n, int(reach),
+                                        _p(neighbour), _p(within), _s(ys)), "mivit_spot_neighbours")
+    return neighbour, within
+
+
 LINK_MAX_DETECTIONS = 1024
 
 

@@ -35,7 +35,11 @@ axis over the rows of matched tracks that lie within --max-distance of their par
 only), the medians of D_msd, D_msd_weighted and of D_cve over the matched tracks, the mean CRLB ((y_std^2 + x_std^2) / 2 over
 the converged rows) beside the median sigma2 that segment_tracks estimates from the covariances of neighbouring increments
 (which also contains the motion blur), the mean deviance per degree of freedom, and with --states --hmm K the fitted Ds with
-sigma2 = 0 and with sigma2 = "crlb".  --intensity PEAK sets the mean of particle_intensity (its spread scaled along), the peak
+sigma2 = 0 and with sigma2 = "crlb".  --neighbours [REACH] (with --mle) adds the column "mle2" beside "mle": the same figures
+for the joint fit of every row with its nearest neighbour of the same frame within REACH pixels (default patch-size // 2;
+csrc/localize2.hip, estimate_track_diffusion(..., localization={..., "neighbours": {...}})), the deviance per degree of freedom
+taken over 5 or 8 parameters row by row, plus the share of rows that have a neighbour and of rows that have more than one.
+--intensity PEAK sets the mean of particle_intensity (its spread scaled along), the peak
 of a spot in the movie's units: photons with --camera.  A tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
@@ -44,7 +48,7 @@ of a spot in the movie's units: photons with --camera.  A tool, not a test: it a
                                           [--cristae 4 30 60 12] [--boundary reflect]
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
-                                          [--camera 10,2,100,1.5] [--mle] [--intensity 300]
+                                          [--camera 10,2,100,1.5] [--mle] [--neighbours [4]] [--intensity 300]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -91,6 +95,7 @@ def main():
     ap.add_argument("--drift-smoothing", type=int, default=0, metavar="H")
     ap.add_argument("--camera", default=None, metavar="BG,GAIN,OFFSET[,READ]")
     ap.add_argument("--mle", action="store_true")
+    ap.add_argument("--neighbours", type=int, nargs="?", const=-1, default=None, metavar="REACH")
     ap.add_argument("--intensity", type=float, default=None, metavar="PEAK")
     args = ap.parse_args()
     camera = None
@@ -104,6 +109,8 @@ def main():
         camera = {"background": v[0], "gain": v[1], "offset": v[2], "read_noise": v[3] if len(v) == 4 else 0.0}
     elif args.mle:
         raise SystemExit("--mle needs --camera: the maximum-likelihood fit assumes photon counts")
+    if args.neighbours is not None and not args.mle:
+        raise SystemExit("--neighbours needs --mle: the joint fit is a maximum-likelihood fit")
     drift = None
     if args.drift is not None:
         try:
@@ -250,29 +257,38 @@ def camera_scores(movie, model, args, norm, truth, score, props, camera, states)
     hmm = states is not None and args.hmm is not None
     out = {"camera": camera, "fit": loc, "peak_photons": props["particle_intensity"][0],
            "photons_true_mean": float(truth["photons"].mean()) if len(truth["photons"]) else nan}
-    for method in ("lsq", "mle") if args.mle else ("lsq",):
-        how = {"method": "mle", "camera": loc} if method == "mle" else {}
+    methods = ("lsq",) + (("mle",) if args.mle else ()) + (("mle2",) if args.neighbours is not None else ())
+    joint = {"reach": args.patch_size // 2 if args.neighbours == -1 else args.neighbours} if args.neighbours is not None else None
+    for method in methods:
+        how = {"method": "mle", "camera": loc} if method != "lsq" else {}
+        if method == "mle2":
+            how.update(frames=fr, neighbours=joint)
         fit = trk.refine_localizations_tensors(patches, y, x, **how)
         err = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1) - want
         ok = (pid >= 0) & (fit["status"] == 0) & (err.pow(2).sum(dim=1).sqrt() <= args.max_distance)
         est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
-                                           segment={}, **({"localization": loc} if method == "mle" else {}))
+                                           segment={}, **({"localization": loc} if method == "mle" else
+                                                          {"localization": dict(loc, neighbours=joint)} if method == "mle2" else {}))
         seg = est["segments"]
         col = {"rows_scored": int(ok.sum()), "rows": int(len(fr)), "converged": float((fit["status"] == 0).double().mean()),
                "rmse_y": float(err[ok, 0].pow(2).mean().sqrt()), "rmse_x": float(err[ok, 1].pow(2).mean().sqrt()),
                "D_true_median": med(score["D_true"]), "D_msd_median": med(est["D_msd"]),
                "D_msd_weighted_median": med(est["D_msd_weighted"]), "D_cve_median": float(seg["D_cve"].nanmedian()),
                "sigma2_from_covariances_median": float(seg["sigma2"].nanmedian())}
-        if method == "mle":
+        if method != "lsq":
             var = (fit["y_std"] ** 2 + fit["x_std"] ** 2) / 2.0
             dof = args.patch_size ** 2 - 5
+            if method == "mle2":
+                dof = args.patch_size ** 2 - torch.where(fit["neighbour"] >= 0, 8, 5)[ok].double().mean()
+                col.update({"rows_with_a_neighbour": float((fit["n_neighbours"] > 0).double().mean()),
+                            "rows_with_more_than_one": float((fit["n_neighbours"] > 1).double().mean()), "reach": joint["reach"]})
             col.update({"rms_error_over_std_y": float((err[ok, 0] / fit["y_std"][ok]).pow(2).mean().sqrt()),
                         "rms_error_over_std_x": float((err[ok, 1] / fit["x_std"][ok]).pow(2).mean().sqrt()),
                         "crlb_mean": float(var[fit["status"] == 0].mean()), "sigma2_loc_median": float(est["sigma2_loc"].nanmedian()),
                         "photons_fitted_mean": float(fit["photons"][ok].mean()), "background_fitted_mean": float(fit["background"][ok].mean()),
-                        "deviance_per_dof": float(fit["deviance"][ok].mean()) / dof})
+                        "deviance_per_dof": float(fit["deviance"][ok].mean() / dof)})
             if hmm:
-                kw = dict(norm=norm, max_gap=args.max_gap, localization=loc)
+                kw = dict(norm=norm, max_gap=args.max_gap, localization=loc if method == "mle" else dict(loc, neighbours=joint))
                 zero = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, states={"K": args.hmm}, **kw)
                 crlb = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size,
                                                     states={"K": args.hmm, "sigma2": "crlb"}, **kw)

@@ -1,0 +1,243 @@
+"""GPU: the joint two-emitter fit kernel and the neighbour search (csrc/localize2.hip) against their host restatements
+(helpers/tracking._fit_mle2_numpy, _spot_neighbours_numpy) on the tables of tests/localize2_common.py -- status and iterations
+equal, parameters, CRLB and deviance at KERNEL_FIT_RTOL --, through ops and through the raw C entry; the same bits alone, in a
+shuffled batch and twice; outputs inside guarded buffers; arguments at the C entry; and the pipeline end to end on a rendered
+pair of particles."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import localize2_common as L2
+import tracking_common as tc
+from gpu_buffers import SENT, Out
+from moleculardiffusion_mivit_amd import _native as N
+from moleculardiffusion_mivit_amd import ops
+from moleculardiffusion_mivit_amd.helpers import tracking as T
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ("N1", "x1", "y1", "N2", "x2", "y2", "sigma", "background")
+
+
+def _kernel(patches, count, guess, **kw):
+    out = ops.fit_spots_mle2(torch.tensor(patches).cuda(), torch.tensor(count).cuda(), torch.tensor(guess).cuda(), **kw)
+    torch.cuda.synchronize()
+    return [o.cpu().numpy() for o in out]
+
+
+def _worst(got, want):
+    """worst relative difference per column, where both are finite; NaN positions must agree"""
+    got, want = got.reshape(len(got), -1), want.reshape(len(want), -1)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.where(want == got, 0.0, np.abs(got - want) / np.abs(want))
+    return np.nanmax(np.where(np.isnan(rel), 0.0, rel), axis=0)
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def _hold(got, want, what):
+    params, crlb, deviance, status, iterations = got
+    n = len(status)
+    assert params.shape == (n, 8) and crlb.shape == (n, 8) and deviance.shape == iterations.shape == (n,)
+    assert status.dtype == iterations.dtype == np.int32
+    assert np.array_equal(status, want[3]), (what, np.nonzero(status != want[3])[0])
+    assert np.array_equal(iterations, want[4]), (what, np.nonzero(iterations != want[4])[0])
+    wp, wc, wd = _worst(params, want[0]), _worst(crlb, want[1]), _worst(deviance, want[2])
+    print(f"{what}: worst relative difference, parameters", dict(zip(NAMES, wp)), "CRLB", dict(zip(NAMES, wc)), "deviance", float(wd[0]))
+    assert (wp <= tc.KERNEL_FIT_RTOL).all() and (wc <= tc.KERNEL_FIT_RTOL).all() and (wd <= tc.KERNEL_FIT_RTOL).all()
+
+
+@pytest.mark.parametrize("n", L2.SIZES)
+@pytest.mark.parametrize("name", sorted(L2.CASES))
+def test_kernel_against_the_restatement(name, n):
+    kw = L2.camera_kwargs(name)
+    patches, count, guess = (a[:n] for a in L2.case_table(name))
+    want = [a[:n] for a in L2.case_reference(name)]
+    got = _kernel(patches, count, guess, **kw)
+    _hold(got, want, f"{name} n = {n}")
+    one = count == 1
+    assert np.isnan(got[0][one][:, 3:6]).all() and np.isnan(got[1][one][:, 3:6]).all()
+    if n > 7:
+        first = 5 if kw["read_var"] == 0 else 6                                                        # the rows built to fail
+        assert (got[3][first:8] == 1).all() and (got[4][first:8] == 0).all() and np.isnan(got[1][first:8]).all()
+    if not kw["fit_sigma"]:
+        assert (got[0][:, 6] == kw["sigma0"]).all() and (got[1][got[3] == 0][:, 6] == 0.0).all()
+
+
+def _entry(patches, count, guess, n, P, outs, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_sigma=1, xtol=T.FIT_XTOL):
+    return N.lib.mivit_fit_spots_mle2(patches, count, guess, n, P, gain, offset, read_var, sigma0, fit_sigma, xtol, *outs, None)
+
+
+@pytest.mark.parametrize("n", [1, 65])
+def test_outputs_inside_guarded_buffers(n):
+    """the raw C entry writes every element of its outputs and nothing else; fp64 outputs are guarded as pairs of int32"""
+    name = "p9_fixed_camera"
+    kw = L2.camera_kwargs(name)
+    patches, count, guess = (torch.tensor(a[:n]).cuda() for a in L2.case_table(name))
+    want = [a[:n] for a in L2.case_reference(name)]
+    bufs = [Out("f32", n, 16, 16), Out("f32", n, 16, 16), Out("f32", n, 2, 2), Out("f32", n, 1, 1), Out("f32", n, 1, 1)]
+    rc = _entry(patches.data_ptr(), count.data_ptr(), guess.data_ptr(), n, 9, [b.ptr for b in bufs], kw["gain"], kw["offset"],
+                kw["read_var"], kw["sigma0"], 1 if kw["fit_sigma"] else 0)
+    assert rc == 0, N.last_error()
+    torch.cuda.synchronize()
+    raw = [b.read().view(torch.int32) for b in bufs]                             # read() checks the guards
+    for r in raw:
+        assert not bool((r == SENT[4]).any()), "an output element was not written"
+    got = [raw[0].contiguous().view(torch.float64).numpy().reshape(n, 8), raw[1].contiguous().view(torch.float64).numpy().reshape(n, 8),
+           raw[2].contiguous().view(torch.float64).numpy().reshape(n), raw[3].numpy().reshape(n), raw[4].numpy().reshape(n)]
+    _hold(got, want, f"C entry, n = {n}")
+    via_ops = _kernel(*(a[:n] for a in L2.case_table(name)), **kw)
+    for a, b in zip(got, via_ops):
+        assert _same_bits(np.ascontiguousarray(a), b)
+
+
+def test_n_zero_and_invalid_arguments_write_nothing():
+    ok, cnt, gs = torch.ones(2, 7, 7, device="cuda"), torch.tensor([1, 2], dtype=torch.int32).cuda(), torch.full((2, 4), 3.0, dtype=torch.float64).cuda()
+    bufs = [Out("f32", 2, 16, 16), Out("f32", 2, 16, 16), Out("f32", 2, 2, 2), Out("f32", 2, 1, 1), Out("f32", 2, 1, 1)]
+    outs = [b.ptr for b in bufs]
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(bool((b.raw.cpu() == SENT[4]).all()) for b in bufs)
+
+    args = dict(patches=ok.data_ptr(), count=cnt.data_ptr(), guess=gs.data_ptr(), n=2, P=7, outs=outs)
+    assert _entry(**dict(args, n=0)) == 0 and _entry(None, None, None, 0, 7, [None] * 5) == 0 and untouched()
+    for bad in ({"n": -1}, {"P": 8}, {"P": 1}, {"P": 17}, {"gain": 0.0}, {"gain": float("nan")}, {"gain": float("inf")},
+                {"offset": float("nan")}, {"offset": float("-inf")}, {"read_var": -1e-9}, {"read_var": float("nan")},
+                {"sigma0": 0.2}, {"sigma0": 7.0}, {"sigma0": float("nan")}, {"fit_sigma": 2}, {"xtol": 0.0}, {"xtol": 1e-7},
+                {"xtol": float("nan")}, {"patches": None}, {"count": None}, {"guess": None}, {"outs": [None] + outs[1:]},
+                {"outs": outs[:4] + [None]}):
+        assert _entry(**dict(args, **bad)) != 0, bad
+        assert N.last_error()
+    assert untouched()
+    fo, ys = torch.tensor([0, 2], dtype=torch.int32).cuda(), torch.tensor([3, 4], dtype=torch.int32).cuda()
+    nb = [Out("f32", 2, 1, 1), Out("f32", 2, 1, 1)]
+    for F, n, reach, ptrs in ((-1, 2, 1, None), (1, -1, 1, None), (1, 2, -1, None), (0, 2, 1, None), (1, 2, 1, (None, ys.data_ptr(), ys.data_ptr())),
+                              (1, 2, 1, (fo.data_ptr(), None, ys.data_ptr()))):
+        ptrs = ptrs or (fo.data_ptr(), ys.data_ptr(), ys.data_ptr())
+        assert N.lib.mivit_spot_neighbours(*ptrs, F, n, reach, nb[0].ptr, nb[1].ptr, None) != 0, (F, n, reach)
+    assert N.lib.mivit_spot_neighbours(fo.data_ptr(), ys.data_ptr(), ys.data_ptr(), 1, 2, 1, None, nb[1].ptr, None) != 0
+    assert N.lib.mivit_spot_neighbours(None, None, None, 0, 0, 1, None, None, None) == 0
+    torch.cuda.synchronize()
+    assert all(bool((b.raw.cpu() == SENT[4]).all()) for b in nb)
+    assert N.lib.mivit_spot_neighbours(fo.data_ptr(), ys.data_ptr(), ys.data_ptr(), 1, 2, 1, nb[0].ptr, nb[1].ptr, None) == 0
+    torch.cuda.synchronize()
+    assert nb[0].read().view(torch.int32).reshape(-1).tolist() == [1, 0] and nb[1].read().view(torch.int32).reshape(-1).tolist() == [1, 1]
+    # the wrappers
+    with pytest.raises(ValueError, match="count"):
+        T.fit_spots_mle2(ok, torch.tensor([1, 3]).cuda(), gs)
+    with pytest.raises(ValueError, match="guess"):
+        T.fit_spots_mle2(ok, cnt, torch.full((2, 4), float("nan"), dtype=torch.float64).cuda())
+    with pytest.raises(ValueError):
+        ops.fit_spots_mle2(ok, cnt.long(), gs)
+    with pytest.raises(RuntimeError):
+        ops.fit_spots_mle2(ok, cnt.cpu(), gs)
+    with pytest.raises(N.MivitError, match="patch side"):
+        ops.fit_spots_mle2(torch.ones(2, 8, 8, device="cuda"), cnt, gs)
+    # a count the C entry cannot see ends with status 3 and NaN, like a non-finite guess or patch
+    odd = ops.fit_spots_mle2(ok.repeat(2, 1, 1), torch.tensor([0, 3, 1, 2], dtype=torch.int32).cuda(),
+                             torch.tensor([[3.0] * 4, [3.0] * 4, [float("nan"), 3.0, 3.0, 3.0], [3.0, 3.0, float("inf"), 3.0]],
+                                          dtype=torch.float64).cuda())
+    assert odd[3].tolist() == [3, 3, 3, 3] and bool(torch.isnan(odd[0]).all()) and bool(torch.isnan(odd[1]).all())
+
+
+@pytest.mark.parametrize("name", ["p9", "p15_camera"])
+def test_same_bits_alone_shuffled_and_twice(name):
+    kw = L2.camera_kwargs(name)
+    patches, count, guess = (a[:65] for a in L2.case_table(name))
+    first, second = _kernel(patches, count, guess, **kw), _kernel(patches, count, guess, **kw)
+    for a, b in zip(first, second):
+        assert _same_bits(a, b)
+    order = np.random.default_rng(5).permutation(65)
+    shuffled = _kernel(patches[order], count[order], guess[order], **kw)
+    for a, b in zip(first, shuffled):
+        assert _same_bits(a[order], b)
+    dev = [torch.tensor(a).cuda() for a in (patches, count, guess)]
+    alone = [ops.fit_spots_mle2(dev[0][k:k + 1], dev[1][k:k + 1], dev[2][k:k + 1], **kw) for k in range(65)]
+    torch.cuda.synchronize()
+    for j, a in enumerate(first):
+        assert _same_bits(a, np.concatenate([o[j].cpu().numpy() for o in alone])), j
+
+
+@pytest.mark.parametrize("name", sorted(L2.neighbour_tables()))
+def test_spot_neighbours_equals_the_restatement(name):
+    frames, ys, xs, reach = L2.neighbour_tables()[name]
+    want = T.spot_neighbours(frames, ys, xs, reach)
+    got = T.spot_neighbours(*(torch.from_numpy(np.asarray(a)).cuda() for a in (frames, ys, xs)), reach)
+    assert got[0].is_cuda and got[0].dtype == got[1].dtype == torch.int64
+    assert np.array_equal(got[0].cpu().numpy(), want[0]) and np.array_equal(got[1].cpu().numpy(), want[1])
+
+
+def test_end_to_end_on_a_rendered_pair():
+    """Checked on the host for the chosen seed before committing: both particles detected in all 20 frames, the joint fit at
+    0.77 / 0.68 of the bar (y / x), the single fit at 16 / 29 times the bar."""
+    movie, pos, sigma, photons = L2.scene()
+    host = L2.scene_pipeline(np.array(movie))
+    dev = L2.scene_pipeline(torch.from_numpy(np.array(movie)).cuda())
+    assert all(np.array_equal(a, b) for a, b in zip(host[:3], dev[:3]))                   # the same detections
+    frames, iy, ix = host[:3]
+    assert np.array_equal(np.bincount(frames), np.full(L2.SCENE["F"], 2))                 # precondition: nothing missed
+    for h, d in zip(host[3:], dev[3:]):
+        assert set(h) == set(d)
+        assert np.array_equal(h["status"], d["status"]) and (d["status"] == 0).all()
+        assert np.array_equal(h["max_intensity"], d["max_intensity"])
+        for k in ("n_neighbours", "neighbour"):
+            assert k not in h or np.array_equal(h[k], d[k]), k
+        for k in set(h) - {"status", "max_intensity", "n_neighbours", "neighbour"}:
+            assert np.allclose(d[k], h[k], rtol=tc.KERNEL_FIT_RTOL, atol=0.0, equal_nan=True), k
+    joint = dev[4]
+    assert (joint["n_neighbours"] == 1).all() and (joint["neighbour"][joint["neighbour"]] == np.arange(len(frames))).all()
+    by, bx = L2.scene_bound()
+    m = L2.stat_margin(len(frames))
+    sy, sx = (L2.rms(e) for e in L2.scene_errors(frames, iy, ix, dev[3]))
+    jy, jx = (L2.rms(e) for e in L2.scene_errors(frames, iy, ix, joint))
+    print(f"rendered pair, {len(frames)} rows: bar (1 + {m:.3f}) sqrt(bound) = y {(1 + m) * math.sqrt(by):.4f} x {(1 + m) * math.sqrt(bx):.4f} px; "
+          f"joint fit RMS error y {jy:.4f} x {jx:.4f}; single fit y {sy:.4f} x {sx:.4f}")
+    assert jy <= (1.0 + m) * math.sqrt(by) and jx <= (1.0 + m) * math.sqrt(bx)
+    assert sy > (1.0 + m) * math.sqrt(by) and sx > (1.0 + m) * math.sqrt(bx)
+
+
+def test_estimate_track_diffusion_passes_neighbours_through():
+    from functools import partial
+
+    import torch.nn.functional as F
+
+    from moleculardiffusion_mivit_amd.helpers import models as M
+    movie, pos, sigma, photons = L2.scene()
+    dm = torch.from_numpy(np.array(movie)).cuda()
+    torch.manual_seed(0)
+    P = L2.SCENE["P"]
+    model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=P, embed_dim=64), 64, 4, 128, 1,
+                                 partial(M.MLPHead, hidden_dim=128, output_dim=1), F.relu, precision="fp32").cuda()
+    cam = {"gain": L2.SCENE["camera"]["gain"], "offset": L2.SCENE["camera"]["offset"], "sigma0": sigma}
+    kw = dict(patch_size=P, dt=0.03, batch_size=16, min_track_length=5)
+    plain = T.estimate_track_diffusion(dm, model, 5, localization=cam, **kw)
+    off = T.estimate_track_diffusion(dm, model, 5, localization=dict(cam, neighbours=None), **kw)
+    res = T.estimate_track_diffusion(dm, model, 5, localization=dict(cam, neighbours=True), **kw)
+    assert set(plain) == set(off) == set(res) and set(plain["localization"]) == set(off["localization"])
+    for k in plain["localization"]:
+        assert _same_bits(plain["localization"][k].cpu().numpy(), off["localization"][k].cpu().numpy()), k
+    assert set(res["localization"]) == set(plain["localization"]) | {"n_neighbours", "neighbour", "photons_neighbour"}
+    default = T.estimate_track_diffusion(dm, model, 5, localization=dict(cam, neighbours={}), **kw)        # {}: the default reach
+    for k, v in res["localization"].items():
+        assert _same_bits(v.cpu().numpy(), default["localization"][k].cpu().numpy()), k
+    # the pieces by hand
+    table, _ = T.track_particles_tensors(dm, return_dog=False, min_track_length=5)
+    fr, y, x, tid, offsets = T.tracks_table_by_track(table)[:5]
+    fit = T.refine_localizations_tensors(T.extract_patches_flat(dm.float(), fr, y, x, P), y, x, method="mle", camera=cam, frames=fr,
+                                         neighbours=True)
+    for k, v in res["localization"].items():
+        assert _same_bits(v.cpu().numpy(), fit[k].cpu().numpy()), k
+    assert len(offsets) == 3 and bool((fit["n_neighbours"] == 1).all())
+    var_row = ((fit["y_std"] ** 2 + fit["x_std"] ** 2) / 2.0).cpu().numpy()
+    o = offsets.cpu().numpy()
+    want = np.array([var_row[a:b].mean() for a, b in zip(o[:-1], o[1:])])
+    assert np.allclose(res["sigma2_loc"].cpu().numpy(), want, rtol=64 * np.finfo(np.float64).eps, atol=0.0)
+    assert not bool((res["sigma2_loc"] == plain["sigma2_loc"]).any())                     # ... and not from the single fit's
+    for k in ("track_id", "length", "n_sequences", "D_model"):
+        assert _same_bits(res[k].cpu().numpy(), plain[k].cpu().numpy()), k
