@@ -341,8 +341,10 @@ int mivit_fit_spots_mle(const float *patches, int N, int P, double gain, double 
  * one and the three entries of emitter 2 are NaN in both; deviance [N] fp64; status [N] int32: 0 converged, 1 damping
  * exhausted (or no photon, a starting centre outside [-1, P], or two starting centres on one point: singular by symmetry, no
  * iteration), 2 iteration cap, 3 non-finite patch or guess, or a count
- * that is neither 1 nor 2 (parameters NaN); iterations [N] int32.  Every sum is taken by one lane in pixel order: the result
- * of a patch does not depend on the batch.  Arguments are validated before any HIP call; N = 0 is a no-op. */
+ * that is neither 1 nor 2; iterations [N] int32.  A row with status 3 holds NaN in all eight parameters, in all eight entries
+ * of crlb and in deviance, and 0 in iterations; count is only compared with 1 and 2, so no value of it can address anything.
+ * Every sum is taken by one lane in pixel order: the result of a patch does not depend on the batch, nor on the rows around
+ * it.  Arguments are validated before any HIP call; N = 0 is a no-op. */
 int mivit_fit_spots_mle2(const float *patches, const int *count, const double *guess, int N, int P, double gain, double offset,
                          double read_var, double sigma0, int fit_sigma, double xtol, double *params, double *crlb,
                          double *deviance, int *status, int *iterations, void *stream);
@@ -351,7 +353,11 @@ int mivit_fit_spots_mle2(const float *patches, const int *count, const double *g
  * thread per row.  frame_offsets [F + 1] int32: rows frame_offsets[f] .. frame_offsets[f + 1] - 1 belong to frame f (clamped to
  * 0 .. n); ys, xs [n] int32 the integer positions; reach >= 0.  out: neighbour [n] int32, the row of the same frame with
  * max(|dy|, |dx|) <= reach that is nearest by squared Euclidean distance, ties to the lower row, -1 if there is none;
- * n_neighbours [n] int32, the number of rows within reach.  Arguments are validated before any HIP call; n = 0 is a no-op. */
+ * n_neighbours [n] int32, the number of rows within reach.  frame_offsets must ascend from 0 to n (only its first entry may
+ * lie below 0 and its last above n: they count as 0 and n).  For offsets that do not ascend or do not cover 0 .. n no frames
+ * are defined, and all a caller may rely on is that nothing outside the five arrays is read or written, that every entry of
+ * both outputs is written, that neighbour[i] is -1 or a row in [0, n) and that n_neighbours[i] lies in [0, n).  Arguments are
+ * validated before any HIP call; n = 0 is a no-op. */
 int mivit_spot_neighbours(const int *frame_offsets, const int *ys, const int *xs, int F, int n, int reach, int *neighbour,
                           int *n_neighbours, void *stream);
 
@@ -465,7 +471,11 @@ int mivit_fgn(const double *z, const double *gamma, const int *gamma_row, int N,
  * out: pos [N, T, 2] fp64 (the vertex components in the order given), arc [N, T] fp64 (s after step t) or NULL, edge [N, T] int32
  * (index within the geometry) or NULL.  No limit on T.  A geometry has at most 512 edges (it is staged in LDS); geom_of and
  * vert_offsets are clamped before use, so nothing is read out of bounds whatever they hold, and sizes that prove a longer
- * polyline are an error, never a launch.  Arguments are validated before any HIP call; N = 0 or T = 0 is a no-op. */
+ * polyline are an error, never a launch.  The rule: g = geom_of[n] clamped to [0, G - 1]; v0 = vert_offsets[g] clamped to
+ * [0, V - 2]; v1 = vert_offsets[g + 1] raised to v0 + 2 if it is smaller, otherwise lowered to V if it is larger; the particle
+ * walks the polyline of the vertices v0 .. v1 - 1 with the edge lengths lengths[v0 .. v1 - 2], of which the first 512 edges
+ * are used, with L = totals[g] as stored (a total beyond the polyline that is left ends in "no edge found").  For packed
+ * geometries this changes nothing.  Arguments are validated before any HIP call; N = 0 or T = 0 is a no-op. */
 int mivit_map_displacements(const double *disp, const double *s0, const int *geom_of, const double *verts, const double *lengths,
                             const int *vert_offsets, const double *totals, int N, int T, int G, int V, int mode, double *pos,
                             double *arc, int *edge, void *stream);

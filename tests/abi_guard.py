@@ -1,5 +1,6 @@
-"""Guarded, poisoned buffers for tests that call the C-ABI directly (tests/test_analysis_abi_gpu.py): tests/gpu_buffers.py for
-any element type.  Plain torch + ctypes; works on the CPU too, which is how tests/test_abi_guard.py tests the harness itself.
+"""Guarded, poisoned buffers for tests that call the C-ABI directly (tests/test_analysis_abi_gpu.py,
+tests/test_simulation_abi_gpu.py, through the harness of tests/abi_call.py): tests/gpu_buffers.py for any element type.
+Plain torch + ctypes; works on the CPU too, which is how tests/test_abi_guard.py tests the harness itself.
 
 A Buf is ONE allocation laid out as [guard | body | guard].  The body has exactly the size the header states for the argument,
 so a kernel that writes one element past its output, or uses more workspace than it reports, changes a guard; and whatever the

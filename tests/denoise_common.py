@@ -14,6 +14,7 @@ ALL_TV0 = 1e-6
 EARLY_TV = 1e-5            # snapshots after iteration <= 2 with a TV term
 LATE_TV_Q = (0.99, 1e-4)   # later snapshots: >= 99 % of pixels within 1e-4 ...
 LATE_TV_MAX = 1e-2         # ... and all within 1e-2
+GAUSS_FILTER_ULPS = 1      # Gaussian filter, kernel against restatement and scipy: the last float32 bit (fp64 sums in another order)
 
 
 def frames_9x9(n, seed=1234, size=9):

@@ -1,10 +1,12 @@
 """The guarded-buffer harness (tests/abi_guard.py) can fail: planted writes into either guard and into an untouched region,
-a planted read-through and a hostile index beyond the guard are all detected, and a clean run is accepted.  CPU only: the
-"kernel" is a few lines of torch on the raw allocation."""
+a planted read-through and a hostile index beyond the guard are all detected, and a clean run is accepted; so can the checks
+of tests/abi_call.py on a finished call (expect, bits_equal).  CPU only: the "kernel" is a few lines of torch on the raw
+allocation."""
 import numpy as np
 import pytest
 import torch
 
+import abi_call as A
 import abi_guard as G
 from abi_guard import Buf
 
@@ -138,3 +140,70 @@ def test_refill_and_write_move_the_reference():
     assert ws.untouched() and bool(ws.poisoned().all())
     ws.write(np.arange(16, dtype=np.uint8))
     assert ws.untouched() and ws.body().tolist() == list(range(16))
+
+
+def _finished_call(written, values, dtype=torch.float64, fill="poison"):
+    """a Call whose one output `y` [6] a "kernel" has written `values` into, at the entries of `written`"""
+    c = A.Call("cpu_kernel")
+    c.outs["y"] = Buf(6, dtype, fill=fill, device="cpu")
+    v = _body_view(c.outs["y"])
+    for i, x in zip(written, values):
+        v[i] = x
+    return c
+
+
+def test_expect_accepts_a_clean_call_and_fails_in_three_ways():
+    want = np.array([1.0, 2.0, 3.0, 4.0, 0.0, 0.0])
+    rows = np.arange(6) < 4                                                # "entries 4 and 5 are not written"
+    A.expect(_finished_call(range(4), want), "y", want, rows)
+    A.expect(_finished_call(range(6), want), "y", want)
+    A.expect(_finished_call(range(4), [1.0, np.nan, 3.0, -0.0]), "y", [1.0, np.nan, 3.0, -0.0, 9.0, 9.0], rows)
+    # an entry that should be written still holds the fill
+    with pytest.raises(AssertionError, match="1 entries the header says are written still hold the fill pattern"):
+        A.expect(_finished_call([0, 1, 3], [1.0, 2.0, 4.0]), "y", want, rows)
+    # an entry outside `written` changed
+    with pytest.raises(AssertionError, match="1 entries written that the header says are not written"):
+        A.expect(_finished_call(range(5), want), "y", want, rows)
+    # a NaN stands where a number is wanted (and the other way round; and the poison's own bits, written by the kernel)
+    with pytest.raises(AssertionError, match=r"1 entries differ, first at \[\[2\]\]"):
+        A.expect(_finished_call(range(4), [1.0, 2.0, np.nan, 4.0]), "y", want, rows)
+    with pytest.raises(AssertionError, match="1 entries differ"):
+        A.expect(_finished_call(range(4), want), "y", [1.0, 2.0, np.nan, 4.0, 0.0, 0.0], rows)
+    with pytest.raises(AssertionError, match="still hold the fill pattern"):
+        A.expect(_finished_call(range(4), [1.0, 2.0, A.POISON64, 4.0]), "y", [1.0, 2.0, np.nan, 4.0, 0.0, 0.0], rows)
+    # under a `close` the comparison is the caller's, the placement checks stay
+    seen = []
+    A.expect(_finished_call(range(4), want), "y", want + 0.5, rows, close=lambda g, w, what: seen.append((g.tolist(), w.tolist())))
+    assert seen == [([1.0, 2.0, 3.0, 4.0], [1.5, 2.5, 3.5, 4.5])]
+    with pytest.raises(AssertionError, match="still hold the fill pattern"):
+        A.expect(_finished_call([0, 1, 3], [1.0, 2.0, 4.0]), "y", want, rows, close=lambda g, w, what: None)
+    # int32 outputs in which -1 is legal start as garbage: a written -1 is a value, an unwritten entry is not
+    ids = _finished_call(range(6), [3, -1, 0, -1, 2, -1], torch.int32, "garbage")
+    A.expect(ids, "y", [3, -1, 0, -1, 2, -1])
+    with pytest.raises(AssertionError, match="still hold the fill pattern"):
+        A.expect(_finished_call(range(5), [3, -1, 0, -1, 2], torch.int32, "garbage"), "y", [3, -1, 0, -1, 2, -1])
+    A.check_all(ids, {"y": [3, -1, 0, -1, 2, -1]})
+    with pytest.raises(AssertionError, match="entries differ"):
+        A.check_all(ids, {"y": [3, -1, 0, -1, 2, 0]})
+
+
+def test_bits_equal_tells_zero_signs_and_treats_all_nans_as_one_value():
+    assert A.bits_equal(np.array([0.0, 1.5]), np.array([0.0, 1.5]))
+    assert not A.bits_equal(np.array([0.0, 1.5]), np.array([-0.0, 1.5]))
+    quiet, negative, payload = np.nan, -np.nan, np.frombuffer(np.uint64(0x7FF8000000000123).tobytes(), np.float64)[0]
+    assert A.bits_equal(np.array([quiet, 2.0]), np.array([negative, 2.0])) and A.bits_equal(np.array([quiet]), np.array([payload]))
+    assert A.bits_equal(np.array([quiet]), np.array([A.POISON64])) and not G.same_bits(np.array([quiet]), np.array([A.POISON64]))
+    assert not A.bits_equal(np.array([np.nan, 2.0]), np.array([2.0, np.nan]))             # the NaNs stand in different places
+    assert not A.bits_equal(np.array([np.nan]), np.array([np.inf]))
+    assert not A.bits_equal(np.zeros(2, np.float32), np.zeros(2, np.float64)) and not A.bits_equal(np.zeros(2), np.zeros(3))
+    assert A.bits_equal(np.array([3, -1], np.int32), np.array([3, -1], np.int32))
+    assert not A.bits_equal(np.array([3, -1], np.int32), np.array([3, 0], np.int32))
+    a, b = _finished_call(range(6), [1.0, np.nan, -0.0, 4.0, 5.0, 6.0]), _finished_call(range(6), [1.0, -np.nan, -0.0, 4.0, 5.0, 6.0])
+    A.same_results(a, b)
+    with pytest.raises(AssertionError, match="y differs between the two runs"):
+        A.same_results(a, _finished_call(range(6), [1.0, np.nan, 0.0, 4.0, 5.0, 6.0]))
+
+
+def test_sanitise_csr_is_the_header_sentence():
+    assert A.sanitise_csr([-3, 2, 1, 9, 12], 10) == [(0, 2), (2, 2), (1, 9), (9, 10)]
+    assert A.sanitise_csr([13, 4], 10) == [(10, 10)]
