@@ -603,6 +603,43 @@ int mivit_drift_frames(const double *pos, int N, const int *pair_row, int M, con
 int mivit_drift_integrate(const double *stat, const int *n_pairs, int F, int half_window, double *velocity, double *drift,
                           void *stream);
 
+/* Per-range maximum-likelihood diffusion coefficient with its standard error, csrc/likelihood.hip: the exact Gaussian
+ * likelihood of the increments of a track whose rows each carry a known localisation variance, under motion blur and with
+ * frames that may be missing (Berglund 2010; Michalet & Berglund 2012; Relich et al. 2016; no counterpart in the reference).
+ * fp64 without contraction, no LDS, no scratch, no atomics; ONE WAVE per range and lane j = candidate j of the search; a
+ * range has NO maximum length (its rows are read from global memory in each of the 8 passes) and its outputs are bitwise the
+ * same alone, anywhere in a batch and in every launch.
+ *
+ * pos [N, 2] fp64 (y, x); var [N, 2] fp64, the variance of each coordinate, or null for zeros; frames [N] int32, or null for
+ * consecutive frames (the row index); use [N] bytes (non-zero: the row may be used), or null for all rows; offsets [n + 1]
+ * int32, the CSR of the row ranges (tracks, segments, runs; entries are clamped to [0, N]: nothing is read out of bounds
+ * whatever they hold).  dt > 0; R in [0, 1/4] the motion-blur coefficient (0: instantaneous exposure, 1/6: the whole frame).
+ * A row is USABLE when its flag is set, both coordinates are finite and both variances are finite and >= 0.  The usable rows
+ * of a range in order, m of them, have frames f_0 < f_1 < .. (the caller's promise; where it is broken the outputs are
+ * defined by the arithmetic below and mean nothing), positions X_k and variances v_k per axis; increments d_k = X_{k+1} - X_k
+ * with gaps g_k = f_{k+1} - f_k, k = 0 .. m - 2.  Per candidate D, with c1 = (2 D) dt, cR = R c1, and per axis (y, then x, for
+ * every k in ascending order; both axes share Q, P and D):
+ *   a_k = (c1 (g_k - 2 R) + v_k) + v_{k+1};   b_{k-1} = cR - v_k
+ *   e_0 = a_0, z_0 = d_0;   l_k = b_{k-1} r_{k-1};   e_k = a_k - l_k b_{k-1};   z_k = d_k - l_k z_{k-1};   r_k = 1 / e_k
+ *   Q = Q + (z_k z_k) r_k;   P = P e_k, kept as mantissa in [0.5, 1) times 2^pe by frexp after every factor (exact)
+ *   cost(D) = -2 log L = ((log(mantissa) + pe log 2) + Q) + 2 (m - 1) log(2 pi)
+ * A candidate with some e_k that is not > 0, or whose cost is not below +inf, has cost +inf.
+ *
+ * The search: D_ref = S / ((4 dt) G) with S = sum_k (dy_k dy_k + dx_k dx_k) and G = sum_k g_k in ascending k.  Bracket
+ * [lo, hi] = [-20, 4]; six rounds of: step = (hi - lo) / 63, u_j = lo + j step, D_j = D_ref exp2(u_j) for j = 0 .. 63; j* the
+ * least cost, the LOWEST j on a tie; [lo, hi] = [u_max(j* - 1, 0), u_min(j* + 1, 63)].  D = D_{j*} of the last round (the
+ * bracket is then 2.4e-8 wide).  status 2 where j* = 0 in every round (the track does not move within its noise): D = 0.
+ * status 3 where j* = 63 in every round.  Then c0, c+, c- = cost at D, D e^h, D e^-h with h = 1 / 64 (the factors as fp64
+ * constants), loglik = -c0 / 2, and the observed information in ln D, I = ((c+ - c0) + (c- - c0)) / (2 h^2); D_std = D /
+ * sqrt(I) where 0 < I < inf, else NaN and status 4 if it was 0.  status 2 has D_std NaN.
+ * out, per range: D, D_std, loglik [n] fp64, n_increments [n] int32 = max(m - 1, 0), status [n] int32: 0 fine, 1 fewer than 2
+ * increments (D, D_std and loglik NaN), 2, 3, 4 as above.  The only operations that may differ from the numpy restatement
+ * (helpers/msd._diffusion_ml_numpy) are log and exp2.  Arguments are validated before any HIP call (sizes, dt, R, null
+ * pointers; pos may be null where N = 0); n = 0 is a no-op. */
+int mivit_track_diffusion_ml(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                             const int *offsets, int n, double dt, double R, double *D, double *D_std, double *loglik,
+                             int *n_increments, int *status, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

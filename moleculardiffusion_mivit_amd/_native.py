@@ -163,6 +163,8 @@ SYMBOLS = {
     "mivit_markov_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_hmm_estep": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 12),
     "mivit_hmm_viterbi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 8),
+    "mivit_track_diffusion_ml": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, ctypes.c_double, ctypes.c_double]
+                                 + [c_void_p] * 6),
     "mivit_drift_frames": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_drift_integrate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes": (c_size_t, [c_int]),

@@ -892,3 +892,200 @@ def subtract_drift(positions, frames, drift):
     if positions.shape[0] and (int(frames.min()) < 0 or int(frames.max()) >= drift.shape[0]):
         raise ValueError(f"frames must lie in [0, {drift.shape[0]}), got {int(frames.min())} .. {int(frames.max())}")
     return positions - drift[frames.long() if is_t else frames.astype(np.int64)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# maximum-likelihood D per track from rows of known variance, with a standard error (csrc/likelihood.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+_ML_CANDIDATES, _ML_ROUNDS, _ML_U_LO, _ML_U_HI = 64, 6, -20.0, 4.0
+_ML_LN2 = 0.6931471805599453                      # np.log(2)
+_ML_EXP_H, _ML_EXP_MH = 1.0157477085866857, 0.9844964370054085           # np.exp(1 / 64), np.exp(-1 / 64)
+
+
+def _ml_cost(Dc, d, g, V, inc, dt, R):
+    """-2 log L of csrc/likelihood.hip::ml_cost for the candidates Dc [n, C] of n ranges at once: d [n, >= inc[0], 2] the
+    increments, g [n, >= inc[0]] their gaps in frames, V [n, >= inc[0] + 1, 2] the row variances, inc [n] >= 1 the increments
+    of each range IN DESCENDING ORDER (the ranges still running at step k are a prefix).  Elementwise the kernel's operations
+    in its order; the two differ in log alone."""
+    n, C = Dc.shape
+    c1 = (2.0 * Dc) * dt
+    cR, tR = R * c1, 2.0 * R
+    Q, pm, pe = np.zeros((n, C)), np.full((n, C), 0.5), np.ones((n, C), np.int64)
+    bad = np.zeros((n, C), bool)
+    rinv, z = np.zeros((2, n, C)), np.zeros((2, n, C))
+    with np.errstate(all="ignore"):
+        for k in range(int(inc[0]) if n else 0):
+            na = int(np.count_nonzero(inc > k))
+            base = c1[:na] * (g[:na, k].astype(np.float64) - tR)[:, None]
+            for ax in (0, 1):
+                pv, v, dd = V[:na, k, ax][:, None], V[:na, k + 1, ax][:, None], d[:na, k, ax][:, None]
+                a = (base + pv) + v
+                if k == 0:
+                    e, zz = a, np.broadcast_to(dd, a.shape)
+                else:
+                    b = cR[:na] - pv
+                    l = b * rinv[ax, :na]
+                    e = a - l * b
+                    zz = dd - l * z[ax, :na]
+                bad[:na] |= ~(e > 0.0)
+                r = 1.0 / e
+                Q[:na] = Q[:na] + (zz * zz) * r
+                m, ex = np.frexp(pm[:na] * e)
+                pm[:na] = m
+                pe[:na] += ex
+                rinv[ax, :na], z[ax, :na] = r, zz
+        cost = ((np.log(pm) + pe.astype(np.float64) * _ML_LN2) + Q) + (2 * inc).astype(np.float64)[:, None] * _LOG_2PI
+        return np.where(bad | ~(cost < np.inf), np.inf, cost)
+
+
+def _diffusion_ml_numpy(pos, var, frames, use, offsets, dt, R):
+    """The arithmetic of csrc/likelihood.hip::ml_kernel in its order (include/mivit_hip.h, mivit_track_diffusion_ml), all
+    ranges at once: pos [N, 2] float64, var [N, 2] float64 or None, frames [N] integers or None, use [N] bool or None, offsets
+    [n + 1] int64 -> (D, D_std, loglik [n] float64, n_increments, status [n] int32).  The same recurrence, the same
+    determinant as a product rescaled by frexp, the same search; np.argmin returns the lowest index among equal minima.
+    Differs from the kernel in log and exp2 alone."""
+    n = len(offsets) - 1
+    D, D_std, loglik = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
+    n_inc, status = np.zeros(n, np.int32), np.ones(n, np.int32)
+    ok = np.isfinite(pos).all(axis=1)
+    if var is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
+    if use is not None:
+        ok &= use.astype(bool)
+    rows = []
+    for k in range(n):
+        a, b = int(offsets[k]), int(offsets[k + 1])
+        rows.append(a + np.nonzero(ok[a:b])[0])
+        n_inc[k] = max(len(rows[k]) - 1, 0)
+    sel = np.nonzero(n_inc >= 2)[0]
+    if not len(sel):
+        return D, D_std, loglik, n_inc, status
+    sel = sel[np.argsort(-n_inc[sel], kind="stable")]                      # descending: the ranges still running are a prefix
+    inc = n_inc[sel].astype(np.int64)
+    ns, Mx = len(sel), int(inc[0]) + 1
+    X, V, Fr = np.zeros((ns, Mx, 2)), np.zeros((ns, Mx, 2)), np.zeros((ns, Mx), np.int64)
+    for i, k in enumerate(sel):
+        r = rows[k]
+        X[i, :len(r)] = pos[r]
+        if var is not None:
+            V[i, :len(r)] = var[r]
+        Fr[i, :len(r)] = frames[r] if frames is not None else r - int(offsets[k])
+    d, g = X[:, 1:] - X[:, :-1], Fr[:, 1:] - Fr[:, :-1]
+    live = np.arange(Mx - 1)[None, :] < inc[:, None]
+    S = np.cumsum(np.where(live, d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], 0.0), axis=1)[:, -1]
+    G = np.where(live, g, 0).sum(axis=1)
+    with np.errstate(all="ignore"):
+        D_ref = S / ((4.0 * dt) * G.astype(np.float64))
+        lo, hi = np.full(ns, _ML_U_LO), np.full(ns, _ML_U_HI)
+        all_lo, all_hi = np.ones(ns, bool), np.ones(ns, bool)
+        lane, each = np.arange(_ML_CANDIDATES, dtype=np.float64), np.arange(ns)
+        Db = np.zeros(ns)
+        for _ in range(_ML_ROUNDS):
+            step = (hi - lo) / 63.0
+            Dj = D_ref[:, None] * np.exp2(lo[:, None] + lane[None, :] * step[:, None])
+            j = np.argmin(_ml_cost(Dj, d, g, V, inc, dt, R), axis=1)
+            all_lo &= j == 0
+            all_hi &= j == _ML_CANDIDATES - 1
+            Db = Dj[each, j]
+            jl, jh = np.maximum(j - 1, 0), np.minimum(j + 1, _ML_CANDIDATES - 1)
+            lo, hi = lo + jl.astype(np.float64) * step, lo + jh.astype(np.float64) * step
+        st = np.where(all_lo, 2, np.where(all_hi, 3, 0)).astype(np.int32)
+        Db = np.where(all_lo, 0.0, Db)
+        c = _ml_cost(np.stack([Db, Db * _ML_EXP_H, Db * _ML_EXP_MH], axis=1), d, g, V, inc, dt, R)
+        info = ((c[:, 1] - c[:, 0]) + (c[:, 2] - c[:, 0])) * 2048.0
+        curved = (info > 0.0) & (info < np.inf)
+        D[sel], loglik[sel] = Db, -0.5 * c[:, 0]
+        D_std[sel] = np.where(curved & (st != 2), Db / np.sqrt(info), np.nan)
+        status[sel] = np.where(~curved & (st == 0), 4, st)
+    return D, D_std, loglik, n_inc, status
+
+
+def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, blur=0.0):
+    """The maximum-likelihood diffusion coefficient of every track with its standard error, from rows that each carry their
+    own localisation variance (Berglund 2010; Michalet & Berglund 2012; Relich et al. 2016): positions [N, 2] (y, x) sorted
+    by track and by frame, offsets [n + 1] (CSR, from 0 to N: tracks, or the seg_offsets / run_offsets of segment_tracks and
+    estimate_track_diffusion) -> dict of the input's kind:
+        D_ml         [n] float64   in pixels^2 per unit of dt; 0 for a track that does not move within its noise (status 2)
+        D_ml_std     [n] float64   its standard error, D_ml / sqrt(observed information in ln D)
+        loglik       [n] float64   the log-likelihood at D_ml
+        n_increments [n] int64     the increments between usable rows
+        status       [n] int64     0 fine; 1 fewer than 2 increments (NaN); 2 the minimum at the lower end of the search
+                                   (D_ml = 0, D_ml_std NaN); 3 at its upper end; 4 the curvature is not positive (D_ml_std NaN)
+    variances: the variance of each coordinate, [N, 2], or [N] (both axes alike), or one number, or None for 0: the squared
+    Cramer-Rao bounds (y_std^2, x_std^2) of fit_spots_mle are what it was made for.  frames [N] integers rising within a
+    track (None: consecutive rows are consecutive frames); a track may have gaps, and a gap-closed table need not be filled.
+    use [N] bool (None: all): a row is left out where it is False, where a coordinate is not finite, and where a variance is
+    negative or not finite; the increment then bridges its neighbours like any other gap.  blur is the motion-blur
+    coefficient R in [0, 1/4] (0: instantaneous exposure, 1/6: exposure over the whole frame).
+
+    The increments of a track are zero-mean Gaussian with a tridiagonal covariance (2 D dt (g - 2 R) + v_k + v_{k+1} on the
+    diagonal, 2 R D dt - v_{k+1} beside it), the two axes independent and sharing D.  The likelihood is evaluated by the
+    LDL^T recurrence and maximised by a fixed grid search over log2 D: six rounds of 64 candidates, from D_ref 2^-20 to D_ref
+    2^4 with D_ref = <d^2> / (4 dt <g>); include/mivit_hip.h has every operation.  Unlike D_cve it uses rows of different
+    quality for what they are worth and needs no gap-free table; unlike D_msd and segments["D_mle"] it is not biased by
+    localisation noise and motion blur.  CUDA tensors go to the kernel (csrc/likelihood.hip: one wave per track, no limit on
+    its length), numpy arrays and CPU tensors to the numpy restatement, which differs from it in log and exp2 alone."""
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    is_t = torch.is_tensor(positions)
+    scalar_var = variances is not None and not torch.is_tensor(variances) and np.ndim(variances) == 0
+    given = [offsets] + [g for g in (None if scalar_var else variances, frames, use) if g is not None]
+    if any(torch.is_tensor(g) != is_t for g in given):
+        raise ValueError("positions, offsets, variances, frames and use must all be tensors or all be arrays")
+    if is_t and any(g.device != positions.device for g in given):
+        raise ValueError(f"positions on {positions.device}, the other arguments elsewhere")
+    if not is_t:
+        positions, offsets = np.asarray(positions, dtype=np.float64), np.asarray(offsets)
+        variances = variances if variances is None or scalar_var else np.asarray(variances, dtype=np.float64)
+        frames = None if frames is None else np.asarray(frames)
+        use = None if use is None else np.asarray(use)
+    n = positions.shape[0]
+    _check_offsets(offsets, n)
+    if scalar_var:
+        if not 0.0 <= float(variances) < float("inf"):
+            raise ValueError(f"a variance must be >= 0 and finite, got {variances}")
+    elif variances is not None and tuple(variances.shape) not in ((n,), (n, 2)):
+        raise ValueError(f"variances must be [N, 2], [N] or a number, got {tuple(variances.shape)} for {n} rows")
+    if frames is not None:
+        _check_frames(frames, n)
+    if use is not None and (tuple(use.shape) != (n,) or use.dtype != (torch.bool if is_t else np.bool_)):
+        raise ValueError(f"use must be bool [N], got {use.dtype} {tuple(use.shape)}")
+    if is_t:
+        as_t = lambda a: a.detach()                                                               # noqa: E731
+    else:
+        as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a) if a.flags.writeable else a.copy())     # noqa: E731
+    pos, off = as_t(positions).double().contiguous(), as_t(offsets).long()
+    if variances is None or (scalar_var and float(variances) == 0.0):
+        var = None
+    elif scalar_var:
+        var = torch.full((n, 2), float(variances), dtype=torch.float64, device=pos.device)
+    else:
+        var = as_t(variances).double()
+        var = (var[:, None].expand(n, 2) if var.dim() == 1 else var).contiguous()
+    fr = None if frames is None else as_t(frames).long()
+    if fr is not None and n > 1:
+        inside = torch.ones(n - 1, dtype=torch.bool, device=pos.device)    # row r and row r + 1 belong to one range
+        starts = off[1:-1]
+        inside[starts[(starts > 0) & (starts < n)] - 1] = False
+        if bool(((fr[1:] <= fr[:-1]) & inside).any()):
+            raise ValueError("frames must rise within every range")
+        if int(fr.min()) < -2 ** 31 or int(fr.max()) >= 2 ** 31:
+            raise ValueError("frames must fit 32 bits")
+    usable = None if use is None else as_t(use).contiguous()
+    if pos.device.type == "cuda":
+        from .. import ops
+        D, D_std, loglik, n_inc, status = ops.track_diffusion_ml(pos, off.int().contiguous(), var,
+                                                                 None if fr is None else fr.int().contiguous(), usable,
+                                                                 float(dt), float(blur))
+        return {"D_ml": D, "D_ml_std": D_std, "loglik": loglik, "n_increments": n_inc.long(), "status": status.long()}
+    D, D_std, loglik, n_inc, status = _diffusion_ml_numpy(
+        pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
+        None if usable is None else usable.numpy(), off.numpy(), float(dt), float(blur))
+    out = {"D_ml": D, "D_ml_std": D_std, "loglik": loglik, "n_increments": n_inc.astype(np.int64),
+           "status": status.astype(np.int64)}
+    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out

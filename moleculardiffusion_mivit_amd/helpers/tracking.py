@@ -1762,7 +1762,7 @@ def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None, fra
 
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
-                             batch_size=4096, segment=None, states=None, drift=None, localization=None, **tracking_kwargs):
+                             batch_size=4096, segment=None, states=None, drift=None, localization=None, ml=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1807,7 +1807,37 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     states["sigma2"] (the key is there only then); it is a ValueError without localization.  localization may also hold
     "neighbours": True or {"reach": r} (refine_localizations_tensors): every row is fitted jointly with its nearest neighbour of
     the same frame inside its patch (csrc/localize2.hip), the positions, "localization" and sigma2_loc come from the joint fit
-    and its bounds, and "localization" gains n_neighbours, neighbour (rows of tracks_table_by_track) and photons_neighbour."""
+    and its bounds, and "localization" gains n_neighbours, neighbour (rows of tracks_table_by_track) and photons_neighbour.
+
+    ml (default None: the code path without it): a dict with keys among blur and sigma2 ({} for the defaults), the arguments of
+    helpers/msd.estimate_diffusion_ml (csrc/likelihood.hip), the maximum-likelihood D of every track from rows of known
+    variance, with a standard error.  blur is the motion-blur coefficient (default 0).  sigma2 is the localisation variance
+    per coordinate: a number (default 0 without localization), with which every row that is not filled is used, or "crlb" (the
+    default with localization; a ValueError without it, like states["sigma2"] = "crlb"): every row carries (y_std^2, x_std^2)
+    of its own fit, and the rows used are those with status 0 that are not filled, the set sigma2_loc is taken over.  It
+    runs on the positions the MSD is taken on (drift-corrected if drift is given) with the frames of the table, so a filled
+    row is a gap of the likelihood, not an interpolated position.  The result gains D_ml, D_ml_std (float64) and ml_status
+    (int64) [n_tracks], and "ml": what estimate_diffusion_ml was called with (positions [N, 2], variances [N, 2] or the
+    number, frames [N], use [N] bool or None, blur).  With segment, "segments" gains D_ml, D_ml_std and ml_status per segment
+    (the same call on seg_offsets), and with states, "states" gains them per run (on run_offsets).  segments["D_mle"] keeps
+    its name and meaning: it is <q> / (4 dt), the maximum-likelihood estimate of a track WITHOUT localisation noise and blur,
+    which noise biases upwards by sigma^2 / dt; D_ml is the estimate under the full model and is the one to hold against
+    D_model."""
+    if ml is not None:
+        if not isinstance(ml, dict) or set(ml) - {"blur", "sigma2"}:
+            raise ValueError("ml must be None or a dict with keys among blur and sigma2")
+        ml = dict(ml)
+        ml.setdefault("blur", 0.0)
+        ml.setdefault("sigma2", "crlb" if localization is not None else 0.0)
+        if isinstance(ml["sigma2"], str):
+            if ml["sigma2"] != "crlb":
+                raise ValueError(f"ml['sigma2'] must be a number or 'crlb', got {ml['sigma2']!r}")
+            if localization is None:
+                raise ValueError("ml['sigma2'] = 'crlb' needs localization: the least-squares fit returns no bound")
+        elif not 0.0 <= float(ml["sigma2"]) < float("inf"):
+            raise ValueError(f"ml['sigma2'] must be >= 0 and finite, got {ml['sigma2']}")
+        if not 0.0 <= float(ml["blur"]) <= 0.25:
+            raise ValueError(f"ml['blur'] must lie in [0, 1/4], got {ml['blur']}")
     neighbours = None
     if localization is not None:
         if not isinstance(localization, dict) or set(localization) - set(_CAMERA_KEYS) - {"neighbours"}:
@@ -1879,6 +1909,19 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         pos = _msd.subtract_drift(pos, fr, drifted["drift"])
         drifted["positions"] = pos
     msd, d_lstsq, d_weighted = ops.track_msd(pos, offsets.int(), float(dt), 0)
+    if ml is not None:
+        from . import msd as _msd
+        filled = by_track[5] if len(by_track) > 5 else None
+        if ml["sigma2"] == "crlb":
+            ml_args = {"variances": torch.stack([fit["y_std"] * fit["y_std"], fit["x_std"] * fit["x_std"]], dim=1), "use": good}
+        else:
+            ml_args = {"variances": float(ml["sigma2"]), "use": None if filled is None else ~filled}
+        ml_args.update(frames=fr, blur=float(ml["blur"]))
+
+        def ml_fit(csr):
+            return _msd.estimate_diffusion_ml(pos, csr, dt=dt, **ml_args)
+
+        ml_tracks = ml_fit(offsets)
     seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
     n_sequences = torch.bincount(seq_track, minlength=n_tracks)
     model.eval()
@@ -1903,6 +1946,9 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         seg_seq, seg_of_seq, _ = track_sequences(movie, fr, y, x, segments["seg_offsets"], seq_len, patch_size, norm, tail)
         segments["n_sequences"] = torch.bincount(seg_of_seq, minlength=len(segments["seg_track"]))
         segments["D_model"] = mean_per_group(seg_seq, segments["n_sequences"])
+        if ml is not None:
+            got = ml_fit(segments["seg_offsets"])
+            segments["D_ml"], segments["D_ml_std"], segments["ml_status"] = got["D_ml"], got["D_ml_std"], got["status"]
     fitted = None
     if states is not None:
         from . import msd as _msd
@@ -1920,6 +1966,9 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         run_seq, run_of_seq, _ = track_sequences(movie, fr, y, x, fitted["run_offsets"], seq_len, patch_size, norm, tail)
         fitted["n_sequences"] = torch.bincount(run_of_seq, minlength=len(first))
         fitted["D_model"] = mean_per_group(run_seq, fitted["n_sequences"])
+        if ml is not None:
+            got = ml_fit(fitted["run_offsets"])
+            fitted["D_ml"], fitted["D_ml_std"], fitted["ml_status"] = got["D_ml"], got["D_ml_std"], got["status"]
     res = {"track_id": tid[offsets[:-1]], "length": lengths, "n_sequences": n_sequences, "D_model": d_model,
            "D_msd": d_lstsq, "D_msd_weighted": d_weighted, "msd": msd}
     if len(by_track) > 5:
@@ -1933,6 +1982,9 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["drift"] = drifted
     if located is not None:
         res["localization"], res["sigma2_loc"] = located, sigma2_loc
+    if ml is not None:
+        res["D_ml"], res["D_ml_std"], res["ml_status"] = ml_tracks["D_ml"], ml_tracks["D_ml_std"], ml_tracks["status"]
+        res["ml"] = dict(ml_args, positions=pos)
     return res
 
 

@@ -1138,6 +1138,61 @@ def hmm_viterbi(pos: torch.Tensor, offsets: torch.Tensor, v: torch.Tensor, A: to
     return state, logp
 
 
+def track_diffusion_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0,
+                       blur: float = 0.0):
+    """The maximum-likelihood diffusion coefficient of every row range with its standard error (csrc/likelihood.hip,
+    mivit_track_diffusion_ml): pos [N, 2] float64 on the GPU (y, x); offsets [n + 1] int32 (CSR, from 0 to N: tracks, segments
+    or runs); var [N, 2] float64, the variance of every coordinate (None: zeros); frames [N] int32, rising within a range
+    (None: consecutive); use [N] bool or uint8 (None: every row); blur the motion-blur coefficient R in [0, 1/4] -> (D, D_std,
+    loglik [n] float64, n_increments, status [n] int32).  A range has no maximum length.  offsets are read back to be
+    checked: every rejection is a ValueError before any launch.  See include/mivit_hip.h for the arithmetic and the status
+    codes and helpers/msd.estimate_diffusion_ml for the front end."""
+    name = "track_diffusion_ml"
+    pos = _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
+    offsets = _seg_tensor(offsets, torch.int32, 1, name, "offsets [n + 1]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"{name}: pos must be [N, 2], got {tuple(pos.shape)}")
+    if offsets.numel() < 1:
+        raise ValueError(f"{name}: offsets must have n + 1 entries")
+    n_rows, n = pos.shape[0], offsets.numel() - 1
+    given = [pos, offsets]
+    if var is not None:
+        var = _seg_tensor(var, torch.float64, 2, name, "var [N, 2]")
+        if tuple(var.shape) != (n_rows, 2):
+            raise ValueError(f"{name}: var must be [{n_rows}, 2], got {tuple(var.shape)}")
+        given.append(var)
+    if frames is not None:
+        frames = _seg_tensor(frames, torch.int32, 1, name, "frames [N]")
+        if frames.numel() != n_rows:
+            raise ValueError(f"{name}: frames must be [{n_rows}], got {tuple(frames.shape)}")
+        given.append(frames)
+    if use is not None:
+        if torch.is_tensor(use) and use.dtype == torch.bool:
+            use = use.view(torch.uint8)
+        use = _seg_tensor(use, torch.uint8, 1, name, "use [N] (bool or uint8)")
+        if use.numel() != n_rows:
+            raise ValueError(f"{name}: use must be [{n_rows}], got {tuple(use.shape)}")
+        given.append(use)
+    if len({t.device for t in given}) != 1:
+        raise ValueError(f"{name}: all tensors must be on one device")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"{name}: dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"{name}: the blur coefficient must lie in [0, 1/4], got {blur}")
+    if n:
+        off = offsets.cpu()
+        if int(off[0]) != 0 or int(off[-1]) != n_rows or bool((off[1:] < off[:-1]).any()):
+            raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
+    elif n_rows:
+        raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
+    D, D_std, loglik = (torch.empty(n, dtype=torch.float64, device=pos.device) for _ in range(3))
+    n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
+    N.check(N.lib.mivit_track_diffusion_ml(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt),
+                                           float(blur), _p(D), _p(D_std), _p(loglik), _p(n_inc), _p(status), _s(pos)),
+            "mivit_track_diffusion_ml")
+    return D, D_std, loglik, n_inc, status
+
+
 DRIFT_MAX_PAIRS = 4096       # csrc/drift.hip: increments of one frame that the median sorts in LDS (8 B a pair, 32 KiB)
 DRIFT_MODES = {"mean": 0, "median": 1}
 

@@ -39,6 +39,10 @@ sigma2 = 0 and with sigma2 = "crlb".  --neighbours [REACH] (with --mle) adds the
 for the joint fit of every row with its nearest neighbour of the same frame within REACH pixels (default patch-size // 2;
 csrc/localize2.hip, estimate_track_diffusion(..., localization={..., "neighbours": {...}})), the deviance per degree of freedom
 taken over 5 or 8 parameters row by row, plus the share of rows that have a neighbour and of rows that have more than one.
+--ml [R] (with --mle; R the motion-blur coefficient, default 1/6: exposure over the whole frame) adds to the columns "mle"
+and "mle2" the maximum-likelihood D of every track from its rows' own bounds (helpers/msd.estimate_diffusion_ml,
+csrc/likelihood.hip, through estimate_track_diffusion(..., ml={"blur": R})): D_ml_median over the matched tracks, next to
+D_msd_median and D_cve_median, the RMS of (D_ml - D_true) / D_ml_std over the matched tracks of status 0, and their count.
 --intensity PEAK sets the mean of particle_intensity (its spread scaled along), the peak
 of a spot in the movie's units: photons with --camera.  A tool, not a test: it asserts no accuracy.
 
@@ -48,7 +52,7 @@ of a spot in the movie's units: photons with --camera.  A tool, not a test: it a
                                           [--cristae 4 30 60 12] [--boundary reflect]
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
-                                          [--camera 10,2,100,1.5] [--mle] [--neighbours [4]] [--intensity 300]
+                                          [--camera 10,2,100,1.5] [--mle] [--neighbours [4]] [--ml [0.1667]] [--intensity 300]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -96,6 +100,7 @@ def main():
     ap.add_argument("--camera", default=None, metavar="BG,GAIN,OFFSET[,READ]")
     ap.add_argument("--mle", action="store_true")
     ap.add_argument("--neighbours", type=int, nargs="?", const=-1, default=None, metavar="REACH")
+    ap.add_argument("--ml", type=float, nargs="?", const=1.0 / 6.0, default=None, metavar="R")
     ap.add_argument("--intensity", type=float, default=None, metavar="PEAK")
     args = ap.parse_args()
     camera = None
@@ -111,6 +116,8 @@ def main():
         raise SystemExit("--mle needs --camera: the maximum-likelihood fit assumes photon counts")
     if args.neighbours is not None and not args.mle:
         raise SystemExit("--neighbours needs --mle: the joint fit is a maximum-likelihood fit")
+    if args.ml is not None and not args.mle:
+        raise SystemExit("--ml needs --mle: the row variances are the bounds of the maximum-likelihood fit")
     drift = None
     if args.drift is not None:
         try:
@@ -267,7 +274,8 @@ def camera_scores(movie, model, args, norm, truth, score, props, camera, states)
         err = torch.stack([fit["y_refined"], fit["x_refined"]], dim=1) - want
         ok = (pid >= 0) & (fit["status"] == 0) & (err.pow(2).sum(dim=1).sqrt() <= args.max_distance)
         est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
-                                           segment={}, **({"localization": loc} if method == "mle" else
+                                           segment={}, **({"ml": {"blur": args.ml}} if args.ml is not None and method != "lsq" else {}),
+                                           **({"localization": loc} if method == "mle" else
                                                           {"localization": dict(loc, neighbours=joint)} if method == "mle2" else {}))
         seg = est["segments"]
         col = {"rows_scored": int(ok.sum()), "rows": int(len(fr)), "converged": float((fit["status"] == 0).double().mean()),
@@ -287,6 +295,12 @@ def camera_scores(movie, model, args, norm, truth, score, props, camera, states)
                         "crlb_mean": float(var[fit["status"] == 0].mean()), "sigma2_loc_median": float(est["sigma2_loc"].nanmedian()),
                         "photons_fitted_mean": float(fit["photons"][ok].mean()), "background_fitted_mean": float(fit["background"][ok].mean()),
                         "deviance_per_dof": float(fit["deviance"][ok].mean() / dof)})
+            if args.ml is not None:
+                fine = track_ok & (est["ml_status"] == 0)
+                pull = (est["D_ml"][fine] - score["D_true"][fine]) / est["D_ml_std"][fine]
+                col.update({"ml_blur": args.ml, "D_ml_median": med(est["D_ml"]), "D_ml_status_0": int(fine.sum()),
+                            "D_ml_tracks_matched": int(track_ok.sum()),
+                            "rms_D_ml_error_over_std": float(pull.pow(2).mean().sqrt()) if bool(fine.any()) else nan})
             if hmm:
                 kw = dict(norm=norm, max_gap=args.max_gap, localization=loc if method == "mle" else dict(loc, neighbours=joint))
                 zero = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, states={"K": args.hmm}, **kw)
