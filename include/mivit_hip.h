@@ -640,6 +640,63 @@ int mivit_track_diffusion_ml(const double *pos, const double *var, const int *fr
                              const int *offsets, int n, double dt, double R, double *D, double *D_std, double *loglik,
                              int *n_increments, int *status, void *stream);
 
+/* Per-range exact log-likelihood of anomalous diffusion, and its maximum over the exponent alpha and the generalised
+ * diffusion coefficient D with error bars, csrc/fbm_ml.hip: the Gaussian likelihood of the increments of a track that is
+ * a fractional Brownian motion averaged over the camera's exposure, whose rows each carry a known localisation variance and
+ * whose frames may be missing (no counterpart in the reference).  fp64 without contraction, no atomics, no scratch.  ONE
+ * WORKGROUP (192 threads, 81 320 B of LDS) per range and candidate; a range's outputs are bitwise the same alone, anywhere in
+ * a batch and in every launch.  LIMITS: a range may have at most 129 usable rows (ops.FBM_ML_MAX_ROWS) and its usable frames
+ * may span at most 1199 (largest - smallest, ops.FBM_ML_MAX_SPAN); a range beyond either gets status 5 and NaN, and nothing
+ * is read or written out of bounds whatever the range holds.  The range itself may be of any length.
+ *
+ * pos, var, frames, use, N, offsets, n, dt: as mivit_track_diffusion_ml, and so is the rule for a USABLE row.  exposure E in
+ * [0, 1], the part of a frame, from its start, over which the camera integrates.  The usable rows of a range, m + 1 of
+ * them, have frames f_0 < f_1 < .. (the caller's promise), positions X_k, variances v_k per axis; d_k = X_{k+1} - X_k, k = 0
+ * .. m - 1.  The structure function at a lag of t >= 0 frames, tau = (double)t:
+ *   E = 0:  S(0) = 0, S(t) = pow(tau, alpha)
+ *   E > 0:  S(0) = (2 pow(E, alpha)) / a12 with a12 = (alpha + 1) (alpha + 2)
+ *           where E > tau / 2 (t = 1 only):  S = ((pow(tau + E, p) + pow(|tau - E|, p)) - 2 pow(tau, p)) / ((E E) a12), p = alpha + 2
+ *           else  S = pow(tau, alpha) sum, sum = 1 + t_1 + .. + t_30 added in this order, t_0 = 1,
+ *                 t_j = (t_{j-1} (((alpha - 2j + 2) (alpha - 2j + 1)) / ((2j + 1) (2j + 2)))) ((E / tau) (E / tau))
+ * Per axis (y, then x; each has its own matrix because each has its own variances) the covariance of the increments, i >= j:
+ *   C_ij = (D dt) (((S|f_{i+1} - f_j| + S|f_i - f_{j+1}|) - S|f_{i+1} - f_{j+1}|) - S|f_i - f_j|), then for j = i:
+ *   (C_ii + v_i) + v_{i+1}, for j = i - 1: C_ij - v_i.  The per-axis ensemble MSD at a lag t is 2 D dt t^alpha (E = 0), and at
+ *   alpha = 1 this is the covariance of mivit_track_diffusion_ml with R = E / 6.
+ * The factorisation is left-looking with the increments as row m (C_mj = d_j): for j = 0 .. m - 1, p_j = C_jj - sum_{k<j} L_jk
+ * L_jk and, for every i > j, L_ij = (C_ij - sum_{k<j} L_ik L_jk) / sqrt(p_j), each sum subtracted term by term in ascending k;
+ * z_j = L_mj.  Q = Q + z_j z_j and P = P p_j (mantissa in [0.5, 1) times 2^pe by frexp after every factor) run over j and over
+ * both axes;  cost(alpha, D) = -2 log L = ((log(mantissa) + pe log 2) + Q) + 2 m log(2 pi).  A candidate with some p_j that
+ * is not > 0, or whose cost is not below +inf, has cost +inf.
+ *
+ * mivit_track_fbm_loglik: alpha [n], D [n] fp64 in -> loglik [n] = -cost / 2 (-inf for a rejected candidate), n_increments
+ * [n] = max(usable rows - 1, 0), status [n]: 0 fine; 5 over a limit; else 1 no increment; else 6 alpha outside (0, 2) or D
+ * negative or not finite; loglik is NaN for 1, 5, 6.
+ *
+ * mivit_track_fbm_ml: the search.  D_ref = S2 / ((4 dt) (f_m - f_0)), S2 = sum_k (dy_k dy_k + dx_k dx_k) in ascending k.  The
+ * bracket starts as alpha in [0.05, 1.95] (helpers/generation.ALPHA_MIN, ALPHA_MAX) and u = log2(D / D_ref) in [-12, 4].
+ * 20 rounds of: sa = (ahi - alo) / 7, su = (uhi - ulo) / 7, candidate c = 8 i + j at alpha_i = alo + i sa, D_j = D_ref exp2(ulo +
+ * j su); c* the least cost, the LOWEST c on a tie; the next bracket is [max(alpha_i* - 2 sa, 0.05), min(alpha_i* + 2 sa, 1.95)]
+ * and [u_j* - 2 su, u_j* + 2 su] (not clamped).  The result is the best candidate of the last round, whose next bracket
+ * would be 2.6e-5 wide in alpha and 2.2e-4 in u.  status 2 where j* = 0 in every round (the track does not move within its
+ * noise): D = 0, alpha and the bars NaN, loglik the likelihood at D = 0.  status 3 where j* = 7 in every round.  Then the cost
+ * c_ab at (alpha + a h, D e^{b h}), a, b in {-1, 0, 1}, h = 1 / 64 (e^h, e^-h as fp64 constants); loglik = -c_00 / 2;
+ *   Haa = ((c_+0 - c_00) + (c_-0 - c_00)) 2048, Hdd = ((c_0+ - c_00) + (c_0- - c_00)) 2048, Had = ((c_++ - c_+-) - (c_-+ - c_--)) 512,
+ *   det = Haa Hdd - Had Had; alpha_std = sqrt(Hdd / det), D_std = D sqrt(Haa / det), corr = -Had / sqrt(Haa Hdd)
+ * where alpha - h >= 0.05, alpha + h <= 1.95, Haa > 0, Hdd > 0 and 0 < det < inf; else the three are NaN and status 4 if it
+ * was 0.  out, per range: alpha, alpha_std, D, D_std, corr, loglik [n] fp64, n_increments, status [n] int32: 0 fine; 5 over a
+ * limit (NaN); else 1 fewer than 3 increments (NaN); 2, 3, 4 as above.  workspace: at least 640 n bytes, 8-byte aligned; its
+ * contents before the call do not matter and mean nothing after it.  The launches (20 x 2 + 2) are queued on the stream
+ * without a host synchronisation.  helpers/msd._fbm_ml_numpy restates the search with LAPACK's Cholesky: equal apart from
+ * the order of the sums, pow, exp2 and log.  Arguments are validated before any HIP call (sizes, n <= 2^24, dt, exposure,
+ * null pointers, the workspace; pos may be null where N = 0); n = 0 is a no-op. */
+int mivit_track_fbm_loglik(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                           const int *offsets, int n, double dt, double exposure, const double *alpha, const double *D,
+                           double *loglik, int *n_increments, int *status, void *stream);
+int mivit_track_fbm_ml(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                       const int *offsets, int n, double dt, double exposure, double *alpha, double *alpha_std, double *D,
+                       double *D_std, double *corr, double *loglik, int *n_increments, int *status, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -1001,35 +1001,12 @@ def _diffusion_ml_numpy(pos, var, frames, use, offsets, dt, R):
     return D, D_std, loglik, n_inc, status
 
 
-def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, blur=0.0):
-    """The maximum-likelihood diffusion coefficient of every track with its standard error, from rows that each carry their
-    own localisation variance (Berglund 2010; Michalet & Berglund 2012; Relich et al. 2016): positions [N, 2] (y, x) sorted
-    by track and by frame, offsets [n + 1] (CSR, from 0 to N: tracks, or the seg_offsets / run_offsets of segment_tracks and
-    estimate_track_diffusion) -> dict of the input's kind:
-        D_ml         [n] float64   in pixels^2 per unit of dt; 0 for a track that does not move within its noise (status 2)
-        D_ml_std     [n] float64   its standard error, D_ml / sqrt(observed information in ln D)
-        loglik       [n] float64   the log-likelihood at D_ml
-        n_increments [n] int64     the increments between usable rows
-        status       [n] int64     0 fine; 1 fewer than 2 increments (NaN); 2 the minimum at the lower end of the search
-                                   (D_ml = 0, D_ml_std NaN); 3 at its upper end; 4 the curvature is not positive (D_ml_std NaN)
-    variances: the variance of each coordinate, [N, 2], or [N] (both axes alike), or one number, or None for 0: the squared
-    Cramer-Rao bounds (y_std^2, x_std^2) of fit_spots_mle are what it was made for.  frames [N] integers rising within a
-    track (None: consecutive rows are consecutive frames); a track may have gaps, and a gap-closed table need not be filled.
-    use [N] bool (None: all): a row is left out where it is False, where a coordinate is not finite, and where a variance is
-    negative or not finite; the increment then bridges its neighbours like any other gap.  blur is the motion-blur
-    coefficient R in [0, 1/4] (0: instantaneous exposure, 1/6: exposure over the whole frame).
-
-    The increments of a track are zero-mean Gaussian with a tridiagonal covariance (2 D dt (g - 2 R) + v_k + v_{k+1} on the
-    diagonal, 2 R D dt - v_{k+1} beside it), the two axes independent and sharing D.  The likelihood is evaluated by the
-    LDL^T recurrence and maximised by a fixed grid search over log2 D: six rounds of 64 candidates, from D_ref 2^-20 to D_ref
-    2^4 with D_ref = <d^2> / (4 dt <g>); include/mivit_hip.h has every operation.  Unlike D_cve it uses rows of different
-    quality for what they are worth and needs no gap-free table; unlike D_msd and segments["D_mle"] it is not biased by
-    localisation noise and motion blur.  CUDA tensors go to the kernel (csrc/likelihood.hip: one wave per track, no limit on
-    its length), numpy arrays and CPU tensors to the numpy restatement, which differs from it in log and exp2 alone."""
+def _ml_arguments(positions, offsets, variances, frames, use, dt):
+    """The argument handling that estimate_diffusion_ml and estimate_anomalous_ml share: the checks, then everything as torch
+    tensors on the input's device -> (is_t, pos [N, 2] float64, off [n + 1] int64, var [N, 2] float64 or None, fr [N] int64 or
+    None, usable [N] bool or None)."""
     if not 0.0 < float(dt) < float("inf"):
         raise ValueError(f"dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(blur) <= 0.25:
-        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
     if len(positions.shape) != 2 or positions.shape[1] != 2:
         raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
     is_t = torch.is_tensor(positions)
@@ -1077,6 +1054,39 @@ def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=N
         if int(fr.min()) < -2 ** 31 or int(fr.max()) >= 2 ** 31:
             raise ValueError("frames must fit 32 bits")
     usable = None if use is None else as_t(use).contiguous()
+    return is_t, pos, off, var, fr, usable
+
+
+def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, blur=0.0):
+    """The maximum-likelihood diffusion coefficient of every track with its standard error, from rows that each carry their
+    own localisation variance (Berglund 2010; Michalet & Berglund 2012; Relich et al. 2016): positions [N, 2] (y, x) sorted
+    by track and by frame, offsets [n + 1] (CSR, from 0 to N: tracks, or the seg_offsets / run_offsets of segment_tracks and
+    estimate_track_diffusion) -> dict of the input's kind:
+        D_ml         [n] float64   in pixels^2 per unit of dt; 0 for a track that does not move within its noise (status 2)
+        D_ml_std     [n] float64   its standard error, D_ml / sqrt(observed information in ln D)
+        loglik       [n] float64   the log-likelihood at D_ml
+        n_increments [n] int64     the increments between usable rows
+        status       [n] int64     0 fine; 1 fewer than 2 increments (NaN); 2 the minimum at the lower end of the search
+                                   (D_ml = 0, D_ml_std NaN); 3 at its upper end; 4 the curvature is not positive (D_ml_std NaN)
+    variances: the variance of each coordinate, [N, 2], or [N] (both axes alike), or one number, or None for 0: the squared
+    Cramer-Rao bounds (y_std^2, x_std^2) of fit_spots_mle are what it was made for.  frames [N] integers rising within a
+    track (None: consecutive rows are consecutive frames); a track may have gaps, and a gap-closed table need not be filled.
+    use [N] bool (None: all): a row is left out where it is False, where a coordinate is not finite, and where a variance is
+    negative or not finite; the increment then bridges its neighbours like any other gap.  blur is the motion-blur
+    coefficient R in [0, 1/4] (0: instantaneous exposure, 1/6: exposure over the whole frame).
+
+    The increments of a track are zero-mean Gaussian with a tridiagonal covariance (2 D dt (g - 2 R) + v_k + v_{k+1} on the
+    diagonal, 2 R D dt - v_{k+1} beside it), the two axes independent and sharing D.  The likelihood is evaluated by the
+    LDL^T recurrence and maximised by a fixed grid search over log2 D: six rounds of 64 candidates, from D_ref 2^-20 to D_ref
+    2^4 with D_ref = <d^2> / (4 dt <g>); include/mivit_hip.h has every operation.  Unlike D_cve it uses rows of different
+    quality for what they are worth and needs no gap-free table; unlike D_msd and segments["D_mle"] it is not biased by
+    localisation noise and motion blur.  CUDA tensors go to the kernel (csrc/likelihood.hip: one wave per track, no limit on
+    its length), numpy arrays and CPU tensors to the numpy restatement, which differs from it in log and exp2 alone."""
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
+    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
     if pos.device.type == "cuda":
         from .. import ops
         D, D_std, loglik, n_inc, status = ops.track_diffusion_ml(pos, off.int().contiguous(), var,
@@ -1089,3 +1099,245 @@ def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=N
     out = {"D_ml": D, "D_ml_std": D_std, "loglik": loglik, "n_increments": n_inc.astype(np.int64),
            "status": status.astype(np.int64)}
     return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# maximum-likelihood anomalous exponent per track from rows of known variance, with error bars (csrc/fbm_ml.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+FBM_ML_MAX_ROWS, FBM_ML_MAX_SPAN = 129, 1199      # csrc/fbm_ml.hip: usable rows of a range, largest - smallest usable frame
+_FBM_GRID, _FBM_ROUNDS, _FBM_U_LO, _FBM_U_HI, _FBM_TERMS, _FBM_H = 8, 20, -12.0, 4.0, 30, 1.0 / 64.0
+
+
+def fbm_structure(alpha, lag, exposure=0.0):
+    """The structure function S of fractional Brownian motion averaged over an exposure E in [0, 1] of a frame, at integer
+    lags (in frames; the sign does not matter), alpha and lag broadcast against each other: the per-axis variance of the
+    difference of two averaged positions that lie `lag` frames apart is 2 D dt (S(lag) - S(0)).  E = 0: |lag|^alpha.  E > 0: the double integral of |lag + s - t|^alpha over the exposure,
+    2 E^alpha / ((alpha + 1)(alpha + 2)) at lag 0, the closed form where E > |lag| / 2 and a series of 30 terms in (E / lag)^2
+    elsewhere, which does not cancel.  The operations of csrc/fbm_ml.hip::fm_structure in their order."""
+    alpha, tau = np.broadcast_arrays(np.asarray(alpha, np.float64), np.abs(np.asarray(lag)).astype(np.float64))
+    E = float(exposure)
+    with np.errstate(all="ignore"):
+        if E == 0.0:
+            return np.where(tau == 0, 0.0, np.power(tau, alpha))
+        a12 = (alpha + 1.0) * (alpha + 2.0)
+        p = alpha + 2.0
+        closed = ((np.power(tau + E, p) + np.power(np.abs(tau - E), p)) - 2.0 * np.power(tau, p)) / ((E * E) * a12)
+        x = E / np.where(tau == 0, 1.0, tau)
+        x2 = x * x
+        term, total = np.ones(tau.shape), np.ones(tau.shape)
+        for m in range(1, _FBM_TERMS + 1):
+            tm = float(2 * m)
+            term = (term * (((alpha - tm + 2.0) * (alpha - tm + 1.0)) / ((tm + 1.0) * (tm + 2.0)))) * x2
+            total = total + term
+        return np.where(tau == 0, (2.0 * np.power(E, alpha)) / a12, np.where(E > 0.5 * tau, closed, np.power(tau, alpha) * total))
+
+
+def _fbm_usable_rows(pos, var, frames, use, offsets):
+    """-> per range (X [M, 2], V [M, 2], F [M] int64) of its usable rows, by the rule of _diffusion_ml_numpy"""
+    ok = np.isfinite(pos).all(axis=1)
+    if var is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
+    if use is not None:
+        ok &= use.astype(bool)
+    out = []
+    for k in range(len(offsets) - 1):
+        a, b = int(offsets[k]), int(offsets[k + 1])
+        r = a + np.nonzero(ok[a:b])[0]
+        out.append((pos[r], np.zeros((len(r), 2)) if var is None else var[r],
+                    (r - a if frames is None else frames[r]).astype(np.int64)))
+    return out
+
+
+def _fbm_over_limit(F):
+    return len(F) > FBM_ML_MAX_ROWS or (len(F) > 0 and int(F.max()) - int(F.min()) > FBM_ML_MAX_SPAN)
+
+
+def _fbm_cost(alpha, D, X, V, F, dt, E):
+    """-2 log L of one range (X [m + 1, 2], V [m + 1, 2], F [m + 1], m >= 1) at the candidates alpha [C], D [C]: the dense
+    covariance of include/mivit_hip.h (mivit_track_fbm_loglik) per axis, LAPACK's Cholesky, +inf where it is not positive
+    definite or the cost is not below +inf."""
+    m = len(X) - 1
+    d = X[1:] - X[:-1]
+    lo, hi = F[:-1] - F.min(), F[1:] - F.min()
+    with np.errstate(all="ignore"):
+        tab = fbm_structure(alpha[:, None], np.arange(int(F.max() - F.min()) + 1)[None, :], E)
+        q = ((tab[:, np.abs(hi[:, None] - lo[None, :])] + tab[:, np.abs(lo[:, None] - hi[None, :])])
+             - tab[:, np.abs(hi[:, None] - hi[None, :])]) - tab[:, np.abs(lo[:, None] - lo[None, :])]
+        base = (D * dt)[:, None, None] * q
+        cost = np.full(len(alpha), float(2 * m) * _LOG_2PI)
+        for ax in (0, 1):
+            v = V[:, ax]
+            C = base + (np.diag(v[:-1] + v[1:]) - np.diag(v[1:-1], 1) - np.diag(v[1:-1], -1))[None]
+            L = np.full(C.shape, np.nan)
+            try:
+                L = np.linalg.cholesky(C)
+            except np.linalg.LinAlgError:
+                for c in range(len(C)):
+                    try:
+                        L[c] = np.linalg.cholesky(C[c])
+                    except np.linalg.LinAlgError:
+                        pass
+            fine = np.isfinite(L).all(axis=(1, 2))
+            L[~fine] = np.eye(m)
+            z = np.linalg.solve(L, np.broadcast_to(d[:, ax, None], (len(C), m, 1)))[..., 0]
+            cost = cost + np.where(fine, 2.0 * np.log(np.diagonal(L, axis1=1, axis2=2)).sum(axis=1) + (z * z).sum(axis=1), np.inf)
+        return np.where(cost < np.inf, cost, np.inf)
+
+
+def _fbm_loglik_numpy(pos, var, frames, use, offsets, dt, E, alpha, D):
+    """csrc/fbm_ml.hip's mivit_track_fbm_loglik restated -> (loglik [n] float64, n_increments, status [n] int32)"""
+    n = len(offsets) - 1
+    loglik, n_inc, status = np.full(n, np.nan), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for k, (X, V, F) in enumerate(_fbm_usable_rows(pos, var, frames, use, offsets)):
+        n_inc[k] = max(len(X) - 1, 0)
+        if _fbm_over_limit(F):
+            status[k] = 5
+        elif n_inc[k] < 1:
+            status[k] = 1
+        elif not (0.0 < alpha[k] < 2.0 and 0.0 <= D[k] < np.inf):
+            status[k] = 6
+        else:
+            loglik[k] = -0.5 * _fbm_cost(alpha[k:k + 1], D[k:k + 1], X, V, F, dt, E)[0]
+    return loglik, n_inc, status
+
+
+def _fbm_ml_numpy(pos, var, frames, use, offsets, dt, E):
+    """The search of csrc/fbm_ml.hip (include/mivit_hip.h, mivit_track_fbm_ml) restated range by range: the same brackets,
+    candidates, arg-min (np.argmin returns the lowest index among equal minima), stencil and statuses, on the cost of
+    _fbm_cost -> (alpha, alpha_std, D, D_std, corr, loglik [n] float64, n_increments, status [n] int32).  Differs from the
+    kernel in the order of the sums of the factorisation, in pow, exp2 and log."""
+    from .generation import ALPHA_MAX, ALPHA_MIN
+    n = len(offsets) - 1
+    alpha, alpha_std, D, D_std, corr, loglik = (np.full(n, np.nan) for _ in range(6))
+    n_inc, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    grid = np.arange(_FBM_GRID, dtype=np.float64)
+    for k, (X, V, F) in enumerate(_fbm_usable_rows(pos, var, frames, use, offsets)):
+        n_inc[k] = max(len(X) - 1, 0)
+        if _fbm_over_limit(F):
+            status[k] = 5
+            continue
+        if n_inc[k] < 3:
+            status[k] = 1
+            continue
+        d = X[1:] - X[:-1]
+        with np.errstate(all="ignore"):
+            D_ref = np.cumsum(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])[-1] / ((4.0 * dt) * float(int(F[-1]) - int(F[0])))
+            alo, ahi, ulo, uhi = ALPHA_MIN, ALPHA_MAX, _FBM_U_LO, _FBM_U_HI
+            all_lo = all_hi = True
+            for _ in range(_FBM_ROUNDS):
+                sa, su = (ahi - alo) / 7.0, (uhi - ulo) / 7.0
+                a_c = np.repeat(alo + grid * sa, _FBM_GRID)
+                D_c = np.tile(D_ref * np.exp2(ulo + grid * su), _FBM_GRID)
+                best = int(np.argmin(_fbm_cost(a_c, D_c, X, V, F, dt, E)))
+                i, j = best >> 3, best & 7
+                ab, ub = alo + float(i) * sa, ulo + float(j) * su
+                alo, ahi, ulo, uhi = max(ab - 2.0 * sa, ALPHA_MIN), min(ab + 2.0 * sa, ALPHA_MAX), ub - 2.0 * su, ub + 2.0 * su
+                all_lo, all_hi = all_lo and j == 0, all_hi and j == _FBM_GRID - 1
+            Db = 0.0 if all_lo else float(D_ref * np.exp2(ub))
+            a_s = np.repeat(ab + np.array([-1.0, 0.0, 1.0]) * _FBM_H, 3)
+            D_s = np.tile(np.array([Db * _ML_EXP_MH, Db, Db * _ML_EXP_H]), 3)
+            c = _fbm_cost(a_s, D_s, X, V, F, dt, E)
+            st = 2 if all_lo else (3 if all_hi else 0)
+            loglik[k], D[k] = -0.5 * c[4], Db
+            if st != 2:
+                alpha[k] = ab
+                Haa = ((c[7] - c[4]) + (c[1] - c[4])) * 2048.0
+                Hdd = ((c[5] - c[4]) + (c[3] - c[4])) * 2048.0
+                Had = ((c[8] - c[6]) - (c[2] - c[0])) * 512.0
+                det = Haa * Hdd - Had * Had
+                if ab - _FBM_H >= ALPHA_MIN and ab + _FBM_H <= ALPHA_MAX and Haa > 0.0 and Hdd > 0.0 and 0.0 < det < np.inf:
+                    alpha_std[k], D_std[k], corr[k] = np.sqrt(Hdd / det), Db * np.sqrt(Haa / det), -Had / np.sqrt(Haa * Hdd)
+                elif st == 0:
+                    st = 4
+            status[k] = st
+    return alpha, alpha_std, D, D_std, corr, loglik, n_inc, status
+
+
+def _fbm_checked(exposure, dt):
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(exposure) <= 1.0:
+        raise ValueError(f"exposure must lie in [0, 1], got {exposure}")
+
+
+def fbm_loglik(positions, offsets, alpha, D, variances=None, frames=None, use=None, dt=1.0, exposure=0.0):
+    """The exact log-likelihood of every range under fractional Brownian motion with the exponent alpha and the generalised
+    diffusion coefficient D (numbers, or one per range [n]; per-axis ensemble MSD 2 D dt lag^alpha), seen through an exposure
+    over the first `exposure` of each frame and localisation noise of the rows' variances: the model of
+    estimate_anomalous_ml at given parameters, to compare hypotheses with -> dict of the input's kind: loglik [n] float64
+    (-inf where the covariance is not positive definite), n_increments [n] int64, status [n] int64 (0 fine, 1 no increment,
+    5 over ops.FBM_ML_MAX_ROWS usable rows or ops.FBM_ML_MAX_SPAN frames, 6 alpha outside (0, 2) or D negative or not finite;
+    loglik is NaN for 1, 5, 6).  The other arguments are those of estimate_diffusion_ml.  CUDA tensors go to the kernel
+    (csrc/fbm_ml.hip), arrays and CPU tensors to the numpy restatement."""
+    _fbm_checked(exposure, dt)
+    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    n = off.numel() - 1
+
+    def per_range(v, what):
+        v = v.detach().to(pos.device, torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64), device=pos.device)
+        if v.dim() == 0:
+            v = v.expand(n)
+        if tuple(v.shape) != (n,):
+            raise ValueError(f"{what} must be a number or [n] = [{n}], got {tuple(v.shape)}")
+        return v.contiguous()
+
+    a, Dv = per_range(alpha, "alpha"), per_range(D, "D")
+    if pos.device.type == "cuda":
+        from .. import ops
+        ll, n_inc, status = ops.track_fbm_loglik(pos, off.int().contiguous(), a, Dv, var, None if fr is None else fr.int().contiguous(),
+                                                 usable, float(dt), float(exposure))
+        return {"loglik": ll, "n_increments": n_inc.long(), "status": status.long()}
+    ll, n_inc, status = _fbm_loglik_numpy(pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
+                                          None if usable is None else usable.numpy(), off.numpy(), float(dt), float(exposure),
+                                          a.numpy(), Dv.numpy())
+    out = {"loglik": ll, "n_increments": n_inc.astype(np.int64), "status": status.astype(np.int64)}
+    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out
+
+
+def estimate_anomalous_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, exposure=0.0):
+    """The maximum-likelihood anomalous exponent and generalised diffusion coefficient of every track with their standard
+    errors, from rows that each carry their own localisation variance: positions, offsets, variances, frames, use and dt as
+    estimate_diffusion_ml takes them; exposure in [0, 1] is the part of a frame, from its start, over which the camera
+    integrates (0: instantaneous, 1: the whole frame; at alpha = 1 it is blur = exposure / 6) -> dict of the input's kind:
+        alpha_ml     [n] float64   the exponent, in [ALPHA_MIN, ALPHA_MAX] of helpers/generation; NaN for status 1, 2, 5
+        alpha_ml_std [n] float64   its standard error
+        D_alpha      [n] float64   the generalised coefficient: the per-axis ensemble MSD at a lag of k frames is
+                                   2 D_alpha dt k^alpha, as fbm_single_state draws it; 0 for status 2
+        D_alpha_std  [n] float64   its standard error
+        corr         [n] float64   the correlation of the two estimates (of alpha and ln D)
+        loglik       [n] float64   the log-likelihood at the estimates
+        lr_brownian  [n] float64   2 (loglik - the loglik of estimate_diffusion_ml(..., blur=exposure / 6)): the likelihood
+                                   ratio against Brownian motion, one more parameter
+        n_increments [n] int64     the increments between usable rows
+        status       [n] int64     0 fine; 1 fewer than 3 increments (NaN); 2 the track does not move within its noise
+                                   (D_alpha = 0, alpha_ml and the bars NaN); 3 D at the upper end of every round; 4 the
+                                   curvature is not positive definite or alpha_ml is within 1/64 of the end of its range
+                                   (the estimates stay, the bars are NaN); 5 more than ops.FBM_ML_MAX_ROWS = 129 usable
+                                   rows or usable frames that span more than ops.FBM_ML_MAX_SPAN = 1199 (NaN)
+    Unlike estimate_alpha, the slope of log MSD against log lag, it is not biased by localisation noise and motion blur, uses
+    gap-closed tracks without filling them and has an error bar.  The increments of a track are zero-mean Gaussian with a
+    DENSE covariance (include/mivit_hip.h has every operation), factorised by Cholesky per candidate; the search is fixed, 20
+    rounds of an 8 x 8 grid over alpha and log2 D that shrinks to the best candidate +- 2 cells, and the error bars come from
+    the second differences of the log-likelihood with a step of 1/64 in alpha and in ln D.  CUDA tensors go to the kernel
+    (csrc/fbm_ml.hip: one workgroup per track and candidate), arrays and CPU tensors to the numpy restatement with LAPACK's
+    Cholesky, which differs from it in the order of sums, pow, exp2 and log."""
+    _fbm_checked(exposure, dt)
+    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    brownian = estimate_diffusion_ml(positions, offsets, variances, frames, use, dt, blur=float(exposure) / 6.0)["loglik"]
+    keys = ("alpha_ml", "alpha_ml_std", "D_alpha", "D_alpha_std", "corr", "loglik", "n_increments", "status")
+    if pos.device.type == "cuda":
+        from .. import ops
+        got = ops.track_fbm_ml(pos, off.int().contiguous(), var, None if fr is None else fr.int().contiguous(), usable, float(dt),
+                               float(exposure))
+        out = dict(zip(keys, got))
+        out["n_increments"], out["status"] = out["n_increments"].long(), out["status"].long()
+    else:
+        got = _fbm_ml_numpy(pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
+                            None if usable is None else usable.numpy(), off.numpy(), float(dt), float(exposure))
+        out = dict(zip(keys, got))
+        out["n_increments"], out["status"] = out["n_increments"].astype(np.int64), out["status"].astype(np.int64)
+        if is_t:
+            out = {k: torch.from_numpy(v) for k, v in out.items()}
+    out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
+    return out

@@ -1762,7 +1762,8 @@ def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None, fra
 
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
-                             batch_size=4096, segment=None, states=None, drift=None, localization=None, ml=None, **tracking_kwargs):
+                             batch_size=4096, segment=None, states=None, drift=None, localization=None, ml=None, anomalous=None,
+                             **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1822,7 +1823,30 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     (the same call on seg_offsets), and with states, "states" gains them per run (on run_offsets).  segments["D_mle"] keeps
     its name and meaning: it is <q> / (4 dt), the maximum-likelihood estimate of a track WITHOUT localisation noise and blur,
     which noise biases upwards by sigma^2 / dt; D_ml is the estimate under the full model and is the one to hold against
-    D_model."""
+    D_model.
+
+    anomalous (default None: the code path without it): a dict with keys among exposure and sigma2 ({} for the defaults), the
+    arguments of helpers/msd.estimate_anomalous_ml (csrc/fbm_ml.hip), the maximum-likelihood anomalous exponent of every
+    track with a standard error.  exposure in [0, 1] is the part of a frame over which the camera integrates (default 0);
+    sigma2 follows the rules of ml["sigma2"], and so do the rows used and the positions (drift-corrected, the frames of the
+    table, a filled row is a gap).  The result gains alpha_ml, alpha_ml_std, D_alpha (float64) and anomalous_status (int64)
+    [n_tracks], and "anomalous": what estimate_anomalous_ml was called with (positions, variances, frames, use, exposure).
+    Tracks only: segments and states do not get an exponent of their own."""
+    if anomalous is not None:
+        if not isinstance(anomalous, dict) or set(anomalous) - {"exposure", "sigma2"}:
+            raise ValueError("anomalous must be None or a dict with keys among exposure and sigma2")
+        anomalous = dict(anomalous)
+        anomalous.setdefault("exposure", 0.0)
+        anomalous.setdefault("sigma2", "crlb" if localization is not None else 0.0)
+        if isinstance(anomalous["sigma2"], str):
+            if anomalous["sigma2"] != "crlb":
+                raise ValueError(f"anomalous['sigma2'] must be a number or 'crlb', got {anomalous['sigma2']!r}")
+            if localization is None:
+                raise ValueError("anomalous['sigma2'] = 'crlb' needs localization: the least-squares fit returns no bound")
+        elif not 0.0 <= float(anomalous["sigma2"]) < float("inf"):
+            raise ValueError(f"anomalous['sigma2'] must be >= 0 and finite, got {anomalous['sigma2']}")
+        if not 0.0 <= float(anomalous["exposure"]) <= 1.0:
+            raise ValueError(f"anomalous['exposure'] must lie in [0, 1], got {anomalous['exposure']}")
     if ml is not None:
         if not isinstance(ml, dict) or set(ml) - {"blur", "sigma2"}:
             raise ValueError("ml must be None or a dict with keys among blur and sigma2")
@@ -1922,6 +1946,15 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
             return _msd.estimate_diffusion_ml(pos, csr, dt=dt, **ml_args)
 
         ml_tracks = ml_fit(offsets)
+    if anomalous is not None:
+        from . import msd as _msd
+        filled = by_track[5] if len(by_track) > 5 else None
+        if anomalous["sigma2"] == "crlb":
+            an_args = {"variances": torch.stack([fit["y_std"] * fit["y_std"], fit["x_std"] * fit["x_std"]], dim=1), "use": good}
+        else:
+            an_args = {"variances": float(anomalous["sigma2"]), "use": None if filled is None else ~filled}
+        an_args.update(frames=fr, exposure=float(anomalous["exposure"]))
+        an_tracks = _msd.estimate_anomalous_ml(pos, offsets, dt=dt, **an_args)
     seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
     n_sequences = torch.bincount(seq_track, minlength=n_tracks)
     model.eval()
@@ -1985,6 +2018,10 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     if ml is not None:
         res["D_ml"], res["D_ml_std"], res["ml_status"] = ml_tracks["D_ml"], ml_tracks["D_ml_std"], ml_tracks["status"]
         res["ml"] = dict(ml_args, positions=pos)
+    if anomalous is not None:
+        res["alpha_ml"], res["alpha_ml_std"], res["D_alpha"] = an_tracks["alpha_ml"], an_tracks["alpha_ml_std"], an_tracks["D_alpha"]
+        res["anomalous_status"] = an_tracks["status"]
+        res["anomalous"] = dict(an_args, positions=pos)
     return res
 
 

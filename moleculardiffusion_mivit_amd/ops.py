@@ -1193,6 +1193,93 @@ def track_diffusion_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frame
     return D, D_std, loglik, n_inc, status
 
 
+FBM_ML_MAX_ROWS = 129        # csrc/fbm_ml.hip: usable rows of a range (128 increments: the packed triangle fills the LDS)
+FBM_ML_MAX_SPAN = 1199       # csrc/fbm_ml.hip: largest - smallest usable frame of a range (the table of the structure function)
+FBM_ML_WS_BYTES = 640        # csrc/fbm_ml.hip: workspace of mivit_track_fbm_ml per range
+
+
+def _fbm_ml_args(name, pos, offsets, var, frames, use, dt, exposure):
+    """the checks track_fbm_loglik and track_fbm_ml share (those of track_diffusion_ml) -> (pos, offsets, var, frames, use, N, n)"""
+    pos = _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
+    offsets = _seg_tensor(offsets, torch.int32, 1, name, "offsets [n + 1]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"{name}: pos must be [N, 2], got {tuple(pos.shape)}")
+    if offsets.numel() < 1:
+        raise ValueError(f"{name}: offsets must have n + 1 entries")
+    n_rows, n = pos.shape[0], offsets.numel() - 1
+    given = [pos, offsets]
+    if var is not None:
+        var = _seg_tensor(var, torch.float64, 2, name, "var [N, 2]")
+        if tuple(var.shape) != (n_rows, 2):
+            raise ValueError(f"{name}: var must be [{n_rows}, 2], got {tuple(var.shape)}")
+        given.append(var)
+    if frames is not None:
+        frames = _seg_tensor(frames, torch.int32, 1, name, "frames [N]")
+        if frames.numel() != n_rows:
+            raise ValueError(f"{name}: frames must be [{n_rows}], got {tuple(frames.shape)}")
+        given.append(frames)
+    if use is not None:
+        if torch.is_tensor(use) and use.dtype == torch.bool:
+            use = use.view(torch.uint8)
+        use = _seg_tensor(use, torch.uint8, 1, name, "use [N] (bool or uint8)")
+        if use.numel() != n_rows:
+            raise ValueError(f"{name}: use must be [{n_rows}], got {tuple(use.shape)}")
+        given.append(use)
+    if len({t.device for t in given}) != 1:
+        raise ValueError(f"{name}: all tensors must be on one device")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"{name}: dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(exposure) <= 1.0:
+        raise ValueError(f"{name}: the exposure must lie in [0, 1], got {exposure}")
+    if n > 1 << 24:
+        raise ValueError(f"{name}: {n} ranges, at most {1 << 24} in one call")
+    if n:
+        off = offsets.cpu()
+        if int(off[0]) != 0 or int(off[-1]) != n_rows or bool((off[1:] < off[:-1]).any()):
+            raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
+    elif n_rows:
+        raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
+    return pos, offsets, var, frames, use, n_rows, n
+
+
+def track_fbm_loglik(pos: torch.Tensor, offsets: torch.Tensor, alpha: torch.Tensor, D: torch.Tensor, var=None, frames=None,
+                     use=None, dt: float = 1.0, exposure: float = 0.0):
+    """The exact log-likelihood of every row range under fractional Brownian motion seen through an exposure and
+    localisation noise of known variance (csrc/fbm_ml.hip, mivit_track_fbm_loglik): pos, offsets, var, frames, use, dt as
+    track_diffusion_ml; alpha [n], D [n] float64 the parameters of every range; exposure in [0, 1] -> (loglik [n] float64,
+    n_increments, status [n] int32).  A range may have at most FBM_ML_MAX_ROWS usable rows over at most FBM_ML_MAX_SPAN frames
+    (status 5).  See include/mivit_hip.h for the arithmetic and the status codes and helpers/msd.fbm_loglik for the front end."""
+    name = "track_fbm_loglik"
+    pos, offsets, var, frames, use, n_rows, n = _fbm_ml_args(name, pos, offsets, var, frames, use, dt, exposure)
+    alpha = _seg_tensor(alpha, torch.float64, 1, name, "alpha [n]")
+    D = _seg_tensor(D, torch.float64, 1, name, "D [n]")
+    if alpha.numel() != n or D.numel() != n or alpha.device != pos.device or D.device != pos.device:
+        raise ValueError(f"{name}: alpha and D must be [{n}] on the device of pos, got {tuple(alpha.shape)} and {tuple(D.shape)}")
+    loglik = torch.empty(n, dtype=torch.float64, device=pos.device)
+    n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
+    N.check(N.lib.mivit_track_fbm_loglik(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt), float(exposure),
+                                         _p(alpha), _p(D), _p(loglik), _p(n_inc), _p(status), _s(pos)), "mivit_track_fbm_loglik")
+    return loglik, n_inc, status
+
+
+def track_fbm_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0, exposure: float = 0.0):
+    """The maximum-likelihood anomalous exponent and generalised diffusion coefficient of every row range with their standard
+    errors (csrc/fbm_ml.hip, mivit_track_fbm_ml): the arguments of track_diffusion_ml with exposure in [0, 1] in the place of
+    blur -> (alpha, alpha_std, D, D_std, corr, loglik [n] float64, n_increments, status [n] int32).  The whole search (20
+    rounds of 64 candidates a range) is queued on the stream without a host synchronisation; the workspace (FBM_ML_WS_BYTES a
+    range) is allocated here.  A range may have at most FBM_ML_MAX_ROWS usable rows over at most FBM_ML_MAX_SPAN frames (status
+    5).  See include/mivit_hip.h for the arithmetic and the status codes and helpers/msd.estimate_anomalous_ml for the front end."""
+    name = "track_fbm_ml"
+    pos, offsets, var, frames, use, n_rows, n = _fbm_ml_args(name, pos, offsets, var, frames, use, dt, exposure)
+    outs = [torch.empty(n, dtype=torch.float64, device=pos.device) for _ in range(6)]
+    n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
+    ws = torch.empty(max(n, 1) * FBM_ML_WS_BYTES // 8, dtype=torch.float64, device=pos.device)
+    N.check(N.lib.mivit_track_fbm_ml(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt), float(exposure),
+                                     *(_p(o) for o in outs), _p(n_inc), _p(status), _p(ws), ws.numel() * 8, _s(pos)),
+            "mivit_track_fbm_ml")
+    return (*outs, n_inc, status)
+
+
 DRIFT_MAX_PAIRS = 4096       # csrc/drift.hip: increments of one frame that the median sorts in LDS (8 B a pair, 32 KiB)
 DRIFT_MODES = {"mean": 0, "median": 1}
 

@@ -9,6 +9,14 @@ blink), --max-gap N closes and fills gaps of up to N missed frames (track_partic
 fractional Brownian particles of that anomalous exponent (simulate_movie's alphas, csrc/fbm.hip) and adds, per track,
 alpha_true and alpha_msd = msd.estimate_alpha of the recovered track's MSD over the lags 1 .. --alpha-max-lag, its median
 over the tracks of at least 20 rows, and the same estimator's median on the truth table and on the truth without motion blur.
+--alpha-ml [SIGMA2] (with --alpha) adds beside alpha_msd the maximum-likelihood exponent of every track with its error bar
+(helpers/msd.estimate_anomalous_ml, csrc/fbm_ml.hip, through estimate_track_diffusion(..., anomalous={"exposure": 1, "sigma2":
+SIGMA2})): alpha_ml, alpha_ml_std, D_alpha and anomalous_status per track, and over the matched tracks of at least 20 rows
+and status 0 the median of alpha_ml, the RMS errors of alpha_ml and alpha_msd and the RMS of (alpha_ml - alpha_true) /
+alpha_ml_std.  SIGMA2 is the localisation variance per coordinate; without it, half the squared RMSE of the matched rows
+(an upper bound: the RMSE also holds every constant offset, and a variance that is too large pushes alpha_ml up).  With
+--camera and --mle the columns "mle" and "mle2" get the same figures from the rows' own Cramer-Rao bounds (sigma2 = "crlb"),
+which is the use the estimator was made for.
 --cristae N SPACING DEPTH WIDTH confines every particle to one serpentine of N cristae (helpers/geometry.cristae_geometry,
 centred in the field; simulate_movie's geometry, csrc/confine.hip), --boundary clamp|reflect is what happens at its two ends;
 D is then the 1-D coefficient along the filament, and the output gains the filament's total length and the medians of D_true,
@@ -48,7 +56,7 @@ of a spot in the movie's units: photons with --camera.  A tool, not a test: it a
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
-                                          [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10]
+                                          [--blink 0.05] [--max-gap 2] [--alpha 0.6] [--alpha-max-lag 10] [--alpha-ml [0.01]]
                                           [--cristae 4 30 60 12] [--boundary reflect]
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
@@ -89,6 +97,7 @@ def main():
     ap.add_argument("--max-gap", type=int, default=0)
     ap.add_argument("--alpha", type=float, default=None)
     ap.add_argument("--alpha-max-lag", type=int, default=10)
+    ap.add_argument("--alpha-ml", type=float, nargs="?", const=-1.0, default=None, metavar="SIGMA2")
     ap.add_argument("--cristae", type=float, nargs=4, default=None, metavar=("N", "SPACING", "DEPTH", "WIDTH"))
     ap.add_argument("--boundary", choices=["clamp", "reflect"], default=None)
     ap.add_argument("--states", type=float, nargs=3, default=None, metavar=("D1", "D2", "P_STAY"))
@@ -118,6 +127,8 @@ def main():
         raise SystemExit("--neighbours needs --mle: the joint fit is a maximum-likelihood fit")
     if args.ml is not None and not args.mle:
         raise SystemExit("--ml needs --mle: the row variances are the bounds of the maximum-likelihood fit")
+    if args.alpha_ml is not None and args.alpha is None:
+        raise SystemExit("--alpha-ml needs --alpha: it is held against the exponent the movie was simulated with")
     drift = None
     if args.drift is not None:
         try:
@@ -207,6 +218,23 @@ def main():
         sharp = truth["pos"][:, ::args.npos].double()
         s_msd = MSD.mean_square_displacements(sharp)
         out["alpha_msd_truth_unblurred_median"] = float(MSD.estimate_alpha(s_msd, max_lag=args.alpha_max_lag).nanmedian())
+        if args.alpha_ml is not None:
+            # the localisation variance per coordinate: the number given, or half the squared RMSE of the matched rows (from the
+            # truth: this is a tool); the movie's positions are frame means, so the exposure is the whole frame
+            sigma2 = args.alpha_ml if args.alpha_ml >= 0 else float(score["rmse"]) ** 2 / 2.0
+            an = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
+                                              anomalous={"exposure": 1.0, "sigma2": sigma2})
+            for row, a, sd, dd, st in zip(out["tracks"], an["alpha_ml"].tolist(), an["alpha_ml_std"].tolist(), an["D_alpha"].tolist(),
+                                          an["anomalous_status"].tolist()):
+                row["alpha_ml"], row["alpha_ml_std"], row["D_alpha"], row["anomalous_status"] = a, sd, dd, st
+            fine = long & (an["anomalous_status"] == 0) & ~torch.isnan(a_true)
+            pull = (an["alpha_ml"][fine] - a_true[fine]) / an["alpha_ml_std"][fine]
+            out["alpha_ml_sigma2"] = sigma2
+            out["alpha_ml_median"] = float(an["alpha_ml"][fine].median()) if bool(fine.any()) else float("nan")
+            out["alpha_ml_n_tracks"] = int(fine.sum())
+            out["alpha_ml_rms_error"] = float((an["alpha_ml"][fine] - a_true[fine]).pow(2).mean().sqrt()) if bool(fine.any()) else float("nan")
+            out["alpha_msd_rms_error"] = float((a_msd[fine] - a_true[fine]).pow(2).mean().sqrt()) if bool(fine.any()) else float("nan")
+            out["rms_alpha_ml_error_over_std"] = float(pull.pow(2).mean().sqrt()) if bool(fine.any()) else float("nan")
     if drift is not None:
         out["drift"] = drift_scores(movie, model, args, norm, truth, score, est, out["tracks"], states)
     if camera is not None:
@@ -275,6 +303,7 @@ def camera_scores(movie, model, args, norm, truth, score, props, camera, states)
         ok = (pid >= 0) & (fit["status"] == 0) & (err.pow(2).sum(dim=1).sqrt() <= args.max_distance)
         est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap,
                                            segment={}, **({"ml": {"blur": args.ml}} if args.ml is not None and method != "lsq" else {}),
+                                           **({"anomalous": {"exposure": 1.0}} if args.alpha_ml is not None and method != "lsq" else {}),
                                            **({"localization": loc} if method == "mle" else
                                                           {"localization": dict(loc, neighbours=joint)} if method == "mle2" else {}))
         seg = est["segments"]
@@ -301,6 +330,16 @@ def camera_scores(movie, model, args, norm, truth, score, props, camera, states)
                 col.update({"ml_blur": args.ml, "D_ml_median": med(est["D_ml"]), "D_ml_status_0": int(fine.sum()),
                             "D_ml_tracks_matched": int(track_ok.sum()),
                             "rms_D_ml_error_over_std": float(pull.pow(2).mean().sqrt()) if bool(fine.any()) else nan})
+            if args.alpha_ml is not None:                   # the rows' own bounds as their variances (sigma2 = "crlb")
+                a_true = truth["alpha"][score["particle_id"].clamp_min(0)]
+                a_msd = MSD.estimate_alpha(est["msd"], max_lag=args.alpha_max_lag)
+                fine = track_ok & (est["anomalous_status"] == 0) & (est["length"] >= 20) & ~torch.isnan(a_msd)
+                rms = lambda v: float(v[fine].pow(2).mean().sqrt()) if bool(fine.any()) else nan                # noqa: E731
+                col.update({"alpha_ml_median": float(est["alpha_ml"][fine].median()) if bool(fine.any()) else nan,
+                            "alpha_msd_median": float(a_msd[fine].median()) if bool(fine.any()) else nan,
+                            "alpha_ml_n_tracks": int(fine.sum()), "alpha_ml_rms_error": rms(est["alpha_ml"] - a_true),
+                            "alpha_msd_rms_error": rms(a_msd - a_true),
+                            "rms_alpha_ml_error_over_std": rms((est["alpha_ml"] - a_true) / est["alpha_ml_std"])})
             if hmm:
                 kw = dict(norm=norm, max_gap=args.max_gap, localization=loc if method == "mle" else dict(loc, neighbours=joint))
                 zero = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, states={"K": args.hmm}, **kw)
