@@ -697,6 +697,70 @@ int mivit_track_fbm_ml(const double *pos, const double *var, const int *frames, 
                        double *D_std, double *corr, double *loglik, int *n_increments, int *status, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* Per-range maximum-likelihood CONFINEMENT radius with error bars, and the exact log-likelihood of confined diffusion at
+ * given parameters, csrc/confined_ml.hip: an isotropic Ornstein-Uhlenbeck process (diffusion in a harmonic well) whose rows
+ * each carry a known localisation variance and whose frames may be missing (no counterpart in the reference).  The exposure
+ * is INSTANTANEOUS: motion blur is not modelled.  fp64 without contraction, no LDS, no scratch, no atomics; ONE WAVE per
+ * range, lane 8 i + j = candidate (D_i, s2_j); a range has NO maximum length (its rows are read from global memory in each
+ * of the 23 passes) and its outputs are bitwise the same alone, anywhere in a batch and in every launch.
+ *
+ * pos, var, frames, use, N, offsets, n, dt: as mivit_track_diffusion_ml, and so is the rule for a USABLE row.  The usable rows
+ * of a range in order, m of them, have frames f_0 < f_1 < .. (the caller's promise), positions y_k and variances v_k per
+ * axis.  Parameters: the diffusion coefficient D and the stationary variance per axis s2; the rate is lam = D / s2 and each
+ * axis has a centre c.  Per candidate ldt = (D / s2) dt; pm = 0.5, pe = 1; per axis (y, then x, within every row) the state
+ * after row 0 is a = y_0, b = 0, P = v_0 (the filter is conditioned on the first usable row: a diffuse prior on the start;
+ * the mean of the state is a + b c), Syy = Syh = Shh = 0.  For every further row k in ascending order, g = f_k - f_{k-1}:
+ *   t = ldt (double)g;   om = -expm1(-t);   phi = 1 - om;   q = s2 (-expm1(-(2 t)))          (shared by the axes)
+ *   Pm = (phi phi) P + q;   F = Pm + v_k;   r = 1 / F;   am = phi a;   eh = phi b + om;   ey = y_k - am;   K = Pm r
+ *   a = am + K ey;   b = eh - K eh;   P = (1 - K) Pm
+ *   Syy = Syy + (ey ey) r;   Syh = Syh + (ey eh) r;   Shh = Shh + (eh eh) r
+ *   the determinant, shared by the axes: pm = pm F, kept as mantissa in [0.5, 1) times 2^pe by frexp after every factor
+ * Centre given:    Q = (Syy - (2 c) Syh) + (c c) Shh per axis.
+ * Centre profiled: c = Syh / Shh and Q = Syy - (Syh Syh) / Shh where Shh > 0, else c = NaN and Q = Syy; the standard error of
+ *                  the centre is 1 / sqrt(Shh).
+ *   cost = -2 log L = ((log(pm) + pe log 2) + (Q_y + Q_x)) + 2 (m - 1) log(2 pi)
+ * A candidate with some F that is not > 0, or whose cost is not below +inf, has cost +inf.  As s2 -> inf at a fixed centre
+ * this is the likelihood of mivit_track_diffusion_ml at R = 0.
+ *
+ * mivit_track_confined_loglik: D [n], s2 [n] fp64 in, centre [n, 2] fp64 (y, x) or null to profile it -> loglik [n] = -cost /
+ * 2 (-inf for a rejected candidate); NaN for a range with fewer than 2 usable rows and where D or s2 is not positive and
+ * finite.  One THREAD per range runs the same device function.
+ *
+ * mivit_track_confined_ml: the search over (u, w) = (log2 D / D_ref, log2 s2 / S_ref).  D_ref = S / ((4 dt) G) as in
+ * mivit_track_diffusion_ml.  S_ref: my = (y_0 + y_1 + ..) / m in ascending order, mx alike, then S_ref = (sum_k ((y_k - my)
+ * (y_k - my) + (x_k - mx) (x_k - mx))) / (2 m) in ascending k: half the summed variance of the usable positions.  Brackets u
+ * in [-12, 4], w in [-6, 18].  20 rounds of: su = (uhi - ulo) / 7, sw = (whi - wlo) / 7, candidate 8 i + j at D_i = D_ref
+ * exp2(ulo + i su), s2_j = S_ref exp2(wlo + j sw) with the centre profiled; the least cost, the LOWEST candidate on a tie;
+ * ub = ulo + i* su, wb = wlo + j* sw; the next brackets are [ub - 2 su, ub + 2 su] and [wb - 2 sw, wb + 2 sw] (not clamped).
+ * The result is the best candidate of the last round, D = D_ref exp2(ub), s2 = S_ref exp2(wb), whose next brackets would
+ * be 2.2e-4 wide in u and 3.3e-4 in w.  lam = D / s2.  status, the first that applies of: 2 where wb >= 18 (s2 left its first
+ * bracket upwards: the well is wider than the search can see, the track is not confined; this holds in particular where
+ * j* = 7 in every round); 3 where lam dt > 4 (the particle relaxes within a frame); 5 where i* = 0 in every round, or i* = 7
+ * in every round, or j* = 0 in every round; else 0.  Then the cost c_ab at (D e^{a h}, s2 e^{b h}), a, b in {-1, 0, 1}, h = 1 /
+ * 64 (e^h, e^-h as fp64 constants; lane 3 (a + 1) + (b + 1), the other lanes repeat lane 0); loglik = -c_00 / 2; the centre and
+ * Shh come from the lane of c_00;
+ *   Hdd = ((c_+0 - c_00) + (c_-0 - c_00)) 2048, Hss = ((c_0+ - c_00) + (c_0- - c_00)) 2048, Hds = ((c_++ - c_+-) - (c_-+ - c_--)) 512,
+ *   det = Hdd Hss - Hds Hds;  pd = Hdd > 0 and Hss > 0 and 0 < det < inf
+ * status 4 where c_00 is not below +inf (no candidate was accepted; whatever the status was), and where pd fails and the
+ * status was 0.  Where pd holds and the status is 0 or 5: D_std = D sqrt(Hss / det), radius_std = (radius / 2) sqrt(Hdd / det),
+ * corr = -Hds / sqrt(Hdd Hss), lambda_std = lam sqrt(vl) with vl = ((Hss + Hdd) + 2 Hds) / det (the delta method: var ln lam =
+ * var ln D + var ln s2 - 2 cov) where vl >= 0; else they are NaN, but status 3 has radius_std = (radius / 2) / sqrt(Hss) where
+ * 0 < Hss < inf (D is not identified; s2 at the D found).
+ * out, per range: D, D_std, radius = sqrt(2 s2) (the RMS distance from the centre in 2-D; +inf for status 2), radius_std,
+ * lambda = lam (0 for status 2), lambda_std, corr, loglik [n] fp64; centre, centre_std [n, 2] fp64 (y, x; NaN for status 2,
+ * centre_std = 1 / sqrt(Shh) where Shh > 0 and NaN for status 4); n_increments [n] int32 = max(m - 1, 0); status [n] int32: 0
+ * fine, 1 fewer than 4 increments (every fp64 output NaN), 2 .. 5 as above.  The only operations that may differ from the
+ * numpy restatement (helpers/msd._confined_ml_numpy) are expm1, exp2 and log.  Arguments are validated before any HIP call
+ * (sizes, dt, null pointers; pos may be null where N = 0; var, frames, use and the centre of the log-likelihood may be null);
+ * n = 0 is a no-op. */
+int mivit_track_confined_ml(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                            const int *offsets, int n, double dt, double *D, double *D_std, double *radius, double *radius_std,
+                            double *lambda, double *lambda_std, double *corr, double *centre, double *centre_std, double *loglik,
+                            int *n_increments, int *status, void *stream);
+int mivit_track_confined_loglik(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                                const int *offsets, int n, double dt, const double *D, const double *s2, const double *centre,
+                                double *loglik, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

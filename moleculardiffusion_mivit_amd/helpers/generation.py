@@ -82,6 +82,65 @@ def brownian_single_state(N: int, T: int, Ds=(1.0, 0.0), alphas: float = 1.0, dt
     return trajs, labels
 
 
+def _radius_vector(radius, n: int) -> torch.Tensor:
+    """radius, a number or [n] values, as a float64 CPU tensor [n] of positive finite numbers (ValueError otherwise)."""
+    try:
+        r = (radius.detach().to("cpu", torch.float64) if torch.is_tensor(radius) else torch.as_tensor(np.asarray(radius, dtype=np.float64))).reshape(-1)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"radius must be a number or hold one radius per particle ({n}), got {radius!r}") from None
+    if r.numel() == 1:
+        r = r.expand(n)
+    if r.numel() != n:
+        raise ValueError(f"radius must be a number or hold one radius per particle ({n}), got {r.numel()}")
+    if n and not bool(((r > 0) & torch.isfinite(r)).all()):
+        raise ValueError("radius must be positive and finite")
+    return r.contiguous()
+
+
+def _ou_walk(z: torch.Tensor, D: torch.Tensor, radius: torch.Tensor, dt: float, stationary: bool) -> torch.Tensor:
+    """The exact discretisation of an isotropic Ornstein-Uhlenbeck process about 0 from standard normals z [T, N, 2] (float64):
+    stationary variance per axis s2 = radius^2 / 2, rate lam = D / s2, phi = exp(-lam dt); x_t = phi x_{t-1} + sqrt(s2 (1 -
+    phi^2)) z_t, with sqrt(s2 (1 - phi^2)) = sqrt(-s2 expm1(-2 lam dt)).  x_0 = sqrt(s2) z_0, the stationary law, or 0 (the
+    centre).  D, radius [N] float64 on z's device -> [T, N, 2] float64.  A plain loop over the steps, vectorised over the
+    particles."""
+    s2 = 0.5 * radius * radius
+    lam = D / s2
+    phi = torch.exp(-lam * dt).view(-1, 1)
+    amp = torch.sqrt(-s2 * torch.expm1(-2.0 * lam * dt)).view(-1, 1)
+    x = torch.empty_like(z)
+    if z.shape[0]:
+        x[0] = torch.sqrt(s2).view(-1, 1) * z[0] if stationary else 0.0
+    for t in range(1, z.shape[0]):
+        x[t] = phi * x[t - 1] + amp * z[t]
+    return x
+
+
+def confined_single_state(N: int, T: int, Ds=(1.0, 0.0), radius=1.0, dt: float = 1.0,
+                          generator: Optional[torch.Generator] = None, device="cpu"):
+    """(T, N, 2) trajectories and (T, N, 3) labels [alpha = 1, D, state = 0] of particles that diffuse in a harmonic well about
+    the origin: an isotropic Ornstein-Uhlenbeck process by its exact discretisation (_ou_walk), so the statistics hold at any
+    dt.  radius, a number or [N] values, is the RMS distance from the centre in 2-D, sqrt(2 s2) with the stationary variance s2
+    per axis; the rate at which a particle is pulled back is D / s2.  Draws, in this order: D exactly as
+    brownian_single_state draws it, then randn(T, N, 2) where the Brownian steps are; row 0, which the free walk throws away,
+    places the particle in the stationary law.  As radius -> inf the steps are those of brownian_single_state.  The model of
+    helpers/msd.estimate_confinement_ml."""
+    mean, var = float(Ds[0]), float(Ds[1])
+    rad = _radius_vector(radius, N).to(device)
+    D = torch.full((N,), mean, device=device)
+    if var > 0:
+        D = mean + math.sqrt(var) * torch.randn(N, generator=generator, device=device)
+        for _ in range(64):                      # redraw non-positive coefficients, as brownian_single_state
+            bad = D <= 1e-4
+            if not bool(bad.any()):
+                break
+            D = torch.where(bad, mean + math.sqrt(var) * torch.randn(N, generator=generator, device=device), D)
+        D = D.clamp_min(1e-4)
+    z = torch.randn(T, N, 2, generator=generator, device=device)
+    trajs = _ou_walk(z.double(), D.double(), rad, float(dt), True).float()
+    labels = torch.stack([torch.ones(T, N, device=device), D.view(1, N).expand(T, N), torch.zeros(T, N, device=device)], dim=-1)
+    return trajs, labels
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # Anomalous diffusion: fractional Brownian motion, MSD = 2 D dt k^alpha per axis (csrc/fbm.hip)
 # ------------------------------------------------------------------------------------------------------------------------
@@ -838,7 +897,8 @@ def _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin):
 
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
-                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None, drift=None, camera=None):
+                   blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None, drift=None, camera=None,
+                   confinement=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -905,7 +965,14 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     keeps its meaning, the peak of the expected image, now in photons; background_intensity and poisson_noise of image_props
     are neither used nor drawn.  truth gains camera (the dict with the defaults filled in) and photons (float64 per row): the
     expected photons of the particle in that frame, amp.sum(-1) * 2 pi (psf_sigma_hr / upsampling_factor)^2.  What
-    tracking.fit_spots_mle takes as read_var is (read_noise / gain)^2."""
+    tracking.fit_spots_mle takes as read_var is (read_noise / gain)^2.
+
+    confinement (default None: free motion, the code path without it): a dict {"radius": a number or [Np] values}, every
+    particle diffuses in a harmonic well centred on its start position (an isotropic Ornstein-Uhlenbeck process, _ou_walk
+    with a step of 1 / nPosPerFrame frames): radius is the RMS distance from the centre in 2-D in pixels, sqrt(2 s2), and D the
+    diffusion coefficient inside the well.  z = randn(Np, T, 2) is drawn where the Brownian steps are and the particle starts
+    at the centre.  truth gains radius [Np] float64 and centre [Np, 2] float64 (y, x).  Not together with alphas, geometry or
+    states (ValueError); drift moves the wells with the stage.  What helpers/msd.estimate_confinement_ml estimates."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -997,6 +1064,13 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
                                   state_M).long()
         D_frame = torch.from_numpy(state_Ds).to(gdev)[state]                                                 # [Np, F] float64
     alpha = None if alphas is None else _draw_alphas(Np, alphas, generator, gdev)
+    well = None
+    if confinement is not None:
+        if alphas is not None or geometry is not None or states is not None:
+            raise ValueError("confinement cannot be combined with alphas, geometry or states")
+        if not isinstance(confinement, dict) or set(confinement) != {"radius"}:
+            raise ValueError("confinement must be None or a dict with the key radius")
+        well = _radius_vector(confinement["radius"], Np)
     T = F_ * npos
     if state is not None:
         # one factor per sub-step in place of the one per particle: sqrt(2 D / npos) in float32, as without states
@@ -1019,7 +1093,10 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     else:
         span = torch.tensor([H - 1 - 2 * margin, W - 1 - 2 * margin], device=gdev)
         start = margin + torch.rand(Np, 2, generator=generator, device=gdev) * span
-        if state is not None:
+        if well is not None:
+            z = torch.randn(Np, T, 2, generator=generator, device=gdev)
+            walk = _ou_walk(z.double().transpose(0, 1), D.to(gdev).double(), well.to(gdev), 1.0 / npos, False).transpose(0, 1)
+        elif state is not None:
             steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * step_scale
         elif alpha is None:
             steps = torch.randn(Np, T, 2, generator=generator, device=gdev) * torch.sqrt(2.0 * D.to(gdev).float() / npos).view(Np, 1, 1)
@@ -1029,9 +1106,12 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             rescale = torch.from_numpy(np.power(float(npos), 1.0 - alpha.numpy())).to(gdev).float()
             z = torch.randn(Np, T, 2, generator=generator, device=gdev)
             steps = fractional_gaussian_noise(z.double(), alpha).float() * torch.sqrt(2.0 * D.to(gdev).float() / npos * rescale).view(Np, 1, 1)
-        if T:
-            steps[:, 0] = 0.0
-        pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
+        if well is not None:
+            pos = (start.view(Np, 1, 2).double() + walk).float().to(dev)
+        else:
+            if T:
+                steps[:, 0] = 0.0
+            pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
     if drift_f is not None:
         drift_f = drift_f.to(dev)
         pos = (pos.double() + drift_f.repeat_interleave(npos, dim=0).view(1, T, 2)).float()     # rounded once
@@ -1078,6 +1158,8 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         truth["arc"], truth["edge"], truth["geometry_id"] = arc.to(dev), edge.to(dev), torch.from_numpy(geom_id).to(dev)
     if drift_f is not None:
         truth["drift"] = drift_f
+    if well is not None:
+        truth["radius"], truth["centre"] = well.to(dev), start.double().to(dev)
     if cam is not None:
         truth["camera"] = cam
         truth["photons"] = amp.double().sum(-1)[pid, frame] * (2.0 * math.pi * (sigma / up) ** 2)

@@ -1341,3 +1341,277 @@ def estimate_anomalous_ml(positions, offsets, variances=None, frames=None, use=N
             out = {k: torch.from_numpy(v) for k, v in out.items()}
     out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# maximum-likelihood confinement radius per track from rows of known variance, with error bars (csrc/confined_ml.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+_CF_GRID, _CF_ROUNDS, _CF_MIN_INCREMENTS = 8, 20, 4
+_CF_U_LO, _CF_U_HI, _CF_W_LO, _CF_W_HI = -12.0, 4.0, -6.0, 18.0          # the first brackets of log2(D / D_ref), log2(s2 / S_ref)
+_CF_FAST = 4.0                                                           # status 3 where lambda dt is above it
+
+
+def _confined_rows(pos, var, frames, use, offsets, sel=None):
+    """The usable rows (the rule of _diffusion_ml_numpy) of the ranges sel (all where None, in the order given), padded:
+    -> (X [ns, Mx, 2], V [ns, Mx, 2], Fr [ns, Mx] int64, cnt [ns] int64, the rows of each range)"""
+    ok = np.isfinite(pos).all(axis=1)
+    if var is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
+    if use is not None:
+        ok &= use.astype(bool)
+    n = len(offsets) - 1
+    rows = [int(offsets[k]) + np.nonzero(ok[int(offsets[k]):int(offsets[k + 1])])[0] for k in range(n)]
+    if sel is None:
+        return rows
+    Mx = max([len(rows[k]) for k in sel], default=0)
+    X, V, Fr = np.zeros((len(sel), Mx, 2)), np.zeros((len(sel), Mx, 2)), np.zeros((len(sel), Mx), np.int64)
+    for i, k in enumerate(sel):
+        r = rows[k]
+        X[i, :len(r)] = pos[r]
+        if var is not None:
+            V[i, :len(r)] = var[r]
+        Fr[i, :len(r)] = frames[r] if frames is not None else r - int(offsets[k])
+    return X, V, Fr
+
+
+def _confined_cost(Dc, Sc, X, V, g, inc, dt, centre=None):
+    """-2 log L of csrc/confined_ml.hip::cf_cost for the candidates (Dc, Sc) [n, C] (D and the stationary variance s2) of n
+    ranges at once: X [n, >= inc[0] + 1, 2] the usable rows, V their variances, g [n, >= inc[0]] the gaps in frames, inc [n]
+    >= 1 the increments of each range IN DESCENDING ORDER; centre [n, C, 2] given, or None to profile it -> (cost [n, C],
+    centre [n, C, 2], Shh [n, C, 2]).  Elementwise the kernel's operations in its order (include/mivit_hip.h,
+    mivit_track_confined_ml); the two differ in expm1 and log alone."""
+    n, C = Dc.shape
+    with np.errstate(all="ignore"):
+        ldt = (Dc / Sc) * dt
+        a = np.stack([np.broadcast_to(X[:, 0, ax][:, None], (n, C)) for ax in (0, 1)]).copy()
+        b = np.zeros((2, n, C))
+        P = np.stack([np.broadcast_to(V[:, 0, ax][:, None], (n, C)) for ax in (0, 1)]).copy()
+        Syy, Syh, Shh = np.zeros((2, n, C)), np.zeros((2, n, C)), np.zeros((2, n, C))
+        pm, pe = np.full((n, C), 0.5), np.ones((n, C), np.int64)
+        bad = np.zeros((n, C), bool)
+        for k in range(int(inc[0]) if n else 0):
+            na = int(np.count_nonzero(inc > k))
+            t = ldt[:na] * g[:na, k].astype(np.float64)[:, None]
+            om = -np.expm1(-t)
+            phi = 1.0 - om
+            q = Sc[:na] * (-np.expm1(-(2.0 * t)))
+            for ax in (0, 1):
+                Pm = (phi * phi) * P[ax, :na] + q
+                F = Pm + V[:na, k + 1, ax][:, None]
+                bad[:na] |= ~(F > 0.0)
+                r = 1.0 / F
+                am = phi * a[ax, :na]
+                eh = phi * b[ax, :na] + om
+                ey = X[:na, k + 1, ax][:, None] - am
+                K = Pm * r
+                a[ax, :na] = am + K * ey
+                b[ax, :na] = eh - K * eh
+                P[ax, :na] = (1.0 - K) * Pm
+                Syy[ax, :na] = Syy[ax, :na] + (ey * ey) * r
+                Syh[ax, :na] = Syh[ax, :na] + (ey * eh) * r
+                Shh[ax, :na] = Shh[ax, :na] + (eh * eh) * r
+                m, ex = np.frexp(pm[:na] * F)
+                pm[:na] = m
+                pe[:na] += ex
+        if centre is None:
+            pos_h = Shh > 0.0
+            c = np.where(pos_h, Syh / Shh, np.nan)
+            Q = np.where(pos_h, Syy - (Syh * Syh) / Shh, Syy)
+        else:
+            c = np.moveaxis(centre, 2, 0)
+            Q = (Syy - ((2.0 * c) * Syh)) + (c * c) * Shh
+        cost = ((np.log(pm) + pe.astype(np.float64) * _ML_LN2) + (Q[0] + Q[1])) + (2 * inc).astype(np.float64)[:, None] * _LOG_2PI
+        cost = np.where(bad | ~(cost < np.inf), np.inf, cost)
+    return cost, np.moveaxis(c, 0, 2), np.moveaxis(Shh, 0, 2)
+
+
+def _confined_loglik_numpy(pos, var, frames, use, offsets, dt, D, s2, centre):
+    """csrc/confined_ml.hip's mivit_track_confined_loglik restated, all ranges at once -> loglik [n] float64: NaN for a
+    range without an increment and where D or s2 is not positive and finite, -inf for a rejected candidate"""
+    n = len(offsets) - 1
+    loglik = np.full(n, np.nan)
+    rows = _confined_rows(pos, var, frames, use, offsets)
+    cnt = np.array([len(r) for r in rows], np.int64)
+    with np.errstate(invalid="ignore"):
+        fine = (cnt >= 2) & (D > 0.0) & (D < np.inf) & (s2 > 0.0) & (s2 < np.inf)
+    sel = np.nonzero(fine)[0]
+    if not len(sel):
+        return loglik
+    sel = sel[np.argsort(-cnt[sel], kind="stable")]
+    X, V, Fr = _confined_rows(pos, var, frames, use, offsets, sel)
+    cost, _, _ = _confined_cost(D[sel][:, None], s2[sel][:, None], X, V, Fr[:, 1:] - Fr[:, :-1], cnt[sel] - 1, dt,
+                                None if centre is None else centre[sel][:, None, :])
+    loglik[sel] = -0.5 * cost[:, 0]
+    return loglik
+
+
+_CF_OUTS = ("D_conf", "D_conf_std", "radius", "radius_std", "lambda", "lambda_std", "corr", "centre", "centre_std", "loglik",
+            "n_increments", "status")
+
+
+def _confined_ml_numpy(pos, var, frames, use, offsets, dt):
+    """The arithmetic of csrc/confined_ml.hip::cf_kernel in its order (include/mivit_hip.h, mivit_track_confined_ml), all
+    ranges at once -> the outputs of _CF_OUTS ([n] float64, centre and centre_std [n, 2], n_increments and status int32).
+    The same Kalman recurrence, determinant by frexp, brackets, candidates, arg-min (np.argmin returns the lowest index among
+    equal minima), stencil and statuses.  Differs from the kernel in expm1, exp2 and log alone."""
+    n = len(offsets) - 1
+    out = {k: np.full((n, 2) if k.startswith("centre") else n, np.nan) for k in _CF_OUTS[:10]}
+    rows = _confined_rows(pos, var, frames, use, offsets)
+    n_inc = np.array([max(len(r) - 1, 0) for r in rows], np.int32).reshape(n)
+    status = np.ones(n, np.int32)
+    sel = np.nonzero(n_inc >= _CF_MIN_INCREMENTS)[0]
+    if not len(sel):
+        return tuple(out[k] for k in _CF_OUTS[:10]) + (n_inc, status)
+    sel = sel[np.argsort(-n_inc[sel], kind="stable")]
+    inc = n_inc[sel].astype(np.int64)
+    ns = len(sel)
+    X, V, Fr = _confined_rows(pos, var, frames, use, offsets, sel)
+    Mx = X.shape[1]
+    d, g = X[:, 1:] - X[:, :-1], Fr[:, 1:] - Fr[:, :-1]
+    live = np.arange(Mx - 1)[None, :] < inc[:, None]
+    rlive = np.arange(Mx)[None, :] <= inc[:, None]
+    with np.errstate(all="ignore"):
+        S = np.cumsum(np.where(live, d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], 0.0), axis=1)[:, -1]
+        G = np.where(live, g, 0).sum(axis=1)
+        D_ref = S / ((4.0 * dt) * G.astype(np.float64))
+        cnt = (inc + 1).astype(np.float64)
+        mean = np.cumsum(np.where(rlive[..., None], X, 0.0), axis=1)[:, -1] / cnt[:, None]
+        dev = X - mean[:, None, :]
+        S_ref = np.cumsum(np.where(rlive, dev[..., 0] * dev[..., 0] + dev[..., 1] * dev[..., 1], 0.0), axis=1)[:, -1] / (2.0 * cnt)
+        ulo, uhi = np.full(ns, _CF_U_LO), np.full(ns, _CF_U_HI)
+        wlo, whi = np.full(ns, _CF_W_LO), np.full(ns, _CF_W_HI)
+        u_lo, u_hi, w_lo = (np.ones(ns, bool) for _ in range(3))
+        lane = np.arange(_CF_GRID * _CF_GRID)
+        li, lj = (lane >> 3).astype(np.float64), (lane & 7).astype(np.float64)
+        ub, wb = np.zeros(ns), np.zeros(ns)
+        for _ in range(_CF_ROUNDS):
+            su, sw = (uhi - ulo) / 7.0, (whi - wlo) / 7.0
+            Dj = D_ref[:, None] * np.exp2(ulo[:, None] + li[None, :] * su[:, None])
+            Sj = S_ref[:, None] * np.exp2(wlo[:, None] + lj[None, :] * sw[:, None])
+            best = np.argmin(_confined_cost(Dj, Sj, X, V, g, inc, dt)[0], axis=1)
+            bi, bj = best >> 3, best & 7
+            ub, wb = ulo + bi.astype(np.float64) * su, wlo + bj.astype(np.float64) * sw
+            ulo, uhi, wlo, whi = ub - 2.0 * su, ub + 2.0 * su, wb - 2.0 * sw, wb + 2.0 * sw
+            u_lo &= bi == 0
+            u_hi &= bi == _CF_GRID - 1
+            w_lo &= bj == 0
+        Db, Sb = D_ref * np.exp2(ub), S_ref * np.exp2(wb)
+        lam = Db / Sb
+        st = np.where(wb >= _CF_W_HI, 2, np.where(lam * dt > _CF_FAST, 3, np.where(u_lo | u_hi | w_lo, 5, 0))).astype(np.int32)
+        fD = np.array([_ML_EXP_MH, 1.0, _ML_EXP_H])
+        Ds = Db[:, None] * np.repeat(fD, 3)[None, :]
+        Ss = Sb[:, None] * np.tile(fD, 3)[None, :]
+        c, cen, hh = _confined_cost(Ds, Ss, X, V, g, inc, dt)
+        c0 = c[:, 4]
+        Hdd = ((c[:, 7] - c0) + (c[:, 1] - c0)) * 2048.0
+        Hss = ((c[:, 5] - c0) + (c[:, 3] - c0)) * 2048.0
+        Hds = ((c[:, 8] - c[:, 6]) - (c[:, 2] - c[:, 0])) * 512.0
+        det = Hdd * Hss - Hds * Hds
+        st = np.where(~(c0 < np.inf), 4, st).astype(np.int32)
+        pd = (Hdd > 0.0) & (Hss > 0.0) & (det > 0.0) & (det < np.inf)
+        st = np.where(~pd & (st == 0), 4, st).astype(np.int32)
+        radius = np.sqrt(2.0 * Sb)
+        vl = ((Hss + Hdd) + 2.0 * Hds) / det
+        full = pd & ((st == 0) | (st == 5))
+        nan = np.full(ns, np.nan)
+        o = {"D_conf": Db, "loglik": -0.5 * c0,
+             "D_conf_std": np.where(full, Db * np.sqrt(Hss / det), nan),
+             "radius": np.where(st == 2, np.inf, radius),
+             "radius_std": np.where(full, (0.5 * radius) * np.sqrt(Hdd / det),
+                                    np.where((st == 3) & (Hss > 0.0) & (Hss < np.inf), (0.5 * radius) / np.sqrt(Hss), nan)),
+             "lambda": np.where(st == 2, 0.0, lam),
+             "lambda_std": np.where(full & (vl >= 0.0), lam * np.sqrt(vl), nan),
+             "corr": np.where(full, -Hds / np.sqrt(Hdd * Hss), nan)}
+        keep = (st != 2)[:, None]
+        o["centre"] = np.where(keep, cen[:, 4, :], np.nan)
+        o["centre_std"] = np.where(keep & (st != 4)[:, None] & (hh[:, 4, :] > 0.0), 1.0 / np.sqrt(hh[:, 4, :]), np.nan)
+    for k, v in o.items():
+        out[k][sel] = v
+    status[sel] = st
+    return tuple(out[k] for k in _CF_OUTS[:10]) + (n_inc, status)
+
+
+def _cf_per_range(v, n, what, device, width=None):
+    v = v.detach().to(device, torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64), device=device)
+    shape = (n,) if width is None else (n, width)
+    if v.dim() == (0 if width is None else 1) and (width is None or tuple(v.shape) == (width,)):
+        v = v.expand(*shape)
+    if tuple(v.shape) != shape:
+        raise ValueError(f"{what} must be {'a number' if width is None else f'[{width}]'} or {list(shape)}, got {tuple(v.shape)}")
+    return v.contiguous()
+
+
+def confined_loglik(positions, offsets, D, s2, centre=None, variances=None, frames=None, use=None, dt=1.0):
+    """The exact log-likelihood of every range under confined diffusion, an isotropic Ornstein-Uhlenbeck process with the
+    diffusion coefficient D and the stationary variance per axis s2 = radius^2 / 2 (numbers, or one per range [n]) about a
+    centre ((y, x) as [2] or [n, 2]; None: each axis takes the centre that maximises the likelihood), seen through
+    localisation noise of the rows' variances: the model of estimate_confinement_ml at given parameters, to compare
+    hypotheses with -> dict of the input's kind: loglik [n] float64 (NaN for a range without an increment and where D or s2
+    is not positive and finite, -inf where an innovation variance is not positive).  The exposure is INSTANTANEOUS: motion
+    blur is not modelled.  The other arguments are those of estimate_diffusion_ml.  CUDA tensors go to the kernel
+    (csrc/confined_ml.hip), arrays and CPU tensors to the numpy restatement."""
+    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    n = off.numel() - 1
+    Dv, Sv = _cf_per_range(D, n, "D", pos.device), _cf_per_range(s2, n, "s2", pos.device)
+    cv = None if centre is None else _cf_per_range(centre, n, "centre", pos.device, 2)
+    if pos.device.type == "cuda":
+        from .. import ops
+        ll = ops.track_confined_loglik(pos, off.int().contiguous(), Dv, Sv, cv, var, None if fr is None else fr.int().contiguous(),
+                                       usable, float(dt))
+        return {"loglik": ll}
+    ll = _confined_loglik_numpy(pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
+                                None if usable is None else usable.numpy(), off.numpy(), float(dt), Dv.numpy(), Sv.numpy(),
+                                None if cv is None else cv.numpy())
+    return {"loglik": torch.from_numpy(ll) if is_t else ll}
+
+
+def estimate_confinement_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0):
+    """The maximum-likelihood confinement radius of every track with its standard error, and the test of whether the track
+    is confined at all, from rows that each carry their own localisation variance: positions, offsets, variances, frames, use
+    and dt as estimate_diffusion_ml takes them -> dict of the input's kind:
+        D_conf, D_conf_std   [n] float64     the diffusion coefficient inside the well
+        radius, radius_std   [n] float64     sqrt(2 s2), the RMS distance from the centre in 2-D (s2: stationary variance per axis)
+        lambda, lambda_std   [n] float64     the rate D / s2 at which the particle is pulled back, per unit of dt
+        corr                 [n] float64     the correlation of the estimates of ln D and ln s2
+        centre, centre_std   [n, 2] float64  (y, x) of the well and its standard error at the estimates
+        loglik               [n] float64     the log-likelihood at the estimates
+        lr_brownian          [n] float64     2 (loglik - the loglik of estimate_diffusion_ml(..., blur=0)): the likelihood ratio
+                                             against free Brownian motion, which the model nests as s2 -> inf; >= 0 up to the
+                                             resolution of the search.  Its null distribution is not chi^2 (the free walk is on
+                                             the boundary s2 = inf): scripts/eval_movie_accuracy.py --confined-ml prints it
+        n_increments         [n] int64       the increments between usable rows
+        status               [n] int64       0 fine; 1 fewer than 4 increments (NaN); 2 s2 left its first bracket upwards: the
+                                             track is not confined (radius inf, lambda 0, centre and bars NaN); 3 lambda dt > 4:
+                                             the particle relaxes within a frame (radius and centre stand, D_conf and lambda are
+                                             lower bounds without bars); 4 the information matrix is not positive definite or no
+                                             candidate was accepted (bars NaN); 5 the optimum at another end of the brackets
+    The model is diffusion in a harmonic well (an isotropic Ornstein-Uhlenbeck process) seen at INSTANTANEOUS exposure (motion
+    blur is not modelled) through Gaussian noise of the rows' variances, frames may be missing; its exact likelihood is a
+    scalar Kalman filter per axis, conditioned on the first usable row, with the centre of each axis profiled out
+    (include/mivit_hip.h has every operation).  The search is fixed: 20 rounds of an 8 x 8 grid over log2 D and log2 s2 that
+    shrinks to the best candidate +- 2 cells; the bars come from the second differences of the log-likelihood with a step of
+    1/64 in ln D and ln s2.  The profile likelihood UNDERESTIMATES s2 on short tracks (the centre is fitted to the same rows):
+    on tracks of 100 rows that span 30 relaxation times the mean pull of ln radius is about -0.5.  CUDA tensors go to the kernel
+    (csrc/confined_ml.hip: one wave per track, no limit on its length), arrays and CPU tensors to the numpy restatement, which
+    differs from it in expm1, exp2 and log alone."""
+    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    brownian = estimate_diffusion_ml(positions, offsets, variances, frames, use, dt, blur=0.0)["loglik"]
+    if pos.device.type == "cuda":
+        from .. import ops
+        out = dict(zip(_CF_OUTS, ops.track_confined_ml(pos, off.int().contiguous(), var, None if fr is None else fr.int().contiguous(),
+                                                       usable, float(dt))))
+        out["n_increments"], out["status"] = out["n_increments"].long(), out["status"].long()
+    else:
+        out = dict(zip(_CF_OUTS, _confined_ml_numpy(pos.numpy(), None if var is None else var.numpy(),
+                                                    None if fr is None else fr.numpy(),
+                                                    None if usable is None else usable.numpy(), off.numpy(), float(dt))))
+        out["n_increments"], out["status"] = out["n_increments"].astype(np.int64), out["status"].astype(np.int64)
+        if is_t:
+            out = {k: torch.from_numpy(v) for k, v in out.items()}
+    if is_t:
+        out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
+    else:
+        with np.errstate(invalid="ignore"):                                # -inf - -inf where no candidate was accepted
+            out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
+    return out

@@ -1763,7 +1763,7 @@ def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None, fra
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
                              batch_size=4096, segment=None, states=None, drift=None, localization=None, ml=None, anomalous=None,
-                             **tracking_kwargs):
+                             confined=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -1831,7 +1831,28 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     sigma2 follows the rules of ml["sigma2"], and so do the rows used and the positions (drift-corrected, the frames of the
     table, a filled row is a gap).  The result gains alpha_ml, alpha_ml_std, D_alpha (float64) and anomalous_status (int64)
     [n_tracks], and "anomalous": what estimate_anomalous_ml was called with (positions, variances, frames, use, exposure).
-    Tracks only: segments and states do not get an exponent of their own."""
+    Tracks only: segments and states do not get an exponent of their own.
+
+    confined (default None: the code path without it): a dict that may hold sigma2 ({} for the default), the argument of
+    helpers/msd.estimate_confinement_ml (csrc/confined_ml.hip), the maximum-likelihood confinement radius of every track
+    with a standard error and the likelihood ratio against free Brownian motion; the exposure is instantaneous (motion blur
+    is not modelled).  sigma2 follows the rules of ml["sigma2"], and so do the rows used and the positions (drift-corrected,
+    the frames of the table, a filled row is a gap).  The result gains radius_ml, radius_ml_std, D_conf, lambda_ml,
+    lr_confined (float64; estimate_confinement_ml's radius, radius_std, D_conf, lambda and lr_brownian) and confined_status
+    (int64) [n_tracks], and "confined": what estimate_confinement_ml was called with (positions, variances, frames, use).
+    Tracks only."""
+    if confined is not None:
+        if not isinstance(confined, dict) or set(confined) - {"sigma2"}:
+            raise ValueError("confined must be None or a dict that may hold sigma2")
+        confined = dict(confined)
+        confined.setdefault("sigma2", "crlb" if localization is not None else 0.0)
+        if isinstance(confined["sigma2"], str):
+            if confined["sigma2"] != "crlb":
+                raise ValueError(f"confined['sigma2'] must be a number or 'crlb', got {confined['sigma2']!r}")
+            if localization is None:
+                raise ValueError("confined['sigma2'] = 'crlb' needs localization: the least-squares fit returns no bound")
+        elif not 0.0 <= float(confined["sigma2"]) < float("inf"):
+            raise ValueError(f"confined['sigma2'] must be >= 0 and finite, got {confined['sigma2']}")
     if anomalous is not None:
         if not isinstance(anomalous, dict) or set(anomalous) - {"exposure", "sigma2"}:
             raise ValueError("anomalous must be None or a dict with keys among exposure and sigma2")
@@ -1955,6 +1976,15 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
             an_args = {"variances": float(anomalous["sigma2"]), "use": None if filled is None else ~filled}
         an_args.update(frames=fr, exposure=float(anomalous["exposure"]))
         an_tracks = _msd.estimate_anomalous_ml(pos, offsets, dt=dt, **an_args)
+    if confined is not None:
+        from . import msd as _msd
+        filled = by_track[5] if len(by_track) > 5 else None
+        if confined["sigma2"] == "crlb":
+            cf_args = {"variances": torch.stack([fit["y_std"] * fit["y_std"], fit["x_std"] * fit["x_std"]], dim=1), "use": good}
+        else:
+            cf_args = {"variances": float(confined["sigma2"]), "use": None if filled is None else ~filled}
+        cf_args.update(frames=fr)
+        cf_tracks = _msd.estimate_confinement_ml(pos, offsets, dt=dt, **cf_args)
     seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
     n_sequences = torch.bincount(seq_track, minlength=n_tracks)
     model.eval()
@@ -2022,6 +2052,10 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["alpha_ml"], res["alpha_ml_std"], res["D_alpha"] = an_tracks["alpha_ml"], an_tracks["alpha_ml_std"], an_tracks["D_alpha"]
         res["anomalous_status"] = an_tracks["status"]
         res["anomalous"] = dict(an_args, positions=pos)
+    if confined is not None:
+        res["radius_ml"], res["radius_ml_std"], res["D_conf"] = cf_tracks["radius"], cf_tracks["radius_std"], cf_tracks["D_conf"]
+        res["lambda_ml"], res["lr_confined"], res["confined_status"] = cf_tracks["lambda"], cf_tracks["lr_brownian"], cf_tracks["status"]
+        res["confined"] = dict(cf_args, positions=pos)
     return res
 
 

@@ -1280,6 +1280,53 @@ def track_fbm_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None
     return (*outs, n_inc, status)
 
 
+def _confined_ml_args(name, pos, offsets, var, frames, use, dt):
+    """the checks track_confined_ml and track_confined_loglik share: those of track_fbm_ml at exposure 0"""
+    return _fbm_ml_args(name, pos, offsets, var, frames, use, dt, 0.0)
+
+
+def track_confined_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0):
+    """The maximum-likelihood confinement radius of every row range with error bars (csrc/confined_ml.hip,
+    mivit_track_confined_ml): diffusion in a harmonic well (an isotropic Ornstein-Uhlenbeck process) seen at instantaneous
+    exposure (motion blur is not modelled) through noise of known variance; the arguments of track_diffusion_ml without blur
+    -> (D_conf, D_conf_std, radius, radius_std, lambda, lambda_std, corr [n] float64, centre, centre_std [n, 2] float64 (y, x),
+    loglik [n] float64, n_increments, status [n] int32).  One launch, one wave per range, no workspace; a range has no maximum
+    length.  See include/mivit_hip.h for the arithmetic and the status codes and helpers/msd.estimate_confinement_ml for the
+    front end."""
+    name = "track_confined_ml"
+    pos, offsets, var, frames, use, n_rows, n = _confined_ml_args(name, pos, offsets, var, frames, use, dt)
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=pos.device)         # noqa: E731
+    outs = [f64(n) for _ in range(7)] + [f64(n, 2), f64(n, 2), f64(n)]
+    n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
+    N.check(N.lib.mivit_track_confined_ml(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt),
+                                          *(_p(o) for o in outs), _p(n_inc), _p(status), _s(pos)), "mivit_track_confined_ml")
+    return (*outs, n_inc, status)
+
+
+def track_confined_loglik(pos: torch.Tensor, offsets: torch.Tensor, D: torch.Tensor, s2: torch.Tensor, centre=None, var=None,
+                          frames=None, use=None, dt: float = 1.0) -> torch.Tensor:
+    """The exact log-likelihood of every row range under confined diffusion at given parameters (csrc/confined_ml.hip,
+    mivit_track_confined_loglik): pos, offsets, var, frames, use, dt as track_diffusion_ml; D [n], s2 [n] float64 the diffusion
+    coefficient and the stationary variance per axis of every range; centre [n, 2] float64 (y, x), or None for the centre
+    that maximises the likelihood -> loglik [n] float64 (NaN without an increment or where D or s2 is not positive and finite,
+    -inf for a rejected candidate).  The exposure is instantaneous.  See include/mivit_hip.h for the arithmetic and
+    helpers/msd.confined_loglik for the front end."""
+    name = "track_confined_loglik"
+    pos, offsets, var, frames, use, n_rows, n = _confined_ml_args(name, pos, offsets, var, frames, use, dt)
+    D = _seg_tensor(D, torch.float64, 1, name, "D [n]")
+    s2 = _seg_tensor(s2, torch.float64, 1, name, "s2 [n]")
+    if D.numel() != n or s2.numel() != n or D.device != pos.device or s2.device != pos.device:
+        raise ValueError(f"{name}: D and s2 must be [{n}] on the device of pos, got {tuple(D.shape)} and {tuple(s2.shape)}")
+    if centre is not None:
+        centre = _seg_tensor(centre, torch.float64, 2, name, "centre [n, 2]")
+        if tuple(centre.shape) != (n, 2) or centre.device != pos.device:
+            raise ValueError(f"{name}: centre must be [{n}, 2] on the device of pos, got {tuple(centre.shape)}")
+    loglik = torch.empty(n, dtype=torch.float64, device=pos.device)
+    N.check(N.lib.mivit_track_confined_loglik(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt), _p(D),
+                                              _p(s2), _p(centre), _p(loglik), _s(pos)), "mivit_track_confined_loglik")
+    return loglik
+
+
 DRIFT_MAX_PAIRS = 4096       # csrc/drift.hip: increments of one frame that the median sorts in LDS (8 B a pair, 32 KiB)
 DRIFT_MODES = {"mean": 0, "median": 1}
 

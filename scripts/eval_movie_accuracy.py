@@ -52,7 +52,13 @@ and "mle2" the maximum-likelihood D of every track from its rows' own bounds (he
 csrc/likelihood.hip, through estimate_track_diffusion(..., ml={"blur": R})): D_ml_median over the matched tracks, next to
 D_msd_median and D_cve_median, the RMS of (D_ml - D_true) / D_ml_std over the matched tracks of status 0, and their count.
 --intensity PEAK sets the mean of particle_intensity (its spread scaled along), the peak
-of a spot in the movie's units: photons with --camera.  A tool, not a test: it asserts no accuracy.
+of a spot in the movie's units: photons with --camera.  --confined RADIUS puts every particle into a harmonic well of that
+RMS radius about its start position (simulate_movie's confinement), and --confined-ml [SIGMA2] (with --confined) adds, per
+track, radius_ml, radius_ml_std, D_conf, lambda_ml, lr_confined and confined_status (helpers/msd.estimate_confinement_ml,
+csrc/confined_ml.hip, through estimate_track_diffusion(..., confined={"sigma2": SIGMA2})), over the matched tracks of at least
+20 rows and status 0 the median radius and D against the truth and the pull of ln radius, and the quantiles of lr_confined on
+that movie and on a FREE Brownian movie of the same settings: the null distribution from which a threshold is picked.  A
+tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
@@ -61,6 +67,7 @@ of a spot in the movie's units: photons with --camera.  A tool, not a test: it a
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
                                           [--camera 10,2,100,1.5] [--mle] [--neighbours [4]] [--ml [0.1667]] [--intensity 300]
+                                          [--confined 3.0] [--confined-ml [0.01]]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -78,6 +85,46 @@ from moleculardiffusion_mivit_amd.helpers import generation as gen
 from moleculardiffusion_mivit_amd.helpers import models as M
 from moleculardiffusion_mivit_amd.helpers import msd as MSD
 from moleculardiffusion_mivit_amd.helpers import tracking as trk
+
+
+def confined_scores(movie, model, args, norm, score, est, rows, props, drift, camera):
+    """--confined-ml: estimate_track_diffusion(..., confined={"sigma2": SIGMA2}) on the movie of wells, held against the radius
+    and the D it was simulated with over the matched tracks of at least 20 rows, and on a FREE movie of the same settings
+    (the same seed, no wells), whose lr_confined is the null distribution a threshold is picked from.  SIGMA2 as for
+    --alpha-ml: the number given, or half the squared RMSE of the matched rows.  The movie's positions are frame means and
+    the model takes the exposure for instantaneous: with --npos > 1 the blur is in the numbers reported here."""
+    sigma2 = args.confined_ml if args.confined_ml >= 0 else float(score["rmse"]) ** 2 / 2.0
+    kw = dict(norm=norm, max_gap=args.max_gap, confined={"sigma2": sigma2})
+    cf = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, **kw)
+    assert torch.equal(cf["track_id"], est["track_id"])
+    cols = ("radius_ml", "radius_ml_std", "D_conf", "lambda_ml", "lr_confined", "confined_status")
+    for row, *vals in zip(rows, *(cf[k].tolist() for k in cols)):
+        row.update(zip(cols, vals))
+    pid = score["particle_id"]
+    long = (est["length"] >= 20) & (pid >= 0)
+    fine = long & (cf["confined_status"] == 0)
+    nan = float("nan")
+    med = lambda v, m: float(v[m].median()) if bool(m.any()) else nan                       # noqa: E731
+    pull = (torch.log(cf["radius_ml"] / args.confined) / (cf["radius_ml_std"] / cf["radius_ml"]))[fine]
+    quantiles = lambda v: [float(q) for q in torch.quantile(v, torch.tensor([0.05, 0.25, 0.5, 0.75, 0.95, 0.99], dtype=v.dtype, device=v.device))]   # noqa: E731
+    out = {"sigma2": sigma2, "n_tracks": int(long.sum()), "n_status_0": int(fine.sum()),
+           "status_counts": torch.bincount(cf["confined_status"][long], minlength=6).tolist(),
+           "radius_true": args.confined, "radius_ml_median": med(cf["radius_ml"], fine),
+           "radius_ml_rms_relative_error": float((cf["radius_ml"][fine] / args.confined - 1.0).pow(2).mean().sqrt()) if bool(fine.any()) else nan,
+           "mean_pull_ln_radius": float(pull.mean()) if bool(fine.any()) else nan,
+           "rms_pull_ln_radius": float(pull.pow(2).mean().sqrt()) if bool(fine.any()) else nan,
+           "D_true_median": med(score["D_true"], fine), "D_conf_median": med(cf["D_conf"], fine), "D_msd_median": med(est["D_msd"], fine),
+           "lr_confined_quantiles_5_25_50_75_95_99": quantiles(cf["lr_confined"][fine]) if bool(fine.any()) else []}
+    g = torch.Generator(device="cuda").manual_seed(args.seed)
+    H, W = args.size
+    free_movie, _ = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props, generator=g,
+                                       device="cuda", blink=args.blink, **({} if drift is None else {"drift": drift}),
+                                       **({} if camera is None else {"camera": camera}))
+    free = trk.estimate_track_diffusion(free_movie, model, args.seq_len, args.patch_size, **kw)
+    ok = (free["length"] >= 20) & ~torch.isnan(free["lr_confined"])
+    out["free_movie"] = {"n_tracks": int(ok.sum()), "status_counts": torch.bincount(free["confined_status"][ok], minlength=6).tolist(),
+                         "lr_confined_quantiles_5_25_50_75_95_99": quantiles(free["lr_confined"][ok]) if bool(ok.any()) else []}
+    return out
 
 
 def main():
@@ -111,6 +158,8 @@ def main():
     ap.add_argument("--neighbours", type=int, nargs="?", const=-1, default=None, metavar="REACH")
     ap.add_argument("--ml", type=float, nargs="?", const=1.0 / 6.0, default=None, metavar="R")
     ap.add_argument("--intensity", type=float, default=None, metavar="PEAK")
+    ap.add_argument("--confined", type=float, default=None, metavar="RADIUS")
+    ap.add_argument("--confined-ml", type=float, nargs="?", const=-1.0, default=None, metavar="SIGMA2")
     args = ap.parse_args()
     camera = None
     if args.camera is not None:
@@ -129,6 +178,10 @@ def main():
         raise SystemExit("--ml needs --mle: the row variances are the bounds of the maximum-likelihood fit")
     if args.alpha_ml is not None and args.alpha is None:
         raise SystemExit("--alpha-ml needs --alpha: it is held against the exponent the movie was simulated with")
+    if args.confined_ml is not None and args.confined is None:
+        raise SystemExit("--confined-ml needs --confined: it is held against the radius the movie was simulated with")
+    if args.confined is not None and (args.alpha is not None or args.cristae is not None or args.states is not None):
+        raise SystemExit("--confined cannot be combined with --alpha, --cristae or --states")
     drift = None
     if args.drift is not None:
         try:
@@ -164,7 +217,8 @@ def main():
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, None if states else tuple(args.D), args.npos,
                                       image_props=props, generator=g, device="cuda", blink=args.blink, alphas=args.alpha,
                                       states=states, **confine, **({} if drift is None else {"drift": drift}),
-                                      **({} if camera is None else {"camera": camera}))
+                                      **({} if camera is None else {"camera": camera}),
+                                      **({} if args.confined is None else {"confinement": {"radius": args.confined}}))
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
@@ -235,6 +289,10 @@ def main():
             out["alpha_ml_rms_error"] = float((an["alpha_ml"][fine] - a_true[fine]).pow(2).mean().sqrt()) if bool(fine.any()) else float("nan")
             out["alpha_msd_rms_error"] = float((a_msd[fine] - a_true[fine]).pow(2).mean().sqrt()) if bool(fine.any()) else float("nan")
             out["rms_alpha_ml_error_over_std"] = float(pull.pow(2).mean().sqrt()) if bool(fine.any()) else float("nan")
+    if args.confined is not None:
+        out["confined_radius"] = args.confined
+        if args.confined_ml is not None:
+            out["confined_ml"] = confined_scores(movie, model, args, norm, score, est, out["tracks"], props, drift, camera)
     if drift is not None:
         out["drift"] = drift_scores(movie, model, args, norm, truth, score, est, out["tracks"], states)
     if camera is not None:
