@@ -6,77 +6,40 @@
 // profiled out in closed form.  include/mivit_hip.h spells the arithmetic out; helpers/msd._confined_ml_numpy restates it.
 //
 // ONE WAVE PER RANGE (a workgroup of 64 threads), lane 8 i + j = candidate (D_i, s2_j) of a fixed 8 x 8 grid search over
-// (log2 D, log2 s2), as in likelihood.hip: every lane walks the same rows, so the row index, the usability test and the loop
+// (log2 D, log2 s2): every lane walks the same rows, so the row index, the usability test and the loop
 // are wave-uniform and only the two parameters differ between lanes.  The filter's state of both axes (mean as a + b c,
 // variance, three sums of the normal equation of the centre), the determinant and the parameters are about 20 doubles a
 // lane and live in registers: no LDS, no scratch, no atomics, no barrier, and a range has no maximum length.  The rows are
 // read again from global memory in each of the 23 passes (two for the reference scales, 20 rounds, one for the stencil of
 // the curvature); a range is a few KiB and stays in cache.
 //
-// The determinant is a PRODUCT rescaled exactly by frexp, as in likelihood.hip: no log in the loop.  The arg-min goes through
+// The determinant is a PRODUCT rescaled exactly by frexp: no log in the loop.  The arg-min goes through
 // xor shuffles (least cost, lowest lane on a tie).  The work of a range does not depend on where it sits in a batch: its
-// outputs are bitwise the same alone, anywhere in a batch and in every launch.
+// outputs are bitwise the same alone, anywhere in a batch and in every launch.  The rows, the reference scale D_ref, the
+// product, the arg-min and the stencil's information matrix are those of track_ml.h.
 //
-// No contraction into FMA, as in likelihood.hip.
+// No contraction into FMA.
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "track_ml.h"
 
 namespace {
 
-constexpr int CF_THREADS = 64;                                            // one wave = the 8 x 8 candidates of a round
+constexpr int CF_THREADS = TM_WAVE;                                       // one wave = the 8 x 8 candidates of a round
 constexpr int CF_ROUNDS = 20;
 constexpr int CF_MIN_INCREMENTS = 4;
 constexpr double CF_U_LO = -12.0, CF_U_HI = 4.0;                          // the first bracket of log2(D / D_ref)
 constexpr double CF_W_LO = -6.0, CF_W_HI = 18.0;                          // the first bracket of log2(s2 / S_ref)
 constexpr double CF_FAST = 4.0;                                           // status 3 where lambda dt is above it
-constexpr double CF_LOG_2PI = 1.8378770664093453;                         // np.log(2 * np.pi)
-constexpr double CF_LN2 = 0.6931471805599453;                             // np.log(2)
-constexpr double CF_EXP_H = 1.0157477085866857;                           // np.exp(1 / 64): the step h of the stencil
-constexpr double CF_EXP_MH = 0.9844964370054085;                          // np.exp(-1 / 64)
-
-struct CfRows {
-    const double *pos, *var;
-    const int *frames;
-    const unsigned char *use;
-    int a, b;                                                             // the range, clamped into [0, N]
-};
-
-struct CfRow {
-    double y, x, vy, vx;
-    int f;
-    bool ok;
-};
 
 struct CfFit {
     double cost, cy, cx, hy, hx;                                          // -2 log L, the centre, Shh per axis
     int cnt;                                                              // usable rows
 };
 
-__device__ __forceinline__ bool cf_finite(double v) { return fabs(v) < INFINITY; }
-
-// row r of the range: usable by the rule of likelihood.hip::ml_row
-__device__ __forceinline__ CfRow cf_row(const CfRows &R, int r) {
-    CfRow w;
-    w.y = R.pos[2 * (int64_t)r];
-    w.x = R.pos[2 * (int64_t)r + 1];
-    w.vy = R.var ? R.var[2 * (int64_t)r] : 0.0;
-    w.vx = R.var ? R.var[2 * (int64_t)r + 1] : 0.0;
-    w.f = R.frames ? R.frames[r] : r - R.a;
-    w.ok = (R.use ? R.use[r] != 0 : true) && cf_finite(w.y) && cf_finite(w.x) && w.vy >= 0.0 && w.vy < INFINITY &&
-           w.vx >= 0.0 && w.vx < INFINITY;
-    return w;
-}
-
-__device__ __forceinline__ void cf_clamp(const int *offsets, int k, int N, int &a, int &b) {
-    a = offsets[k], b = offsets[k + 1];
-    a = a < 0 ? 0 : (a > N ? N : a);                                      // never read outside [0, N), whatever offsets holds
-    b = b < a ? a : (b > N ? N : b);
-}
-
 // one axis of one row: predict over the gap, the innovation and its variance, the sums of the centre's normal equation, update
 __device__ __forceinline__ void cf_axis(double phi, double om, double q, double y, double v, double &a, double &b, double &P,
-                                        double &Syy, double &Syh, double &Shh, double &pm, int &pe, bool &bad) {
+                                        double &Syy, double &Syh, double &Shh, TmProd &det, bool &bad) {
     const double Pm = (phi * phi) * P + q;
     const double F = Pm + v;
     if (!(F > 0.0)) bad = true;                                           // not positive (or NaN): the candidate is rejected
@@ -91,21 +54,20 @@ __device__ __forceinline__ void cf_axis(double phi, double om, double q, double 
     Syy = Syy + (ey * ey) * r;
     Syh = Syh + (ey * eh) * r;
     Shh = Shh + (eh * eh) * r;
-    int ex;
-    pm = frexp(pm * F, &ex);
-    pe += ex;
+    det.mul(F);
 }
 
 // -2 log L of the range at (D, s2), this lane's candidate, with the centre (gy, gx) where `given`, else profiled; +inf for a
 // rejected candidate and for a cost that is not a number
-__device__ __forceinline__ CfFit cf_cost(const CfRows &R, double D, double s2, double dt, bool given, double gy, double gx) {
+__device__ __forceinline__ CfFit cf_cost(const TmRows &R, double D, double s2, double dt, bool given, double gy, double gx) {
     const double ldt = (D / s2) * dt;
     double ay = 0.0, by = 0.0, Py = 0.0, ax = 0.0, bx = 0.0, Px = 0.0;
-    double Syy_y = 0.0, Syh_y = 0.0, Shh_y = 0.0, Syy_x = 0.0, Syh_x = 0.0, Shh_x = 0.0, pm = 0.5;
-    int pf = 0, cnt = 0, pe = 1;
+    double Syy_y = 0.0, Syh_y = 0.0, Shh_y = 0.0, Syy_x = 0.0, Syh_x = 0.0, Shh_x = 0.0;
+    TmProd det;
+    int pf = 0, cnt = 0;
     bool bad = false;
     for (int r = R.a; r < R.b; ++r) {
-        const CfRow w = cf_row(R, r);
+        const TmRow w = tm_row(R, r);
         if (!w.ok) continue;                                              // wave-uniform
         if (cnt == 0) {
             ay = w.y, Py = w.vy, ax = w.x, Px = w.vx;                     // conditioned on the first usable row
@@ -114,8 +76,8 @@ __device__ __forceinline__ CfFit cf_cost(const CfRows &R, double D, double s2, d
             const double om = -expm1(-t);
             const double phi = 1.0 - om;
             const double q = s2 * (-expm1(-(2.0 * t)));
-            cf_axis(phi, om, q, w.y, w.vy, ay, by, Py, Syy_y, Syh_y, Shh_y, pm, pe, bad);
-            cf_axis(phi, om, q, w.x, w.vx, ax, bx, Px, Syy_x, Syh_x, Shh_x, pm, pe, bad);
+            cf_axis(phi, om, q, w.y, w.vy, ay, by, Py, Syy_y, Syh_y, Shh_y, det, bad);
+            cf_axis(phi, om, q, w.x, w.vx, ax, bx, Px, Syy_x, Syh_x, Shh_x, det, bad);
         }
         pf = w.f;
         ++cnt;
@@ -132,13 +94,12 @@ __device__ __forceinline__ CfFit cf_cost(const CfRows &R, double D, double s2, d
         Qy = Shh_y > 0.0 ? Syy_y - (Syh_y * Syh_y) / Shh_y : Syy_y;
         Qx = Shh_x > 0.0 ? Syy_x - (Syh_x * Syh_x) / Shh_x : Syy_x;
     }
-    const double cost = ((log(pm) + (double)pe * CF_LN2) + (Qy + Qx)) + (double)(2 * (cnt - 1)) * CF_LOG_2PI;
-    fit.cost = (bad || !(cost < INFINITY)) ? INFINITY : cost;
+    fit.cost = tm_finish_cost(det, Qy + Qx, cnt - 1, bad);
     fit.hy = Shh_y, fit.hx = Shh_x, fit.cnt = cnt;
     return fit;
 }
 
-__device__ __forceinline__ double cf_stencil_factor(int i) { return i == 0 ? CF_EXP_MH : (i == 1 ? 1.0 : CF_EXP_H); }
+__device__ __forceinline__ double cf_stencil_factor(int i) { return i == 0 ? TM_EXP_MH : (i == 1 ? 1.0 : TM_EXP_H); }
 
 struct CfOut {
     double *D, *D_std, *radius, *radius_std, *lambda, *lambda_std, *corr, *centre, *centre_std, *loglik;
@@ -149,27 +110,13 @@ __global__ __launch_bounds__(CF_THREADS) void cf_kernel(const double *__restrict
                                                         const int *__restrict__ frames, const unsigned char *__restrict__ use,
                                                         int N, const int *__restrict__ offsets, double dt, CfOut out) {
     const int k = blockIdx.x, lane = threadIdx.x;
-    CfRows R;
+    TmRows R;
     R.pos = pos, R.var = var, R.frames = frames, R.use = use;
-    cf_clamp(offsets, k, N, R.a, R.b);
+    tm_clamp_range(offsets, k, N, R.a, R.b);
 
-    // pass 0: the usable rows, D_ref of likelihood.hip and the sums of the positions; the same in every lane
-    double S = 0.0, sy = 0.0, sx = 0.0, py = 0.0, px = 0.0;
-    int64_t G = 0;
-    int pf = 0, cnt = 0;
-    for (int r = R.a; r < R.b; ++r) {
-        const CfRow w = cf_row(R, r);
-        if (!w.ok) continue;
-        if (cnt > 0) {
-            const double dy = w.y - py, dx = w.x - px;
-            S = S + (dy * dy + dx * dx);
-            G += w.f - pf;
-        }
-        sy = sy + w.y, sx = sx + w.x;
-        py = w.y, px = w.x, pf = w.f;
-        ++cnt;
-    }
-    const int n_inc = cnt > 0 ? cnt - 1 : 0;
+    // pass 0: the usable rows, D_ref and the sums of the positions; the same in every lane
+    const TmScale sc = tm_scale(R);
+    const int n_inc = sc.n_inc(), cnt = sc.cnt;
     if (n_inc < CF_MIN_INCREMENTS) {                                      // wave-uniform
         if (lane == 0) {
             out.D[k] = NAN, out.D_std[k] = NAN, out.radius[k] = NAN, out.radius_std[k] = NAN, out.lambda[k] = NAN;
@@ -180,12 +127,12 @@ __global__ __launch_bounds__(CF_THREADS) void cf_kernel(const double *__restrict
         }
         return;
     }
-    const double D_ref = S / ((4.0 * dt) * (double)G);
+    const double D_ref = tm_d_ref(sc.S, dt, sc.G);
     // pass 0, second half: S_ref, half the summed variance of the usable positions about their mean
-    const double my = sy / (double)cnt, mx = sx / (double)cnt;
+    const double my = sc.sy / (double)cnt, mx = sc.sx / (double)cnt;
     double ss = 0.0;
     for (int r = R.a; r < R.b; ++r) {
-        const CfRow w = cf_row(R, r);
+        const TmRow w = tm_row(R, r);
         if (!w.ok) continue;
         const double dy = w.y - my, dx = w.x - mx;
         ss = ss + (dy * dy + dx * dx);
@@ -202,12 +149,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_kernel(const double *__restrict
         const double Dj = D_ref * exp2(ulo + li * su), Sj = S_ref * exp2(wlo + lj * sw);
         double c = cf_cost(R, Dj, Sj, dt, false, 0.0, 0.0).cost;
         int j = lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {                                // every lane ends with the least cost and its lowest lane
-            const double oc = __shfl_xor(c, o, CF_THREADS);
-            const int oj = __shfl_xor(j, o, CF_THREADS);
-            if (oc < c || (oc == c && oj < j)) c = oc, j = oj;
-        }
+        tm_wave_argmin(c, j);
         const int bi = j >> 3, bj = j & 7;
         ub = ulo + (double)bi * su, wb = wlo + (double)bj * sw;
         ulo = ub - 2.0 * su, uhi = ub + 2.0 * su, wlo = wb - 2.0 * sw, whi = wb + 2.0 * sw;
@@ -226,12 +168,10 @@ __global__ __launch_bounds__(CF_THREADS) void cf_kernel(const double *__restrict
     const double cy = __shfl(fit.cy, 4, CF_THREADS), cx = __shfl(fit.cx, 4, CF_THREADS);
     const double hy = __shfl(fit.hy, 4, CF_THREADS), hx = __shfl(fit.hx, 4, CF_THREADS);
     const double c0 = c[4];
-    const double Hdd = ((c[7] - c0) + (c[1] - c0)) * 2048.0;
-    const double Hss = ((c[5] - c0) + (c[3] - c0)) * 2048.0;
-    const double Hds = ((c[8] - c[6]) - (c[2] - c[0])) * 512.0;
-    const double det = Hdd * Hss - Hds * Hds;
+    const TmHess2 H(c);                                                   // u = ln D, v = ln s2
+    const double Hdd = H.uu, Hss = H.vv, Hds = H.uv, det = H.det;
     if (!(c0 < INFINITY)) st = 4;                                         // no candidate was accepted
-    const bool pd = Hdd > 0.0 && Hss > 0.0 && det > 0.0 && det < INFINITY;
+    const bool pd = H.pd();
     if (!pd && st == 0) st = 4;
     const bool full = pd && (st == 0 || st == 5);
     if (lane == 0) {
@@ -262,23 +202,14 @@ __global__ __launch_bounds__(CF_THREADS) void cf_loglik_kernel(const double *__r
                                                                const double *__restrict__ centre, double *__restrict__ loglik) {
     const int k = blockIdx.x * CF_THREADS + threadIdx.x;
     if (k >= n) return;
-    CfRows R;
+    TmRows R;
     R.pos = pos, R.var = var, R.frames = frames, R.use = use;
-    cf_clamp(offsets, k, N, R.a, R.b);
+    tm_clamp_range(offsets, k, N, R.a, R.b);
     const double Dk = D[k], Sk = s2[k];
     const bool given = centre != nullptr;
     const CfFit fit = cf_cost(R, Dk, Sk, dt, given, given ? centre[2 * (int64_t)k] : 0.0, given ? centre[2 * (int64_t)k + 1] : 0.0);
     const bool fine = fit.cnt >= 2 && Dk > 0.0 && Dk < INFINITY && Sk > 0.0 && Sk < INFINITY;
     loglik[k] = fine ? -0.5 * fit.cost : NAN;
-}
-
-int cf_check(const char *name, const double *pos, int N, const int *offsets, int n, double dt) {
-    MIVIT_CHECK(N >= 0 && n >= 0, "%s: N = %d, n = %d: negative size", name, N, n);
-    MIVIT_CHECK(dt > 0.0 && dt < INFINITY, "%s: dt = %g must be positive and finite", name, dt);
-    if (n == 0) return 0;
-    MIVIT_CHECK(offsets, "%s: null pointer", name);
-    MIVIT_CHECK(pos || N == 0, "%s: null pointer", name);
-    return 0;
 }
 
 }  // namespace
@@ -287,7 +218,7 @@ extern "C" int mivit_track_confined_ml(const double *pos, const double *var, con
                                        const int *offsets, int n, double dt, double *D, double *D_std, double *radius,
                                        double *radius_std, double *lambda, double *lambda_std, double *corr, double *centre,
                                        double *centre_std, double *loglik, int *n_increments, int *status, void *stream) {
-    if (int rc = cf_check("track_confined_ml", pos, N, offsets, n, dt)) return rc;
+    if (int rc = tm_check_rows("track_confined_ml", pos, N, offsets, n, dt)) return rc;
     if (n == 0) return 0;
     MIVIT_CHECK(D && D_std && radius && radius_std && lambda && lambda_std && corr && centre && centre_std && loglik &&
                     n_increments && status,
@@ -303,7 +234,7 @@ extern "C" int mivit_track_confined_ml(const double *pos, const double *var, con
 extern "C" int mivit_track_confined_loglik(const double *pos, const double *var, const int *frames, const unsigned char *use,
                                            int N, const int *offsets, int n, double dt, const double *D, const double *s2,
                                            const double *centre, double *loglik, void *stream) {
-    if (int rc = cf_check("track_confined_loglik", pos, N, offsets, n, dt)) return rc;
+    if (int rc = tm_check_rows("track_confined_loglik", pos, N, offsets, n, dt)) return rc;
     if (n == 0) return 0;
     MIVIT_CHECK(D && s2 && loglik, "track_confined_loglik: null pointer");
     prof_set_tag(MIVIT_PROF_OP);

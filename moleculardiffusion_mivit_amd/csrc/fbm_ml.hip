@@ -10,8 +10,9 @@
 // leaves L^-1 d in that row: thread i owns row i and forms its own dot products in ascending k and the running value of its
 // own pivot, which it publishes in the diagonal's place one column before the others need it, so a column costs one barrier
 // and no value crosses threads through anything but LDS.  The thread of the increments' row takes the determinant as an exactly
-// rescaled product (frexp, as csrc/likelihood.hip) and the quadratic form in column order.  The two axes have their own
-// variances and therefore their own factorisation, one after the other in the same triangle.
+// rescaled product (frexp) and the quadratic form in column order.  The two axes have their own
+// variances and therefore their own factorisation, one after the other in the same triangle.  The usable-row rule, the
+// product, the closing of the cost and the stencil's information matrix are those of track_ml.h.
 //
 // The search runs without the host: per round one launch of n x 64 workgroups writes the 64 costs of every range into the
 // caller's workspace and a one-thread-per-range kernel takes the arg-min (lowest index on a tie) and writes the next
@@ -19,7 +20,7 @@
 // fp64 without contraction, no atomics, no scratch; a range's work does not depend on where it sits in a batch.
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "track_ml.h"
 
 namespace {
 
@@ -33,11 +34,6 @@ constexpr int FM_LDS_BYTES = FM_LDS_DOUBLES * 8 + (FM_MAX_ROWS + 3) * 4;  // + f
 constexpr int FM_CAND = 64, FM_ROUNDS = 20, FM_TERMS = 30;
 constexpr double FM_ALPHA_MIN = 0.05, FM_ALPHA_MAX = 1.95;               // helpers/generation.ALPHA_MIN, ALPHA_MAX
 constexpr double FM_U_LO = -12.0, FM_U_HI = 4.0;                          // the first bracket of log2(D / D_ref)
-constexpr double FM_H = 0.015625;                                         // 1 / 64: the stencil's step in alpha and in ln D
-constexpr double FM_EXP_H = 1.0157477085866857;                           // np.exp(1 / 64)
-constexpr double FM_EXP_MH = 0.9844964370054085;                          // np.exp(-1 / 64)
-constexpr double FM_LOG_2PI = 1.8378770664093453;                         // np.log(2 * np.pi)
-constexpr double FM_LN2 = 0.6931471805599453;                             // np.log(2)
 // the workspace of a range, in doubles: 64 costs (the stencil's 9 over the first of them), the bracket, the two flags, the
 // best candidate, and what the last kernel needs of the range
 constexpr int FM_WS = 80, FM_WS_ALO = 64, FM_WS_AHI = 65, FM_WS_ULO = 66, FM_WS_UHI = 67, FM_WS_ALL_LO = 68, FM_WS_ALL_HI = 69,
@@ -53,8 +49,6 @@ struct FmIn {
     int N;
     double dt, E;
 };
-
-__device__ __forceinline__ bool fm_finite(double v) { return fabs(v) < INFINITY; }
 
 // the structure function of fractional Brownian motion averaged over the exposure E, at a lag of t frames
 __device__ __forceinline__ double fm_structure(double alpha, int t, double E) {
@@ -81,24 +75,15 @@ __device__ __forceinline__ double fm_structure(double alpha, int t, double E) {
 // FM_MAX_ROWS of them).  Xy, Xx receive the positions.
 __device__ __forceinline__ int fm_compact(const FmIn &in, int k, double *Xy, double *Xx, double *vy, double *vx, int *fr, int *wcnt) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int a = in.offsets[k], b = in.offsets[k + 1];
-    a = a < 0 ? 0 : (a > in.N ? in.N : a);                                // never read outside [0, N), whatever offsets holds
-    b = b < a ? a : (b > in.N ? in.N : b);
+    TmRows R;
+    R.pos = in.pos, R.var = in.var, R.frames = in.frames, R.use = in.use;
+    tm_clamp_range(in.offsets, k, in.N, R.a, R.b);
     int base = 0;
-    for (int r0 = a; r0 < b; r0 += FM_THREADS) {                          // r0 <= N - 1: r0 + tid cannot overflow for N <= 2^31 - 192
+    for (int r0 = R.a; r0 < R.b; r0 += FM_THREADS) {                      // r0 <= N - 1: r0 + tid cannot overflow for N <= 2^31 - 192
         const int r = r0 + tid;
-        double y = 0.0, x = 0.0, wy = 0.0, wx = 0.0;
-        int f = 0;
-        bool ok = false;
-        if (r < b) {
-            y = in.pos[2 * (int64_t)r];
-            x = in.pos[2 * (int64_t)r + 1];
-            wy = in.var ? in.var[2 * (int64_t)r] : 0.0;
-            wx = in.var ? in.var[2 * (int64_t)r + 1] : 0.0;
-            f = in.frames ? in.frames[r] : r - a;
-            ok = (in.use ? in.use[r] != 0 : true) && fm_finite(y) && fm_finite(x) && wy >= 0.0 && wy < INFINITY && wx >= 0.0 &&
-                 wx < INFINITY;
-        }
+        TmRow row{};                                                      // not usable beyond the range's end
+        if (r < R.b) row = tm_row(R, r);
+        const bool ok = row.ok;
         const unsigned long long bal = __ballot(ok);
         if (lane == 0) wcnt[wave] = __popcll(bal);
         __syncthreads();
@@ -109,7 +94,7 @@ __device__ __forceinline__ int fm_compact(const FmIn &in, int k, double *Xy, dou
             total += c;
         }
         const int idx = base + before + __popcll(bal & ((1ull << lane) - 1ull));
-        if (ok && idx < FM_MAX_ROWS) Xy[idx] = y, Xx[idx] = x, vy[idx] = wy, vx[idx] = wx, fr[idx] = f;
+        if (ok && idx < FM_MAX_ROWS) Xy[idx] = row.y, Xx[idx] = row.x, vy[idx] = row.vy, vx[idx] = row.vx, fr[idx] = row.f;
         base += total;
         __syncthreads();
     }
@@ -117,9 +102,9 @@ __device__ __forceinline__ int fm_compact(const FmIn &in, int k, double *Xy, dou
 }
 
 // -2 log L of one axis: the triangle of this axis' covariance with the increments d below it, factorised in place.  Returns
-// in thread m (the increments' row) the sum log det C + d^T C^-1 d through (pm, pe, Q); bad where a pivot is not positive.
+// in thread m (the increments' row) the sum log det C + d^T C^-1 d through (det, Q); bad where a pivot is not positive.
 __device__ __forceinline__ void fm_axis(double *Lp, const double *tab, const double *d, const double *v, const int *fr, int m, double Ddt,
-                        double &Q, double &pm, int &pe, bool &bad) {
+                        double &Q, TmProd &det, bool &bad) {
     const int i = threadIdx.x;
     double *ri = Lp + (i * (i + 1)) / 2;                                  // used where i <= m only
     if (i < m) {
@@ -151,9 +136,7 @@ __device__ __forceinline__ void fm_axis(double *Lp, const double *tab, const dou
             if (i == m) {
                 if (!(p > 0.0)) bad = true;                               // not positive definite (or NaN): the candidate is rejected
                 Q = Q + s * s;
-                int ex;
-                pm = frexp(pm * p, &ex);
-                pe += ex;
+                det.mul(p);
             } else {
                 pi = pi - s * s;
                 if (i == j + 1) ri[i] = pi;
@@ -221,7 +204,7 @@ __global__ __launch_bounds__(FM_THREADS) void fm_cost_kernel(FmIn in, const doub
     if (MODE != FM_LOGLIK) {
         double S = 0.0;
         for (int r = 0; r < m; ++r) S = S + (dy[r] * dy[r] + dx[r] * dx[r]);
-        const double D_ref = S / ((4.0 * in.dt) * (double)((int64_t)fr[m] - (int64_t)fr[0]));
+        const double D_ref = tm_d_ref(S, in.dt, (int64_t)fr[m] - (int64_t)fr[0]);
         if (MODE == FM_ROUND) {
             const double alo = round ? w[FM_WS_ALO] : FM_ALPHA_MIN, ahi = round ? w[FM_WS_AHI] : FM_ALPHA_MAX;
             const double ulo = round ? w[FM_WS_ULO] : FM_U_LO, uhi = round ? w[FM_WS_UHI] : FM_U_HI;
@@ -230,8 +213,8 @@ __global__ __launch_bounds__(FM_THREADS) void fm_cost_kernel(FmIn in, const doub
         } else {
             const double Db = w[FM_WS_ALL_LO] != 0.0 ? 0.0 : D_ref * exp2(w[FM_WS_U]);
             const int ia = c / 3 - 1, id = c % 3 - 1;
-            alpha = w[FM_WS_ALPHA] + (double)ia * FM_H;
-            D = id > 0 ? Db * FM_EXP_H : (id < 0 ? Db * FM_EXP_MH : Db);
+            alpha = w[FM_WS_ALPHA] + (double)ia * TM_H;
+            D = id > 0 ? Db * TM_EXP_H : (id < 0 ? Db * TM_EXP_MH : Db);
             if (c == 4 && tid == 0) w[FM_WS_NINC] = (double)n_inc, w[FM_WS_STATUS] = 0.0, w[FM_WS_D] = Db;
         }
     }
@@ -239,14 +222,13 @@ __global__ __launch_bounds__(FM_THREADS) void fm_cost_kernel(FmIn in, const doub
     __syncthreads();                                                      // also: the positions in Lp are no longer needed
 
     const double Ddt = D * in.dt;
-    double Q = 0.0, pm = 0.5;
-    int pe = 1;
+    double Q = 0.0;
+    TmProd det;
     bool bad = false;
-    fm_axis(Lp, tab, dy, vy, fr, m, Ddt, Q, pm, pe, bad);
-    fm_axis(Lp, tab, dx, vx, fr, m, Ddt, Q, pm, pe, bad);
+    fm_axis(Lp, tab, dy, vy, fr, m, Ddt, Q, det, bad);
+    fm_axis(Lp, tab, dx, vx, fr, m, Ddt, Q, det, bad);
     if (tid == m) {
-        double cost = ((log(pm) + (double)pe * FM_LN2) + Q) + (double)(2 * m) * FM_LOG_2PI;
-        if (bad || !(cost < INFINITY)) cost = INFINITY;
+        const double cost = tm_finish_cost(det, Q, m, bad);
         if (MODE == FM_LOGLIK)
             loglik[k] = -0.5 * cost, n_increments[k] = n_inc, status[k] = 0;
         else
@@ -300,14 +282,12 @@ __global__ void fm_finish_kernel(int n, const double *__restrict__ ws, double *_
         Dk = w[FM_WS_D];
         if (st != 2) {
             a = w[FM_WS_ALPHA];
-            const double Haa = ((w[7] - c0) + (w[1] - c0)) * 2048.0;     // 1 / (2 h^2): half the second difference
-            const double Hdd = ((w[5] - c0) + (w[3] - c0)) * 2048.0;
-            const double Had = ((w[8] - w[6]) - (w[2] - w[0])) * 512.0;  // 1 / (8 h^2)
-            const double det = Haa * Hdd - Had * Had;
-            if (a - FM_H >= FM_ALPHA_MIN && a + FM_H <= FM_ALPHA_MAX && Haa > 0.0 && Hdd > 0.0 && det > 0.0 && det < INFINITY) {
-                as = sqrt(Hdd / det);
-                Ds = Dk * sqrt(Haa / det);
-                co = -Had / sqrt(Haa * Hdd);
+            const TmHess2 H(w);                                           // u = alpha, v = ln D: the stencil's costs are w[0 .. 8]
+            const bool pd = H.pd();
+            if (a - TM_H >= FM_ALPHA_MIN && a + TM_H <= FM_ALPHA_MAX && pd) {
+                as = sqrt(H.vv / H.det);
+                Ds = Dk * sqrt(H.uu / H.det);
+                co = -H.uv / sqrt(H.uu * H.vv);
             } else if (st == 0) {
                 st = 4;
             }
@@ -330,13 +310,10 @@ int fm_launch_cost(const FmIn &in, const double *alpha, const double *D, int n, 
 }
 
 int fm_check(const char *name, const double *pos, int N, const int *offsets, int n, double dt, double exposure) {
-    MIVIT_CHECK(N >= 0 && n >= 0, "%s: N = %d, n = %d: negative size", name, N, n);
+    if (int rc = tm_check_rows(name, pos, N, offsets, n, dt)) return rc;
     MIVIT_CHECK(N <= 2147483647 - FM_THREADS, "%s: N = %d rows, at most %d", name, N, 2147483647 - FM_THREADS);
     MIVIT_CHECK(n <= (1 << 24), "%s: n = %d ranges, at most %d in one call", name, n, 1 << 24);
-    MIVIT_CHECK(dt > 0.0 && dt < INFINITY, "%s: dt = %g must be positive and finite", name, dt);
     MIVIT_CHECK(exposure >= 0.0 && exposure <= 1.0, "%s: exposure = %g outside [0, 1]", name, exposure);
-    if (n == 0) return 0;
-    MIVIT_CHECK(offsets && (pos || N == 0), "%s: null pointer", name);
     return 0;
 }
 

@@ -898,8 +898,76 @@ def subtract_drift(positions, frames, drift):
 # maximum-likelihood D per track from rows of known variance, with a standard error (csrc/likelihood.hip)
 # ----------------------------------------------------------------------------------------------------------------------
 _ML_CANDIDATES, _ML_ROUNDS, _ML_U_LO, _ML_U_HI = 64, 6, -20.0, 4.0
+# what the three fits of this family share (csrc/track_ml.h has the same pieces for the kernels)
 _ML_LN2 = 0.6931471805599453                      # np.log(2)
+_ML_H = 1.0 / 64.0                                # the step of the curvature's differences
 _ML_EXP_H, _ML_EXP_MH = 1.0157477085866857, 0.9844964370054085           # np.exp(1 / 64), np.exp(-1 / 64)
+
+
+def _ml_usable(pos, var, frames, use, offsets):
+    """The usable rows of every range, a list of n index arrays into the rows: a row is usable when its flag is set (use
+    None: all are), both coordinates are finite and both variances are finite and >= 0 (var None: zeros).  frames plays no
+    part; it is taken so that the restatements hand over their arguments as they got them."""
+    ok = np.isfinite(pos).all(axis=1)
+    if var is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
+    if use is not None:
+        ok &= use.astype(bool)
+    return [int(offsets[k]) + np.nonzero(ok[int(offsets[k]):int(offsets[k + 1])])[0] for k in range(len(offsets) - 1)]
+
+
+def _ml_padded(rows, sel, pos, var, frames, offsets):
+    """The usable rows (rows: of _ml_usable) of the ranges sel, in the order given, padded with zeros to the longest: -> (X
+    [ns, Mx, 2], V [ns, Mx, 2], Fr [ns, Mx] int64); a row's frame is its place in its range where frames is None"""
+    Mx = max([len(rows[k]) for k in sel], default=0)
+    X, V, Fr = np.zeros((len(sel), Mx, 2)), np.zeros((len(sel), Mx, 2)), np.zeros((len(sel), Mx), np.int64)
+    for i, k in enumerate(sel):
+        r = rows[k]
+        X[i, :len(r)] = pos[r]
+        if var is not None:
+            V[i, :len(r)] = var[r]
+        Fr[i, :len(r)] = frames[r] if frames is not None else r - int(offsets[k])
+    return X, V, Fr
+
+
+def _ml_prod_mul(pm, pe, x):
+    """one factor more into the determinant of the first len(x) ranges, kept as a product rescaled exactly: pm the mantissa in
+    [0.5, 1), pe the integer exponent, both changed in place"""
+    m, ex = np.frexp(pm[:len(x)] * x)
+    pm[:len(x)] = m
+    pe[:len(x)] += ex
+
+
+def _ml_finish_cost(pm, pe, Q, inc, bad):
+    """-2 log L [n, C] = log det (the product pm 2^pe) + Q + 2 inc log 2 pi; +inf where bad and where it is not below +inf"""
+    cost = ((np.log(pm) + pe.astype(np.float64) * _ML_LN2) + Q) + (2 * inc).astype(np.float64)[:, None] * _LOG_2PI
+    return np.where(bad | ~(cost < np.inf), np.inf, cost)
+
+
+def _ml_d_ref(d, g, inc, dt):
+    """The reference scale sum d^2 (both axes) / (4 dt sum g) over the first inc [n] increments of each range: d [n, M, 2] the
+    increments, g [n, M] their gaps in frames; the sum of the squares in the kernels' order"""
+    live = np.arange(d.shape[1])[None, :] < inc[:, None]
+    S = np.cumsum(np.where(live, d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], 0.0), axis=1)[:, -1]
+    G = np.where(live, g, 0).sum(axis=1)
+    return S / ((4.0 * dt) * G.astype(np.float64))
+
+
+def _ml_curvature(cp, c0, cm):
+    """half the second difference of the cost over h^2, h = 1 / 64"""
+    return ((cp - c0) + (cm - c0)) * 2048.0
+
+
+def _ml_hessian(c):
+    """The 2 x 2 observed information in (u, v) from the nine costs c [..., 9] of the stencil, c[..., 3 a + b] at (u + (a - 1)
+    h, v + (b - 1) h) -> (uu, vv, uv, det, whether it is positive definite)"""
+    c0 = c[..., 4]
+    uu = _ml_curvature(c[..., 7], c0, c[..., 1])
+    vv = _ml_curvature(c[..., 5], c0, c[..., 3])
+    uv = ((c[..., 8] - c[..., 6]) - (c[..., 2] - c[..., 0])) * 512.0       # 1 / (8 h^2)
+    det = uu * vv - uv * uv
+    return uu, vv, uv, det, (uu > 0.0) & (vv > 0.0) & (det > 0.0) & (det < np.inf)
 
 
 def _ml_cost(Dc, d, g, V, inc, dt, R):
@@ -930,12 +998,9 @@ def _ml_cost(Dc, d, g, V, inc, dt, R):
                 bad[:na] |= ~(e > 0.0)
                 r = 1.0 / e
                 Q[:na] = Q[:na] + (zz * zz) * r
-                m, ex = np.frexp(pm[:na] * e)
-                pm[:na] = m
-                pe[:na] += ex
+                _ml_prod_mul(pm, pe, e)
                 rinv[ax, :na], z[ax, :na] = r, zz
-        cost = ((np.log(pm) + pe.astype(np.float64) * _ML_LN2) + Q) + (2 * inc).astype(np.float64)[:, None] * _LOG_2PI
-        return np.where(bad | ~(cost < np.inf), np.inf, cost)
+        return _ml_finish_cost(pm, pe, Q, inc, bad)
 
 
 def _diffusion_ml_numpy(pos, var, frames, use, offsets, dt, R):
@@ -946,37 +1011,19 @@ def _diffusion_ml_numpy(pos, var, frames, use, offsets, dt, R):
     Differs from the kernel in log and exp2 alone."""
     n = len(offsets) - 1
     D, D_std, loglik = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
-    n_inc, status = np.zeros(n, np.int32), np.ones(n, np.int32)
-    ok = np.isfinite(pos).all(axis=1)
-    if var is not None:
-        with np.errstate(invalid="ignore"):
-            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
-    if use is not None:
-        ok &= use.astype(bool)
-    rows = []
-    for k in range(n):
-        a, b = int(offsets[k]), int(offsets[k + 1])
-        rows.append(a + np.nonzero(ok[a:b])[0])
-        n_inc[k] = max(len(rows[k]) - 1, 0)
+    status = np.ones(n, np.int32)
+    rows = _ml_usable(pos, var, frames, use, offsets)
+    n_inc = np.array([max(len(r) - 1, 0) for r in rows], np.int32).reshape(n)
     sel = np.nonzero(n_inc >= 2)[0]
     if not len(sel):
         return D, D_std, loglik, n_inc, status
     sel = sel[np.argsort(-n_inc[sel], kind="stable")]                      # descending: the ranges still running are a prefix
     inc = n_inc[sel].astype(np.int64)
-    ns, Mx = len(sel), int(inc[0]) + 1
-    X, V, Fr = np.zeros((ns, Mx, 2)), np.zeros((ns, Mx, 2)), np.zeros((ns, Mx), np.int64)
-    for i, k in enumerate(sel):
-        r = rows[k]
-        X[i, :len(r)] = pos[r]
-        if var is not None:
-            V[i, :len(r)] = var[r]
-        Fr[i, :len(r)] = frames[r] if frames is not None else r - int(offsets[k])
+    ns = len(sel)
+    X, V, Fr = _ml_padded(rows, sel, pos, var, frames, offsets)
     d, g = X[:, 1:] - X[:, :-1], Fr[:, 1:] - Fr[:, :-1]
-    live = np.arange(Mx - 1)[None, :] < inc[:, None]
-    S = np.cumsum(np.where(live, d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], 0.0), axis=1)[:, -1]
-    G = np.where(live, g, 0).sum(axis=1)
     with np.errstate(all="ignore"):
-        D_ref = S / ((4.0 * dt) * G.astype(np.float64))
+        D_ref = _ml_d_ref(d, g, inc, dt)
         lo, hi = np.full(ns, _ML_U_LO), np.full(ns, _ML_U_HI)
         all_lo, all_hi = np.ones(ns, bool), np.ones(ns, bool)
         lane, each = np.arange(_ML_CANDIDATES, dtype=np.float64), np.arange(ns)
@@ -993,7 +1040,7 @@ def _diffusion_ml_numpy(pos, var, frames, use, offsets, dt, R):
         st = np.where(all_lo, 2, np.where(all_hi, 3, 0)).astype(np.int32)
         Db = np.where(all_lo, 0.0, Db)
         c = _ml_cost(np.stack([Db, Db * _ML_EXP_H, Db * _ML_EXP_MH], axis=1), d, g, V, inc, dt, R)
-        info = ((c[:, 1] - c[:, 0]) + (c[:, 2] - c[:, 0])) * 2048.0
+        info = _ml_curvature(c[:, 1], c[:, 0], c[:, 2])
         curved = (info > 0.0) & (info < np.inf)
         D[sel], loglik[sel] = Db, -0.5 * c[:, 0]
         D_std[sel] = np.where(curved & (st != 2), Db / np.sqrt(info), np.nan)
@@ -1057,6 +1104,35 @@ def _ml_arguments(positions, offsets, variances, frames, use, dt):
     return is_t, pos, off, var, fr, usable
 
 
+def _ml_per_range(v, n, what, device, width=None):
+    """a parameter given as a number (width: as [width]) or per range -> float64 tensor [n] ([n, width]) on the device"""
+    v = v.detach().to(device, torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64), device=device)
+    shape = (n,) if width is None else (n, width)
+    if v.dim() == (0 if width is None else 1) and (width is None or tuple(v.shape) == (width,)):
+        v = v.expand(*shape)
+    if tuple(v.shape) != shape:
+        raise ValueError(f"{what} must be {'a number' if width is None else f'[{width}]'} or {list(shape)}, got {tuple(v.shape)}")
+    return v.contiguous()
+
+
+def _ml_dispatch(args, kernel, restated, keys):
+    """The tail that the front ends of this family share.  args: what _ml_arguments returned.  CUDA tensors go to
+    kernel(ops, pos, offsets int32, var, frames int32, use), everything else to restated(pos, var, frames, use, offsets) as
+    numpy arrays (None stays None) -> dict of the outputs under keys, of the input's kind, n_increments and status as int64."""
+    is_t, pos, off, var, fr, usable = args
+    on_gpu = pos.device.type == "cuda"
+    if on_gpu:
+        from .. import ops
+        got = kernel(ops, pos, off.int().contiguous(), var, None if fr is None else fr.int().contiguous(), usable)
+    else:
+        got = restated(*(None if t is None else t.numpy() for t in (pos, var, fr, usable, off)))
+    out = dict(zip(keys, got if isinstance(got, tuple) else (got,)))
+    for k in ("n_increments", "status"):
+        if k in out:
+            out[k] = out[k].long() if on_gpu else out[k].astype(np.int64)
+    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t and not on_gpu else out
+
+
 def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, blur=0.0):
     """The maximum-likelihood diffusion coefficient of every track with its standard error, from rows that each carry their
     own localisation variance (Berglund 2010; Michalet & Berglund 2012; Relich et al. 2016): positions [N, 2] (y, x) sorted
@@ -1086,26 +1162,17 @@ def estimate_diffusion_ml(positions, offsets, variances=None, frames=None, use=N
         raise ValueError(f"dt must be positive and finite, got {dt}")
     if not 0.0 <= float(blur) <= 0.25:
         raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
-    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
-    if pos.device.type == "cuda":
-        from .. import ops
-        D, D_std, loglik, n_inc, status = ops.track_diffusion_ml(pos, off.int().contiguous(), var,
-                                                                 None if fr is None else fr.int().contiguous(), usable,
-                                                                 float(dt), float(blur))
-        return {"D_ml": D, "D_ml_std": D_std, "loglik": loglik, "n_increments": n_inc.long(), "status": status.long()}
-    D, D_std, loglik, n_inc, status = _diffusion_ml_numpy(
-        pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
-        None if usable is None else usable.numpy(), off.numpy(), float(dt), float(blur))
-    out = {"D_ml": D, "D_ml_std": D_std, "loglik": loglik, "n_increments": n_inc.astype(np.int64),
-           "status": status.astype(np.int64)}
-    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out
+    return _ml_dispatch(_ml_arguments(positions, offsets, variances, frames, use, dt),
+                        lambda ops, pos, off, var, fr, usable: ops.track_diffusion_ml(pos, off, var, fr, usable, float(dt), float(blur)),
+                        lambda *rows: _diffusion_ml_numpy(*rows, float(dt), float(blur)),
+                        ("D_ml", "D_ml_std", "loglik", "n_increments", "status"))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # maximum-likelihood anomalous exponent per track from rows of known variance, with error bars (csrc/fbm_ml.hip)
 # ----------------------------------------------------------------------------------------------------------------------
 FBM_ML_MAX_ROWS, FBM_ML_MAX_SPAN = 129, 1199      # csrc/fbm_ml.hip: usable rows of a range, largest - smallest usable frame
-_FBM_GRID, _FBM_ROUNDS, _FBM_U_LO, _FBM_U_HI, _FBM_TERMS, _FBM_H = 8, 20, -12.0, 4.0, 30, 1.0 / 64.0
+_FBM_GRID, _FBM_ROUNDS, _FBM_U_LO, _FBM_U_HI, _FBM_TERMS = 8, 20, -12.0, 4.0, 30
 
 
 def fbm_structure(alpha, lag, exposure=0.0):
@@ -1133,20 +1200,9 @@ def fbm_structure(alpha, lag, exposure=0.0):
 
 
 def _fbm_usable_rows(pos, var, frames, use, offsets):
-    """-> per range (X [M, 2], V [M, 2], F [M] int64) of its usable rows, by the rule of _diffusion_ml_numpy"""
-    ok = np.isfinite(pos).all(axis=1)
-    if var is not None:
-        with np.errstate(invalid="ignore"):
-            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
-    if use is not None:
-        ok &= use.astype(bool)
-    out = []
-    for k in range(len(offsets) - 1):
-        a, b = int(offsets[k]), int(offsets[k + 1])
-        r = a + np.nonzero(ok[a:b])[0]
-        out.append((pos[r], np.zeros((len(r), 2)) if var is None else var[r],
-                    (r - a if frames is None else frames[r]).astype(np.int64)))
-    return out
+    """-> per range (X [M, 2], V [M, 2], F [M] int64) of its usable rows"""
+    rows = _ml_usable(pos, var, frames, use, offsets)
+    return [tuple(t[0] for t in _ml_padded(rows, [k], pos, var, frames, offsets)) for k in range(len(rows))]
 
 
 def _fbm_over_limit(F):
@@ -1235,18 +1291,15 @@ def _fbm_ml_numpy(pos, var, frames, use, offsets, dt, E):
                 alo, ahi, ulo, uhi = max(ab - 2.0 * sa, ALPHA_MIN), min(ab + 2.0 * sa, ALPHA_MAX), ub - 2.0 * su, ub + 2.0 * su
                 all_lo, all_hi = all_lo and j == 0, all_hi and j == _FBM_GRID - 1
             Db = 0.0 if all_lo else float(D_ref * np.exp2(ub))
-            a_s = np.repeat(ab + np.array([-1.0, 0.0, 1.0]) * _FBM_H, 3)
+            a_s = np.repeat(ab + np.array([-1.0, 0.0, 1.0]) * _ML_H, 3)
             D_s = np.tile(np.array([Db * _ML_EXP_MH, Db, Db * _ML_EXP_H]), 3)
             c = _fbm_cost(a_s, D_s, X, V, F, dt, E)
             st = 2 if all_lo else (3 if all_hi else 0)
             loglik[k], D[k] = -0.5 * c[4], Db
             if st != 2:
                 alpha[k] = ab
-                Haa = ((c[7] - c[4]) + (c[1] - c[4])) * 2048.0
-                Hdd = ((c[5] - c[4]) + (c[3] - c[4])) * 2048.0
-                Had = ((c[8] - c[6]) - (c[2] - c[0])) * 512.0
-                det = Haa * Hdd - Had * Had
-                if ab - _FBM_H >= ALPHA_MIN and ab + _FBM_H <= ALPHA_MAX and Haa > 0.0 and Hdd > 0.0 and 0.0 < det < np.inf:
+                Haa, Hdd, Had, det, pd = _ml_hessian(c)                    # u = alpha, v = ln D
+                if ab - _ML_H >= ALPHA_MIN and ab + _ML_H <= ALPHA_MAX and pd:
                     alpha_std[k], D_std[k], corr[k] = np.sqrt(Hdd / det), Db * np.sqrt(Haa / det), -Had / np.sqrt(Haa * Hdd)
                 elif st == 0:
                     st = 4
@@ -1271,28 +1324,13 @@ def fbm_loglik(positions, offsets, alpha, D, variances=None, frames=None, use=No
     loglik is NaN for 1, 5, 6).  The other arguments are those of estimate_diffusion_ml.  CUDA tensors go to the kernel
     (csrc/fbm_ml.hip), arrays and CPU tensors to the numpy restatement."""
     _fbm_checked(exposure, dt)
-    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
-    n = off.numel() - 1
-
-    def per_range(v, what):
-        v = v.detach().to(pos.device, torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64), device=pos.device)
-        if v.dim() == 0:
-            v = v.expand(n)
-        if tuple(v.shape) != (n,):
-            raise ValueError(f"{what} must be a number or [n] = [{n}], got {tuple(v.shape)}")
-        return v.contiguous()
-
-    a, Dv = per_range(alpha, "alpha"), per_range(D, "D")
-    if pos.device.type == "cuda":
-        from .. import ops
-        ll, n_inc, status = ops.track_fbm_loglik(pos, off.int().contiguous(), a, Dv, var, None if fr is None else fr.int().contiguous(),
-                                                 usable, float(dt), float(exposure))
-        return {"loglik": ll, "n_increments": n_inc.long(), "status": status.long()}
-    ll, n_inc, status = _fbm_loglik_numpy(pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
-                                          None if usable is None else usable.numpy(), off.numpy(), float(dt), float(exposure),
-                                          a.numpy(), Dv.numpy())
-    out = {"loglik": ll, "n_increments": n_inc.astype(np.int64), "status": status.astype(np.int64)}
-    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out
+    args = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    n, device = args[2].numel() - 1, args[1].device
+    a, Dv = _ml_per_range(alpha, n, "alpha", device), _ml_per_range(D, n, "D", device)
+    return _ml_dispatch(args,
+                        lambda ops, pos, off, var, fr, usable: ops.track_fbm_loglik(pos, off, a, Dv, var, fr, usable, float(dt), float(exposure)),
+                        lambda *rows: _fbm_loglik_numpy(*rows, float(dt), float(exposure), a.numpy(), Dv.numpy()),
+                        ("loglik", "n_increments", "status"))
 
 
 def estimate_anomalous_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, exposure=0.0):
@@ -1323,22 +1361,12 @@ def estimate_anomalous_ml(positions, offsets, variances=None, frames=None, use=N
     (csrc/fbm_ml.hip: one workgroup per track and candidate), arrays and CPU tensors to the numpy restatement with LAPACK's
     Cholesky, which differs from it in the order of sums, pow, exp2 and log."""
     _fbm_checked(exposure, dt)
-    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    args = _ml_arguments(positions, offsets, variances, frames, use, dt)
     brownian = estimate_diffusion_ml(positions, offsets, variances, frames, use, dt, blur=float(exposure) / 6.0)["loglik"]
-    keys = ("alpha_ml", "alpha_ml_std", "D_alpha", "D_alpha_std", "corr", "loglik", "n_increments", "status")
-    if pos.device.type == "cuda":
-        from .. import ops
-        got = ops.track_fbm_ml(pos, off.int().contiguous(), var, None if fr is None else fr.int().contiguous(), usable, float(dt),
-                               float(exposure))
-        out = dict(zip(keys, got))
-        out["n_increments"], out["status"] = out["n_increments"].long(), out["status"].long()
-    else:
-        got = _fbm_ml_numpy(pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
-                            None if usable is None else usable.numpy(), off.numpy(), float(dt), float(exposure))
-        out = dict(zip(keys, got))
-        out["n_increments"], out["status"] = out["n_increments"].astype(np.int64), out["status"].astype(np.int64)
-        if is_t:
-            out = {k: torch.from_numpy(v) for k, v in out.items()}
+    out = _ml_dispatch(args,
+                       lambda ops, pos, off, var, fr, usable: ops.track_fbm_ml(pos, off, var, fr, usable, float(dt), float(exposure)),
+                       lambda *rows: _fbm_ml_numpy(*rows, float(dt), float(exposure)),
+                       ("alpha_ml", "alpha_ml_std", "D_alpha", "D_alpha_std", "corr", "loglik", "n_increments", "status"))
     out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
     return out
 
@@ -1349,30 +1377,6 @@ def estimate_anomalous_ml(positions, offsets, variances=None, frames=None, use=N
 _CF_GRID, _CF_ROUNDS, _CF_MIN_INCREMENTS = 8, 20, 4
 _CF_U_LO, _CF_U_HI, _CF_W_LO, _CF_W_HI = -12.0, 4.0, -6.0, 18.0          # the first brackets of log2(D / D_ref), log2(s2 / S_ref)
 _CF_FAST = 4.0                                                           # status 3 where lambda dt is above it
-
-
-def _confined_rows(pos, var, frames, use, offsets, sel=None):
-    """The usable rows (the rule of _diffusion_ml_numpy) of the ranges sel (all where None, in the order given), padded:
-    -> (X [ns, Mx, 2], V [ns, Mx, 2], Fr [ns, Mx] int64, cnt [ns] int64, the rows of each range)"""
-    ok = np.isfinite(pos).all(axis=1)
-    if var is not None:
-        with np.errstate(invalid="ignore"):
-            ok &= ((var >= 0.0) & (var < np.inf)).all(axis=1)
-    if use is not None:
-        ok &= use.astype(bool)
-    n = len(offsets) - 1
-    rows = [int(offsets[k]) + np.nonzero(ok[int(offsets[k]):int(offsets[k + 1])])[0] for k in range(n)]
-    if sel is None:
-        return rows
-    Mx = max([len(rows[k]) for k in sel], default=0)
-    X, V, Fr = np.zeros((len(sel), Mx, 2)), np.zeros((len(sel), Mx, 2)), np.zeros((len(sel), Mx), np.int64)
-    for i, k in enumerate(sel):
-        r = rows[k]
-        X[i, :len(r)] = pos[r]
-        if var is not None:
-            V[i, :len(r)] = var[r]
-        Fr[i, :len(r)] = frames[r] if frames is not None else r - int(offsets[k])
-    return X, V, Fr
 
 
 def _confined_cost(Dc, Sc, X, V, g, inc, dt, centre=None):
@@ -1411,9 +1415,7 @@ def _confined_cost(Dc, Sc, X, V, g, inc, dt, centre=None):
                 Syy[ax, :na] = Syy[ax, :na] + (ey * ey) * r
                 Syh[ax, :na] = Syh[ax, :na] + (ey * eh) * r
                 Shh[ax, :na] = Shh[ax, :na] + (eh * eh) * r
-                m, ex = np.frexp(pm[:na] * F)
-                pm[:na] = m
-                pe[:na] += ex
+                _ml_prod_mul(pm, pe, F)
         if centre is None:
             pos_h = Shh > 0.0
             c = np.where(pos_h, Syh / Shh, np.nan)
@@ -1421,8 +1423,7 @@ def _confined_cost(Dc, Sc, X, V, g, inc, dt, centre=None):
         else:
             c = np.moveaxis(centre, 2, 0)
             Q = (Syy - ((2.0 * c) * Syh)) + (c * c) * Shh
-        cost = ((np.log(pm) + pe.astype(np.float64) * _ML_LN2) + (Q[0] + Q[1])) + (2 * inc).astype(np.float64)[:, None] * _LOG_2PI
-        cost = np.where(bad | ~(cost < np.inf), np.inf, cost)
+        cost = _ml_finish_cost(pm, pe, Q[0] + Q[1], inc, bad)
     return cost, np.moveaxis(c, 0, 2), np.moveaxis(Shh, 0, 2)
 
 
@@ -1431,7 +1432,7 @@ def _confined_loglik_numpy(pos, var, frames, use, offsets, dt, D, s2, centre):
     range without an increment and where D or s2 is not positive and finite, -inf for a rejected candidate"""
     n = len(offsets) - 1
     loglik = np.full(n, np.nan)
-    rows = _confined_rows(pos, var, frames, use, offsets)
+    rows = _ml_usable(pos, var, frames, use, offsets)
     cnt = np.array([len(r) for r in rows], np.int64)
     with np.errstate(invalid="ignore"):
         fine = (cnt >= 2) & (D > 0.0) & (D < np.inf) & (s2 > 0.0) & (s2 < np.inf)
@@ -1439,7 +1440,7 @@ def _confined_loglik_numpy(pos, var, frames, use, offsets, dt, D, s2, centre):
     if not len(sel):
         return loglik
     sel = sel[np.argsort(-cnt[sel], kind="stable")]
-    X, V, Fr = _confined_rows(pos, var, frames, use, offsets, sel)
+    X, V, Fr = _ml_padded(rows, sel, pos, var, frames, offsets)
     cost, _, _ = _confined_cost(D[sel][:, None], s2[sel][:, None], X, V, Fr[:, 1:] - Fr[:, :-1], cnt[sel] - 1, dt,
                                 None if centre is None else centre[sel][:, None, :])
     loglik[sel] = -0.5 * cost[:, 0]
@@ -1457,7 +1458,7 @@ def _confined_ml_numpy(pos, var, frames, use, offsets, dt):
     equal minima), stencil and statuses.  Differs from the kernel in expm1, exp2 and log alone."""
     n = len(offsets) - 1
     out = {k: np.full((n, 2) if k.startswith("centre") else n, np.nan) for k in _CF_OUTS[:10]}
-    rows = _confined_rows(pos, var, frames, use, offsets)
+    rows = _ml_usable(pos, var, frames, use, offsets)
     n_inc = np.array([max(len(r) - 1, 0) for r in rows], np.int32).reshape(n)
     status = np.ones(n, np.int32)
     sel = np.nonzero(n_inc >= _CF_MIN_INCREMENTS)[0]
@@ -1466,15 +1467,11 @@ def _confined_ml_numpy(pos, var, frames, use, offsets, dt):
     sel = sel[np.argsort(-n_inc[sel], kind="stable")]
     inc = n_inc[sel].astype(np.int64)
     ns = len(sel)
-    X, V, Fr = _confined_rows(pos, var, frames, use, offsets, sel)
-    Mx = X.shape[1]
+    X, V, Fr = _ml_padded(rows, sel, pos, var, frames, offsets)
     d, g = X[:, 1:] - X[:, :-1], Fr[:, 1:] - Fr[:, :-1]
-    live = np.arange(Mx - 1)[None, :] < inc[:, None]
-    rlive = np.arange(Mx)[None, :] <= inc[:, None]
+    rlive = np.arange(X.shape[1])[None, :] <= inc[:, None]
     with np.errstate(all="ignore"):
-        S = np.cumsum(np.where(live, d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1], 0.0), axis=1)[:, -1]
-        G = np.where(live, g, 0).sum(axis=1)
-        D_ref = S / ((4.0 * dt) * G.astype(np.float64))
+        D_ref = _ml_d_ref(d, g, inc, dt)
         cnt = (inc + 1).astype(np.float64)
         mean = np.cumsum(np.where(rlive[..., None], X, 0.0), axis=1)[:, -1] / cnt[:, None]
         dev = X - mean[:, None, :]
@@ -1504,12 +1501,8 @@ def _confined_ml_numpy(pos, var, frames, use, offsets, dt):
         Ss = Sb[:, None] * np.tile(fD, 3)[None, :]
         c, cen, hh = _confined_cost(Ds, Ss, X, V, g, inc, dt)
         c0 = c[:, 4]
-        Hdd = ((c[:, 7] - c0) + (c[:, 1] - c0)) * 2048.0
-        Hss = ((c[:, 5] - c0) + (c[:, 3] - c0)) * 2048.0
-        Hds = ((c[:, 8] - c[:, 6]) - (c[:, 2] - c[:, 0])) * 512.0
-        det = Hdd * Hss - Hds * Hds
+        Hdd, Hss, Hds, det, pd = _ml_hessian(c)                            # u = ln D, v = ln s2
         st = np.where(~(c0 < np.inf), 4, st).astype(np.int32)
-        pd = (Hdd > 0.0) & (Hss > 0.0) & (det > 0.0) & (det < np.inf)
         st = np.where(~pd & (st == 0), 4, st).astype(np.int32)
         radius = np.sqrt(2.0 * Sb)
         vl = ((Hss + Hdd) + 2.0 * Hds) / det
@@ -1532,16 +1525,6 @@ def _confined_ml_numpy(pos, var, frames, use, offsets, dt):
     return tuple(out[k] for k in _CF_OUTS[:10]) + (n_inc, status)
 
 
-def _cf_per_range(v, n, what, device, width=None):
-    v = v.detach().to(device, torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64), device=device)
-    shape = (n,) if width is None else (n, width)
-    if v.dim() == (0 if width is None else 1) and (width is None or tuple(v.shape) == (width,)):
-        v = v.expand(*shape)
-    if tuple(v.shape) != shape:
-        raise ValueError(f"{what} must be {'a number' if width is None else f'[{width}]'} or {list(shape)}, got {tuple(v.shape)}")
-    return v.contiguous()
-
-
 def confined_loglik(positions, offsets, D, s2, centre=None, variances=None, frames=None, use=None, dt=1.0):
     """The exact log-likelihood of every range under confined diffusion, an isotropic Ornstein-Uhlenbeck process with the
     diffusion coefficient D and the stationary variance per axis s2 = radius^2 / 2 (numbers, or one per range [n]) about a
@@ -1551,19 +1534,14 @@ def confined_loglik(positions, offsets, D, s2, centre=None, variances=None, fram
     is not positive and finite, -inf where an innovation variance is not positive).  The exposure is INSTANTANEOUS: motion
     blur is not modelled.  The other arguments are those of estimate_diffusion_ml.  CUDA tensors go to the kernel
     (csrc/confined_ml.hip), arrays and CPU tensors to the numpy restatement."""
-    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
-    n = off.numel() - 1
-    Dv, Sv = _cf_per_range(D, n, "D", pos.device), _cf_per_range(s2, n, "s2", pos.device)
-    cv = None if centre is None else _cf_per_range(centre, n, "centre", pos.device, 2)
-    if pos.device.type == "cuda":
-        from .. import ops
-        ll = ops.track_confined_loglik(pos, off.int().contiguous(), Dv, Sv, cv, var, None if fr is None else fr.int().contiguous(),
-                                       usable, float(dt))
-        return {"loglik": ll}
-    ll = _confined_loglik_numpy(pos.numpy(), None if var is None else var.numpy(), None if fr is None else fr.numpy(),
-                                None if usable is None else usable.numpy(), off.numpy(), float(dt), Dv.numpy(), Sv.numpy(),
-                                None if cv is None else cv.numpy())
-    return {"loglik": torch.from_numpy(ll) if is_t else ll}
+    args = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    n, device = args[2].numel() - 1, args[1].device
+    Dv, Sv = _ml_per_range(D, n, "D", device), _ml_per_range(s2, n, "s2", device)
+    cv = None if centre is None else _ml_per_range(centre, n, "centre", device, 2)
+    return _ml_dispatch(args,
+                        lambda ops, pos, off, var, fr, usable: ops.track_confined_loglik(pos, off, Dv, Sv, cv, var, fr, usable, float(dt)),
+                        lambda *rows: _confined_loglik_numpy(*rows, float(dt), Dv.numpy(), Sv.numpy(), None if cv is None else cv.numpy()),
+                        ("loglik",))
 
 
 def estimate_confinement_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0):
@@ -1595,23 +1573,10 @@ def estimate_confinement_ml(positions, offsets, variances=None, frames=None, use
     on tracks of 100 rows that span 30 relaxation times the mean pull of ln radius is about -0.5.  CUDA tensors go to the kernel
     (csrc/confined_ml.hip: one wave per track, no limit on its length), arrays and CPU tensors to the numpy restatement, which
     differs from it in expm1, exp2 and log alone."""
-    is_t, pos, off, var, fr, usable = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    args = _ml_arguments(positions, offsets, variances, frames, use, dt)
     brownian = estimate_diffusion_ml(positions, offsets, variances, frames, use, dt, blur=0.0)["loglik"]
-    if pos.device.type == "cuda":
-        from .. import ops
-        out = dict(zip(_CF_OUTS, ops.track_confined_ml(pos, off.int().contiguous(), var, None if fr is None else fr.int().contiguous(),
-                                                       usable, float(dt))))
-        out["n_increments"], out["status"] = out["n_increments"].long(), out["status"].long()
-    else:
-        out = dict(zip(_CF_OUTS, _confined_ml_numpy(pos.numpy(), None if var is None else var.numpy(),
-                                                    None if fr is None else fr.numpy(),
-                                                    None if usable is None else usable.numpy(), off.numpy(), float(dt))))
-        out["n_increments"], out["status"] = out["n_increments"].astype(np.int64), out["status"].astype(np.int64)
-        if is_t:
-            out = {k: torch.from_numpy(v) for k, v in out.items()}
-    if is_t:
+    out = _ml_dispatch(args, lambda ops, pos, off, var, fr, usable: ops.track_confined_ml(pos, off, var, fr, usable, float(dt)),
+                       lambda *rows: _confined_ml_numpy(*rows, float(dt)), _CF_OUTS)
+    with np.errstate(invalid="ignore"):                                    # arrays: -inf - -inf where no candidate was accepted
         out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
-    else:
-        with np.errstate(invalid="ignore"):                                # -inf - -inf where no candidate was accepted
-            out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
     return out

@@ -1138,16 +1138,10 @@ def hmm_viterbi(pos: torch.Tensor, offsets: torch.Tensor, v: torch.Tensor, A: to
     return state, logp
 
 
-def track_diffusion_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0,
-                       blur: float = 0.0):
-    """The maximum-likelihood diffusion coefficient of every row range with its standard error (csrc/likelihood.hip,
-    mivit_track_diffusion_ml): pos [N, 2] float64 on the GPU (y, x); offsets [n + 1] int32 (CSR, from 0 to N: tracks, segments
-    or runs); var [N, 2] float64, the variance of every coordinate (None: zeros); frames [N] int32, rising within a range
-    (None: consecutive); use [N] bool or uint8 (None: every row); blur the motion-blur coefficient R in [0, 1/4] -> (D, D_std,
-    loglik [n] float64, n_increments, status [n] int32).  A range has no maximum length.  offsets are read back to be
-    checked: every rejection is a ValueError before any launch.  See include/mivit_hip.h for the arithmetic and the status
-    codes and helpers/msd.estimate_diffusion_ml for the front end."""
-    name = "track_diffusion_ml"
+def _track_ml_args(name, pos, offsets, var, frames, use, dt, check=None):
+    """The checks that the per-track maximum-likelihood fits share (track_diffusion_ml, track_fbm_*, track_confined_*): shapes,
+    dtypes, one device, dt, then `check()`, the caller's own checks of its scalars, and last the offsets, which are read back
+    -> (pos, offsets, var, frames, use, N, n)"""
     pos = _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
     offsets = _seg_tensor(offsets, torch.int32, 1, name, "offsets [n + 1]")
     if pos.shape[1] != 2:
@@ -1177,14 +1171,33 @@ def track_diffusion_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frame
         raise ValueError(f"{name}: all tensors must be on one device")
     if not 0.0 < float(dt) < float("inf"):
         raise ValueError(f"{name}: dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(blur) <= 0.25:
-        raise ValueError(f"{name}: the blur coefficient must lie in [0, 1/4], got {blur}")
+    if check is not None:
+        check(n)
     if n:
         off = offsets.cpu()
         if int(off[0]) != 0 or int(off[-1]) != n_rows or bool((off[1:] < off[:-1]).any()):
             raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
     elif n_rows:
         raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
+    return pos, offsets, var, frames, use, n_rows, n
+
+
+def track_diffusion_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0,
+                       blur: float = 0.0):
+    """The maximum-likelihood diffusion coefficient of every row range with its standard error (csrc/likelihood.hip,
+    mivit_track_diffusion_ml): pos [N, 2] float64 on the GPU (y, x); offsets [n + 1] int32 (CSR, from 0 to N: tracks, segments
+    or runs); var [N, 2] float64, the variance of every coordinate (None: zeros); frames [N] int32, rising within a range
+    (None: consecutive); use [N] bool or uint8 (None: every row); blur the motion-blur coefficient R in [0, 1/4] -> (D, D_std,
+    loglik [n] float64, n_increments, status [n] int32).  A range has no maximum length.  offsets are read back to be
+    checked: every rejection is a ValueError before any launch.  See include/mivit_hip.h for the arithmetic and the status
+    codes and helpers/msd.estimate_diffusion_ml for the front end."""
+    name = "track_diffusion_ml"
+
+    def check(n):
+        if not 0.0 <= float(blur) <= 0.25:
+            raise ValueError(f"{name}: the blur coefficient must lie in [0, 1/4], got {blur}")
+
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt, check)
     D, D_std, loglik = (torch.empty(n, dtype=torch.float64, device=pos.device) for _ in range(3))
     n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
     N.check(N.lib.mivit_track_diffusion_ml(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt),
@@ -1198,48 +1211,14 @@ FBM_ML_MAX_SPAN = 1199       # csrc/fbm_ml.hip: largest - smallest usable frame 
 FBM_ML_WS_BYTES = 640        # csrc/fbm_ml.hip: workspace of mivit_track_fbm_ml per range
 
 
-def _fbm_ml_args(name, pos, offsets, var, frames, use, dt, exposure):
-    """the checks track_fbm_loglik and track_fbm_ml share (those of track_diffusion_ml) -> (pos, offsets, var, frames, use, N, n)"""
-    pos = _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
-    offsets = _seg_tensor(offsets, torch.int32, 1, name, "offsets [n + 1]")
-    if pos.shape[1] != 2:
-        raise ValueError(f"{name}: pos must be [N, 2], got {tuple(pos.shape)}")
-    if offsets.numel() < 1:
-        raise ValueError(f"{name}: offsets must have n + 1 entries")
-    n_rows, n = pos.shape[0], offsets.numel() - 1
-    given = [pos, offsets]
-    if var is not None:
-        var = _seg_tensor(var, torch.float64, 2, name, "var [N, 2]")
-        if tuple(var.shape) != (n_rows, 2):
-            raise ValueError(f"{name}: var must be [{n_rows}, 2], got {tuple(var.shape)}")
-        given.append(var)
-    if frames is not None:
-        frames = _seg_tensor(frames, torch.int32, 1, name, "frames [N]")
-        if frames.numel() != n_rows:
-            raise ValueError(f"{name}: frames must be [{n_rows}], got {tuple(frames.shape)}")
-        given.append(frames)
-    if use is not None:
-        if torch.is_tensor(use) and use.dtype == torch.bool:
-            use = use.view(torch.uint8)
-        use = _seg_tensor(use, torch.uint8, 1, name, "use [N] (bool or uint8)")
-        if use.numel() != n_rows:
-            raise ValueError(f"{name}: use must be [{n_rows}], got {tuple(use.shape)}")
-        given.append(use)
-    if len({t.device for t in given}) != 1:
-        raise ValueError(f"{name}: all tensors must be on one device")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"{name}: dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(exposure) <= 1.0:
-        raise ValueError(f"{name}: the exposure must lie in [0, 1], got {exposure}")
-    if n > 1 << 24:
-        raise ValueError(f"{name}: {n} ranges, at most {1 << 24} in one call")
-    if n:
-        off = offsets.cpu()
-        if int(off[0]) != 0 or int(off[-1]) != n_rows or bool((off[1:] < off[:-1]).any()):
-            raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
-    elif n_rows:
-        raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n_rows}")
-    return pos, offsets, var, frames, use, n_rows, n
+def _fbm_ml_check(name, exposure):
+    """the checks of their own that track_fbm_loglik and track_fbm_ml hand to _track_ml_args"""
+    def check(n):
+        if not 0.0 <= float(exposure) <= 1.0:
+            raise ValueError(f"{name}: the exposure must lie in [0, 1], got {exposure}")
+        if n > 1 << 24:
+            raise ValueError(f"{name}: {n} ranges, at most {1 << 24} in one call")
+    return check
 
 
 def track_fbm_loglik(pos: torch.Tensor, offsets: torch.Tensor, alpha: torch.Tensor, D: torch.Tensor, var=None, frames=None,
@@ -1250,7 +1229,8 @@ def track_fbm_loglik(pos: torch.Tensor, offsets: torch.Tensor, alpha: torch.Tens
     n_increments, status [n] int32).  A range may have at most FBM_ML_MAX_ROWS usable rows over at most FBM_ML_MAX_SPAN frames
     (status 5).  See include/mivit_hip.h for the arithmetic and the status codes and helpers/msd.fbm_loglik for the front end."""
     name = "track_fbm_loglik"
-    pos, offsets, var, frames, use, n_rows, n = _fbm_ml_args(name, pos, offsets, var, frames, use, dt, exposure)
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt,
+                                                               _fbm_ml_check(name, exposure))
     alpha = _seg_tensor(alpha, torch.float64, 1, name, "alpha [n]")
     D = _seg_tensor(D, torch.float64, 1, name, "D [n]")
     if alpha.numel() != n or D.numel() != n or alpha.device != pos.device or D.device != pos.device:
@@ -1270,7 +1250,8 @@ def track_fbm_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None
     range) is allocated here.  A range may have at most FBM_ML_MAX_ROWS usable rows over at most FBM_ML_MAX_SPAN frames (status
     5).  See include/mivit_hip.h for the arithmetic and the status codes and helpers/msd.estimate_anomalous_ml for the front end."""
     name = "track_fbm_ml"
-    pos, offsets, var, frames, use, n_rows, n = _fbm_ml_args(name, pos, offsets, var, frames, use, dt, exposure)
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt,
+                                                               _fbm_ml_check(name, exposure))
     outs = [torch.empty(n, dtype=torch.float64, device=pos.device) for _ in range(6)]
     n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
     ws = torch.empty(max(n, 1) * FBM_ML_WS_BYTES // 8, dtype=torch.float64, device=pos.device)
@@ -1278,11 +1259,6 @@ def track_fbm_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None
                                      *(_p(o) for o in outs), _p(n_inc), _p(status), _p(ws), ws.numel() * 8, _s(pos)),
             "mivit_track_fbm_ml")
     return (*outs, n_inc, status)
-
-
-def _confined_ml_args(name, pos, offsets, var, frames, use, dt):
-    """the checks track_confined_ml and track_confined_loglik share: those of track_fbm_ml at exposure 0"""
-    return _fbm_ml_args(name, pos, offsets, var, frames, use, dt, 0.0)
 
 
 def track_confined_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0):
@@ -1294,7 +1270,7 @@ def track_confined_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames
     length.  See include/mivit_hip.h for the arithmetic and the status codes and helpers/msd.estimate_confinement_ml for the
     front end."""
     name = "track_confined_ml"
-    pos, offsets, var, frames, use, n_rows, n = _confined_ml_args(name, pos, offsets, var, frames, use, dt)
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt)
     f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=pos.device)         # noqa: E731
     outs = [f64(n) for _ in range(7)] + [f64(n, 2), f64(n, 2), f64(n)]
     n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
@@ -1312,7 +1288,7 @@ def track_confined_loglik(pos: torch.Tensor, offsets: torch.Tensor, D: torch.Ten
     -inf for a rejected candidate).  The exposure is instantaneous.  See include/mivit_hip.h for the arithmetic and
     helpers/msd.confined_loglik for the front end."""
     name = "track_confined_loglik"
-    pos, offsets, var, frames, use, n_rows, n = _confined_ml_args(name, pos, offsets, var, frames, use, dt)
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt)
     D = _seg_tensor(D, torch.float64, 1, name, "D [n]")
     s2 = _seg_tensor(s2, torch.float64, 1, name, "s2 [n]")
     if D.numel() != n or s2.numel() != n or D.device != pos.device or s2.device != pos.device:

@@ -33,7 +33,8 @@ def device_asm(src, extra=()):
     from moleculardiffusion_mivit_amd.csrc import build as b
     out = os.path.join(tempfile.gettempdir(), "mivit_isa_" + os.path.basename(src).replace(".hip", "".join(extra).replace("-D", "_") + ".s"))
     srcp = os.path.join(CSRC, src)
-    deps = [srcp, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "stream_prims.h"), os.path.join(CSRC, "elem.h"), b.__file__]
+    deps = [srcp, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "stream_prims.h"), os.path.join(CSRC, "elem.h"),
+            os.path.join(CSRC, "track_ml.h"), b.__file__]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         cmd = [b._hipcc()] + b.FLAGS + list(extra) + ["--cuda-device-only", "-S", srcp, "-o", out]
         r = subprocess.run(cmd, capture_output=True, text=True)

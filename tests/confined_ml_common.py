@@ -4,6 +4,8 @@ first row, np.linalg.slogdet and solve), a drawer of tracks from the exact discr
 ranges on which the kernel (csrc/confined_ml.hip) is held against the numpy restatement."""
 import numpy as np
 
+from likelihood_common import close, usable_rows  # noqa: F401  (one home; the tests reach them through this module)
+
 LOGLIK_BAR = 1e-9             # the restatement against the dense statement, relative (as fbm_ml_common.LOGLIK_BAR)
 NESTING_BAR = 1e-8            # the log-likelihood at s2 = 1e9 D against estimate_diffusion_ml(blur=0), relative
 SEARCH_LOSS_BAR = 1e-5        # -2 log L that the fixed search may lose to a polish of the dense likelihood
@@ -179,21 +181,3 @@ def batch():
             "D": np.array(Ds), "s2": np.array(S2s), "centre": np.ascontiguousarray(np.array(cens))}
 
 
-def usable_rows(b, k):
-    """(X, v, f) of the usable rows of range k of a batch"""
-    a, e = int(b["offsets"][k]), int(b["offsets"][k + 1])
-    with np.errstate(invalid="ignore"):
-        ok = b["use"][a:e] & np.isfinite(b["pos"][a:e]).all(1) & ((b["var"][a:e] >= 0) & (b["var"][a:e] < np.inf)).all(1)
-    return b["pos"][a:e][ok], b["var"][a:e][ok], b["frames"][a:e][ok].astype(np.int64)
-
-
-def close(tol, relative=True):
-    """equal where both are NaN, both the same infinity or exactly equal; within tol (relative or absolute) elsewhere"""
-    def check(got, want, what=""):
-        got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN in other places"
-        with np.errstate(invalid="ignore", divide="ignore"):
-            err = np.abs(got - want) / (np.abs(want) if relative else 1.0)
-            err = np.where((got == want) | np.isnan(want), 0.0, err)
-        assert err.max(initial=0.0) <= tol, f"{what}: worst difference {err.max():.3g} > {tol:g} at {int(err.argmax())}"
-    return check

@@ -11,6 +11,8 @@ from decimal import Decimal, getcontext
 
 import numpy as np
 
+from likelihood_common import close, usable_rows  # noqa: F401  (one home; the tests reach them through this module)
+
 BARS = {"alpha": 1e-4, "D": 1e-3, "loglik": 1e-5, "alpha_std": 1e-2, "D_std": 1e-2}
 LOGLIK_BAR = 1e-9             # against the dense statement, relative
 
@@ -173,21 +175,3 @@ def batch():
             "alpha": np.array(alphas), "D": np.array(Ds)}
 
 
-def usable_rows(b, k):
-    """(X, v, f) of the usable rows of range k of a batch"""
-    a, e = int(b["offsets"][k]), int(b["offsets"][k + 1])
-    with np.errstate(invalid="ignore"):
-        ok = b["use"][a:e] & np.isfinite(b["pos"][a:e]).all(1) & ((b["var"][a:e] >= 0) & (b["var"][a:e] < np.inf)).all(1)
-    return b["pos"][a:e][ok], b["var"][a:e][ok], b["frames"][a:e][ok].astype(np.int64)
-
-
-def close(tol, relative=True):
-    """equal where both are NaN, both the same infinity or exactly equal; within tol (relative or absolute) elsewhere"""
-    def check(got, want, what=""):
-        got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN in other places"
-        with np.errstate(invalid="ignore", divide="ignore"):
-            err = np.abs(got - want) / (np.abs(want) if relative else 1.0)
-            err = np.where((got == want) | np.isnan(want), 0.0, err)
-        assert err.max(initial=0.0) <= tol, f"{what}: worst difference {err.max():.3g} > {tol:g} at {int(err.argmax())}"
-    return check

@@ -122,12 +122,21 @@ def batch():
             "offsets": np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64), "names": names}
 
 
-def close(rtol):
-    """equal where both are NaN, both the same infinity or exactly equal; within rtol relative elsewhere"""
+def usable_rows(b, k):
+    """(X, v, f) of the usable rows of range k of a batch (this one's, or that of fbm_ml_common or confined_ml_common)"""
+    a, e = int(b["offsets"][k]), int(b["offsets"][k + 1])
+    with np.errstate(invalid="ignore"):
+        ok = b["use"][a:e] & np.isfinite(b["pos"][a:e]).all(1) & ((b["var"][a:e] >= 0) & (b["var"][a:e] < np.inf)).all(1)
+    return b["pos"][a:e][ok], b["var"][a:e][ok], b["frames"][a:e][ok].astype(np.int64)
+
+
+def close(tol, relative=True):
+    """equal where both are NaN, both the same infinity or exactly equal; within tol (relative or absolute) elsewhere"""
     def check(got, want, what=""):
         got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
         assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN in other places"
         with np.errstate(invalid="ignore", divide="ignore"):
-            rel = np.where((got == want) | np.isnan(want), 0.0, np.abs(got - want) / np.abs(want))
-        assert rel.max(initial=0.0) <= rtol, f"{what}: worst relative difference {rel.max():.3g} > {rtol:g} at {int(rel.argmax())}"
+            err = np.abs(got - want) / (np.abs(want) if relative else 1.0)
+            err = np.where((got == want) | np.isnan(want), 0.0, err)
+        assert err.max(initial=0.0) <= tol, f"{what}: worst difference {err.max():.3g} > {tol:g} at {int(err.argmax())}"
     return check

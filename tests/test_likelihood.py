@@ -216,3 +216,56 @@ def test_argument_errors():
         T.estimate_track_diffusion(movie, None, 4, ml={"sigma2": "crlb"})
     with pytest.raises(ValueError, match="CUDA movie"):
         T.estimate_track_diffusion(movie, None, 4, ml={})
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the pieces that the maximum-likelihood fits share (helpers/msd._ml_usable, _ml_hessian; csrc/track_ml.h for the kernels)
+# ----------------------------------------------------------------------------------------------------------------------
+def test_the_usable_row_rule_row_by_row():
+    """_ml_usable against the rule stated one row at a time: 40 rows that hold every way a row can be unusable, three ranges
+    of which one is empty, and var, frames and use each left out in turn"""
+    N = 40
+    pos = np.stack([10.0 + 0.25 * np.arange(N), 50.0 - 0.5 * np.arange(N)], axis=1)
+    var, use, frames = np.full((N, 2), 0.01), np.ones(N, bool), 3 * np.arange(N)
+    use[[1, 23]] = False
+    pos[3, 0], pos[4, 1], pos[23, 0] = np.nan, np.nan, np.nan
+    pos[6, 0], pos[7, 1], pos[8, 0], pos[9, 1] = np.inf, -np.inf, -np.inf, np.inf
+    var[11, 0], var[12, 1], var[25, 0] = -1e-3, -1e-300, -np.inf
+    var[14, 0], var[15, 1] = np.nan, np.nan
+    var[17, 0], var[18, 1] = np.inf, np.inf
+    var[20, 0], var[21, 1] = -0.0, -0.0                                     # usable: -0.0 >= 0
+    var[30], var[31, 1] = 0.0, 1e300                                       # usable
+    offsets = np.array([0, 16, 16, N])
+    by_flag, by_pos, by_var = {1, 23}, {3, 4, 6, 7, 8, 9, 23}, {11, 12, 14, 15, 17, 18, 25}
+
+    def rule(r, var, use):
+        if use is not None and not use[r]:
+            return False
+        if not (abs(float(pos[r, 0])) < float("inf") and abs(float(pos[r, 1])) < float("inf")):
+            return False
+        return var is None or all(0.0 <= float(v) < float("inf") for v in var[r])
+
+    for v, f, u, out in ((var, frames, use, by_flag | by_pos | by_var), (None, frames, use, by_flag | by_pos),
+                         (var, None, use, by_flag | by_pos | by_var), (var, frames, None, by_pos | by_var)):
+        got = M._ml_usable(pos, v, f, u, offsets)
+        assert len(got) == 3 and len(got[1]) == 0
+        for k, rows in enumerate(got):
+            assert rows.dtype.kind == "i"
+            want = [r for r in range(int(offsets[k]), int(offsets[k + 1])) if rule(r, v, u)]
+            assert rows.tolist() == want, (k, rows.tolist(), want)
+        assert sorted(set(range(N)) - set(np.concatenate(got).tolist())) == sorted(out)       # the rule itself is the one meant
+
+
+def test_the_hessian_of_an_exact_quadratic():
+    """_ml_hessian on a u^2 + b v^2 + c u v + d sampled at the stencil's points with h = 1 / 64: with dyadic a, b, c every
+    difference is exact, so the entries are a, b and c / 2 to the bit"""
+    h = 1.0 / 64.0
+    quads = [(1.5, 0.75, -0.5, 1000.0), (0.25, 3.0, 1.0, -7.0), (-0.5, 2.0, 0.25, 0.0), (1.0, 1.0, 2.0, 3.0)]
+    c = np.array([[a * u * u + b * v * v + m * u * v + d for u in (-h, 0.0, h) for v in (-h, 0.0, h)] for a, b, m, d in quads])
+    uu, vv, uv, det, pd = M._ml_hessian(c)
+    for i, (a, b, m, d) in enumerate(quads):
+        want = np.array([a, b, 0.5 * m, a * b - (0.5 * m) * (0.5 * m)])
+        assert np.array([uu[i], vv[i], uv[i], det[i]]).tobytes() == want.tobytes(), (i, uu[i], vv[i], uv[i], det[i])
+        one = M._ml_hessian(c[i])                                          # one range: the fit of the anomalous exponent
+        assert np.array(one[:4]).tobytes() == want.tobytes() and bool(one[4]) == bool(pd[i])
+    assert pd.tolist() == [True, True, False, False]                       # a < 0; det = 0
