@@ -298,6 +298,44 @@ int mivit_dog_peaks(const float *movie, int F, int H, int W, const double *w1, i
                     float threshold_percentage, int min_distance, int cap, int *count, int *n_candidates, int *coords,
                     float *values, float *dog, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Likelihood-ratio particle detection on the photon-counting camera, csrc/detect.hip: an opt-in detector beside
+ * mivit_dog_peaks, in two stages.  Both take the movie [F, H, W] fp32 in camera units, the camera scalars of mivit_fit_spots_mle
+ * (d = max((adu - offset) / gain, 0) + read_var; gain > 0, read_var >= 0, finite) and e: a HOST array of 2 r + 1 fp64 values,
+ * e[k + r] the pixel-integrated Gaussian profile at offset k from a pixel centre (each in (0, 1]), 1 <= r <= 7, H, W > r.  The
+ * template is g(dy, dx) = e[dy] e[dx] and the window of a pixel is the in-frame pixels with |dy|, |dx| <= r (clipped).
+ *
+ * mivit_score_peaks: the score (Rao) statistic of every pixel.  Column pass A = sum e[dy] d, B = sum d over ascending dy, row
+ * pass Sgd = sum e[dx] A, Sd = sum B over ascending dx; per axis the count, sum e and sum e^2 of the valid offsets in ascending
+ * order, n = ny nx, Sg = gy gx, Sgg = qy qx; mu0 = Sd / n, U = Sgd - mu0 Sg, V = mu0 (Sgg - Sg Sg / n),
+ * S = U > 0 && V > 0 ? U U / V : 0, all fp64 in this order without contraction, S stored as fp32.  Candidates by the rule of
+ * mivit_dog_peaks with the absolute `threshold` (finite, >= 0) in place of threshold_percentage * max: a maximum of its clipped
+ * (2 min_distance + 1)^2 window strictly above the threshold, none in a frame whose pixels are all equal, ordered by value
+ * descending and row-major index ascending, kept greedily at Chebyshev distance > min_distance (1 .. 16).  cap (1 .. 2048),
+ * count, n_candidates, coords, values and the workspace as mivit_dog_peaks; map [F, H, W] fp32 or NULL (it then lives in the
+ * workspace: mivit_score_peaks_workspace_bytes(F, H, W, cap, map != NULL)).
+ *
+ * mivit_lrt_peaks: the exact Poisson likelihood ratio at the candidates count_in [F] / coords_in [F, cap, 2] / values_in
+ * [F, cap] that mivit_score_peaks left.  One wave per frame, one lane per candidate.  Over the window row-major: n, Sd, Sgd,
+ * Sg, Sgg, then mu0, U and den = Sgg - Sg Sg / n as above; a candidate without U, den, mu0 > 0 has T = 0.  Otherwise
+ * mu_k = theta g_k + beta is fitted by the damped loop of mivit_fit_spots_mle (lambda schedule, slack 1e-13 of 2 sum(mu + d),
+ * stopping rule on the undamped step at 1e-11 of max(|theta|, |beta|), 100 iterations) on the 2 x 2 Fisher matrix from
+ * theta = U / den, beta = mu0 - theta Sg / n (where that beta is not positive: beta = mu0 / 1000, theta = (Sd - n beta) / Sg);
+ * a trial point with theta <= 0 or a pixel with mu <= 0 is rejected.  T = max(0, 2 sum d log(mu / mu0) - 2 (sum mu - Sd)) with
+ * 0 log = 0.  A candidate is kept when T > threshold and the kept ones are compacted per frame in their order.  out: count [F]
+ * int32, coords [F, cap, 2] int32, stats [F, cap, 4] fp64 (T, photons = theta, background = beta - read_var, the stage-1 S),
+ * status [F, cap] int32: 0 converged, 1 damping exhausted, 2 iteration cap (T is then that of the last accepted point, a lower
+ * bound).  Entries beyond count are not written; the outputs must not alias the inputs.  A candidate outside the frame is
+ * dropped and count_in is read as at most cap.
+ *
+ * Arguments are validated before any HIP call; F = 0 is a no-op.  The movie must be finite. */
+size_t mivit_score_peaks_workspace_bytes(int F, int H, int W, int cap, int store_map);
+int mivit_score_peaks(const float *movie, int F, int H, int W, const double *e, int r, double gain, double offset,
+                      double read_var, float threshold, int min_distance, int cap, int *count, int *n_candidates, int *coords,
+                      float *values, float *map, void *workspace, size_t workspace_bytes, void *stream);
+int mivit_lrt_peaks(const float *movie, int F, int H, int W, const double *e, int r, double gain, double offset,
+                    double read_var, double threshold, int cap, const int *count_in, const int *coords_in,
+                    const float *values_in, int *count, int *coords, double *stats, int *status, void *stream);
+
 /* Sub-pixel localisation: the five-parameter fit inside the reference's add_refined_localization_to_dataframe
  * (helpers/helpersTracking.py:555-604, one scipy.optimize.curve_fit per patch), csrc/tracking.hip, one thread per patch.
  * patches [N, P, P] fp32, P odd, 3 .. 15.  Model offset + amplitude exp(-((x - x0)^2 + (y - y0)^2) / (2 sigma^2)) on the

@@ -139,6 +139,11 @@ SYMBOLS = {
     "mivit_dog_peaks_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "mivit_dog_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mivit_score_peaks_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "mivit_score_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [ctypes.c_double] * 3
+                          + [c_float, c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "mivit_lrt_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [ctypes.c_double] * 4 + [c_int]
+                        + [c_void_p] * 8),
     "mivit_refine_gaussian": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mivit_fit_spots_mle": (c_int, [c_void_p, c_int, c_int] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double] + [c_void_p] * 6),
     "mivit_fit_spots_mle2": (c_int, [c_void_p] * 3 + [c_int, c_int] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double]

@@ -3,7 +3,7 @@
 // scipy.ndimage.gaussian_filter calls + skimage.feature.peak_local_max per frame) and the scipy.optimize.curve_fit inside
 // add_refined_localization_to_dataframe (:555-604).  Linking is in csrc/linking.hip.
 //
-// mivit_dog_peaks, four launches whatever the frame count:
+// mivit_dog_peaks, four launches whatever the frame count (kernels 1, 3 and 4 are in csrc/peaks.h, shared with csrc/detect.hip):
 //   1. tk_init_kernel    per frame: max / min keys and the candidate counter.
 //   2. tk_dog_kernel     one workgroup per 16 x 64 tile of a frame.  The tile and a halo of radius(sigma2) pixels (indices
 //                        reflected as scipy's 'reflect' mode does, d c b a | a b c d | d c b a) go to LDS once; the axis-0 pass
@@ -31,23 +31,14 @@
 #pragma clang fp contract(off)
 
 #include "common.h"
+#include "peaks.h"
 
 namespace {
 
 constexpr int TK_MAX_RADIUS = 16;     // int(4 sigma + 0.5) of the wider Gaussian
-constexpr int TK_TX = 64, TK_TY = 16; // tile of one workgroup (256 threads)
-constexpr int TK_MAX_MIN_DISTANCE = 16;
-constexpr int TK_MAX_CAP = 2048;      // candidates per frame: 8-byte keys + kept (y, x) in LDS, 32 KiB
 constexpr int RG_MAX_P = 15;
 constexpr int RG_MAX_ITER = 100;
 constexpr double RG_COST_SLACK = 1.0 + 1e-13;
-
-// float <-> int whose signed order is the float order (no NaN in a filtered finite movie)
-__device__ __forceinline__ int ordered_key(float v) {
-    const int i = __float_as_int(v);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ordered_value(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
 
 // scipy 'reflect' (half-sample symmetric), one reflection; clamped so that rows / columns of a tile that lie outside the frame
 // (their results are discarded) still read inside it
@@ -64,14 +55,6 @@ struct DogArgs {
     int H, W, r1, r2, tiles_x, tiles_y;
     double w1[TK_MAX_RADIUS + 1], w2[TK_MAX_RADIUS + 1];   // w[0] centre, w[k] weight at distance k
 };
-
-__global__ __launch_bounds__(256) void tk_init_kernel(int *maxkey, int *minkey, int *ncand, int F) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    maxkey[f] = INT32_MIN;
-    minkey[f] = INT32_MAX;
-    ncand[f] = 0;
-}
 
 __global__ __launch_bounds__(256) void tk_dog_kernel(const DogArgs a) {
     extern __shared__ float tk_lds[];
@@ -130,85 +113,6 @@ __global__ __launch_bounds__(256) void tk_dog_kernel(const DogArgs a) {
         atomicMax(a.maxkey + f, smax);
         atomicMin(a.minkey + f, smin);
     }
-}
-
-__global__ __launch_bounds__(256) void tk_mask_kernel(const float *__restrict__ dog, const int *__restrict__ maxkey,
-                                                      const int *__restrict__ minkey, int *ncand,
-                                                      unsigned long long *cand, int64_t total, int H, int W, int m, int cap,
-                                                      float threshold_percentage) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= total) return;
-    const int HW = H * W;
-    const int f = (int)(p / HW), idx = (int)(p - (int64_t)f * HW);
-    const int mk = maxkey[f];
-    if (mk == minkey[f]) return;                                          // flat frame: every pixel is a maximum -> none
-    const float thr = threshold_percentage * ordered_value(mk);
-    const float *d = dog + (int64_t)f * HW;
-    const float v = d[idx];
-    if (!(v > thr)) return;
-    const int y = idx / W, x = idx - y * W;
-    const int ya = y - m < 0 ? 0 : y - m, yb = y + m > H - 1 ? H - 1 : y + m;
-    const int xa = x - m < 0 ? 0 : x - m, xb = x + m > W - 1 ? W - 1 : x + m;
-    for (int yy = ya; yy <= yb; ++yy)
-        for (int xx = xa; xx <= xb; ++xx)
-            if (d[yy * W + xx] > v) return;
-    const int slot = atomicAdd(ncand + f, 1);
-    if (slot >= cap) return;                                              // counted, reported, never stored out of bounds
-    const unsigned hi = ~((unsigned)ordered_key(v) ^ 0x80000000u);        // larger value -> smaller key
-    cand[(int64_t)f * cap + slot] = ((unsigned long long)hi << 32) | (unsigned)idx;
-}
-
-__global__ __launch_bounds__(256) void tk_select_kernel(const unsigned long long *__restrict__ cand,
-                                                        const int *__restrict__ ncand, int W, int m, int cap, int n2max,
-                                                        int *count, int *coords, float *values) {
-    extern __shared__ unsigned long long tk_keys[];                       // n2max keys, then cap kept (y, x) pairs
-    __shared__ int nkept;
-    int *kept = reinterpret_cast<int *>(tk_keys + n2max);
-    const int f = blockIdx.x;
-    const int nc = ncand[f];
-    const int n = nc < cap ? nc : cap;
-    int n2 = 1;
-    while (n2 < n) n2 <<= 1;
-    for (int i = threadIdx.x; i < n2; i += blockDim.x) tk_keys[i] = i < n ? cand[(int64_t)f * cap + i] : ~0ull;
-    if (threadIdx.x == 0) nkept = 0;
-    __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += blockDim.x) {
-                const int o = i ^ j;
-                if (o > i) {
-                    const unsigned long long x = tk_keys[i], y = tk_keys[o];
-                    if ((x > y) == ((i & k) == 0)) {
-                        tk_keys[i] = y;
-                        tk_keys[o] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    // greedy spacing in sorted order: keep a candidate unless a kept one lies within Chebyshev distance m
-    for (int i = 0; i < n; ++i) {
-        const unsigned long long key = tk_keys[i];
-        const int idx = (int)(unsigned)(key & 0xffffffffu);
-        const int y = idx / W, x = idx - y * W;
-        const int nk = nkept;
-        int clash = 0;
-        for (int j = threadIdx.x; j < nk; j += blockDim.x) {
-            const int dy = kept[2 * j] - y, dx = kept[2 * j + 1] - x;
-            if ((dy < 0 ? -dy : dy) <= m && (dx < 0 ? -dx : dx) <= m) clash = 1;
-        }
-        clash = __syncthreads_or(clash);
-        if (!clash && threadIdx.x == 0) {
-            kept[2 * nk] = y;
-            kept[2 * nk + 1] = x;
-            coords[((int64_t)f * cap + nk) * 2] = y;
-            coords[((int64_t)f * cap + nk) * 2 + 1] = x;
-            values[(int64_t)f * cap + nk] = ordered_value((int)(~(unsigned)(key >> 32) ^ 0x80000000u));
-            nkept = nk + 1;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) count[f] = nkept;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -323,12 +227,6 @@ __global__ __launch_bounds__(64) void rg_kernel(const float *__restrict__ patche
     status[i] = st;
 }
 
-int next_pow2(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 }  // namespace
 
 extern "C" size_t mivit_dog_peaks_workspace_bytes(int F, int H, int W, int cap, int store_dog) {
@@ -386,7 +284,7 @@ extern "C" int mivit_dog_peaks(const float *movie, int F, int H, int W, const do
     hipLaunchKernelGGL(tk_dog_kernel, dim3((unsigned)tiles), dim3(256), lds, s, a);
     MIVIT_LAUNCH_CHECK();
     hipLaunchKernelGGL(tk_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.dog, a.maxkey, a.minkey,
-                       n_candidates, cand, total, H, W, min_distance, cap, threshold_percentage);
+                       n_candidates, cand, total, H, W, min_distance, cap, threshold_percentage, 0);
     MIVIT_LAUNCH_CHECK();
     const int n2max = next_pow2(cap);
     hipLaunchKernelGGL(tk_select_kernel, dim3((unsigned)F), dim3(256),

@@ -12,7 +12,9 @@ per frame pair: by default (linking="host") scipy's, in a loop over the frames o
 linking="device" all frame pairs of a movie are solved in one launch of csrc/linking.hip and the track ids are chained on the
 device (link_particles_movie, chain_tracks, track_particles_tensors); with max_gap > 0 the end of a track is then linked to the
 start of a later one across up to max_gap missed frames (close_gaps_movie) and the missed frames become rows with an
-interpolated position (fill_gaps), so that every track stays contiguous in frames.  Movies are filtered as float32.  pandas and scipy are only
+interpolated position (fill_gaps), so that every track stays contiguous in frames.  Beside the reference's detector stands a
+likelihood-ratio detector on the photon-counting camera model with a per-pixel false-alarm probability
+(detect_particles_lrt_movie, csrc/detect.hip; detector={"method": "lrt", ...} on the tracking functions).  Movies are filtered as float32.  pandas and scipy are only
 imported by the functions that need them: detect_particles_movie, track_particles_flat, extract_patches_flat and
 refine_localizations need neither pandas nor (except for linking) scipy."""
 import math
@@ -121,10 +123,14 @@ def _window_max(frame, m):
     return v
 
 
-def _peaks_numpy(dog, threshold_percentage, min_distance):
+def _peaks_numpy(dog, threshold_percentage, min_distance, absolute=None):
     """peak_local_max(dog, min_distance, threshold_abs=threshold_percentage * dog.max(), exclude_border=False) of one float32
-    frame -> (coords [n, 2] int64 (y, x), number of candidates before spacing)."""
-    thr = np.float32(threshold_percentage) * dog.max()             # one float32 product, as numpy 2 does it
+    frame -> (coords [n, 2] int64 (y, x), number of candidates before spacing).  absolute: a float32 threshold that takes the
+    place of threshold_percentage * dog.max() (the likelihood-ratio detector)."""
+    if absolute is not None:
+        thr = np.float32(absolute)
+    else:
+        thr = np.float32(threshold_percentage) * dog.max()         # one float32 product, as numpy 2 does it
     mask = dog == _window_max(dog, min_distance)
     if mask.all():                                                 # a flat frame has no peak
         return np.zeros((0, 2), np.int64), 0
@@ -186,6 +192,347 @@ def detect_particles(image, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, mi
         raise ValueError(f"image must be [H, W], got {tuple(image.shape)}; use detect_particles_movie for a movie")
     coords, dog = detect_particles_movie(image[None], sigma1, sigma2, threshold_percentage, min_distance)
     return coords[0], dog[0]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# likelihood-ratio detection on the photon-counting camera (csrc/detect.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+LRT_MAX_RADIUS = 7
+LRT_MAX_PEAKS = 2048
+_DETECTOR_DEFAULTS = {"gain": 1.0, "offset": 0.0, "read_var": 0.0, "sigma0": 1.0, "radius": None, "p_fa": 1e-6}
+
+
+def detection_threshold(p_fa):
+    """The threshold t = z^2, z = -Phi^-1(p_fa), at which a statistic whose square root is a one-sided standard normal under
+    "background only" is exceeded with probability p_fa per pixel; 0 < p_fa <= 0.5."""
+    from statistics import NormalDist
+    p = float(p_fa)
+    if not 0.0 < p <= 0.5:
+        raise ValueError(f"p_fa must lie in (0, 0.5], got {p_fa}")
+    z = -NormalDist().inv_cdf(p)
+    return z * z
+
+
+def psf_profile(sigma0, radius=None):
+    """The pixel-integrated Gaussian of fit_spots_mle centred on a pixel centre: e[i + r] = 1/2 [erf((i + 1/2) / (sqrt(2)
+    sigma0)) - erf((i - 1/2) / (sqrt(2) sigma0))] for i = -r .. r, float64 [2 r + 1]; r = radius, by default ceil(3 sigma0),
+    from 1 to LRT_MAX_RADIUS."""
+    s = float(sigma0)
+    if not (s > 0 and math.isfinite(s)):
+        raise ValueError(f"sigma0 must be finite and > 0, got {sigma0}")
+    r = math.ceil(3.0 * s) if radius is None else radius
+    if int(r) != r or not 1 <= r <= LRT_MAX_RADIUS:
+        raise ValueError(f"radius must be an integer from 1 to {LRT_MAX_RADIUS}, got {r}"
+                         + (f" = ceil(3 sigma0) for sigma0 = {sigma0}" if radius is None else ""))
+    r = int(r)
+    w = _SQRT2 * s
+    e = np.array([0.5 * (math.erf((i + 0.5) / w) - math.erf((i - 0.5) / w)) for i in range(-r, r + 1)], dtype=np.float64)
+    if not e.min() > 0.0:
+        raise ValueError(f"sigma0 = {sigma0} is too small for a radius of {r}: the profile vanishes at its ends")
+    return e
+
+
+def _lrt_axis(n_pix, e):
+    """Count, sum e and sum e^2 over the offsets of the clipped window of every index of one axis, in ascending order."""
+    r = len(e) // 2
+    idx = np.arange(n_pix)
+    n, g, q = np.zeros(n_pix), np.zeros(n_pix), np.zeros(n_pix)
+    for k in range(-r, r + 1):
+        valid = (idx + k >= 0) & (idx + k < n_pix)
+        n = n + valid
+        g = g + np.where(valid, e[k + r], 0.0)
+        q = q + np.where(valid, e[k + r] * e[k + r], 0.0)
+    return n, g, q
+
+
+def _score_numpy(movie32, e, gain=1.0, offset=0.0, read_var=0.0, chunk=16, dtype=np.float32):
+    """The score map of csrc/detect.hip::sc_map_kernel for a float32 movie [F, H, W], bitwise: S = U^2 / V where U, V > 0
+    and 0 elsewhere, float32 (dtype=np.float64: the statistic before that rounding).  Windows are clipped at the frame edge;
+    a pixel outside the frame enters a sum as + 0.0, which leaves every bit of it, so the passes run over a zero-padded
+    copy."""
+    F, H, W = movie32.shape
+    r = len(e) // 2
+    ny, gy, qy = _lrt_axis(H, e)
+    nx, gx, qx = _lrt_axis(W, e)
+    n, Sg, Sgg = ny[:, None] * nx[None, :], gy[:, None] * gx[None, :], qy[:, None] * qx[None, :]
+    out = np.empty(movie32.shape, dtype)
+    for f0 in range(0, F, chunk):
+        d = _mle_data(movie32[f0:f0 + chunk], gain, offset, read_var)
+        dp = np.pad(d, ((0, 0), (r, r), (0, 0)))
+        A, B = np.zeros(d.shape), np.zeros(d.shape)
+        for k in range(2 * r + 1):                                # ascending dy
+            v = dp[:, k:k + H, :]
+            A = A + e[k] * v
+            B = B + v
+        Ap, Bp = np.pad(A, ((0, 0), (0, 0), (r, r))), np.pad(B, ((0, 0), (0, 0), (r, r)))
+        Sgd, Sd = np.zeros(d.shape), np.zeros(d.shape)
+        for k in range(2 * r + 1):                                # ascending dx
+            Sgd = Sgd + e[k] * Ap[:, :, k:k + W]
+            Sd = Sd + Bp[:, :, k:k + W]
+        with np.errstate(all="ignore"):
+            mu0 = Sd / n
+            U = Sgd - mu0 * Sg
+            V = mu0 * (Sgg - Sg * Sg / n)
+            ok = (U > 0.0) & (V > 0.0)
+            out[f0:f0 + chunk] = np.where(ok, U * U / np.where(ok, V, 1.0), 0.0).astype(dtype)
+    return out
+
+
+def _lrt_solve(n, lam):
+    """(A + lam diag(A)) step = -g of the 2 x 2 system by Cholesky (lr_solve) -> (d_theta, d_beta, ok)."""
+    with np.errstate(all="ignore"):
+        s = n["a00"] + lam * n["a00"]
+        ok = (s > 0.0) & (s < 1e300)
+        L00 = np.sqrt(np.where(ok, s, 1.0))
+        L10 = n["a10"] / L00
+        s = n["a11"] + lam * n["a11"]
+        s = s - L10 * L10
+        ok &= (s > 0.0) & (s < 1e300)
+        L11 = np.sqrt(np.where(ok, s, 1.0))
+        z0 = -n["g0"] / L00
+        z1 = (-n["g1"] - L10 * z0) / L11
+        d1 = z1 / L11
+        d0 = (z0 - L10 * d1) / L00
+    return d0, d1, ok
+
+
+def _lrt_eval(d, g, valid, theta, beta):
+    """lr_eval: deviance, 2 sum(mu + d), gradient, Fisher matrix and the out-of-domain flag of mu = theta g + beta for windows
+    d / g / valid [n, K] flattened row-major; a pixel outside the frame adds + 0.0 to every sum."""
+    n = len(theta)
+    acc = {k: np.zeros(n) for k in ("cost", "mag", "g0", "g1", "a00", "a10", "a11")}
+    whole = bool(valid.all())
+    with np.errstate(all="ignore"):
+        bad = ~(theta > 0.0)
+        for t in range(d.shape[1]):
+            ok = valid[:, t]
+            if not whole and not ok.any():
+                continue
+            m = (lambda v: v) if whole else (lambda v: np.where(ok, v, 0.0))
+            gt, dd = g[:, t], d[:, t]
+            mu = theta * gt + beta
+            bad |= ok & ~(mu > 0.0)
+            rm = 1.0 / mu
+            r = dd * rm
+            pos = dd > 0.0
+            acc["cost"] = acc["cost"] + m(np.where(pos, (mu - dd) + dd * np.log(np.where(pos, r, 1.0)), mu))
+            acc["mag"] = acc["mag"] + m(mu + dd)
+            w = 1.0 - r
+            acc["g0"] = acc["g0"] + m(gt * w)
+            acc["g1"] = acc["g1"] + m(w)
+            gr = gt * rm
+            acc["a00"] = acc["a00"] + m(gr * gt)
+            acc["a10"] = acc["a10"] + m(rm * gt)
+            acc["a11"] = acc["a11"] + m(rm)
+        acc["cost"], acc["mag"] = 2.0 * acc["cost"], 2.0 * acc["mag"]
+    acc["bad"] = bad
+    return acc
+
+
+def _lrt_numpy(movie32, e, gain, offset, read_var, frames, ys, xs, xtol=FIT_XTOL, max_iter=FIT_MAX_ITER, chunk=1 << 16):
+    """The likelihood ratio of csrc/detect.hip::lr_fit at the pixels (frames, ys, xs) [n] of a float32 movie [F, H, W], all of
+    them side by side -> (T [n], theta [n], beta [n] float64, status [n] int32).  mu = theta g + beta over the clipped window,
+    every sum in window row-major order; equal to the kernel apart from log.  Start: the least-squares point theta = U / den,
+    beta = mu0 - theta Sg / n; where that beta is not positive, beta = mu0 / 1000 and theta = (Sd - n beta) / Sg, which keeps
+    the window's total.  A pixel whose U, den or mu0 is not positive has its maximum at theta = 0: T = 0, beta = mu0."""
+    frames, ys, xs = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (frames, ys, xs))
+    N = len(frames)
+    if N > chunk:
+        parts = [_lrt_numpy(movie32, e, gain, offset, read_var, frames[a:a + chunk], ys[a:a + chunk], xs[a:a + chunk], xtol,
+                            max_iter, chunk) for a in range(0, N, chunk)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+    T, theta, beta, status = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N, np.int32)
+    if N == 0:
+        return T, theta, beta, status
+    _, H, W = movie32.shape
+    r = len(e) // 2
+    K = 2 * r + 1
+    off = np.arange(-r, r + 1)
+    yy, xx = ys[:, None] + off, xs[:, None] + off
+    valid = (((yy >= 0) & (yy < H))[:, :, None] & ((xx >= 0) & (xx < W))[:, None, :]).reshape(N, K * K)
+    raw = movie32[frames[:, None, None], np.clip(yy, 0, H - 1)[:, :, None], np.clip(xx, 0, W - 1)[:, None, :]]
+    d = np.where(valid, _mle_data(raw, gain, offset, read_var).reshape(N, K * K), 0.0)
+    g = np.where(valid, (e[:, None] * e[None, :]).reshape(1, K * K), 0.0)
+    n, Sd, Sgd, Sg, Sgg = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N)
+    for t in range(K * K):
+        n = n + valid[:, t]
+        Sd = Sd + d[:, t]
+        Sgd = Sgd + g[:, t] * d[:, t]
+        Sg = Sg + g[:, t]
+        Sgg = Sgg + g[:, t] * g[:, t]
+    with np.errstate(all="ignore"):
+        mu0 = Sd / n
+        U = Sgd - mu0 * Sg
+        den = Sgg - Sg * Sg / n
+        live = (U > 0.0) & (den > 0.0) & (mu0 > 0.0)
+        beta[:] = mu0
+        idx = np.nonzero(live)[0]
+        if len(idx) == 0:
+            return T, theta, beta, status
+        d, g, valid, n, Sd, Sg, mu0 = d[idx], g[idx], valid[idx], n[idx], Sd[idx], Sg[idx], mu0[idx]
+        th = U[idx] / den[idx]
+        be = mu0 - th * Sg / n
+        low = ~(be > 0.0)
+        be = np.where(low, 1e-3 * mu0, be)
+        th = np.where(low, (Sd - n * be) / Sg, th)
+    cur = _lrt_eval(d, g, valid, th, be)
+    st = np.where(cur["bad"], 1, 2).astype(np.int32)
+    lam = np.full(len(idx), 1e-3)
+    keys = ("cost", "mag", "g0", "g1", "a00", "a10", "a11", "bad")
+    for _ in range(max_iter):
+        act = np.nonzero(st == 2)[0]
+        if len(act) == 0:
+            break
+        sub = {k: cur[k][act] for k in keys}
+        d0, d1, ok = _lrt_solve(sub, lam[act])
+        fail = act[~ok]
+        lam[fail] *= 10.0
+        st[fail[lam[fail] > 1e10]] = 1
+        act, d0, d1 = act[ok], d0[ok], d1[ok]
+        if len(act) == 0:
+            continue
+        sub = {k: cur[k][act] for k in keys}
+        sc = np.maximum(np.abs(th[act]), np.abs(be[act]))
+        u0, u1, ok0 = _lrt_solve(sub, 0.0)
+        with np.errstate(invalid="ignore"):
+            small = ok0 & (np.abs(u0) <= xtol * sc) & (np.abs(u1) <= xtol * sc)
+        qt, qb = th[act] + d0, be[act] + d1
+        nxt = _lrt_eval(d[act], g[act], valid[act], qt, qb)
+        with np.errstate(invalid="ignore"):
+            better = ~nxt["bad"] & (nxt["cost"] <= sub["cost"] + MLE_COST_SLACK * sub["mag"])
+        up = act[better]
+        th[up], be[up] = qt[better], qb[better]
+        for k in keys:
+            cur[k][up] = nxt[k][better]
+        lam[up] = np.maximum(lam[up] * 0.1, 1e-12)
+        down = act[~better]
+        lam[down] *= 10.0
+        st[down[lam[down] > 1e10]] = 1
+        st[act[small]] = 0
+    good = ~cur["bad"]
+    s1, s2 = np.zeros(len(idx)), np.zeros(len(idx))
+    with np.errstate(all="ignore"):
+        for t in range(K * K):
+            mu = th * g[:, t] + be
+            pos = valid[:, t] & (d[:, t] > 0.0)
+            s1 = s1 + np.where(pos, d[:, t] * np.log(np.where(pos, mu / mu0, 1.0)), 0.0)
+            s2 = s2 + np.where(valid[:, t], mu, 0.0)
+        t_ = 2.0 * s1 - 2.0 * (s2 - Sd)
+    T[idx] = np.where(good & (t_ > 0.0), t_, 0.0)
+    theta[idx] = np.where(good, th, 0.0)
+    beta[idx] = np.where(good, be, mu0)
+    status[idx] = st
+    return T, theta, beta, status
+
+
+def _check_lrt_args(shape, gain, offset, read_var, sigma0, radius, p_fa, min_distance, max_peaks_per_frame):
+    """-> (profile e, the threshold rounded to float32 as a Python float)."""
+    if len(shape) != 3:
+        raise ValueError(f"movie must be [F, H, W], got {tuple(shape)}")
+    if not (gain > 0 and math.isfinite(gain)):
+        raise ValueError(f"gain must be finite and > 0, got {gain}")
+    if not math.isfinite(offset):
+        raise ValueError(f"offset must be finite, got {offset}")
+    if not (read_var >= 0 and math.isfinite(read_var)):
+        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    e = psf_profile(sigma0, radius)
+    r = len(e) // 2
+    if shape[1] <= r or shape[2] <= r:
+        raise ValueError(f"frames of {shape[1]} x {shape[2]} (H x W) are not larger than the radius {r}")
+    if int(min_distance) != min_distance or not 1 <= min_distance <= 16:
+        raise ValueError(f"min_distance must be an integer from 1 to 16, got {min_distance}")
+    if int(max_peaks_per_frame) != max_peaks_per_frame or not 1 <= max_peaks_per_frame <= LRT_MAX_PEAKS:
+        raise ValueError(f"max_peaks_per_frame must be an integer from 1 to {LRT_MAX_PEAKS}, got {max_peaks_per_frame}")
+    return e, float(np.float32(detection_threshold(p_fa)))
+
+
+def _check_detector(detector, localization=None):
+    """detector= of the tracking functions -> the keyword arguments of the likelihood-ratio detector (camera keys missing
+    from it are those of `localization`, the camera model of the fit, when that is given)."""
+    if not isinstance(detector, dict) or set(detector) - set(_DETECTOR_DEFAULTS) - {"method"}:
+        raise ValueError(f"detector must be None or a dict with keys among method, {', '.join(_DETECTOR_DEFAULTS)}, got "
+                         f"{detector!r}")
+    if detector.get("method") != "lrt":
+        raise ValueError(f"detector['method'] must be 'lrt', got {detector.get('method')!r}")
+    out = dict(_DETECTOR_DEFAULTS)
+    out.update({k: v for k, v in (localization or {}).items() if k in ("gain", "offset", "read_var", "sigma0")})
+    out.update({k: v for k, v in detector.items() if k != "method"})
+    return out
+
+
+def _lrt_detect_cuda(movie, e, thr, gain, offset, read_var, min_distance, max_peaks_per_frame, return_map):
+    """Both stages on the GPU -> (count [F], coords [F, cap, 2], stats [F, cap, 4], status [F, cap], score map or None)."""
+    from .. import ops
+    movie = movie.float()
+    if not bool(torch.isfinite(movie).all()):
+        raise ValueError("movie must be finite")
+    count, coords, values, smap = ops.score_peaks(movie, e, gain, offset, read_var, thr, int(min_distance),
+                                                  int(max_peaks_per_frame), return_map)
+    kept, kcoords, stats, status = ops.lrt_peaks(movie, e, gain, offset, read_var, thr, count, coords, values)
+    return kept, kcoords, stats, status, smap
+
+
+def _lrt_detect_numpy(arr, e, thr, gain, offset, read_var, min_distance, max_peaks_per_frame):
+    """Both stages on the host for a float32 movie -> (list of F coords [n_f, 2] int64, list of F stats [n_f, 5] float64,
+    score map [F, H, W] float32)."""
+    if not np.isfinite(arr).all():
+        raise ValueError("movie must be finite")
+    smap = _score_numpy(arr, e, gain, offset, read_var)
+    cand = []
+    for f in range(len(smap)):
+        c, n_cand = _peaks_numpy(smap[f], None, int(min_distance), absolute=np.float32(thr))
+        if n_cand > max_peaks_per_frame:
+            raise RuntimeError(f"a frame has {n_cand} peak candidates but max_peaks_per_frame = {max_peaks_per_frame}; raise "
+                               f"max_peaks_per_frame (up to {LRT_MAX_PEAKS}) or lower p_fa")
+        cand.append(c)
+    fr = np.concatenate([np.full(len(c), f, np.int64) for f, c in enumerate(cand)]) if cand else np.zeros(0, np.int64)
+    yx = np.concatenate(cand) if cand else np.zeros((0, 2), np.int64)
+    T, theta, beta, status = _lrt_numpy(arr, e, gain, offset, read_var, fr, yx[:, 0], yx[:, 1])
+    keep = T > thr
+    table = np.stack([T, theta, beta - read_var, smap[fr, yx[:, 0], yx[:, 1]].astype(np.float64),
+                      status.astype(np.float64)], axis=1)
+    coords = [yx[(fr == f) & keep] for f in range(len(smap))]
+    stats = [table[(fr == f) & keep] for f in range(len(smap))]
+    return coords, stats, smap
+
+
+def detect_particles_lrt_movie(movie, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, radius=None, p_fa=1e-6, min_distance=3,
+                               max_peaks_per_frame=512, return_map=True):
+    """Likelihood-ratio detection of every frame of a movie [F, H, W] in camera units (photons = max((adu - offset) / gain,
+    0), read_var the readout variance in photons^2, as fit_spots_mle): per pixel "local background only" against "background
+    plus one spot of width sigma0 centred here" over the clipped (2 radius + 1)^2 window (radius from 1 to LRT_MAX_RADIUS,
+    default ceil(3 sigma0)), at the per-pixel false-alarm probability p_fa in (0, 0.5].  Stage 1: the score statistic of
+    every pixel and its local maxima above detection_threshold(p_fa) by the rule of detect_particles_movie (min_distance, at
+    most max_peaks_per_frame candidates per frame or it raises).  Stage 2: the exact Poisson likelihood ratio T at those
+    candidates; a detection has T above the same threshold -> (list of F coordinate arrays [n_f, 2] int64 (y, x) in stage-1
+    order, list of F arrays [n_f, 5] float64 (T, photons, background per pixel, the stage-1 statistic, status: 0 converged, 1
+    damping exhausted, 2 iteration cap, T then being a lower bound), the score map [F, H, W] float32 of the input's kind or
+    None with return_map=False).  A CUDA tensor runs csrc/detect.hip, anything else the restatements _score_numpy and
+    _lrt_numpy.  The threshold does not depend on the frame: an empty frame yields nothing, a bright spot hides no dim one."""
+    gain, offset, read_var = float(gain), float(offset), float(read_var)
+    e, thr = _check_lrt_args(movie.shape, gain, offset, read_var, sigma0, radius, p_fa, min_distance, max_peaks_per_frame)
+    if _is_cuda(movie):
+        kept, kcoords, stats, status, smap = _lrt_detect_cuda(movie, e, thr, gain, offset, read_var, min_distance,
+                                                              max_peaks_per_frame, return_map)
+        kept = kept.cpu().numpy()
+        top = int(kept.max()) if len(kept) else 0
+        kcoords = kcoords[:, :top].cpu().numpy().astype(np.int64)
+        table = torch.cat([stats[:, :top], status[:, :top, None].double()], dim=2).cpu().numpy()
+        return ([kcoords[f, :kept[f]] for f in range(len(kept))], [table[f, :kept[f]] for f in range(len(kept))], smap)
+    was_tensor = torch.is_tensor(movie)
+    arr = np.ascontiguousarray(movie.detach().numpy() if was_tensor else np.asarray(movie), dtype=np.float32)
+    coords, stats, smap = _lrt_detect_numpy(arr, e, thr, gain, offset, read_var, min_distance, max_peaks_per_frame)
+    if not return_map:
+        return coords, stats, None
+    return coords, stats, (torch.from_numpy(smap) if was_tensor else smap)
+
+
+def detect_particles_lrt(image, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, radius=None, p_fa=1e-6, min_distance=3):
+    """detect_particles_lrt_movie of one frame [H, W] -> (coordinates [n, 2] (y, x), stats [n, 5], score map [H, W])."""
+    if len(image.shape) != 2:
+        raise ValueError(f"image must be [H, W], got {tuple(image.shape)}; use detect_particles_lrt_movie for a movie")
+    coords, stats, smap = detect_particles_lrt_movie(image[None], gain, offset, read_var, sigma0, radius, p_fa, min_distance)
+    return coords[0], stats[0], smap[0]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -589,7 +936,7 @@ def _check_gap_args(max_gap, max_gap_distance, max_linking_distance):
 
 def track_particles_tensors(movie, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
                             max_linking_distance=15, min_track_length=3, max_peaks_per_frame=512, movie_start=None,
-                            return_dog=True, max_gap=0, max_gap_distance=None):
+                            return_dog=True, max_gap=0, max_gap_distance=None, detector=None):
     """Detection, linking, chaining, length filter and renumbering of a CUDA movie [F, H, W] without a copy of the
     coordinates to the host -> (dict of CUDA tensors frame, y, x, track_id (int64 [N], the reference's detections table in its
     row order), in_long_track (bool [N]: the rows whose track has >= min_track_length positions and so carries a renumbered
@@ -597,17 +944,30 @@ def track_particles_tensors(movie, sigma1=1.0, sigma2=2.0, threshold_percentage=
     extract_patches_flat and refine_localizations as they are.  movie_start [F] marks the first frames of several movies
     concatenated along F.  max_gap > 0 (up to LINK_MAX_GAP) closes gaps of up to that many missed frames within
     max_gap_distance pixels (default: max_linking_distance; close_gaps_movie) and fills them (fill_gaps): the dict gains
-    filled (bool [N], the interpolated rows), and min_track_length keeps counting detections."""
+    filled (bool [N], the interpolated rows), and min_track_length keeps counting detections.  detector (default None: the
+    difference of Gaussians, the code path without it): {"method": "lrt"} with any of gain, offset, read_var, sigma0, radius
+    and p_fa, the arguments of detect_particles_lrt_movie, which then detects (csrc/detect.hip, both stages on the device);
+    sigma1, sigma2 and threshold_percentage are unused and the second result is the score map."""
     if not _is_cuda(movie):
         raise ValueError("track_particles_tensors needs a CUDA movie; use track_particles_flat(..., linking='device') on the host")
     max_gap, gap_distance = _check_gap_args(max_gap, max_gap_distance, max_linking_distance)
-    w1, w2 = _check_detection_args(movie.shape, sigma1, sigma2, min_distance)
+    if detector is not None:
+        det = _check_detector(detector)
+        gain, offset, read_var = float(det["gain"]), float(det["offset"]), float(det["read_var"])
+        e, thr = _check_lrt_args(movie.shape, gain, offset, read_var, det["sigma0"], det["radius"], det["p_fa"], min_distance,
+                                 max_peaks_per_frame)
+    else:
+        w1, w2 = _check_detection_args(movie.shape, sigma1, sigma2, min_distance)
     if max_peaks_per_frame > LINK_MAX_DETECTIONS:
         raise ValueError(f"max_peaks_per_frame = {max_peaks_per_frame}, the linking kernel's limit is {LINK_MAX_DETECTIONS} "
                          f"(LINK_MAX_DETECTIONS)")
     from .. import ops
-    count, coords, _, dog = ops.dog_peaks(movie.float(), w1, w2, threshold_percentage, int(min_distance), max_peaks_per_frame,
-                                          return_dog)
+    if detector is not None:
+        count, coords, _, _, dog = _lrt_detect_cuda(movie, e, thr, gain, offset, read_var, min_distance, max_peaks_per_frame,
+                                                    return_dog)
+    else:
+        count, coords, _, dog = ops.dog_peaks(movie.float(), w1, w2, threshold_percentage, int(min_distance),
+                                              max_peaks_per_frame, return_dog)
     link = ops.link_frames(coords, count, float(max_linking_distance), movie_start)
     if max_gap > 0:
         gap_partner, gap_frames = ops.close_gaps(coords, count, link, max_gap, gap_distance, movie_start)
@@ -631,13 +991,25 @@ def _tracks_from_table(fr, y, x, tid, in_long):
     return {int(tid[a]): list(zip(frames[a:b], y[a:b], x[a:b])) for a, b in zip(starts, ends) if b > a}
 
 
+def _detect_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame, detector):
+    """(coordinates per frame, DoG movie) of detect_particles_movie, or with a detector those of detect_particles_lrt_movie
+    and its score map."""
+    if detector is None:
+        return detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
+    det = _check_detector(detector)
+    coords, _, smap = detect_particles_lrt_movie(movie, min_distance=min_distance, max_peaks_per_frame=max_peaks_per_frame,
+                                                 **det)
+    return coords, smap
+
+
 def _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance, max_linking_distance, min_track_length, verbose,
-                  max_peaks_per_frame, max_gap=0, gap_distance=None):
+                  max_peaks_per_frame, max_gap=0, gap_distance=None, detector=None):
     """track_particles_flat with linking="device": the kernels for a CUDA movie, their restatements for anything else."""
     filled = None
     if _is_cuda(movie):
         t, dog = track_particles_tensors(movie, sigma1, sigma2, threshold_percentage, min_distance, max_linking_distance,
-                                         min_track_length, max_peaks_per_frame, max_gap=max_gap, max_gap_distance=gap_distance)
+                                         min_track_length, max_peaks_per_frame, max_gap=max_gap, max_gap_distance=gap_distance,
+                                         detector=detector)
         keys = ("frame", "y", "x", "track_id", "in_long_track") + (("filled",) if max_gap > 0 else ())
         packed = torch.stack([t[k].long() for k in keys]).cpu().numpy()          # the one copy to the host
         fr, y, x, tid, in_long = packed[0], packed[1], packed[2], packed[3], packed[4].astype(bool)
@@ -645,7 +1017,7 @@ def _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance, max
             filled = packed[5].astype(bool)
         n_all = int(t["n_tracks"])
     else:
-        coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
+        coords, dog = _detect_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame, detector)
         padded, counts = _padded_detections(coords, None)
         link = link_particles_movie(padded, counts, max_linking_distance)
         if max_gap > 0:
@@ -671,7 +1043,7 @@ def _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance, max
 
 def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_percentage=0.1, min_distance=3,
                          max_linking_distance=15, min_track_length=3, verbose=False, max_peaks_per_frame=512, linking="host",
-                         max_gap=0, max_gap_distance=None):
+                         max_gap=0, max_gap_distance=None, detector=None):
     """track_particles without pandas: (tracks, detections as a dict of int64 arrays frame / y / x / track_id, DoG movie
     [F, H, W]).  linking="host" (default): scipy's assignment per frame in a loop on the host, rows in the order of the
     reference's active tracks.  linking="device": all frame pairs in one launch of csrc/linking.hip and the ids chained on the
@@ -679,7 +1051,8 @@ def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_perce
     result wherever every frame pair has a single optimal assignment (see link_particles_movie).  max_gap > 0 (with
     linking="device" only) closes gaps of up to max_gap missed frames within max_gap_distance pixels (default:
     max_linking_distance) and fills them with interpolated positions: tracks and detections include the filled rows, and the
-    detections gain the bool column filled."""
+    detections gain the bool column filled.  detector (default None: the difference of Gaussians): {"method": "lrt", ...} as
+    track_particles_tensors, with either linking; the third result is then the score map."""
     if linking not in ("host", "device"):
         raise ValueError(f"linking must be 'host' or 'device', got {linking!r}")
     max_gap, gap_distance = _check_gap_args(max_gap, max_gap_distance, max_linking_distance)
@@ -691,10 +1064,10 @@ def track_particles_flat(image_sequence, sigma1=1.0, sigma2=2.0, threshold_perce
     if linking == "device":
         tracks, det, dog, n_all = _track_device(movie, sigma1, sigma2, threshold_percentage, min_distance,
                                                 max_linking_distance, min_track_length, verbose, max_peaks_per_frame,
-                                                max_gap, gap_distance)
+                                                max_gap, gap_distance, detector)
         print(f"Tracking complete: {n_all} total tracks, {len(tracks)} tracks with ≥{min_track_length} frames")
         return tracks, det, dog
-    coords, dog = detect_particles_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame)
+    coords, dog = _detect_movie(movie, sigma1, sigma2, threshold_percentage, min_distance, max_peaks_per_frame, detector)
     if verbose:
         for f, c in enumerate(coords):
             print(f"Frame {f}: {len(c)} particles detected")
@@ -1810,6 +2183,9 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     the same frame inside its patch (csrc/localize2.hip), the positions, "localization" and sigma2_loc come from the joint fit
     and its bounds, and "localization" gains n_neighbours, neighbour (rows of tracks_table_by_track) and photons_neighbour.
 
+    detector (one of tracking_kwargs, default None: the difference of Gaussians): {"method": "lrt", ...}, the likelihood-ratio
+    detector of track_particles_tensors; gain, offset, read_var and sigma0 it does not name are those of localization.
+
     ml (default None: the code path without it): a dict with keys among blur and sigma2 ({} for the defaults), the arguments of
     helpers/msd.estimate_diffusion_ml (csrc/likelihood.hip), the maximum-likelihood D of every track from rows of known
     variance, with a standard error.  blur is the motion-blur coefficient (default 0).  sigma2 is the localisation variance
@@ -1893,6 +2269,10 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
             neighbours = None
         if not refine:
             raise ValueError("localization needs refine=True: it is the refinement")
+    if tracking_kwargs.get("detector") is not None:
+        # the detector looks through the camera of the fit: gain, offset, read_var and sigma0 it does not name are localization's
+        det = _check_detector(tracking_kwargs["detector"], localization)
+        tracking_kwargs["detector"] = {"method": "lrt", **det}
     if isinstance(states, dict) and isinstance(states.get("sigma2"), str):
         if states["sigma2"] != "crlb":
             raise ValueError(f"states['sigma2'] must be a number or 'crlb', got {states['sigma2']!r}")

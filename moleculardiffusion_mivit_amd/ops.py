@@ -606,6 +606,99 @@ def dog_peaks(movie: torch.Tensor, w1, w2, threshold_percentage: float = 0.1, mi
     return count, coords, values, dog
 
 
+SCORE_PEAKS_MAX_RADIUS = 7
+
+
+def _score_args(name, movie, e, gain, offset, read_var, threshold, cap):
+    """The checks the two stages of the likelihood-ratio detector share -> (movie, e as float64, radius, cap)."""
+    import math
+    import numpy as np
+    movie = _frames_f32(movie, name)
+    if movie.dim() != 3:
+        raise ValueError(f"movie must be [F, H, W], got {tuple(movie.shape)}")
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    if e.ndim != 1 or e.size % 2 != 1 or not 1 <= e.size // 2 <= SCORE_PEAKS_MAX_RADIUS:
+        raise ValueError(f"e must hold the 2 radius + 1 profile values of a radius from 1 to {SCORE_PEAKS_MAX_RADIUS}, got "
+                         f"shape {e.shape}")
+    r = e.size // 2
+    if not (np.all(e > 0) and np.all(e <= 1)):
+        raise ValueError("e must lie in (0, 1]")
+    if movie.shape[1] <= r or movie.shape[2] <= r:
+        raise ValueError(f"frames of {movie.shape[1]} x {movie.shape[2]} are not larger than the radius {r}")
+    if not (gain > 0 and math.isfinite(gain)):
+        raise ValueError(f"gain must be finite and > 0, got {gain}")
+    if not math.isfinite(offset):
+        raise ValueError(f"offset must be finite, got {offset}")
+    if not (read_var >= 0 and math.isfinite(read_var)):
+        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    if not (threshold >= 0 and math.isfinite(threshold)):
+        raise ValueError(f"threshold must be finite and >= 0, got {threshold}")
+    cap = int(cap)
+    if not 1 <= cap <= DOG_PEAKS_MAX_CAPACITY:
+        raise ValueError(f"max_peaks_per_frame must be from 1 to {DOG_PEAKS_MAX_CAPACITY}, got {cap}")
+    return movie, e, r, cap
+
+
+def score_peaks(movie: torch.Tensor, e, gain: float = 1.0, offset: float = 0.0, read_var: float = 0.0,
+                threshold: float = 0.0, min_distance: int = 3, max_peaks_per_frame: int = 512, return_map: bool = True):
+    """Stage 1 of the likelihood-ratio detector (csrc/detect.hip, mivit_score_peaks): the score statistic of "background
+    plus a spot centred here" against "background only" at every pixel of movie [F, H, W] (float32 on the GPU, camera units
+    as fit_spots_mle), and its local maxima strictly above the absolute threshold.  e: the 2 r + 1 float64 values of the
+    pixel-integrated profile, as helpers/tracking.psf_profile builds them -> (count [F] int32, coords [F, cap, 2] int32
+    (y, x), values [F, cap] float32, score map [F, H, W] float32 or None), in the layout and order of dog_peaks.  Raises if
+    a frame has more candidates than max_peaks_per_frame."""
+    gain, offset, read_var, threshold = float(gain), float(offset), float(read_var), float(threshold)
+    movie, e, r, cap = _score_args("score_peaks", movie, e, gain, offset, read_var, threshold, max_peaks_per_frame)
+    if int(min_distance) != min_distance or not 1 <= min_distance <= 16:
+        raise ValueError(f"min_distance must be an integer from 1 to 16, got {min_distance}")
+    F, H, W = movie.shape
+    dev = movie.device
+    count = torch.zeros(F, dtype=torch.int32, device=dev)
+    ncand = torch.zeros(F, dtype=torch.int32, device=dev)
+    coords = torch.zeros(F, cap, 2, dtype=torch.int32, device=dev)
+    values = torch.zeros(F, cap, dtype=torch.float32, device=dev)
+    smap = torch.empty(F, H, W, dtype=torch.float32, device=dev) if return_map else None
+    wsb = N.lib.mivit_score_peaks_workspace_bytes(F, H, W, cap, 1 if return_map else 0)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    N.check(N.lib.mivit_score_peaks(_p(movie), F, H, W, e.ctypes.data_as(ctypes.c_void_p), r, gain, offset, read_var,
+                                    threshold, int(min_distance), cap, _p(count), _p(ncand), _p(coords), _p(values),
+                                    _p(smap), _p(ws), ws.numel(), _s(movie)), "mivit_score_peaks")
+    worst = int(ncand.max()) if F else 0
+    if worst > cap:
+        raise RuntimeError(f"score_peaks: a frame has {worst} peak candidates but max_peaks_per_frame = {cap}; raise "
+                           f"max_peaks_per_frame (up to {DOG_PEAKS_MAX_CAPACITY}) or lower p_fa")
+    return count, coords, values, smap
+
+
+def lrt_peaks(movie: torch.Tensor, e, gain: float, offset: float, read_var: float, threshold: float, count: torch.Tensor,
+              coords: torch.Tensor, values: torch.Tensor):
+    """Stage 2 of the likelihood-ratio detector (csrc/detect.hip, mivit_lrt_peaks): the exact Poisson likelihood ratio T of
+    mu = theta g + beta against a constant at every candidate that score_peaks returned (count [F] int32, coords [F, cap, 2]
+    int32, values [F, cap] float32 on the GPU), kept where T > threshold and compacted per frame in their order, without a
+    copy to the host -> (count [F] int32, coords [F, cap, 2] int32, stats [F, cap, 4] float64 (T, photons, background per
+    pixel, the stage-1 statistic), status [F, cap] int32: 0 converged, 1 damping exhausted, 2 iteration cap).  Entries past
+    count are zero."""
+    gain, offset, read_var, threshold = float(gain), float(offset), float(read_var), float(threshold)
+    if coords.dim() != 3 or coords.shape[2] != 2:
+        raise ValueError(f"coords must be [F, cap, 2], got {tuple(coords.shape)}")
+    movie, e, r, cap = _score_args("lrt_peaks", movie, e, gain, offset, read_var, threshold, coords.shape[1])
+    F, H, W = movie.shape
+    dev = movie.device
+    for name, t, dt, shape in (("count", count, torch.int32, (F,)), ("coords", coords, torch.int32, (F, cap, 2)),
+                               ("values", values, torch.float32, (F, cap))):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == dt and tuple(t.shape) == shape):
+            raise ValueError(f"{name} must be a {dt} tensor of shape {shape} on {dev}")
+    count, coords, values = count.contiguous(), coords.contiguous(), values.contiguous()
+    kept = torch.zeros(F, dtype=torch.int32, device=dev)
+    kcoords = torch.zeros(F, cap, 2, dtype=torch.int32, device=dev)
+    stats = torch.zeros(F, cap, 4, dtype=torch.float64, device=dev)
+    status = torch.zeros(F, cap, dtype=torch.int32, device=dev)
+    N.check(N.lib.mivit_lrt_peaks(_p(movie), F, H, W, e.ctypes.data_as(ctypes.c_void_p), r, gain, offset, read_var, threshold,
+                                  cap, _p(count), _p(coords), _p(values), _p(kept), _p(kcoords), _p(stats), _p(status),
+                                  _s(movie)), "mivit_lrt_peaks")
+    return kept, kcoords, stats, status
+
+
 def refine_gaussian(patches: torch.Tensor, xtol: float = 1e-11):
     """Five-parameter Gaussian fit of every patch (csrc/tracking.hip, mivit_refine_gaussian): patches [N, P, P] float32 on the
     GPU, P odd, 3 .. 15 -> (params [N, 5] float64 (amplitude, x0, y0, sigma, offset), peak [N] float32 = patch.max(),

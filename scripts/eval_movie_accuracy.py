@@ -57,7 +57,10 @@ RMS radius about its start position (simulate_movie's confinement), and --confin
 track, radius_ml, radius_ml_std, D_conf, lambda_ml, lr_confined and confined_status (helpers/msd.estimate_confinement_ml,
 csrc/confined_ml.hip, through estimate_track_diffusion(..., confined={"sigma2": SIGMA2})), over the matched tracks of at least
 20 rows and status 0 the median radius and D against the truth and the pull of ln radius, and the quantiles of lr_confined on
-that movie and on a FREE Brownian movie of the same settings: the null distribution from which a threshold is picked.  A
+that movie and on a FREE Brownian movie of the same settings: the null distribution from which a threshold is picked.
+--detector lrt [--p-fa P] (with --camera) adds "detector": score_tracking's recall, precision and RMSE of the difference of
+Gaussians and of the likelihood-ratio detector at the per-pixel false-alarm probability P (default 1e-6; csrc/detect.hip,
+track_particles_tensors(..., detector={...})) on the same movie with the same linking, also printed to stderr.  A
 tool, not a test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
@@ -66,7 +69,7 @@ tool, not a test: it asserts no accuracy.
                                           [--cristae 4 30 60 12] [--boundary reflect]
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
-                                          [--camera 10,2,100,1.5] [--mle] [--neighbours [4]] [--ml [0.1667]] [--intensity 300]
+                                          [--camera 10,2,100,1.5] [--detector lrt [--p-fa 1e-6]] [--mle] [--neighbours [4]] [--ml [0.1667]] [--intensity 300]
                                           [--confined 3.0] [--confined-ml [0.01]]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
@@ -160,6 +163,8 @@ def main():
     ap.add_argument("--intensity", type=float, default=None, metavar="PEAK")
     ap.add_argument("--confined", type=float, default=None, metavar="RADIUS")
     ap.add_argument("--confined-ml", type=float, nargs="?", const=-1.0, default=None, metavar="SIGMA2")
+    ap.add_argument("--detector", choices=["lrt"], default=None)
+    ap.add_argument("--p-fa", type=float, default=1e-6, metavar="P")
     args = ap.parse_args()
     camera = None
     if args.camera is not None:
@@ -172,6 +177,8 @@ def main():
         camera = {"background": v[0], "gain": v[1], "offset": v[2], "read_noise": v[3] if len(v) == 4 else 0.0}
     elif args.mle:
         raise SystemExit("--mle needs --camera: the maximum-likelihood fit assumes photon counts")
+    if args.detector is not None and camera is None:
+        raise SystemExit("--detector lrt needs --camera: the likelihood ratio assumes photon counts")
     if args.neighbours is not None and not args.mle:
         raise SystemExit("--neighbours needs --mle: the joint fit is a maximum-likelihood fit")
     if args.ml is not None and not args.mle:
@@ -297,6 +304,8 @@ def main():
         out["drift"] = drift_scores(movie, model, args, norm, truth, score, est, out["tracks"], states)
     if camera is not None:
         out["camera"] = camera_scores(movie, model, args, norm, truth, score, props, camera, states)
+    if args.detector is not None:
+        out["detector"] = detector_scores(movie, args, truth, props, camera)
     if states is not None:
         out["states"] = args.states
         out["segmentation"] = [segmentation_scores(movie, model, args, norm, truth, score, fr, float(p)) for p in args.penalties]
@@ -328,6 +337,24 @@ def drift_scores(movie, model, args, norm, truth, score, est, rows, states):
         raw = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap, **hmm)
         out["hmm_Ds"], out["hmm_Ds_corrected"] = raw["states"]["Ds"].tolist(), cor["states"]["Ds"].tolist()
         out["planted_Ds"] = sorted(states["Ds"])
+    return out
+
+
+def detector_scores(movie, args, truth, props, camera):
+    """score_tracking's recall and precision of the difference of Gaussians and of the likelihood-ratio detector at --p-fa on
+    the same camera movie, with the same linking"""
+    det = {"method": "lrt", "gain": camera["gain"], "offset": camera["offset"],
+           "read_var": (camera["read_noise"] / camera["gain"]) ** 2, "sigma0": gen.psf_sigma_hr(props) / props["upsampling_factor"],
+           "p_fa": args.p_fa}
+    out = {"p_fa": args.p_fa, "threshold": trk.detection_threshold(args.p_fa), "sigma0": det["sigma0"]}
+    for name, how in (("dog", None), ("lrt", det)):
+        table, _ = trk.track_particles_tensors(movie, return_dog=False, max_gap=args.max_gap, detector=how)
+        fr, y, x, tid = trk.tracks_table_by_track(table)[:4]
+        sc = trk.score_tracking(fr, y, x, tid, truth, max_distance=args.max_distance)
+        out[name] = {"recall": float(sc["recall"]), "precision": float(sc["precision"]), "rmse": float(sc["rmse"]),
+                     "rows": int(len(fr)), "n_tracks": int(len(sc["track_id"]))}
+        print(f"detector {name}: recall {out[name]['recall']:.4f} precision {out[name]['precision']:.4f} "
+              f"({out[name]['rows']} rows in {out[name]['n_tracks']} tracks)", file=sys.stderr)
     return out
 
 
