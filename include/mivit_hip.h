@@ -799,6 +799,58 @@ int mivit_track_confined_loglik(const double *pos, const double *var, const int 
                                 const int *offsets, int n, double dt, const double *D, const double *s2, const double *centre,
                                 double *loglik, void *stream);
 
+/* Per-range maximum-likelihood VELOCITY and diffusion coefficient of directed motion with error bars, and the exact
+ * log-likelihood of directed motion at given parameters, csrc/directed_ml.hip: the model of mivit_track_diffusion_ml with a
+ * mean, diffusion plus a constant velocity u per axis (no counterpart in the reference).  The increments keep their
+ * tridiagonal covariance; their mean is u m_k with m_k = g_k dt (an exposure average shifts every row of a track of constant
+ * velocity alike, so blur leaves the mean alone).  fp64 without contraction, no LDS, no scratch, no atomics; ONE WAVE per
+ * range and lane j = candidate j of the search over D; a range has NO maximum length (its rows are read from global memory
+ * in each of the 9 passes) and its outputs are bitwise the same alone, anywhere in a batch and in every launch.
+ *
+ * pos, var, frames, use, N, offsets, n, dt, R: as mivit_track_diffusion_ml, and so are the rule for a USABLE row and the names
+ * X_k, v_k, f_k, d_k, g_k of the m usable rows and their m - 1 increments.
+ * The cost at D ABOUT A VELOCITY (wy, wx): per increment g = (double)g_k, mk = g dt, and per axis (y, then x, for every k in
+ * ascending order) dd_k = d_k - w mk; c1 = (2 D) dt, cR = R c1; a_k, b_{k-1}, l_k, e_k, r_k as in mivit_track_diffusion_ml, and
+ *   z_0 = dd_0, t_0 = mk;   z_k = dd_k - l_k z_{k-1};   t_k = mk - l_k t_{k-1}      (two residuals under one multiplier and pivot)
+ *   A = A + (z_k z_k) r_k;   B = B + (z_k t_k) r_k;   C = C + (t_k t_k) r_k         (per axis)
+ *   P = P e_k, shared by the axes, kept as mantissa in [0.5, 1) times 2^pe by frexp after every factor (exact)
+ * Velocity given (it is w):  Q = A_y + A_x.
+ * Velocity profiled:         Q = (A_y - (B_y B_y) / C_y) + (A_x - (B_x B_x) / C_x).
+ * Either way the velocity of the fit is u = w + B / C per axis and its standard error at this D is 1 / sqrt(C): for Gaussian
+ * data the mean and the covariance parameters share no Fisher information.
+ *   cost = -2 log L = ((log(mantissa) + pe log 2) + Q) + 2 (m - 1) log(2 pi)
+ * A candidate with some e_k that is not > 0, with a C that is not > 0 or not finite, or whose cost is not below +inf, has cost
+ * +inf.  The profile does not depend on w in exact arithmetic (A - B B / C is invariant under d -> d - w m, and u with it);
+ * in fp64 a w near the answer keeps A, B and C of the size of the noise however fast the track is, so nothing cancels.
+ *
+ * mivit_track_directed_ml.  Pass 0: m, G = sum_k g_k, and the UNWEIGHTED velocity u0 = (X_{m-1} - X_0) / ((double)G dt) per
+ * axis.  Pass 1: D_ref = S / ((4 dt) G) with S = sum_k (dd_k,y dd_k,y + dd_k,x dd_k,x) in ascending k and dd taken about u0: the
+ * reference scale holds no velocity, so a fast, quiet track keeps its optimum inside the bracket and a velocity added to a
+ * track changes D by rounding alone.  Then the search of mivit_track_diffusion_ml (bracket [-20, 4], six rounds of 64
+ * candidates, D_j = D_ref exp2(u_j), the LOWEST j on a tie, statuses 2 and 3) on the profiled cost about w = u0, the three
+ * costs at D, D e^h, D e^-h (lanes 0, 1, 2), loglik = -c0 / 2, D_std = D / sqrt(I) and status 4 as there.  Lane 0 writes v = u0
+ * + B / C and v_std = 1 / sqrt(C) of its own sums at D, per axis, where c0 is below +inf, else NaN (status 2 with zero
+ * variances: the likelihood at D = 0 does not exist).  This is plain maximum likelihood, not REML: D is low by about one part
+ * in m - 1.
+ * out, per range: D, D_std [n], v, v_std [n, 2] (y, x) in pixels per unit of dt, loglik [n] fp64, n_increments [n] int32 = max(m -
+ * 1, 0), status [n] int32: 0 fine, 1 fewer than 2 increments (every fp64 output NaN), 2 the minimum at the lower end (D = 0,
+ * D_std NaN), 3 at the upper end, 4 the curvature is not positive (D_std NaN).
+ *
+ * mivit_track_directed_loglik: D [n] fp64 in; v [n, 2] fp64 (y, x) in, or null to profile the velocity (w is then u0 of pass
+ * 0) -> loglik [n] = -cost / 2 (-inf for a rejected candidate); NaN for a range with fewer than 2 usable rows, where D is
+ * negative or not finite and where a given velocity is not finite.  v_hat, v_hat_std [n, 2] fp64 or null: where given, the
+ * velocity u of the fit and 1 / sqrt(C), NaN where loglik is not finite.  One THREAD per range runs the same device function.
+ * With v = 0 the cost is that of mivit_track_diffusion_ml at D but for the order in which Q is added up.
+ * The only operations that may differ from the numpy restatements (helpers/msd._directed_ml_numpy, _directed_loglik_numpy)
+ * are log and exp2.  Arguments are validated before any HIP call (sizes, dt, R, null pointers; pos may be null where N = 0;
+ * var, frames, use, v, v_hat and v_hat_std may be null); n = 0 is a no-op. */
+int mivit_track_directed_ml(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                            const int *offsets, int n, double dt, double R, double *D, double *D_std, double *v, double *v_std,
+                            double *loglik, int *n_increments, int *status, void *stream);
+int mivit_track_directed_loglik(const double *pos, const double *var, const int *frames, const unsigned char *use, int N,
+                                const int *offsets, int n, double dt, double R, const double *D, const double *v, double *loglik,
+                                double *v_hat, double *v_hat_std, void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -176,6 +176,10 @@ SYMBOLS = {
                            + [c_void_p] * 9 + [c_size_t, c_void_p]),
     "mivit_track_confined_ml": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 13),
     "mivit_track_confined_loglik": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 5),
+    "mivit_track_directed_ml": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, ctypes.c_double, ctypes.c_double]
+                                + [c_void_p] * 8),
+    "mivit_track_directed_loglik": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, ctypes.c_double, ctypes.c_double]
+                                    + [c_void_p] * 6),
     "mivit_drift_frames": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_drift_integrate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes": (c_size_t, [c_int]),

@@ -1,4 +1,4 @@
-// What the per-track maximum-likelihood fits share (likelihood.hip, fbm_ml.hip, confined_ml.hip): the usable-row rule, the
+// What the per-track maximum-likelihood fits share (likelihood.hip, fbm_ml.hip, confined_ml.hip, directed_ml.hip): the usable-row rule, the
 // clamp of a range, the pass for the reference scale, the determinant as an exactly rescaled product with the closing of
 // the cost, the arg-min of a wave, the 3 x 3 stencil of the observed information, and the host checks of the common
 // arguments.  Nothing here knows a model: recurrences, searches and outputs are in the model's file.  The numpy restatement

@@ -82,6 +82,34 @@ def brownian_single_state(N: int, T: int, Ds=(1.0, 0.0), alphas: float = 1.0, dt
     return trajs, labels
 
 
+def _velocity_matrix(velocity, n: int) -> torch.Tensor:
+    """velocity, (vy, vx) as [2] or one per particle [n, 2], as a float64 CPU tensor [n, 2] of finite numbers (ValueError
+    otherwise)."""
+    what = f"velocity must be a real (vy, vx) pair or [{n}, 2] values"
+    try:
+        v = (velocity if torch.is_tensor(velocity) else torch.from_numpy(np.array(velocity))).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}, got {velocity!r}") from None
+    if v.dtype == torch.bool or v.is_complex() or tuple(v.shape) not in ((2,), (n, 2)):
+        raise ValueError(f"{what}, got {v.dtype} {tuple(v.shape)}")
+    v = v.double()
+    if not bool(torch.isfinite(v).all()):
+        raise ValueError("velocity must be finite")
+    return (v.view(1, 2).expand(n, 2) if v.dim() == 1 else v).contiguous()
+
+
+def directed_single_state(N: int, T: int, Ds=(1.0, 0.0), velocity=(0.0, 0.0), dt: float = 1.0,
+                          generator: Optional[torch.Generator] = None, device="cpu"):
+    """(T, N, 2) trajectories and (T, N, 3) labels [alpha = 1, D, state = 0] of directed motion: diffusion plus a constant
+    velocity, (vy, vx) as [2] or one per particle [N, 2], in units of length per unit of dt.  It draws exactly what
+    brownian_single_state draws and adds velocity * t * dt at step t (in float64, rounded once): a zero velocity gives its
+    trajectories bit for bit.  What helpers/msd.estimate_directed_ml estimates."""
+    vel = _velocity_matrix(velocity, N)
+    trajs, labels = brownian_single_state(N, T, Ds, 1.0, dt, generator, device)
+    t = torch.arange(T, dtype=torch.float64, device=trajs.device) * float(dt)
+    return (trajs.double() + t.view(T, 1, 1) * vel.to(trajs.device).view(1, N, 2)).to(trajs.dtype), labels
+
+
 def _radius_vector(radius, n: int) -> torch.Tensor:
     """radius, a number or [n] values, as a float64 CPU tensor [n] of positive finite numbers (ValueError otherwise)."""
     try:
@@ -898,7 +926,7 @@ def _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin):
 def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerFrame: int, image_props: Optional[dict] = None,
                    margin: Optional[float] = None, lifetimes=None, generator: Optional[torch.Generator] = None, device="cpu",
                    blink=None, alphas=None, geometry=None, geometry_of=None, boundary="clamp", states=None, drift=None, camera=None,
-                   confinement=None):
+                   confinement=None, velocity=None):
     """A field of view with known truth -> (movie [F, H, W] float32 on `device`, truth).
 
     n_particles free Brownian particles: start positions uniform in [margin, H - 1 - margin] x [margin, W - 1 - margin]
@@ -972,7 +1000,15 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     with a step of 1 / nPosPerFrame frames): radius is the RMS distance from the centre in 2-D in pixels, sqrt(2 s2), and D the
     diffusion coefficient inside the well.  z = randn(Np, T, 2) is drawn where the Brownian steps are and the particle starts
     at the centre.  truth gains radius [Np] float64 and centre [Np, 2] float64 (y, x).  Not together with alphas, geometry or
-    states (ValueError); drift moves the wells with the stage.  What helpers/msd.estimate_confinement_ml estimates."""
+    states (ValueError); drift moves the wells with the stage.  What helpers/msd.estimate_confinement_ml estimates.
+
+    velocity (default None: no directed motion, the code path without it): a pair (vy, vx) or [Np, 2] values in pixels per
+    frame, the constant velocity of every particle on top of its diffusion (motor-driven transport, flow).  velocity * (t /
+    nPosPerFrame) is added to sub-position t once the trajectories are built and before drift, in float64, rounded once, the
+    way drift is added; truth["y"], truth["x"] are the means of the moved sub-positions.  Nothing is drawn for it; a zero
+    velocity gives the movie and the truth of velocity = None bit for bit.  truth gains velocity [Np, 2] float64.  Allowed with
+    free motion, alphas and states; with a geometry or confinement it is a ValueError.  helpers/msd.estimate_drift removes
+    whatever velocity all tracks share: what helpers/msd.estimate_directed_ml finds after it is each particle's own."""
     props = dict(DEFAULT_IMAGE_PROPS)
     props.update(image_props or {})
     Np, F_, npos, H, W = int(n_particles), int(n_frames), int(nPosPerFrame), int(H), int(W)
@@ -1020,6 +1056,11 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError("drift must be finite")
         if drift_f.dim() == 1:
             drift_f = torch.arange(F_, dtype=torch.float64).view(F_, 1) * drift_f.view(1, 2)
+    vel = None
+    if velocity is not None:
+        if geometry is not None or confinement is not None:
+            raise ValueError("velocity cannot be combined with a geometry or confinement")
+        vel = _velocity_matrix(velocity, Np)
     cam = None
     if camera is not None:
         if not isinstance(camera, dict) or "background" not in camera or set(camera) - {"background", "gain", "offset", "read_noise"}:
@@ -1112,6 +1153,10 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             if T:
                 steps[:, 0] = 0.0
             pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
+    if vel is not None:
+        vel = vel.to(dev)
+        sub = torch.arange(T, dtype=torch.float64, device=dev) / npos
+        pos = (pos.double() + vel.view(Np, 1, 2) * sub.view(1, T, 1)).float()                    # rounded once
     if drift_f is not None:
         drift_f = drift_f.to(dev)
         pos = (pos.double() + drift_f.repeat_interleave(npos, dim=0).view(1, T, 2)).float()     # rounded once
@@ -1158,6 +1203,8 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
         truth["arc"], truth["edge"], truth["geometry_id"] = arc.to(dev), edge.to(dev), torch.from_numpy(geom_id).to(dev)
     if drift_f is not None:
         truth["drift"] = drift_f
+    if vel is not None:
+        truth["velocity"] = vel
     if well is not None:
         truth["radius"], truth["centre"] = well.to(dev), start.double().to(dev)
     if cam is not None:

@@ -1580,3 +1580,223 @@ def estimate_confinement_ml(positions, offsets, variances=None, frames=None, use
     with np.errstate(invalid="ignore"):                                    # arrays: -inf - -inf where no candidate was accepted
         out["lr_brownian"] = 2.0 * (out["loglik"] - brownian)
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# maximum-likelihood velocity per track from rows of known variance, with error bars (csrc/directed_ml.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _directed_cost(Dc, d, g, V, inc, dt, R, given=False):
+    """-2 log L of csrc/directed_ml.hip::dm_cost for the candidates Dc [n, C] of n ranges at once: d [n, >= inc[0], 2] the
+    increments LESS THE SHARE OF THE VELOCITY THE RECURRENCE RUNS ABOUT (the unweighted one, or the caller's), g [n, >=
+    inc[0]] their gaps in frames, V [n, >= inc[0] + 1, 2] the row variances, inc [n] >= 1 the increments of each range IN
+    DESCENDING ORDER; given: the quadratic form is A (the velocity stands), else A - B B / C (the velocity is profiled) ->
+    (cost [n, C], B / C [n, C, 2] what the profiled velocity adds to the one d was taken about, C [n, C, 2]).  Elementwise
+    the kernel's operations in its order (include/mivit_hip.h, mivit_track_directed_ml); the two differ in log alone."""
+    n, C = Dc.shape
+    c1 = (2.0 * Dc) * dt
+    cR, tR = R * c1, 2.0 * R
+    pm, pe = np.full((n, C), 0.5), np.ones((n, C), np.int64)
+    bad = np.zeros((n, C), bool)
+    rinv, z, w = np.zeros((2, n, C)), np.zeros((2, n, C)), np.zeros((2, n, C))
+    A, B, Cc = np.zeros((2, n, C)), np.zeros((2, n, C)), np.zeros((2, n, C))
+    with np.errstate(all="ignore"):
+        for k in range(int(inc[0]) if n else 0):
+            na = int(np.count_nonzero(inc > k))
+            gk = g[:na, k].astype(np.float64)
+            base = c1[:na] * (gk - tR)[:, None]
+            m = (gk * dt)[:, None]
+            for ax in (0, 1):
+                pv, v, dd = V[:na, k, ax][:, None], V[:na, k + 1, ax][:, None], d[:na, k, ax][:, None]
+                a = (base + pv) + v
+                if k == 0:
+                    e, zz, ww = a, np.broadcast_to(dd, a.shape), np.broadcast_to(m, a.shape)
+                else:
+                    b = cR[:na] - pv
+                    l = b * rinv[ax, :na]
+                    e = a - l * b
+                    zz = dd - l * z[ax, :na]
+                    ww = m - l * w[ax, :na]
+                bad[:na] |= ~(e > 0.0)
+                r = 1.0 / e
+                A[ax, :na] = A[ax, :na] + (zz * zz) * r
+                B[ax, :na] = B[ax, :na] + (zz * ww) * r
+                Cc[ax, :na] = Cc[ax, :na] + (ww * ww) * r
+                _ml_prod_mul(pm, pe, e)
+                rinv[ax, :na], z[ax, :na], w[ax, :na] = r, zz, ww
+        bad |= ~((Cc[0] > 0.0) & (Cc[0] < np.inf) & (Cc[1] > 0.0) & (Cc[1] < np.inf))
+        Q = A[0] + A[1] if given else (A[0] - (B[0] * B[0]) / Cc[0]) + (A[1] - (B[1] * B[1]) / Cc[1])
+        cost = _ml_finish_cost(pm, pe, Q, inc, bad)
+        return cost, np.moveaxis(B / Cc, 0, 2), np.moveaxis(Cc, 0, 2)
+
+
+def _directed_rows(pos, var, frames, offsets, rows, sel, inc, dt, velocity=None):
+    """What the two restatements of csrc/directed_ml.hip share: the padded rows of the ranges sel -> (d [ns, M, 2] the
+    increments less the velocity's share, the velocity being `velocity` [ns, 2] or, where None, the unweighted one (last
+    usable position - first) / (G dt) of dm_start; g [ns, M] the gaps; V the variances; that velocity [ns, 2])"""
+    X, V, Fr = _ml_padded(rows, sel, pos, var, frames, offsets)
+    g = Fr[:, 1:] - Fr[:, :-1]
+    live = np.arange(g.shape[1])[None, :] < inc[:, None]
+    with np.errstate(all="ignore"):
+        if velocity is None:
+            T = np.where(live, g, 0).sum(axis=1).astype(np.float64) * dt
+            velocity = (X[np.arange(len(sel)), inc] - X[:, 0]) / T[:, None]
+        m = g.astype(np.float64) * dt
+        d = (X[:, 1:] - X[:, :-1]) - velocity[:, None, :] * m[:, :, None]
+    return d, g, V, velocity
+
+
+def _directed_ml_numpy(pos, var, frames, use, offsets, dt, R):
+    """The arithmetic of csrc/directed_ml.hip::dm_kernel in its order (include/mivit_hip.h, mivit_track_directed_ml), all
+    ranges at once: the arguments of _diffusion_ml_numpy -> (D, D_std [n] float64, velocity, velocity_std [n, 2] float64,
+    loglik [n] float64, n_increments, status [n] int32).  The same two recurrences, three sums, determinant by frexp and
+    search; np.argmin returns the lowest index among equal minima.  Differs from the kernel in log and exp2 alone."""
+    n = len(offsets) - 1
+    D, D_std, loglik = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
+    vel, vel_std = np.full((n, 2), np.nan), np.full((n, 2), np.nan)
+    status = np.ones(n, np.int32)
+    rows = _ml_usable(pos, var, frames, use, offsets)
+    n_inc = np.array([max(len(r) - 1, 0) for r in rows], np.int32).reshape(n)
+    sel = np.nonzero(n_inc >= 2)[0]
+    if not len(sel):
+        return D, D_std, vel, vel_std, loglik, n_inc, status
+    sel = sel[np.argsort(-n_inc[sel], kind="stable")]                      # descending: the ranges still running are a prefix
+    inc = n_inc[sel].astype(np.int64)
+    ns = len(sel)
+    d, g, V, u0 = _directed_rows(pos, var, frames, offsets, rows, sel, inc, dt)
+    with np.errstate(all="ignore"):
+        D_ref = _ml_d_ref(d, g, inc, dt)
+        lo, hi = np.full(ns, _ML_U_LO), np.full(ns, _ML_U_HI)
+        all_lo, all_hi = np.ones(ns, bool), np.ones(ns, bool)
+        lane, each = np.arange(_ML_CANDIDATES, dtype=np.float64), np.arange(ns)
+        Db = np.zeros(ns)
+        for _ in range(_ML_ROUNDS):
+            step = (hi - lo) / 63.0
+            Dj = D_ref[:, None] * np.exp2(lo[:, None] + lane[None, :] * step[:, None])
+            j = np.argmin(_directed_cost(Dj, d, g, V, inc, dt, R)[0], axis=1)
+            all_lo &= j == 0
+            all_hi &= j == _ML_CANDIDATES - 1
+            Db = Dj[each, j]
+            jl, jh = np.maximum(j - 1, 0), np.minimum(j + 1, _ML_CANDIDATES - 1)
+            lo, hi = lo + jl.astype(np.float64) * step, lo + jh.astype(np.float64) * step
+        st = np.where(all_lo, 2, np.where(all_hi, 3, 0)).astype(np.int32)
+        Db = np.where(all_lo, 0.0, Db)
+        c, bc, Cc = _directed_cost(np.stack([Db, Db * _ML_EXP_H, Db * _ML_EXP_MH], axis=1), d, g, V, inc, dt, R)
+        info = _ml_curvature(c[:, 1], c[:, 0], c[:, 2])
+        curved = (info > 0.0) & (info < np.inf)
+        fine = (c[:, 0] < np.inf)[:, None]
+        D[sel], loglik[sel] = Db, -0.5 * c[:, 0]
+        D_std[sel] = np.where(curved & (st != 2), Db / np.sqrt(info), np.nan)
+        vel[sel] = np.where(fine, u0 + bc[:, 0, :], np.nan)
+        vel_std[sel] = np.where(fine, 1.0 / np.sqrt(Cc[:, 0, :]), np.nan)
+        status[sel] = np.where(~curved & (st == 0), 4, st)
+    return D, D_std, vel, vel_std, loglik, n_inc, status
+
+
+def _directed_loglik_numpy(pos, var, frames, use, offsets, dt, R, D, velocity):
+    """csrc/directed_ml.hip's mivit_track_directed_loglik restated, all ranges at once -> (loglik [n], velocity [n, 2],
+    velocity_std [n, 2]) float64: loglik NaN for a range without an increment and where D is negative or not finite or a
+    given velocity is not finite, -inf for a rejected candidate; the velocity of the fit and its standard error, NaN where
+    loglik is not finite"""
+    n = len(offsets) - 1
+    loglik, vel, vel_std = np.full(n, np.nan), np.full((n, 2), np.nan), np.full((n, 2), np.nan)
+    rows = _ml_usable(pos, var, frames, use, offsets)
+    cnt = np.array([len(r) for r in rows], np.int64)
+    with np.errstate(invalid="ignore"):
+        fine = (cnt >= 2) & (D >= 0.0) & (D < np.inf)
+        if velocity is not None:
+            fine &= np.isfinite(velocity).all(axis=1)
+    sel = np.nonzero(fine)[0]
+    if not len(sel):
+        return loglik, vel, vel_std
+    sel = sel[np.argsort(-cnt[sel], kind="stable")]
+    inc = cnt[sel] - 1
+    d, g, V, u = _directed_rows(pos, var, frames, offsets, rows, sel, inc, dt, None if velocity is None else velocity[sel])
+    cost, bc, Cc = _directed_cost(D[sel][:, None], d, g, V, inc, dt, R, given=velocity is not None)
+    with np.errstate(all="ignore"):
+        has = (cost[:, 0] < np.inf)[:, None]
+        loglik[sel] = -0.5 * cost[:, 0]
+        vel[sel] = np.where(has, u + bc[:, 0, :], np.nan)
+        vel_std[sel] = np.where(has, 1.0 / np.sqrt(Cc[:, 0, :]), np.nan)
+    return loglik, vel, vel_std
+
+
+def _check_blur(blur):
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
+
+
+def directed_loglik(positions, offsets, D, velocity=None, variances=None, frames=None, use=None, dt=1.0, blur=0.0):
+    """The exact log-likelihood of every range under directed motion: diffusion with the coefficient D (a number, or one per
+    range [n]) plus a constant velocity ((y, x) in pixels per unit of dt as [2] or [n, 2]; None: each axis takes the velocity
+    that maximises the likelihood), seen through localisation noise of the rows' variances and motion blur: the model of
+    estimate_directed_ml at given parameters, to compare hypotheses with -> dict of the input's kind: loglik [n] float64 (NaN
+    for a range without an increment and where D is negative or not finite or a given velocity is not finite, -inf where the
+    covariance is not positive definite), and with velocity=None also velocity [n, 2] and velocity_std [n, 2], the profiled
+    velocity and its standard error at that D.  With velocity 0 it is the likelihood of estimate_diffusion_ml at D.  The
+    other arguments are those of estimate_diffusion_ml.  CUDA tensors go to the kernel (csrc/directed_ml.hip), arrays and
+    CPU tensors to the numpy restatement."""
+    _check_blur(blur)
+    args = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    n, device = args[2].numel() - 1, args[1].device
+    Dv = _ml_per_range(D, n, "D", device)
+    vv = None if velocity is None else _ml_per_range(velocity, n, "velocity", device, 2)
+    keys = ("loglik", "velocity", "velocity_std") if vv is None else ("loglik",)
+
+    def restated(*rows):
+        got = _directed_loglik_numpy(*rows, float(dt), float(blur), Dv.numpy(), None if vv is None else vv.numpy())
+        return got if vv is None else got[0]
+
+    return _ml_dispatch(args, lambda ops, pos, off, var, fr, usable: ops.track_directed_loglik(pos, off, Dv, vv, var, fr, usable,
+                                                                                                float(dt), float(blur)),
+                        restated, keys)
+
+
+_DM_OUTS = ("D_dir", "D_dir_std", "velocity", "velocity_std", "loglik", "n_increments", "status")
+
+
+def estimate_directed_ml(positions, offsets, variances=None, frames=None, use=None, dt=1.0, blur=0.0):
+    """The maximum-likelihood velocity of every track with its standard error, and the test of whether the track is directed
+    at all, from rows that each carry their own localisation variance: positions, offsets, variances, frames, use, dt and
+    blur as estimate_diffusion_ml takes them -> dict of the input's kind:
+        D_dir, D_dir_std        [n] float64     the diffusion coefficient about the directed path; 0 at status 2
+        velocity, velocity_std  [n, 2] float64  (y, x) in pixels per unit of dt, and its standard error 1 / sqrt(C) at D_dir
+        speed, speed_std        [n] float64     |velocity| and its standard error by the delta method, sqrt(vy^2 sy^2 + vx^2
+                                                sx^2) / speed (NaN at speed 0)
+        loglik                  [n] float64     the log-likelihood at the estimates
+        lr_brownian             [n] float64     2 (loglik - the loglik of estimate_diffusion_ml(..., blur=blur)): the likelihood
+                                                ratio against free diffusion, which the model nests at velocity 0; >= 0 up to
+                                                the resolution of the searches
+        p_brownian              [n] float64     exp(-lr_brownian / 2), the chi^2 survival function at 2 degrees of freedom: 1
+                                                where lr_brownian <= 0, NaN where either fit has status 1
+        n_increments            [n] int64       the increments between usable rows
+        status                  [n] int64       0 fine; 1 fewer than 2 increments (NaN); 2 the minimum at the lower end of the
+                                                search: the track is a straight line within its noise (D_dir 0, D_dir_std NaN;
+                                                velocity and velocity_std stand where the likelihood at D = 0 is finite); 3 at
+                                                its upper end; 4 the curvature is not positive (D_dir_std NaN)
+    The increments of a track are Gaussian with the tridiagonal covariance of estimate_diffusion_ml about velocity * gap *
+    dt (an exposure average shifts every row of a constant-velocity track alike, so blur leaves the mean alone).  The
+    velocity enters linearly and is profiled out in closed form inside the LDL^T recurrence: a second recurrence on the
+    regressor gap * dt and three sums per axis, u = B / C with the variance 1 / C at fixed D; mean and covariance parameters
+    of a Gaussian share no Fisher information, so these are the bars at D_dir, and D_dir_std comes from the curvature of the
+    profile likelihood in ln D.  The search is that of estimate_diffusion_ml, about a D_ref taken from the residuals about the
+    unweighted velocity (last usable position - first) / elapsed time, so that a velocity added to a track changes the
+    velocity by that much and nothing else (include/mivit_hip.h has every operation).  This is plain maximum likelihood, not
+    REML, so that lr_brownian compares nested models on the same data: D_dir is low by about one part in n_increments (the
+    velocity is fitted to the same rows), a mean pull of ln D of about -0.27 on tracks of 100 rows.  estimate_drift removes
+    whatever velocity all tracks share; what this fit sees after it is each track's own.  CUDA tensors go to the kernel
+    (csrc/directed_ml.hip: one wave per track, no limit on its length), arrays and CPU tensors to the numpy restatement,
+    which differs from it in log and exp2 alone."""
+    _check_blur(blur)
+    args = _ml_arguments(positions, offsets, variances, frames, use, dt)
+    free = estimate_diffusion_ml(positions, offsets, variances, frames, use, dt, blur=blur)
+    out = _ml_dispatch(args, lambda ops, pos, off, var, fr, usable: ops.track_directed_ml(pos, off, var, fr, usable, float(dt),
+                                                                                         float(blur)),
+                       lambda *rows: _directed_ml_numpy(*rows, float(dt), float(blur)), _DM_OUTS)
+    xp = torch if args[0] else np
+    v, s = out["velocity"], out["velocity_std"]
+    with np.errstate(invalid="ignore", divide="ignore"):                   # arrays: 0 / 0 at speed 0, -inf - -inf
+        out["speed"] = xp.sqrt(v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1])
+        out["speed_std"] = xp.sqrt((v[:, 0] * v[:, 0]) * (s[:, 0] * s[:, 0]) + (v[:, 1] * v[:, 1]) * (s[:, 1] * s[:, 1])) / out["speed"]
+        out["lr_brownian"] = 2.0 * (out["loglik"] - free["loglik"])
+        out["p_brownian"] = xp.exp(-0.5 * out["lr_brownian"].clip(min=0.0))
+    return out

@@ -2136,7 +2136,7 @@ def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None, fra
 
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
                              batch_size=4096, segment=None, states=None, drift=None, localization=None, ml=None, anomalous=None,
-                             confined=None, **tracking_kwargs):
+                             confined=None, directed=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -2216,7 +2216,33 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     the frames of the table, a filled row is a gap).  The result gains radius_ml, radius_ml_std, D_conf, lambda_ml,
     lr_confined (float64; estimate_confinement_ml's radius, radius_std, D_conf, lambda and lr_brownian) and confined_status
     (int64) [n_tracks], and "confined": what estimate_confinement_ml was called with (positions, variances, frames, use).
-    Tracks only."""
+    Tracks only.
+
+    directed (default None: the code path without it): a dict with keys among blur and sigma2 ({} for the defaults), the
+    arguments of helpers/msd.estimate_directed_ml (csrc/directed_ml.hip), the maximum-likelihood velocity of every track
+    with a standard error and the likelihood ratio against free diffusion.  blur and sigma2 follow the rules of ml, and so
+    do the rows used and the positions (the frames of the table, a filled row is a gap); it runs after drift, so the
+    velocity that all tracks share is gone and what it reports is each track's own.  The result gains velocity_ml,
+    velocity_ml_std [n_tracks, 2] ((y, x) in pixels per unit of dt), speed_ml, speed_ml_std, D_dir, D_dir_std, lr_directed,
+    p_directed (float64; estimate_directed_ml's velocity, velocity_std, speed, speed_std, D_dir, D_dir_std, lr_brownian and
+    p_brownian) and directed_status (int64) [n_tracks], and "directed": what estimate_directed_ml was called with (positions,
+    variances, frames, use, blur).  Tracks only: the function takes any CSR offsets, so segments["seg_offsets"] or
+    states["run_offsets"] can be passed to it with the arguments reported here."""
+    if directed is not None:
+        if not isinstance(directed, dict) or set(directed) - {"blur", "sigma2"}:
+            raise ValueError("directed must be None or a dict with keys among blur and sigma2")
+        directed = dict(directed)
+        directed.setdefault("blur", 0.0)
+        directed.setdefault("sigma2", "crlb" if localization is not None else 0.0)
+        if isinstance(directed["sigma2"], str):
+            if directed["sigma2"] != "crlb":
+                raise ValueError(f"directed['sigma2'] must be a number or 'crlb', got {directed['sigma2']!r}")
+            if localization is None:
+                raise ValueError("directed['sigma2'] = 'crlb' needs localization: the least-squares fit returns no bound")
+        elif not 0.0 <= float(directed["sigma2"]) < float("inf"):
+            raise ValueError(f"directed['sigma2'] must be >= 0 and finite, got {directed['sigma2']}")
+        if not 0.0 <= float(directed["blur"]) <= 0.25:
+            raise ValueError(f"directed['blur'] must lie in [0, 1/4], got {directed['blur']}")
     if confined is not None:
         if not isinstance(confined, dict) or set(confined) - {"sigma2"}:
             raise ValueError("confined must be None or a dict that may hold sigma2")
@@ -2365,6 +2391,15 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
             cf_args = {"variances": float(confined["sigma2"]), "use": None if filled is None else ~filled}
         cf_args.update(frames=fr)
         cf_tracks = _msd.estimate_confinement_ml(pos, offsets, dt=dt, **cf_args)
+    if directed is not None:
+        from . import msd as _msd
+        filled = by_track[5] if len(by_track) > 5 else None
+        if directed["sigma2"] == "crlb":
+            dm_args = {"variances": torch.stack([fit["y_std"] * fit["y_std"], fit["x_std"] * fit["x_std"]], dim=1), "use": good}
+        else:
+            dm_args = {"variances": float(directed["sigma2"]), "use": None if filled is None else ~filled}
+        dm_args.update(frames=fr, blur=float(directed["blur"]))
+        dm_tracks = _msd.estimate_directed_ml(pos, offsets, dt=dt, **dm_args)
     seq, seq_track, _ = track_sequences(movie, fr, y, x, offsets, seq_len, patch_size, norm, tail)
     n_sequences = torch.bincount(seq_track, minlength=n_tracks)
     model.eval()
@@ -2436,6 +2471,12 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["radius_ml"], res["radius_ml_std"], res["D_conf"] = cf_tracks["radius"], cf_tracks["radius_std"], cf_tracks["D_conf"]
         res["lambda_ml"], res["lr_confined"], res["confined_status"] = cf_tracks["lambda"], cf_tracks["lr_brownian"], cf_tracks["status"]
         res["confined"] = dict(cf_args, positions=pos)
+    if directed is not None:
+        for k, key in (("velocity_ml", "velocity"), ("velocity_ml_std", "velocity_std"), ("speed_ml", "speed"),
+                       ("speed_ml_std", "speed_std"), ("D_dir", "D_dir"), ("D_dir_std", "D_dir_std"), ("lr_directed", "lr_brownian"),
+                       ("p_directed", "p_brownian"), ("directed_status", "status")):
+            res[k] = dm_tracks[key]
+        res["directed"] = dict(dm_args, positions=pos)
     return res
 
 

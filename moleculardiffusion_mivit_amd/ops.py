@@ -1396,7 +1396,62 @@ def track_confined_loglik(pos: torch.Tensor, offsets: torch.Tensor, D: torch.Ten
     return loglik
 
 
-DRIFT_MAX_PAIRS = 4096       # csrc/drift.hip: increments of one frame that the median sorts in LDS (8 B a pair, 32 KiB)
+def _directed_ml_check(name, blur):
+    """the check of their own that track_directed_ml and track_directed_loglik hand to _track_ml_args"""
+    def check(n):
+        if not 0.0 <= float(blur) <= 0.25:
+            raise ValueError(f"{name}: the blur coefficient must lie in [0, 1/4], got {blur}")
+    return check
+
+
+def track_directed_ml(pos: torch.Tensor, offsets: torch.Tensor, var=None, frames=None, use=None, dt: float = 1.0,
+                      blur: float = 0.0):
+    """The maximum-likelihood velocity and diffusion coefficient of every row range under directed motion, with error bars
+    (csrc/directed_ml.hip, mivit_track_directed_ml): the model of track_diffusion_ml about a mean velocity * gap * dt, the
+    velocity of each axis profiled out in closed form; the arguments of track_diffusion_ml -> (D, D_std [n] float64, velocity,
+    velocity_std [n, 2] float64 (y, x) in pixels per unit of dt, loglik [n] float64, n_increments, status [n] int32).  One
+    launch, one wave per range, no workspace; a range has no maximum length.  See include/mivit_hip.h for the arithmetic and
+    the status codes and helpers/msd.estimate_directed_ml for the front end."""
+    name = "track_directed_ml"
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt,
+                                                               _directed_ml_check(name, blur))
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=pos.device)         # noqa: E731
+    D, D_std, v, v_std, loglik = f64(n), f64(n), f64(n, 2), f64(n, 2), f64(n)
+    n_inc, status = (torch.empty(n, dtype=torch.int32, device=pos.device) for _ in range(2))
+    N.check(N.lib.mivit_track_directed_ml(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt), float(blur),
+                                          _p(D), _p(D_std), _p(v), _p(v_std), _p(loglik), _p(n_inc), _p(status), _s(pos)),
+            "mivit_track_directed_ml")
+    return D, D_std, v, v_std, loglik, n_inc, status
+
+
+def track_directed_loglik(pos: torch.Tensor, offsets: torch.Tensor, D: torch.Tensor, velocity=None, var=None, frames=None,
+                          use=None, dt: float = 1.0, blur: float = 0.0):
+    """The exact log-likelihood of every row range under directed motion at given parameters (csrc/directed_ml.hip,
+    mivit_track_directed_loglik): pos, offsets, var, frames, use, dt, blur as track_diffusion_ml; D [n] float64 the diffusion
+    coefficient of every range; velocity [n, 2] float64 (y, x), or None for the velocity that maximises the likelihood ->
+    loglik [n] float64 with a velocity given, (loglik, velocity [n, 2], velocity_std [n, 2]) with None.  loglik is NaN without
+    an increment and where D is negative or not finite or a given velocity is not finite, -inf for a rejected candidate.  See
+    include/mivit_hip.h for the arithmetic and helpers/msd.directed_loglik for the front end."""
+    name = "track_directed_loglik"
+    pos, offsets, var, frames, use, n_rows, n = _track_ml_args(name, pos, offsets, var, frames, use, dt,
+                                                               _directed_ml_check(name, blur))
+    D = _seg_tensor(D, torch.float64, 1, name, "D [n]")
+    if D.numel() != n or D.device != pos.device:
+        raise ValueError(f"{name}: D must be [{n}] on the device of pos, got {tuple(D.shape)}")
+    if velocity is not None:
+        velocity = _seg_tensor(velocity, torch.float64, 2, name, "velocity [n, 2]")
+        if tuple(velocity.shape) != (n, 2) or velocity.device != pos.device:
+            raise ValueError(f"{name}: velocity must be [{n}, 2] on the device of pos, got {tuple(velocity.shape)}")
+    loglik = torch.empty(n, dtype=torch.float64, device=pos.device)
+    v_hat, v_hat_std = (None, None) if velocity is not None else (torch.empty(n, 2, dtype=torch.float64, device=pos.device)
+                                                                  for _ in range(2))
+    N.check(N.lib.mivit_track_directed_loglik(_p(pos), _p(var), _p(frames), _p(use), n_rows, _p(offsets), n, float(dt),
+                                              float(blur), _p(D), _p(velocity), _p(loglik), _p(v_hat), _p(v_hat_std), _s(pos)),
+            "mivit_track_directed_loglik")
+    return loglik if velocity is not None else (loglik, v_hat, v_hat_std)
+
+
+DRIFT_MAX_PAIRS = 4096      # csrc/drift.hip: increments of one frame that the median sorts in LDS (8 B a pair, 32 KiB)
 DRIFT_MODES = {"mean": 0, "median": 1}
 
 

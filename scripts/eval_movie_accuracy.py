@@ -58,6 +58,12 @@ track, radius_ml, radius_ml_std, D_conf, lambda_ml, lr_confined and confined_sta
 csrc/confined_ml.hip, through estimate_track_diffusion(..., confined={"sigma2": SIGMA2})), over the matched tracks of at least
 20 rows and status 0 the median radius and D against the truth and the pull of ln radius, and the quantiles of lr_confined on
 that movie and on a FREE Brownian movie of the same settings: the null distribution from which a threshold is picked.
+--velocity SPEED gives every particle that speed (pixels per frame) in a seeded random direction (simulate_movie's velocity),
+and --directed-ml [SIGMA2] (with --velocity) adds, per track, velocity_ml, speed_ml, D_dir, lr_directed, p_directed and
+directed_status (helpers/msd.estimate_directed_ml, csrc/directed_ml.hip, through estimate_track_diffusion(..., directed={"blur":
+R, "sigma2": SIGMA2}), R = 1/6 with --npos > 1), over the matched tracks of at least 20 rows and status 0 the median speed
+against the truth, the RMS pull of both velocity components, D_dir against the truth and the quantiles of lr_directed, and
+from the same seed WITHOUT velocity the null quantiles and the fraction with p_directed < 0.05.
 --detector lrt [--p-fa P] (with --camera) adds "detector": score_tracking's recall, precision and RMSE of the difference of
 Gaussians and of the likelihood-ratio detector at the per-pixel false-alarm probability P (default 1e-6; csrc/detect.hip,
 track_particles_tensors(..., detector={...})) on the same movie with the same linking, also printed to stderr.  A
@@ -70,13 +76,14 @@ tool, not a test: it asserts no accuracy.
                                           [--states 0.02 0.5 0.98] [--penalties 1 2 3 4 6 8] [--hmm 2]
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
                                           [--camera 10,2,100,1.5] [--detector lrt [--p-fa 1e-6]] [--mle] [--neighbours [4]] [--ml [0.1667]] [--intensity 300]
-                                          [--confined 3.0] [--confined-ml [0.01]]
+                                          [--confined 3.0] [--confined-ml [0.01]] [--velocity 0.2] [--directed-ml [0.01]]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
 """
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -130,6 +137,49 @@ def confined_scores(movie, model, args, norm, score, est, rows, props, drift, ca
     return out
 
 
+def directed_scores(movie, model, args, norm, truth, score, est, rows, props, drift, camera):
+    """--directed-ml: estimate_track_diffusion(..., directed={"blur": R, "sigma2": SIGMA2}) on the movie of directed particles,
+    held against the velocity and the D it was simulated with over the matched tracks of at least 20 rows, and on a movie of
+    the same settings and seed WITHOUT velocity, whose lr_directed is the null distribution (chi^2 with 2 degrees of freedom
+    if the model holds) and whose fraction with p_directed < 0.05 is the false-positive rate of that threshold.  SIGMA2 as for
+    --alpha-ml: the number given, or half the squared RMSE of the matched rows.  The movie's positions are frame means: with
+    --npos > 1 the exposure is the whole frame, R = 1/6."""
+    sigma2 = args.directed_ml if args.directed_ml >= 0 else float(score["rmse"]) ** 2 / 2.0
+    kw = dict(norm=norm, max_gap=args.max_gap, directed={"blur": 1.0 / 6.0 if args.npos > 1 else 0.0, "sigma2": sigma2},
+              **({} if drift is None else {"drift": {}}))
+    dm = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, **kw)
+    assert torch.equal(dm["track_id"], est["track_id"])
+    for row, v, sp, dd, lr, pv, st in zip(rows, dm["velocity_ml"].tolist(), dm["speed_ml"].tolist(), dm["D_dir"].tolist(),
+                                          dm["lr_directed"].tolist(), dm["p_directed"].tolist(), dm["directed_status"].tolist()):
+        row.update(velocity_ml=v, speed_ml=sp, D_dir=dd, lr_directed=lr, p_directed=pv, directed_status=st)
+    pid = score["particle_id"]
+    long = (est["length"] >= 20) & (pid >= 0)
+    fine = long & (dm["directed_status"] == 0)
+    nan = float("nan")
+    med = lambda v, m: float(v[m].median()) if bool(m.any()) else nan                       # noqa: E731
+    quantiles = lambda v: [float(q) for q in torch.quantile(v, torch.tensor([0.05, 0.25, 0.5, 0.75, 0.95, 0.99], dtype=v.dtype, device=v.device))]   # noqa: E731
+    v_true = truth["velocity"][pid.clamp_min(0)]
+    pull = ((dm["velocity_ml"] - v_true) / dm["velocity_ml_std"])[fine]
+    out = {"sigma2": sigma2, "blur": kw["directed"]["blur"], "n_tracks": int(long.sum()), "n_status_0": int(fine.sum()),
+           "status_counts": torch.bincount(dm["directed_status"][long], minlength=5).tolist(),
+           "speed_true": args.velocity, "speed_ml_median": med(dm["speed_ml"], fine),
+           "rms_pull_velocity": float(pull.pow(2).mean().sqrt()) if bool(fine.any()) else nan,
+           "D_true_median": med(score["D_true"], fine), "D_dir_median": med(dm["D_dir"], fine), "D_msd_median": med(est["D_msd"], fine),
+           "fraction_p_directed_below_0.05": float((dm["p_directed"][fine] < 0.05).double().mean()) if bool(fine.any()) else nan,
+           "lr_directed_quantiles_5_25_50_75_95_99": quantiles(dm["lr_directed"][fine]) if bool(fine.any()) else []}
+    g = torch.Generator(device="cuda").manual_seed(args.seed)
+    H, W = args.size
+    free_movie, _ = gen.simulate_movie(args.particles, args.frames, H, W, tuple(args.D), args.npos, image_props=props, generator=g,
+                                       device="cuda", blink=args.blink, **({} if drift is None else {"drift": drift}),
+                                       **({} if camera is None else {"camera": camera}))
+    free = trk.estimate_track_diffusion(free_movie, model, args.seq_len, args.patch_size, **kw)
+    ok = (free["length"] >= 20) & (free["directed_status"] == 0)
+    out["free_movie"] = {"n_tracks": int(ok.sum()), "status_counts": torch.bincount(free["directed_status"][free["length"] >= 20], minlength=5).tolist(),
+                         "fraction_p_directed_below_0.05": float((free["p_directed"][ok] < 0.05).double().mean()) if bool(ok.any()) else nan,
+                         "lr_directed_quantiles_5_25_50_75_95_99": quantiles(free["lr_directed"][ok]) if bool(ok.any()) else []}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint")
@@ -163,6 +213,8 @@ def main():
     ap.add_argument("--intensity", type=float, default=None, metavar="PEAK")
     ap.add_argument("--confined", type=float, default=None, metavar="RADIUS")
     ap.add_argument("--confined-ml", type=float, nargs="?", const=-1.0, default=None, metavar="SIGMA2")
+    ap.add_argument("--velocity", type=float, default=None, metavar="SPEED")
+    ap.add_argument("--directed-ml", type=float, nargs="?", const=-1.0, default=None, metavar="SIGMA2")
     ap.add_argument("--detector", choices=["lrt"], default=None)
     ap.add_argument("--p-fa", type=float, default=1e-6, metavar="P")
     args = ap.parse_args()
@@ -189,6 +241,14 @@ def main():
         raise SystemExit("--confined-ml needs --confined: it is held against the radius the movie was simulated with")
     if args.confined is not None and (args.alpha is not None or args.cristae is not None or args.states is not None):
         raise SystemExit("--confined cannot be combined with --alpha, --cristae or --states")
+    if args.directed_ml is not None and args.velocity is None:
+        raise SystemExit("--directed-ml needs --velocity: it is held against the velocity the movie was simulated with")
+    if args.velocity is not None and (args.confined is not None or args.cristae is not None or args.states is not None):
+        raise SystemExit("--velocity cannot be combined with --confined, --cristae or --states")
+    directed = {}
+    if args.velocity is not None:                            # a generator of its own: the movie's draws stay those without velocity
+        phi = torch.rand(args.particles, generator=torch.Generator().manual_seed(args.seed), dtype=torch.float64) * (2.0 * math.pi)
+        directed = {"velocity": args.velocity * torch.stack([torch.sin(phi), torch.cos(phi)], dim=1)}
     drift = None
     if args.drift is not None:
         try:
@@ -225,7 +285,7 @@ def main():
                                       image_props=props, generator=g, device="cuda", blink=args.blink, alphas=args.alpha,
                                       states=states, **confine, **({} if drift is None else {"drift": drift}),
                                       **({} if camera is None else {"camera": camera}),
-                                      **({} if args.confined is None else {"confinement": {"radius": args.confined}}))
+                                      **({} if args.confined is None else {"confinement": {"radius": args.confined}}), **directed)
     model = M.GeneralTransformer(M.LinearProjectionEmbedding, dict(patch_size=args.patch_size, embed_dim=64), 64, 4, 128, 2,
                                  M.MLPHead, F.relu).cuda()
     if args.checkpoint:
@@ -300,6 +360,10 @@ def main():
         out["confined_radius"] = args.confined
         if args.confined_ml is not None:
             out["confined_ml"] = confined_scores(movie, model, args, norm, score, est, out["tracks"], props, drift, camera)
+    if args.velocity is not None:
+        out["velocity"] = args.velocity
+        if args.directed_ml is not None:
+            out["directed_ml"] = directed_scores(movie, model, args, norm, truth, score, est, out["tracks"], props, drift, camera)
     if drift is not None:
         out["drift"] = drift_scores(movie, model, args, norm, truth, score, est, out["tracks"], states)
     if camera is not None:

@@ -12,8 +12,8 @@ Run by `__graft_entry__.build()` and by tests/test_isa_invariants.py (CPU, needs
   3. The store counts that `wait_vm<N>` call sites count on as a LOWER bound: mlp_block_bwd / attn_out_bwd issue (at least) four
      8-byte row stores per tile and wave; a rowstream epilogue pass issues at least one 16-byte store.
   4. No inline-asm VALU instruction is the first reader of an MFMA result (no hazard wait states would separate them).
-  5. The kernels of csrc/confined_ml.hip keep the whole Kalman state of a candidate in registers: no scratch and no LDS
-     (include/mivit_hip.h promises both).
+  5. The kernels of csrc/confined_ml.hip keep the whole Kalman state of a candidate in registers, and those of
+     csrc/directed_ml.hip both recurrences and the three sums per axis: no scratch and no LDS (include/mivit_hip.h promises both).
 
 Exit status 0 = all invariants hold; otherwise the violations are listed and the status is 1.
 """
@@ -282,16 +282,17 @@ def main():
                 need = 1 if m and int(m.group(1)) > 256 else 2
                 if c < need:
                     errs.append(f"{n}: {c} 16-byte stores in the tile loop; the tile wait counts on >= {need} per epilogue")
-    # ---- confined_ml.hip: the state of a candidate lives in registers ----
-    kc = kernels(device_asm("confined_ml.hip"))
-    for want in ("cf_kernel", "cf_loglik_kernel"):
-        found = [n for n in kc if want + "E" in n]
-        if not found:
-            errs.append(f"confined_ml.hip: {want} not found")
-        for n in found:
-            sb, lds = scratch_bytes(kc[n][1]), kc[n][1].get("amdhsa_group_segment_fixed_size", kc[n][1].get("group_segment_fixed_size"))
-            if sb != 0 or lds is None or int(lds, 0) != 0:
-                errs.append(f"{n}: scratch bytes = {sb}, LDS bytes = {lds} (both must be 0)")
+    # ---- confined_ml.hip, directed_ml.hip: the state of a candidate lives in registers ----
+    for src, wants in (("confined_ml.hip", ("cf_kernel", "cf_loglik_kernel")), ("directed_ml.hip", ("dm_kernel", "dm_loglik_kernel"))):
+        kc = kernels(device_asm(src))
+        for want in wants:
+            found = [n for n in kc if want + "E" in n]
+            if not found:
+                errs.append(f"{src}: {want} not found")
+            for n in found:
+                sb, lds = scratch_bytes(kc[n][1]), kc[n][1].get("amdhsa_group_segment_fixed_size", kc[n][1].get("group_segment_fixed_size"))
+                if sb != 0 or lds is None or int(lds, 0) != 0:
+                    errs.append(f"{n}: scratch bytes = {sb}, LDS bytes = {lds} (both must be 0)")
     if errs:
         print("\n".join(errs))
         return 1
