@@ -851,6 +851,54 @@ int mivit_track_directed_loglik(const double *pos, const double *var, const int 
                                 const int *offsets, int n, double dt, double R, const double *D, const double *v, double *loglik,
                                 double *v_hat, double *v_hat_std, void *stream);
 
+/* Run-and-pause transport, csrc/transport.hip: tracks whose VELOCITY changes (motor-driven cargo that runs, pauses and runs
+ * again; no counterpart in the reference).  Both in fp64 without contraction, no atomics, a track's / stretch's result bitwise
+ * the same alone, in any batch and in every launch.
+ *
+ * mivit_segment_transport: the optimal partition of every track into stretches that are each diffusive (class 0: zero-mean
+ * increments of one variance) or directed (class 1: one variance about a constant velocity), one wave per track.  pos, offsets
+ * and max_len as mivit_segment_tracks takes them, max_len <= 4096 (cs2, csy, csx, F and prev live in LDS, 36 B a row: 147 456 B
+ * at the limit; a larger value is an error, never a launch).  A track of L rows has Linc = L - 1 increments (dy_k, dx_k)
+ * between rows k and k + 1, and three prefix sums, each summed in ascending k by one lane (np.cumsum bit for bit):
+ *   cs2[j] = sum_{k<j} (dy_k dy_k + dx_k dx_k);   csy[j] = sum_{k<j} dy_k;   csx[j] = sum_{k<j} dx_k
+ * With n = j - i, SS = cs2[j] - cs2[i], Sy = csy[j] - csy[i], Sx = csx[j] - csx[i], lg = log(Linc), beta = penalty * lg and
+ * gamma = velocity_penalty * lg:
+ *   C0(i, j) = (2 n) * log(max(SS / (2 n), min_var))                                  the cost of mivit_segment_tracks
+ *   C1(i, j) = (2 n) * log(max((SS - (Sy Sy + Sx Sx) / n) / (2 n), min_var)) + gamma  the velocity profiled out per axis
+ *   classes 0 (both):      C = C1 if C1 < C0 else C0, class 1 only where C1 is strictly lower (a tie and a NaN are diffusive)
+ *   classes 1 (directed):  C = C1, class 1;      classes 2 (diffusive): C = C0, class 0
+ *   F(0) = -beta;  F(j) = min over i in {0} and [min_len, j - min_len] of (F(i) + C(i, j)) + beta,   j = min_len .. Linc
+ * max keeps a NaN and lifts a residual that rounding made negative.  prev[j] is the LOWEST i among equal minima, with the class
+ * of the stretch (i, j) in bit 30; backtracking prev from Linc gives the changepoints and the class of every stretch (bit 31
+ * marks the first row of a stretch, bit 29 carries the class to every row of it).  Linc < 2 min_len leaves only i = 0; 1 <=
+ * Linc < min_len has no step and gets F(Linc) = (F(0) + C(0, Linc)) + beta with its class by the same rule.  Where every
+ * candidate is NaN, prev[j] = 0 and the class is 0.  The sums are not centred: SS - S^2 / n cancels for a fast track, but by
+ * less than the rounding of F at any speed a linker can follow.
+ * out: seg_start [N] int32, 1 on the first row of every stretch as mivit_segment_tracks writes it; seg_class [N] int32, the
+ * class of the stretch each row belongs to (a one-row track: 0); cost [n_tracks] fp64 = F(Linc), NaN where Linc < 1.  An empty
+ * track writes nothing.  With classes = 2 seg_start and cost are those of mivit_segment_tracks bit for bit.  The only
+ * operation that may differ from the numpy restatement (helpers/msd._transport_numpy) is log.  min_len >= 2, penalty >= 0,
+ * velocity_penalty >= 0, min_var > 0 and finite.  Arguments are validated before any HIP call; n_tracks = 0 is a no-op.
+ *
+ * mivit_transport_stats: one row of estimates per stretch about the stretch's own velocity, one thread per stretch.
+ * seg_offsets, seg_track_end, the rows and the bridging increment as mivit_segment_stats; n the number of increments.  Sums
+ * in ascending index, starting from 0.0:
+ *   pass 1:  my = (sum_k dy_k) / n,  mx = (sum_k dx_k) / n;   velocity[s] = (my / dt, mx / dt)
+ *   pass 2:  ey_k = dy_k - my,  ex_k = dx_k - mx
+ *            S2 = sum_k (ey_k ey_k + ex_k ex_k);   S11 = sum_k (ey_k ey_{k+1} + ex_k ex_{k+1}) over the n - 1 neighbouring pairs
+ *   D_res  = S2 / ((4 n) dt)
+ *   D_cve  = D_res + S11 / ((2 (n - 1)) dt)                             Vestergaard et al. 2014 about the velocity:
+ *   sigma2 = (R S2) / (2 n) + ((2 R - 1) S11) / (2 (n - 1))             localisation noise and blur cancel as above
+ * NaN where n < 1 (velocity, D_res) and where n < 2 (D_cve, sigma2); velocity [n_seg, 2], n_increments [n_seg] int32.  No
+ * log: bitwise the numpy restatement (helpers/msd._transport_stats_numpy).  Rows are clamped to [0, N - 1].  dt > 0, R in [0,
+ * 1/4].  n_seg = 0 is a no-op. */
+int mivit_segment_transport(const double *pos, int N, const int *offsets, int n_tracks, int max_len, int min_len, double penalty,
+                            double velocity_penalty, double min_var, int classes, int *seg_start, int *seg_class, double *cost,
+                            void *stream);
+int mivit_transport_stats(const double *pos, int N, const int *seg_offsets, const int *seg_track_end, int n_seg, double dt,
+                          double R, double *velocity, double *d_res, double *d_cve, double *sigma2, int *n_increments,
+                          void *stream);
+
 /* LayerNorm-1 backward + out-projection backward in one pass (autograd of x1 = LN1(x + out_proj(ctx)), models.py:57,100-102,
  * between the feed-forward block's input gradient and the attention core), csrc/fused_bwd.hip:
  * in : dy = dL/dx1 [M,E] bf16, n1 / rstd1 (LN1's normalised output, 1/std), gamma1, ctx [M,E] (out_proj's input), Wo bf16 [E,E];

@@ -180,6 +180,10 @@ SYMBOLS = {
                                 + [c_void_p] * 8),
     "mivit_track_directed_loglik": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, ctypes.c_double, ctypes.c_double]
                                     + [c_void_p] * 6),
+    "mivit_segment_transport": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mivit_transport_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mivit_drift_frames": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mivit_drift_integrate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mivit_attn_out_bwd_workspace_bytes": (c_size_t, [c_int]),

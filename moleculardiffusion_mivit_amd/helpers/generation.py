@@ -382,16 +382,38 @@ def markov_states(u, p0, M):
     return torch.from_numpy(out) if is_t else out
 
 
+def _state_velocities(velocities, K: int, name: str):
+    """velocities [K, 2] (vy, vx) per state as a float64 CPU tensor of finite numbers, or None where it is None or all zeros
+    (the code path without it); ValueError otherwise."""
+    if velocities is None:
+        return None
+    what = f"{name} must be real [{K}, 2] values (vy, vx), one pair per state"
+    try:
+        v = (velocities if torch.is_tensor(velocities) else torch.from_numpy(np.array(velocities))).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}, got {velocities!r}") from None
+    if v.dtype == torch.bool or v.is_complex() or tuple(v.shape) != (K, 2):
+        raise ValueError(f"{what}, got {v.dtype} {tuple(v.shape)}")
+    v = v.double()
+    if not bool(torch.isfinite(v).all()):
+        raise ValueError(f"{name} must be finite")
+    return v if bool((v != 0).any()) else None
+
+
 def multi_state(N: int, T: int, Ds, M, p0=None, dt: float = 1.0, generator: Optional[torch.Generator] = None, device="cpu",
-                return_states: bool = True):
+                return_states: bool = True, velocities=None):
     """(T, N, 2) Brownian trajectories whose diffusion coefficient follows a Markov chain, in the layout of
     brownian_single_state, and (with return_states) states [N, T] int64: stands in for
     ``andi_datasets.models_phenom().multi_state(N, L=0, T, Ds, M)`` with alpha = 1 in every state.  Ds [K] the coefficient of
     each state, M [K, K] the transition matrix per step, p0 [K] the distribution of the first state (default: the stationary
     distribution of M).  Draws, in this order: torch.rand(N, T) for the states, torch.randn(T, N, 2) for the steps.  Step t
     has variance 2 Ds[state[t]] dt per axis; position 0 is 0.  The state path comes from csrc/segment.hip on a GPU generator
-    and from its numpy restatement otherwise."""
+    and from its numpy restatement otherwise.  velocities (default None: none): [K, 2] (vy, vx) per state in units of length
+    per unit of dt (run-and-pause transport).  Step t adds velocities[state[t]] * dt, accumulated along the path in float64 and
+    added to the trajectory once, rounded once; nothing is drawn for it, and None or all zeros give today's trajectories bit
+    for bit.  What helpers/msd.segment_transport cuts."""
     Dsv, Mv, p0v = _markov_args(Ds, M, p0)
+    Vv = _state_velocities(velocities, len(Dsv), "velocities")
     gdev = generator.device if generator is not None else torch.device(device)
     u = torch.rand(N, T, generator=generator, device=gdev, dtype=torch.float64)
     states = markov_states(u, p0v, Mv).long()
@@ -399,7 +421,12 @@ def multi_state(N: int, T: int, Ds, M, p0=None, dt: float = 1.0, generator: Opti
     steps = torch.randn(T, N, 2, generator=generator, device=gdev) * scale.t().unsqueeze(-1)
     if T:
         steps[0] = 0.0
-    trajs = torch.cumsum(steps, dim=0).to(device)
+    trajs = torch.cumsum(steps, dim=0)
+    if Vv is not None and T:
+        inc = Vv.to(gdev)[states] * dt                                                                        # [N, T, 2] float64
+        inc[:, 0] = 0.0
+        trajs = (trajs.double() + torch.cumsum(inc, dim=1).transpose(0, 1)).float()                           # rounded once
+    trajs = trajs.to(device)
     return (trajs, states.to(device)) if return_states else trajs
 
 
@@ -977,6 +1004,11 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
     them.  The state is constant over the sub-positions of a frame: sub-step t of frame f has variance 2 Ds[state[p, f]] /
     nPosPerFrame.  truth gains state (int64 per row) and D_row (float64 per row); truth["D"] is the mean of D_row over the
     lifetime, so score_tracking keeps working.  Not together with alphas; with a geometry the steps run along the filament.
+    "velocity", [K, 2] (vy, vx) per state in pixels per frame (run-and-pause transport): sub-step t of frame f adds
+    velocity[state[p, f]] / nPosPerFrame, accumulated along the particle's path in float64 and added once the trajectories are
+    built, before velocity and drift (rounded once; sub-step 0 stays at the start).  Nothing is drawn for it: without the key
+    or with all zeros the movie and the truth are the same bit for bit.  truth gains velocity_row [rows, 2] float64.  Together
+    with a geometry, confinement or the velocity argument it is a ValueError.  What helpers/msd.segment_transport cuts.
 
     drift (default None: a stage at rest, the code path without it): the offset of the stage in every frame, a finite real
     [F, 2] array or tensor (y, x) in pixels, or a pair (vy, vx) in pixels per frame for drift[f] = f * (vy, vx).  Row f is added
@@ -1082,7 +1114,7 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError("geometry_of and boundary need a geometry")
     else:
         packed, geom_id = _movie_geometries(geometry, geometry_of, boundary, Np, H, W, margin)
-    state = None
+    state = state_V = state_V_given = None
     if states is None:
         D = _draw_diffusion_coefficients(Np, Ds, generator, gdev)
     else:
@@ -1090,9 +1122,14 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             raise ValueError("states and alphas cannot be combined: an exponent per state is not supported")
         if Ds is not None:
             raise ValueError("with states the coefficients are states['Ds']: Ds must be None")
-        if not isinstance(states, dict) or "Ds" not in states or "M" not in states or set(states) - {"Ds", "M", "p0", "path"}:
-            raise ValueError("states must be a dict with the keys Ds and M and optionally p0 and path")
+        if not isinstance(states, dict) or "Ds" not in states or "M" not in states or set(states) - {"Ds", "M", "p0", "path", "velocity"}:
+            raise ValueError("states must be a dict with the keys Ds and M and optionally p0, path and velocity")
         state_Ds, state_M, state_p0 = _markov_args(states["Ds"], states["M"], states.get("p0"))
+        if "velocity" in states and states["velocity"] is not None:
+            if geometry is not None or confinement is not None or velocity is not None:
+                raise ValueError("states['velocity'] cannot be combined with a geometry, confinement or the velocity argument")
+            state_V = _state_velocities(states["velocity"], len(state_Ds), "states['velocity']")
+            state_V_given = torch.zeros(len(state_Ds), 2, dtype=torch.float64) if state_V is None else state_V
         if states.get("path") is not None:
             path = torch.as_tensor(states["path"]).detach().cpu()
             if path.is_floating_point() or path.dtype == torch.bool or tuple(path.shape) != (Np, F_):
@@ -1153,6 +1190,12 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
             if T:
                 steps[:, 0] = 0.0
             pos = (start.view(Np, 1, 2) + torch.cumsum(steps, dim=1)).float().to(dev)
+    if state_V is not None:
+        # V[state] / npos per sub-step, accumulated along the particle's path in float64 (sub-step 0 stays at the start)
+        inc = (state_V.to(dev)[state.to(dev)] / npos).repeat_interleave(npos, dim=1)                          # [Np, T, 2]
+        if T:
+            inc[:, 0] = 0.0
+        pos = (pos.double() + torch.cumsum(inc, dim=1)).float()                                  # rounded once
     if vel is not None:
         vel = vel.to(dev)
         sub = torch.arange(T, dtype=torch.float64, device=dev) / npos
@@ -1195,6 +1238,8 @@ def simulate_movie(n_particles: int, n_frames: int, H: int, W: int, Ds, nPosPerF
              "D": D.to(dev), "pos": pos, "amp": amp, "first": first, "last": last}
     if state is not None:
         truth["state"], truth["D_row"] = state[pid, frame], D_row
+        if state_V_given is not None:
+            truth["velocity_row"] = state_V_given.to(dev)[truth["state"]]
     if blink is not None:
         truth["visible"] = ~dark[pid, frame]
     if alpha is not None:

@@ -1800,3 +1800,187 @@ def estimate_directed_ml(positions, offsets, variances=None, frames=None, use=No
         out["lr_brownian"] = 2.0 * (out["loglik"] - free["loglik"])
         out["p_brownian"] = xp.exp(-0.5 * out["lr_brownian"].clip(min=0.0))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# run-and-pause transport: changepoints of the velocity and one row of estimates per stretch (csrc/transport.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+_TRANSPORT_CLASSES = {"both": 0, "directed": 1, "diffusive": 2}
+
+
+def _transport_numpy(pos, offsets, min_len, penalty, velocity_penalty, min_var, classes, return_margin=False):
+    """The arithmetic of csrc/transport.hip::transport_kernel in its order (include/mivit_hip.h, mivit_segment_transport):
+    np.cumsum is the sequential prefix sum, np.argmin returns the lowest index among equal minima.  pos [N, 2] float64,
+    offsets [n_tracks + 1] int64, classes 0 (both), 1 (directed) or 2 (diffusive) -> (seg_start [N] int32, seg_class [N]
+    int32, cost [n_tracks] float64).  Differs from the kernel in log alone.  return_margin: also margin [n_tracks], the smallest
+    over the backtracked path of two gaps: between the chosen candidate and the runner-up, and (classes 0) |C0 - C1| at the
+    chosen candidate -- a class flip is as much a change of the answer as a moved cut.  inf where neither exists."""
+    n_tracks = len(offsets) - 1
+    seg_start = np.zeros(len(pos), np.int32)
+    seg_class = np.zeros(len(pos), np.int32)
+    cost = np.full(n_tracks, np.nan)
+    margin = np.full(n_tracks, np.inf)
+    for k in range(n_tracks):
+        a, b = int(offsets[k]), int(offsets[k + 1])
+        L = b - a
+        if L >= 1:
+            seg_start[a] = 1
+        Linc = L - 1
+        if Linc < 1:
+            continue
+        p = pos[a:b]
+        dy, dx = p[1:, 0] - p[:-1, 0], p[1:, 1] - p[:-1, 1]
+        cs2 = np.concatenate([np.zeros(1), np.cumsum(dy * dy + dx * dx)])
+        csy = np.concatenate([np.zeros(1), np.cumsum(dy)])
+        csx = np.concatenate([np.zeros(1), np.cumsum(dx)])
+        lg = np.log(float(Linc))
+        beta, gamma = penalty * lg, velocity_penalty * lg
+
+        def step(j, cand):
+            n = (j - cand).astype(np.float64)
+            tn = 2.0 * n
+            SS, Sy, Sx = cs2[j] - cs2[cand], csy[j] - csy[cand], csx[j] - csx[cand]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                C0 = tn * np.log(np.maximum(SS / tn, min_var))
+                C1 = tn * np.log(np.maximum((SS - (Sy * Sy + Sx * Sx) / n) / tn, min_var)) + gamma
+                if classes == 1:
+                    cls, C, flip = np.ones(len(cand), np.int32), C1, np.full(len(cand), np.inf)
+                elif classes == 2:
+                    cls, C, flip = np.zeros(len(cand), np.int32), C0, np.full(len(cand), np.inf)
+                else:
+                    pick = C1 < C0
+                    cls, C, flip = pick.astype(np.int32), np.where(pick, C1, C0), np.abs(C0 - C1)
+                return (F[cand] + C) + beta, cls, flip
+
+        F = np.full(Linc + 1, np.nan)
+        F[0] = -beta
+        prev = np.zeros(Linc + 1, np.int64)
+        pcls = np.zeros(Linc + 1, np.int32)
+        gap = np.full(Linc + 1, np.inf)
+        if Linc < min_len:
+            v, cls, flip = step(Linc, np.zeros(1, np.int64))
+            F[Linc], pcls[Linc], gap[Linc] = v[0], cls[0], flip[0]
+        for j in range(min_len, Linc + 1):
+            cand = np.concatenate([np.zeros(1, np.int64), np.arange(min_len, j - min_len + 1, dtype=np.int64)])
+            v, cls, flip = step(j, cand)
+            if np.isnan(v).all():
+                F[j] = v[0]
+                continue
+            m = int(np.argmin(v))
+            F[j], prev[j], pcls[j] = v[m], cand[m], cls[m]
+            if return_margin:
+                gap[j] = min(flip[m], np.partition(v, 1)[1] - v[m]) if len(v) > 1 else flip[m]
+        cost[k] = F[Linc]
+        j = Linc
+        while j > 0:
+            margin[k] = min(margin[k], gap[j])
+            i = int(prev[j])
+            seg_class[a + i:a + (L if j == Linc else j)] = pcls[j]
+            if i > 0:
+                seg_start[a + i] = 1
+            j = i
+    return (seg_start, seg_class, cost, margin) if return_margin else (seg_start, seg_class, cost)
+
+
+def _transport_stats_numpy(pos, seg_offsets, seg_track_end, dt, blur):
+    """The arithmetic of csrc/transport.hip::transport_stats_kernel in its order: np.cumsum(...)[-1] is a sequential sum.  ->
+    (velocity [n_seg, 2], D_res, D_cve, sigma2 [n_seg] float64, n_increments [n_seg] int32), bitwise the kernel's."""
+    n_seg = len(seg_track_end)
+    velocity = np.full((n_seg, 2), np.nan)
+    d_res, d_cve, sigma2 = np.full(n_seg, np.nan), np.full(n_seg, np.nan), np.full(n_seg, np.nan)
+    n_inc = np.zeros(n_seg, np.int32)
+    R = float(blur)
+    for s in range(n_seg):
+        r0 = max(int(seg_offsets[s]), 0)
+        r1 = min(int(seg_offsets[s + 1]), int(seg_track_end[s]) - 1, len(pos) - 1)
+        n = max(r1 - r0, 0)
+        n_inc[s] = n
+        if n < 1:
+            continue
+        p = pos[r0:r1 + 1]
+        dy, dx = p[1:, 0] - p[:-1, 0], p[1:, 1] - p[:-1, 1]
+        my, mx = np.cumsum(dy)[-1] / float(n), np.cumsum(dx)[-1] / float(n)
+        velocity[s, 0], velocity[s, 1] = my / dt, mx / dt
+        ey, ex = dy - my, dx - mx
+        S2 = np.cumsum(ey * ey + ex * ex)[-1]
+        d_res[s] = S2 / ((4.0 * float(n)) * dt)
+        if n >= 2:
+            S11 = np.cumsum(ey[:-1] * ey[1:] + ex[:-1] * ex[1:])[-1]
+            m1 = 2.0 * float(n - 1)
+            d_cve[s] = d_res[s] + S11 / (m1 * dt)
+            sigma2[s] = (R * S2) / (2.0 * float(n)) + ((2.0 * R - 1.0) * S11) / m1
+    return velocity, d_res, d_cve, sigma2, n_inc
+
+
+def segment_transport(positions, offsets, dt=1.0, min_len=4, penalty=3.0, velocity_penalty=3.0, min_var=1e-12, classes="both",
+                      blur=0.0):
+    """Tracks whose velocity changes (run and pause): the optimal partition of every track into stretches that are each
+    diffusive (class 0: zero-mean increments of one variance) or directed (class 1: one variance about a constant velocity),
+    and the estimates of each stretch about its own velocity.  positions, offsets, dt, min_len, penalty, min_var and blur as
+    segment_tracks takes them -> dict:
+        seg_offsets [n_seg + 1] int64, seg_track [n_seg] int64      as segment_tracks returns them
+        seg_class   [n_seg] int64       0 diffusive, 1 directed
+        velocity    [n_seg, 2] float64  the mean increment / dt as (y, x), whatever the class; speed [n_seg] its length
+        D_res       [n_seg] float64     the maximum-likelihood D about that velocity, without localisation noise
+        D_cve, sigma2 [n_seg] float64   Vestergaard's estimators on the increments minus their mean: noise and blur cancel
+        n_increments [n_seg] int64, cost [n_tracks] float64
+    Penalised likelihood as in segment_tracks, with two models per stretch: a directed stretch pays gamma = velocity_penalty *
+    log(increments of the track) for its two velocity components on top of beta per changepoint, and a stretch is directed
+    only where that is strictly cheaper.  classes "directed" gives every stretch a velocity, "diffusive" none (the partition
+    and cost of segment_tracks bit for bit).  A whole-track fit (estimate_directed_ml) averages a run with a pause; pass
+    seg_offsets to it, or to estimate_diffusion_ml, for the per-stretch fits with error bars.  include/mivit_hip.h has the
+    arithmetic.  CUDA tensors go to the kernels (csrc/transport.hip: two launches; a track has at most ops.TRANSPORT_MAX_LEN
+    rows), numpy arrays and CPU tensors to the numpy restatements; the output is of the input's kind."""
+    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
+        raise ValueError(f"min_len must be an integer >= 2, got {min_len}")
+    if not float(penalty) >= 0.0:
+        raise ValueError(f"penalty must be >= 0, got {penalty}")
+    if not float(velocity_penalty) >= 0.0:
+        raise ValueError(f"velocity_penalty must be >= 0, got {velocity_penalty}")
+    if not 0.0 < float(min_var) < float("inf"):
+        raise ValueError(f"min_var must be positive and finite, got {min_var}")
+    if not isinstance(classes, str) or classes not in _TRANSPORT_CLASSES:
+        raise ValueError(f"classes must be one of {', '.join(_TRANSPORT_CLASSES)}, got {classes!r}")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    if torch.is_tensor(positions) != torch.is_tensor(offsets):
+        raise ValueError("positions and offsets must both be tensors or both be arrays")
+    if torch.is_tensor(positions) and positions.device != offsets.device:
+        raise ValueError(f"positions on {positions.device}, offsets on {offsets.device}")
+    offsets = offsets if torch.is_tensor(offsets) else np.asarray(offsets)
+    _check_offsets(offsets, positions.shape[0])
+    min_len, penalty, velocity_penalty, min_var = int(min_len), float(penalty), float(velocity_penalty), float(min_var)
+    dt, blur = float(dt), float(blur)
+    is_t = torch.is_tensor(positions)
+    if is_t and positions.device.type == "cuda":
+        from .. import ops
+        lengths = offsets[1:] - offsets[:-1]
+        if len(lengths) and int(lengths.max()) > ops.TRANSPORT_MAX_LEN:
+            raise ValueError(f"a track of {int(lengths.max())} rows on the GPU, the kernel's limit is {ops.TRANSPORT_MAX_LEN} "
+                             f"(ops.TRANSPORT_MAX_LEN)")
+        pos = positions.detach().double().contiguous()
+        seg_start, row_class, cost = ops.segment_transport(pos, offsets.int().contiguous(), min_len, penalty, velocity_penalty,
+                                                           min_var, classes)
+        first = torch.nonzero(seg_start, as_tuple=True)[0]
+        seg_offsets = torch.cat([first, torch.full((1,), pos.shape[0], dtype=torch.int64, device=pos.device)])
+        seg_track = torch.searchsorted(offsets.long().contiguous(), first, right=True) - 1
+        track_end = offsets.long()[seg_track + 1]
+        velocity, d_res, d_cve, sigma2, n_inc = ops.transport_stats(pos, seg_offsets.int(), track_end.int(), dt, blur)
+        return {"seg_offsets": seg_offsets, "seg_track": seg_track, "seg_class": row_class[first].long(), "velocity": velocity,
+                "speed": torch.sqrt(velocity[:, 0] * velocity[:, 0] + velocity[:, 1] * velocity[:, 1]), "D_res": d_res,
+                "D_cve": d_cve, "sigma2": sigma2, "n_increments": n_inc.long(), "cost": cost}
+    pos = positions.detach().double().numpy() if is_t else np.asarray(positions, dtype=np.float64)
+    off = (offsets.detach().numpy() if is_t else offsets).astype(np.int64)
+    seg_start, row_class, cost = _transport_numpy(pos, off, min_len, penalty, velocity_penalty, min_var, _TRANSPORT_CLASSES[classes])
+    first = np.nonzero(seg_start)[0].astype(np.int64)
+    seg_offsets = np.concatenate([first, np.full(1, len(pos), np.int64)])
+    seg_track = np.searchsorted(off, first, side="right").astype(np.int64) - 1
+    velocity, d_res, d_cve, sigma2, n_inc = _transport_stats_numpy(pos, seg_offsets, off[seg_track + 1], dt, blur)
+    out = {"seg_offsets": seg_offsets, "seg_track": seg_track, "seg_class": row_class[first].astype(np.int64), "velocity": velocity,
+           "speed": np.sqrt(velocity[:, 0] * velocity[:, 0] + velocity[:, 1] * velocity[:, 1]), "D_res": d_res, "D_cve": d_cve,
+           "sigma2": sigma2, "n_increments": n_inc.astype(np.int64), "cost": cost}
+    return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out

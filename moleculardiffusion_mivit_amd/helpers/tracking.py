@@ -2134,9 +2134,24 @@ def refine_localizations_tensors(patches, ys, xs, method="lsq", camera=None, fra
     return res
 
 
+_TRANSPORT_KEYS = ("min_len", "penalty", "velocity_penalty", "min_var", "classes", "blur")
+
+
+def transport_per_track(seg_offsets, seg_track, seg_class, lengths):
+    """What a track's stretches (helpers/msd.segment_transport: seg_offsets [n_seg + 1], seg_track, seg_class [n_seg]) say
+    about the track as a whole, for tracks of lengths [n_tracks] rows; int64 tensors on one device -> (run_fraction [n_tracks]
+    float64, the share of the track's rows that lie in directed stretches (NaN for a track without rows); n_runs [n_tracks]
+    int64, its directed stretches)."""
+    n_tracks = len(lengths)
+    rows = (seg_offsets[1:] - seg_offsets[:-1]) * seg_class
+    run_rows = torch.zeros(n_tracks, dtype=torch.int64, device=lengths.device).index_add_(0, seg_track, rows)
+    n_runs = torch.zeros(n_tracks, dtype=torch.int64, device=lengths.device).index_add_(0, seg_track, seg_class)
+    return run_rows.double() / lengths.double(), n_runs
+
+
 def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=None, refine=True, tail="drop",
                              batch_size=4096, segment=None, states=None, drift=None, localization=None, ml=None, anomalous=None,
-                             confined=None, directed=None, **tracking_kwargs):
+                             confined=None, directed=None, transport=None, **tracking_kwargs):
     """One diffusion coefficient per track of a CUDA movie [F, H, W], from a trained model and from the classical MSD estimate
     it is compared with, without leaving the device: track_particles_tensors(movie, **tracking_kwargs), tracks_table_by_track,
     (with refine) extract_patches_flat + refine_localizations_tensors, helpers/msd.track_msd on (y_refined, x_refined) -- on
@@ -2227,7 +2242,20 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     p_directed (float64; estimate_directed_ml's velocity, velocity_std, speed, speed_std, D_dir, D_dir_std, lr_brownian and
     p_brownian) and directed_status (int64) [n_tracks], and "directed": what estimate_directed_ml was called with (positions,
     variances, frames, use, blur).  Tracks only: the function takes any CSR offsets, so segments["seg_offsets"] or
-    states["run_offsets"] can be passed to it with the arguments reported here."""
+    states["run_offsets"] can be passed to it with the arguments reported here.
+
+    transport (default None: the code path without it): a dict of helpers/msd.segment_transport arguments (min_len, penalty,
+    velocity_penalty, min_var, classes, blur; {} for the defaults; dt is this function's): run-and-pause tracks, whose VELOCITY
+    changes along the track.  The result gains "transport": the segment_transport dict computed on the positions segment
+    uses (drift-corrected if drift is given; csrc/transport.hip), plus n_sequences and D_model [n_seg] from the windows of
+    plan_sequences(seg_offsets, seq_len, tail) exactly as for segment, so that no window straddles a cut.  With directed given
+    it also holds velocity_ml, velocity_ml_std [n_seg, 2], speed_ml, D_dir, D_dir_std, lr_directed, p_directed and
+    directed_status per stretch (estimate_directed_ml on seg_offsets with the arguments reported under "directed"), and with
+    ml given D_ml, D_ml_std and ml_status per stretch.  Per track the result gains run_fraction (float64 [n_tracks]: the share
+    of a track's rows that lie in directed stretches) and n_runs (int64 [n_tracks]: its directed stretches).  Every other
+    entry is unchanged."""
+    if transport is not None and (not isinstance(transport, dict) or set(transport) - set(_TRANSPORT_KEYS)):
+        raise ValueError(f"transport must be None or a dict with keys among {', '.join(_TRANSPORT_KEYS)}")
     if directed is not None:
         if not isinstance(directed, dict) or set(directed) - {"blur", "sigma2"}:
             raise ValueError("directed must be None or a dict with keys among blur and sigma2")
@@ -2427,6 +2455,22 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         if ml is not None:
             got = ml_fit(segments["seg_offsets"])
             segments["D_ml"], segments["D_ml_std"], segments["ml_status"] = got["D_ml"], got["D_ml_std"], got["status"]
+    transported = None
+    if transport is not None:
+        from . import msd as _msd
+        transported = _msd.segment_transport(pos, offsets, dt=dt, **transport)
+        tr_seq, tr_of_seq, _ = track_sequences(movie, fr, y, x, transported["seg_offsets"], seq_len, patch_size, norm, tail)
+        transported["n_sequences"] = torch.bincount(tr_of_seq, minlength=len(transported["seg_track"]))
+        transported["D_model"] = mean_per_group(tr_seq, transported["n_sequences"])
+        if directed is not None:
+            got = _msd.estimate_directed_ml(pos, transported["seg_offsets"], dt=dt, **dm_args)
+            for k, key in (("velocity_ml", "velocity"), ("velocity_ml_std", "velocity_std"), ("speed_ml", "speed"), ("D_dir", "D_dir"),
+                           ("D_dir_std", "D_dir_std"), ("lr_directed", "lr_brownian"), ("p_directed", "p_brownian"),
+                           ("directed_status", "status")):
+                transported[k] = got[key]
+        if ml is not None:
+            got = ml_fit(transported["seg_offsets"])
+            transported["D_ml"], transported["D_ml_std"], transported["ml_status"] = got["D_ml"], got["D_ml_std"], got["status"]
     fitted = None
     if states is not None:
         from . import msd as _msd
@@ -2456,6 +2500,10 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
         res["segments"] = segments
     if fitted is not None:
         res["states"] = fitted
+    if transported is not None:
+        res["transport"] = transported
+        res["run_fraction"], res["n_runs"] = transport_per_track(transported["seg_offsets"], transported["seg_track"],
+                                                                 transported["seg_class"], lengths)
     if drifted is not None:
         res["drift"] = drifted
     if located is not None:

@@ -66,8 +66,13 @@ against the truth, the RMS pull of both velocity components, D_dir against the t
 from the same seed WITHOUT velocity the null quantiles and the fraction with p_directed < 0.05.
 --detector lrt [--p-fa P] (with --camera) adds "detector": score_tracking's recall, precision and RMSE of the difference of
 Gaussians and of the likelihood-ratio detector at the per-pixel false-alarm probability P (default 1e-6; csrc/detect.hip,
-track_particles_tensors(..., detector={...})) on the same movie with the same linking, also printed to stderr.  A
-tool, not a test: it asserts no accuracy.
+track_particles_tensors(..., detector={...})) on the same movie with the same linking, also printed to stderr.
+--states D1 D2 P_STAY --state-velocity "VY,VX[;VY,VX]" --transport gives the states a velocity each in pixels per frame (one
+pair: the first state pauses and the second runs at it; simulate_movie's states["velocity"]), runs
+estimate_track_diffusion(..., transport={}, directed={}) (helpers/msd.segment_transport, csrc/transport.hip) and adds
+"transport": over the tracks matched to a particle the recall and precision of the planted switches of the velocity, the
+share of rows whose stretch has the right class, and the speed of the directed stretches against the truth.  A tool, not a
+test: it asserts no accuracy.
 
     python scripts/eval_movie_accuracy.py [--checkpoint STATE_DICT.pt] [--particles 20] [--frames 200] [--size 256 256]
                                           [--D 0.05 0.0004] [--npos 10] [--seq-len 30] [--patch-size 9] [--seed 0] [--noise-free]
@@ -77,6 +82,7 @@ tool, not a test: it asserts no accuracy.
                                           [--drift 0.0,0.2] [--drift-estimator median] [--drift-smoothing 2]
                                           [--camera 10,2,100,1.5] [--detector lrt [--p-fa 1e-6]] [--mle] [--neighbours [4]] [--ml [0.1667]] [--intensity 300]
                                           [--confined 3.0] [--confined-ml [0.01]] [--velocity 0.2] [--directed-ml [0.01]]
+                                          [--states 0.05 0.05 0.98 --state-velocity "0,0.5" --transport]
 
 Without --checkpoint the model is a freshly initialised GeneralTransformer of the shipped shape (its D_model says nothing
 about the data; the column is there so that the pipeline runs end to end); with it, the state dict is loaded into that shape.
@@ -216,6 +222,8 @@ def main():
     ap.add_argument("--velocity", type=float, default=None, metavar="SPEED")
     ap.add_argument("--directed-ml", type=float, nargs="?", const=-1.0, default=None, metavar="SIGMA2")
     ap.add_argument("--detector", choices=["lrt"], default=None)
+    ap.add_argument("--state-velocity", default=None, metavar="VY,VX[;VY,VX]")
+    ap.add_argument("--transport", action="store_true")
     ap.add_argument("--p-fa", type=float, default=1e-6, metavar="P")
     args = ap.parse_args()
     camera = None
@@ -281,6 +289,18 @@ def main():
     if args.states is not None:
         d1, d2, stay = args.states
         states = {"Ds": [d1, d2], "M": [[stay, 1.0 - stay], [1.0 - stay, stay]]}
+    if args.state_velocity is not None or args.transport:
+        if states is None or args.state_velocity is None or not args.transport:
+            raise SystemExit("--state-velocity and --transport go together and need --states")
+        try:
+            sv = [[float(t) for t in pair.split(",")] for pair in args.state_velocity.split(";")]
+        except ValueError:
+            sv = []
+        if len(sv) == 1:                                     # one pair: the first state pauses, the second runs at it
+            sv = [[0.0, 0.0]] + sv
+        if len(sv) != 2 or any(len(pair) != 2 for pair in sv):
+            raise SystemExit("--state-velocity takes VY,VX (the second state's; the first pauses) or VY,VX;VY,VX, in pixels per frame")
+        states["velocity"] = sv
     movie, truth = gen.simulate_movie(args.particles, args.frames, H, W, None if states else tuple(args.D), args.npos,
                                       image_props=props, generator=g, device="cuda", blink=args.blink, alphas=args.alpha,
                                       states=states, **confine, **({} if drift is None else {"drift": drift}),
@@ -375,6 +395,8 @@ def main():
         out["segmentation"] = [segmentation_scores(movie, model, args, norm, truth, score, fr, float(p)) for p in args.penalties]
         if args.hmm is not None:
             out["hmm"] = hmm_scores(movie, model, args, norm, truth, score, fr, states)
+        if args.transport:
+            out["transport"] = transport_scores(movie, model, args, norm, truth, score, fr)
     print(json.dumps(out))
 
 
@@ -580,6 +602,69 @@ def segmentation_scores(movie, model, args, norm, truth, score, fr, penalty, tol
             "changepoint_recall": n_hit / n_true if n_true else nan, "changepoint_precision": n_hit / n_found if n_found else nan,
             "mae_D_cve": mae(seg["D_cve"][row_seg]), "mae_D_mle": mae(seg["D_mle"][row_seg]), "mae_D_msd": mae(est["D_msd"][row_track]),
             "rows_scored": int(ok.sum()), "rows": n_rows}
+
+
+def transport_scores(movie, model, args, norm, truth, score, fr, tol=5):
+    """--transport: estimate_track_diffusion(..., transport={}, directed={}) on a movie of --states with --state-velocity.  Over
+    the tracks matched to a particle: the recall and precision of the planted switches of the velocity (a switch of the state
+    counts where the two states' velocities differ; a found cut matches a true one within tol frames, every true one once), the
+    share of rows whose stretch has the right class (1 where the row's true speed is above zero), and over the rows of
+    directed stretches that are truly runs the mean absolute error of the stretch's speed (the mean increment's, and the
+    maximum-likelihood one's) against the true speed, with the rms of (velocity_ml - truth) / velocity_ml_std per stretch."""
+    est = trk.estimate_track_diffusion(movie, model, args.seq_len, args.patch_size, norm=norm, max_gap=args.max_gap, transport={},
+                                       directed={})
+    tr = est["transport"]
+    Np, F_ = args.particles, args.frames
+    nan = float("nan")
+    v_true = torch.full((Np, F_, 2), nan, dtype=torch.float64, device=movie.device)
+    v_true[truth["particle_id"], truth["frame"]] = truth["velocity_row"]
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=movie.device), torch.cumsum(est["length"], 0)])
+    row_track = torch.repeat_interleave(torch.arange(len(est["length"]), device=movie.device), est["length"])
+    seg_len = tr["seg_offsets"][1:] - tr["seg_offsets"][:-1]
+    row_seg = torch.repeat_interleave(torch.arange(len(seg_len), device=movie.device), seg_len)
+    pid = score["particle_id"][row_track]
+    want = v_true[pid.clamp_min(0), fr.clamp(0, F_ - 1)]                   # [rows, 2]
+    ok = (pid >= 0) & ~torch.isnan(want[:, 0])
+    speed_true = want.pow(2).sum(dim=1).sqrt()
+    right = (tr["seg_class"][row_seg] == (speed_true > 0).long()) & ok
+    runs = ok & (speed_true > 0) & (tr["seg_class"][row_seg] == 1)
+    mae = lambda col: float((col[row_seg][runs] - speed_true[runs]).abs().nanmean()) if bool(runs.any()) else nan           # noqa: E731
+    n_true = n_found = n_hit = 0
+    off, so, st, frames = offsets.tolist(), tr["seg_offsets"].tolist(), tr["seg_track"].tolist(), fr.tolist()
+    starts = {}
+    for s, k in enumerate(st):
+        starts.setdefault(k, []).append(so[s])
+    v_h = v_true.cpu()
+    for k, p in enumerate(score["particle_id"].tolist()):
+        if p < 0 or off[k + 1] <= off[k]:
+            continue
+        f0, f1 = frames[off[k]], frames[off[k + 1] - 1]
+        path = v_h[p, f0:f1 + 1]
+        moved = ((path[1:] != path[:-1]).any(dim=1)) & ~torch.isnan(path[1:, 0]) & ~torch.isnan(path[:-1, 0])
+        true_cp = [f0 + 1 + int(i) for i in torch.nonzero(moved).view(-1)]
+        found = [frames[r] for r in starts.get(k, [])[1:]]
+        n_true, n_found = n_true + len(true_cp), n_found + len(found)
+        free = set(true_cp)
+        for f in found:
+            near = [t for t in free if abs(t - f) <= tol]
+            if near:
+                free.discard(min(near, key=lambda t: abs(t - f)))
+                n_hit += 1
+    # per directed stretch that lies inside one true run: the pull of the maximum-likelihood velocity
+    first, last = tr["seg_offsets"][:-1], (tr["seg_offsets"][1:] - 1).clamp_min(0)
+    inside = (tr["seg_class"] == 1) & (seg_len > 0)
+    inside = inside & ok[first.clamp(max=len(ok) - 1)] & (want[first.clamp(max=len(ok) - 1)] == want[last]).all(dim=1)
+    inside = inside & (tr["directed_status"] == 0)
+    pull = ((tr["velocity_ml"] - want[first.clamp(max=len(ok) - 1)]) / tr["velocity_ml_std"])[inside]
+    return {"state_velocity": args.state_velocity, "n_stretches": len(seg_len), "n_directed_stretches": int(tr["seg_class"].sum()),
+            "n_true_switches": n_true, "n_found_cuts": n_found, "switch_recall": n_hit / n_true if n_true else nan,
+            "cut_precision": n_hit / n_found if n_found else nan,
+            "class_accuracy_per_row": float(right.sum()) / float(ok.sum()) if bool(ok.any()) else nan,
+            "mae_speed": mae(tr["speed"]), "mae_speed_ml": mae(tr["speed_ml"]),
+            "mean_true_speed_of_runs": float(speed_true[runs].mean()) if bool(runs.any()) else nan,
+            "rms_velocity_ml_error_over_std": float(pull.pow(2).mean().sqrt()) if pull.numel() else nan,
+            "n_stretches_in_pull": int(inside.sum()), "mean_run_fraction": float(est["run_fraction"].nanmean()),
+            "rows_scored": int(ok.sum()), "rows": len(fr)}
 
 
 if __name__ == "__main__":
