@@ -851,15 +851,16 @@ int mivit_track_directed_loglik(const double *pos, const double *var, const int 
                                 const int *offsets, int n, double dt, double R, const double *D, const double *v, double *loglik,
                                 double *v_hat, double *v_hat_std, void *stream);
 
-/* Run-and-pause transport, csrc/transport.hip: tracks whose VELOCITY changes (motor-driven cargo that runs, pauses and runs
+/* Run-and-pause transport, csrc/segment.hip: tracks whose VELOCITY changes (motor-driven cargo that runs, pauses and runs
  * again; no counterpart in the reference).  Both in fp64 without contraction, no atomics, a track's / stretch's result bitwise
  * the same alone, in any batch and in every launch.
  *
  * mivit_segment_transport: the optimal partition of every track into stretches that are each diffusive (class 0: zero-mean
  * increments of one variance) or directed (class 1: one variance about a constant velocity), one wave per track.  pos, offsets
  * and max_len as mivit_segment_tracks takes them, max_len <= 4096 (cs2, csy, csx, F and prev live in LDS, 36 B a row: 147 456 B
- * at the limit; a larger value is an error, never a launch).  A track of L rows has Linc = L - 1 increments (dy_k, dx_k)
- * between rows k and k + 1, and three prefix sums, each summed in ascending k by one lane (np.cumsum bit for bit):
+ * at the limit; classes = 2 runs the kernel of mivit_segment_tracks, 20 B a row; a larger value is an error, never a launch).
+ * A track of L rows has Linc = L - 1 increments (dy_k, dx_k) between rows k and k + 1, and three prefix sums, each summed in
+ * ascending k by one lane (np.cumsum bit for bit):
  *   cs2[j] = sum_{k<j} (dy_k dy_k + dx_k dx_k);   csy[j] = sum_{k<j} dy_k;   csx[j] = sum_{k<j} dx_k
  * With n = j - i, SS = cs2[j] - cs2[i], Sy = csy[j] - csy[i], Sx = csx[j] - csx[i], lg = log(Linc), beta = penalty * lg and
  * gamma = velocity_penalty * lg:
@@ -868,12 +869,12 @@ int mivit_track_directed_loglik(const double *pos, const double *var, const int 
  *   classes 0 (both):      C = C1 if C1 < C0 else C0, class 1 only where C1 is strictly lower (a tie and a NaN are diffusive)
  *   classes 1 (directed):  C = C1, class 1;      classes 2 (diffusive): C = C0, class 0
  *   F(0) = -beta;  F(j) = min over i in {0} and [min_len, j - min_len] of (F(i) + C(i, j)) + beta,   j = min_len .. Linc
- * max keeps a NaN and lifts a residual that rounding made negative.  prev[j] is the LOWEST i among equal minima, with the class
- * of the stretch (i, j) in bit 30; backtracking prev from Linc gives the changepoints and the class of every stretch (bit 31
- * marks the first row of a stretch, bit 29 carries the class to every row of it).  Linc < 2 min_len leaves only i = 0; 1 <=
- * Linc < min_len has no step and gets F(Linc) = (F(0) + C(0, Linc)) + beta with its class by the same rule.  Where every
- * candidate is NaN, prev[j] = 0 and the class is 0.  The sums are not centred: SS - S^2 / n cancels for a fast track, but by
- * less than the rounding of F at any speed a linker can follow.
+ * max keeps a NaN and lifts a residual that rounding made negative.  prev[j] is the LOWEST i among equal minima, kept as 2 i +
+ * the class of the stretch (i, j); backtracking prev from Linc gives the changepoints and the class of every stretch, which the
+ * wave writes to the stretch's rows as it walks.  Linc < 2 min_len leaves only i = 0; 1 <= Linc < min_len has no step and gets
+ * F(Linc) = (F(0) + C(0, Linc)) + beta with its class by the same rule.  Where every candidate is NaN, prev[j] = 0 and the
+ * class is 0.  The sums are not centred: SS - S^2 / n cancels for a fast track, but by less than the rounding of F at any
+ * speed a linker can follow.
  * out: seg_start [N] int32, 1 on the first row of every stretch as mivit_segment_tracks writes it; seg_class [N] int32, the
  * class of the stretch each row belongs to (a one-row track: 0); cost [n_tracks] fp64 = F(Linc), NaN where Linc < 1.  An empty
  * track writes nothing.  With classes = 2 seg_start and cost are those of mivit_segment_tracks bit for bit.  The only

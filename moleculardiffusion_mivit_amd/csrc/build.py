@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_fast.hip", "embed.hip", "rowstream.hip", "wavestream.hip", "gemm_dma.hip", "wgrad_dma.hip", "wgrad_small.hip", "fused_fwd.hip", "fused_bwd.hip", "render.hip", "movie.hip", "features.hip", "deconv.hip", "tracking.hip", "detect.hip", "localize.hip", "localize2.hip", "linking.hip", "diffusion.hip", "fbm.hip", "confine.hip", "segment.hip", "hmm.hip", "likelihood.hip", "fbm_ml.hip", "confined_ml.hip", "directed_ml.hip", "drift.hip", "deepresnet.hip", "deepresnet_train.hip", "misc.hip", "engine.hip", "transport.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_fast.hip", "embed.hip", "rowstream.hip", "wavestream.hip", "gemm_dma.hip", "wgrad_dma.hip", "wgrad_small.hip", "fused_fwd.hip", "fused_bwd.hip", "render.hip", "movie.hip", "features.hip", "deconv.hip", "tracking.hip", "detect.hip", "localize.hip", "localize2.hip", "linking.hip", "diffusion.hip", "fbm.hip", "confine.hip", "segment.hip", "hmm.hip", "likelihood.hip", "fbm_ml.hip", "confined_ml.hip", "directed_ml.hip", "drift.hip", "deepresnet.hip", "deepresnet_train.hip", "misc.hip", "engine.hip"]
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "stream_prims.h"), os.path.join(HERE, "elem.h"),
            os.path.join(HERE, "trajfeat.h"), os.path.join(HERE, "slab_defer.h"), os.path.join(HERE, "track_ml.h"), os.path.join(HERE, "peaks.h"),
            os.path.join(ROOT, "include", "mivit_hip.h")]

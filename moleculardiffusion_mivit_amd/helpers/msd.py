@@ -167,7 +167,7 @@ def track_msd(positions, offsets, dt=1.0, max_lag=None):
 # multi-state tracks: changepoints of the step variance and one row of estimates per segment (csrc/segment.hip)
 # ----------------------------------------------------------------------------------------------------------------------
 def _segment_numpy(pos, offsets, min_len, penalty, min_var, return_margin=False):
-    """The arithmetic of csrc/segment.hip::seg_tracks_kernel in its order (include/mivit_hip.h, mivit_segment_tracks):
+    """The arithmetic of csrc/segment.hip::partition_kernel<VarianceModel> in its order (include/mivit_hip.h, mivit_segment_tracks):
     np.cumsum is the sequential prefix sum, np.argmin returns the lowest index among equal minima.  pos [N, 2] float64,
     offsets [n_tracks + 1] int64 -> (seg_start [N] int32, cost [n_tracks] float64).  Differs from the kernel in log alone.
     return_margin: also margin [n_tracks], the smallest gap between the chosen candidate and the runner-up over the steps j
@@ -220,7 +220,7 @@ def _segment_numpy(pos, offsets, min_len, penalty, min_var, return_margin=False)
 
 
 def _segment_stats_numpy(pos, seg_offsets, seg_track_end, dt, blur):
-    """The arithmetic of csrc/segment.hip::seg_stats_kernel in its order: np.cumsum(...)[-1] is a sequential sum.  -> (D_cve,
+    """The arithmetic of csrc/segment.hip::stretch_stats_kernel<false> in its order: np.cumsum(...)[-1] is a sequential sum.  -> (D_cve,
     D_mle, sigma2 [n_seg] float64, n_increments [n_seg] int32), bitwise the kernel's."""
     n_seg = len(seg_track_end)
     d_cve, d_mle, sigma2 = np.full(n_seg, np.nan), np.full(n_seg, np.nan), np.full(n_seg, np.nan)
@@ -245,6 +245,52 @@ def _segment_stats_numpy(pos, seg_offsets, seg_track_end, dt, blur):
     return d_cve, d_mle, sigma2, n_inc
 
 
+def _check_partition_args(positions, offsets, dt, min_len, penalty, min_var, blur, limit_name):
+    """What segment_tracks and segment_transport check alike -> offsets (a tensor as it came, anything else as an array).
+    limit_name: the caller's name for ops.SEG_MAX_LEN, for the message."""
+    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
+        raise ValueError(f"min_len must be an integer >= 2, got {min_len}")
+    if not float(penalty) >= 0.0:
+        raise ValueError(f"penalty must be >= 0, got {penalty}")
+    if not 0.0 < float(min_var) < float("inf"):
+        raise ValueError(f"min_var must be positive and finite, got {min_var}")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
+    if len(positions.shape) != 2 or positions.shape[1] != 2:
+        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
+    if torch.is_tensor(positions) != torch.is_tensor(offsets):
+        raise ValueError("positions and offsets must both be tensors or both be arrays")
+    if torch.is_tensor(positions) and positions.device != offsets.device:
+        raise ValueError(f"positions on {positions.device}, offsets on {offsets.device}")
+    offsets = offsets if torch.is_tensor(offsets) else np.asarray(offsets)
+    _check_offsets(offsets, positions.shape[0])
+    if torch.is_tensor(positions) and positions.device.type == "cuda":
+        from .. import ops
+        lengths = offsets[1:] - offsets[:-1]
+        if len(lengths) and int(lengths.max()) > ops.SEG_MAX_LEN:
+            raise ValueError(f"a track of {int(lengths.max())} rows on the GPU, the kernel's limit is {ops.SEG_MAX_LEN} "
+                             f"(ops.{limit_name})")
+    return offsets
+
+
+def _stretch_layout(seg_start, offsets, n_rows):
+    """seg_start [N] (1 on the first row of every stretch) and offsets [n_tracks + 1] int64, both tensors or both arrays ->
+    (first [n_seg] int64, the first row of every stretch; seg_offsets [n_seg + 1] int64, their CSR over the rows; seg_track
+    [n_seg] int64; track_end [n_seg] int64, the row at which each stretch's track ends)."""
+    if torch.is_tensor(seg_start):
+        first = torch.nonzero(seg_start, as_tuple=True)[0]
+        seg_offsets = torch.cat([first, torch.full((1,), n_rows, dtype=torch.int64, device=first.device)])
+        seg_track = torch.searchsorted(offsets, first, right=True) - 1
+    else:
+        first = np.nonzero(seg_start)[0].astype(np.int64)
+        seg_offsets = np.concatenate([first, np.full(1, n_rows, np.int64)])
+        seg_track = np.searchsorted(offsets, first, side="right").astype(np.int64) - 1
+    # an empty track shares its offset with the next one: the LAST track that starts at or before the row owns it
+    return first, seg_offsets, seg_track, offsets[seg_track + 1]
+
+
 def segment_tracks(positions, offsets, dt=1.0, min_len=4, penalty=3.0, min_var=1e-12, blur=0.0):
     """Tracks whose diffusion coefficient changes: the optimal partition of every track into stretches of constant step
     variance, and the estimates of each stretch.  positions [N, 2] (y, x) sorted by track and by frame, offsets [n_tracks + 1]
@@ -264,49 +310,22 @@ def segment_tracks(positions, offsets, dt=1.0, min_len=4, penalty=3.0, min_var=1
     whole frame).  D_cve and sigma2 are NaN for a segment of fewer than 2 increments.  include/mivit_hip.h has the
     arithmetic.  CUDA tensors go to the kernels (csrc/segment.hip: two launches; a track has at most ops.SEG_MAX_LEN rows),
     numpy arrays and CPU tensors to the numpy restatements; the output is of the input's kind."""
-    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
-        raise ValueError(f"min_len must be an integer >= 2, got {min_len}")
-    if not float(penalty) >= 0.0:
-        raise ValueError(f"penalty must be >= 0, got {penalty}")
-    if not 0.0 < float(min_var) < float("inf"):
-        raise ValueError(f"min_var must be positive and finite, got {min_var}")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(blur) <= 0.25:
-        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
-    if len(positions.shape) != 2 or positions.shape[1] != 2:
-        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
-    if torch.is_tensor(positions) != torch.is_tensor(offsets):
-        raise ValueError("positions and offsets must both be tensors or both be arrays")
-    if torch.is_tensor(positions) and positions.device != offsets.device:
-        raise ValueError(f"positions on {positions.device}, offsets on {offsets.device}")
-    offsets = offsets if torch.is_tensor(offsets) else np.asarray(offsets)
-    _check_offsets(offsets, positions.shape[0])
+    offsets = _check_partition_args(positions, offsets, dt, min_len, penalty, min_var, blur, "SEG_MAX_LEN")
     min_len, penalty, min_var, dt, blur = int(min_len), float(penalty), float(min_var), float(dt), float(blur)
     is_t = torch.is_tensor(positions)
     if is_t and positions.device.type == "cuda":
         from .. import ops
-        lengths = offsets[1:] - offsets[:-1]
-        if len(lengths) and int(lengths.max()) > ops.SEG_MAX_LEN:
-            raise ValueError(f"a track of {int(lengths.max())} rows on the GPU, the kernel's limit is {ops.SEG_MAX_LEN} "
-                             f"(ops.SEG_MAX_LEN)")
         pos = positions.detach().double().contiguous()
         seg_start, cost = ops.segment_tracks(pos, offsets.int().contiguous(), min_len, penalty, min_var)
-        first = torch.nonzero(seg_start, as_tuple=True)[0]
-        seg_offsets = torch.cat([first, torch.full((1,), pos.shape[0], dtype=torch.int64, device=pos.device)])
-        seg_track = torch.searchsorted(offsets.long().contiguous(), first, right=True) - 1
-        # an empty track shares its offset with the next one: the LAST track that starts at or before the row owns it
-        track_end = offsets.long()[seg_track + 1]
+        _, seg_offsets, seg_track, track_end = _stretch_layout(seg_start, offsets.long().contiguous(), pos.shape[0])
         d_cve, d_mle, sigma2, n_inc = ops.segment_stats(pos, seg_offsets.int(), track_end.int(), dt, blur)
         return {"seg_offsets": seg_offsets, "seg_track": seg_track, "D_cve": d_cve, "D_mle": d_mle, "sigma2": sigma2,
                 "n_increments": n_inc.long(), "cost": cost}
     pos = positions.detach().double().numpy() if is_t else np.asarray(positions, dtype=np.float64)
     off = (offsets.detach().numpy() if is_t else offsets).astype(np.int64)
     seg_start, cost = _segment_numpy(pos, off, min_len, penalty, min_var)
-    first = np.nonzero(seg_start)[0].astype(np.int64)
-    seg_offsets = np.concatenate([first, np.full(1, len(pos), np.int64)])
-    seg_track = np.searchsorted(off, first, side="right").astype(np.int64) - 1
-    d_cve, d_mle, sigma2, n_inc = _segment_stats_numpy(pos, seg_offsets, off[seg_track + 1], dt, blur)
+    _, seg_offsets, seg_track, track_end = _stretch_layout(seg_start, off, len(pos))
+    d_cve, d_mle, sigma2, n_inc = _segment_stats_numpy(pos, seg_offsets, track_end, dt, blur)
     out = {"seg_offsets": seg_offsets, "seg_track": seg_track, "D_cve": d_cve, "D_mle": d_mle, "sigma2": sigma2,
            "n_increments": n_inc.astype(np.int64), "cost": cost}
     return {k: torch.from_numpy(v) for k, v in out.items()} if is_t else out
@@ -1803,13 +1822,13 @@ def estimate_directed_ml(positions, offsets, variances=None, frames=None, use=No
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# run-and-pause transport: changepoints of the velocity and one row of estimates per stretch (csrc/transport.hip)
+# run-and-pause transport: changepoints of the velocity and one row of estimates per stretch (csrc/segment.hip)
 # ----------------------------------------------------------------------------------------------------------------------
 _TRANSPORT_CLASSES = {"both": 0, "directed": 1, "diffusive": 2}
 
 
 def _transport_numpy(pos, offsets, min_len, penalty, velocity_penalty, min_var, classes, return_margin=False):
-    """The arithmetic of csrc/transport.hip::transport_kernel in its order (include/mivit_hip.h, mivit_segment_transport):
+    """The arithmetic of csrc/segment.hip::partition_kernel<TransportModel> in its order (include/mivit_hip.h, mivit_segment_transport):
     np.cumsum is the sequential prefix sum, np.argmin returns the lowest index among equal minima.  pos [N, 2] float64,
     offsets [n_tracks + 1] int64, classes 0 (both), 1 (directed) or 2 (diffusive) -> (seg_start [N] int32, seg_class [N]
     int32, cost [n_tracks] float64).  Differs from the kernel in log alone.  return_margin: also margin [n_tracks], the smallest
@@ -1883,7 +1902,7 @@ def _transport_numpy(pos, offsets, min_len, penalty, velocity_penalty, min_var, 
 
 
 def _transport_stats_numpy(pos, seg_offsets, seg_track_end, dt, blur):
-    """The arithmetic of csrc/transport.hip::transport_stats_kernel in its order: np.cumsum(...)[-1] is a sequential sum.  ->
+    """The arithmetic of csrc/segment.hip::stretch_stats_kernel<true> in its order: np.cumsum(...)[-1] is a sequential sum.  ->
     (velocity [n_seg, 2], D_res, D_cve, sigma2 [n_seg] float64, n_increments [n_seg] int32), bitwise the kernel's."""
     n_seg = len(seg_track_end)
     velocity = np.full((n_seg, 2), np.nan)
@@ -1929,46 +1948,22 @@ def segment_transport(positions, offsets, dt=1.0, min_len=4, penalty=3.0, veloci
     only where that is strictly cheaper.  classes "directed" gives every stretch a velocity, "diffusive" none (the partition
     and cost of segment_tracks bit for bit).  A whole-track fit (estimate_directed_ml) averages a run with a pause; pass
     seg_offsets to it, or to estimate_diffusion_ml, for the per-stretch fits with error bars.  include/mivit_hip.h has the
-    arithmetic.  CUDA tensors go to the kernels (csrc/transport.hip: two launches; a track has at most ops.TRANSPORT_MAX_LEN
+    arithmetic.  CUDA tensors go to the kernels (csrc/segment.hip: two launches; a track has at most ops.TRANSPORT_MAX_LEN
     rows), numpy arrays and CPU tensors to the numpy restatements; the output is of the input's kind."""
-    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
-        raise ValueError(f"min_len must be an integer >= 2, got {min_len}")
-    if not float(penalty) >= 0.0:
-        raise ValueError(f"penalty must be >= 0, got {penalty}")
     if not float(velocity_penalty) >= 0.0:
         raise ValueError(f"velocity_penalty must be >= 0, got {velocity_penalty}")
-    if not 0.0 < float(min_var) < float("inf"):
-        raise ValueError(f"min_var must be positive and finite, got {min_var}")
     if not isinstance(classes, str) or classes not in _TRANSPORT_CLASSES:
         raise ValueError(f"classes must be one of {', '.join(_TRANSPORT_CLASSES)}, got {classes!r}")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(blur) <= 0.25:
-        raise ValueError(f"blur must lie in [0, 1/4], got {blur}")
-    if len(positions.shape) != 2 or positions.shape[1] != 2:
-        raise ValueError(f"positions must be [N, 2], got {tuple(positions.shape)}")
-    if torch.is_tensor(positions) != torch.is_tensor(offsets):
-        raise ValueError("positions and offsets must both be tensors or both be arrays")
-    if torch.is_tensor(positions) and positions.device != offsets.device:
-        raise ValueError(f"positions on {positions.device}, offsets on {offsets.device}")
-    offsets = offsets if torch.is_tensor(offsets) else np.asarray(offsets)
-    _check_offsets(offsets, positions.shape[0])
+    offsets = _check_partition_args(positions, offsets, dt, min_len, penalty, min_var, blur, "TRANSPORT_MAX_LEN")
     min_len, penalty, velocity_penalty, min_var = int(min_len), float(penalty), float(velocity_penalty), float(min_var)
     dt, blur = float(dt), float(blur)
     is_t = torch.is_tensor(positions)
     if is_t and positions.device.type == "cuda":
         from .. import ops
-        lengths = offsets[1:] - offsets[:-1]
-        if len(lengths) and int(lengths.max()) > ops.TRANSPORT_MAX_LEN:
-            raise ValueError(f"a track of {int(lengths.max())} rows on the GPU, the kernel's limit is {ops.TRANSPORT_MAX_LEN} "
-                             f"(ops.TRANSPORT_MAX_LEN)")
         pos = positions.detach().double().contiguous()
         seg_start, row_class, cost = ops.segment_transport(pos, offsets.int().contiguous(), min_len, penalty, velocity_penalty,
                                                            min_var, classes)
-        first = torch.nonzero(seg_start, as_tuple=True)[0]
-        seg_offsets = torch.cat([first, torch.full((1,), pos.shape[0], dtype=torch.int64, device=pos.device)])
-        seg_track = torch.searchsorted(offsets.long().contiguous(), first, right=True) - 1
-        track_end = offsets.long()[seg_track + 1]
+        first, seg_offsets, seg_track, track_end = _stretch_layout(seg_start, offsets.long().contiguous(), pos.shape[0])
         velocity, d_res, d_cve, sigma2, n_inc = ops.transport_stats(pos, seg_offsets.int(), track_end.int(), dt, blur)
         return {"seg_offsets": seg_offsets, "seg_track": seg_track, "seg_class": row_class[first].long(), "velocity": velocity,
                 "speed": torch.sqrt(velocity[:, 0] * velocity[:, 0] + velocity[:, 1] * velocity[:, 1]), "D_res": d_res,
@@ -1976,10 +1971,8 @@ def segment_transport(positions, offsets, dt=1.0, min_len=4, penalty=3.0, veloci
     pos = positions.detach().double().numpy() if is_t else np.asarray(positions, dtype=np.float64)
     off = (offsets.detach().numpy() if is_t else offsets).astype(np.int64)
     seg_start, row_class, cost = _transport_numpy(pos, off, min_len, penalty, velocity_penalty, min_var, _TRANSPORT_CLASSES[classes])
-    first = np.nonzero(seg_start)[0].astype(np.int64)
-    seg_offsets = np.concatenate([first, np.full(1, len(pos), np.int64)])
-    seg_track = np.searchsorted(off, first, side="right").astype(np.int64) - 1
-    velocity, d_res, d_cve, sigma2, n_inc = _transport_stats_numpy(pos, seg_offsets, off[seg_track + 1], dt, blur)
+    first, seg_offsets, seg_track, track_end = _stretch_layout(seg_start, off, len(pos))
+    velocity, d_res, d_cve, sigma2, n_inc = _transport_stats_numpy(pos, seg_offsets, track_end, dt, blur)
     out = {"seg_offsets": seg_offsets, "seg_track": seg_track, "seg_class": row_class[first].astype(np.int64), "velocity": velocity,
            "speed": np.sqrt(velocity[:, 0] * velocity[:, 0] + velocity[:, 1] * velocity[:, 1]), "D_res": d_res, "D_cve": d_cve,
            "sigma2": sigma2, "n_increments": n_inc.astype(np.int64), "cost": cost}

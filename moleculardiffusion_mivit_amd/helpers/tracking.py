@@ -2247,7 +2247,7 @@ def estimate_track_diffusion(movie, model, seq_len, patch_size=7, dt=1.0, norm=N
     transport (default None: the code path without it): a dict of helpers/msd.segment_transport arguments (min_len, penalty,
     velocity_penalty, min_var, classes, blur; {} for the defaults; dt is this function's): run-and-pause tracks, whose VELOCITY
     changes along the track.  The result gains "transport": the segment_transport dict computed on the positions segment
-    uses (drift-corrected if drift is given; csrc/transport.hip), plus n_sequences and D_model [n_seg] from the windows of
+    uses (drift-corrected if drift is given; csrc/segment.hip), plus n_sequences and D_model [n_seg] from the windows of
     plan_sequences(seg_offsets, seq_len, tail) exactly as for segment, so that no window straddles a cut.  With directed given
     it also holds velocity_ml, velocity_ml_std [n_seg, 2], speed_ml, D_dir, D_dir_std, lr_directed, p_directed and
     directed_status per stretch (estimate_directed_ml on seg_offsets with the arguments reported under "directed"), and with

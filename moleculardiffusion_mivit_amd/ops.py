@@ -1079,7 +1079,10 @@ def _map_displacements_checked(disp, s0, geom_of, verts, lengths, vert_offsets, 
     return pos, arc, edge
 
 
-SEG_MAX_LEN = 4096           # csrc/segment.hip: rows of a track whose recurrence state (20 B a row) fits in LDS
+# csrc/segment.hip: rows of a track whose recurrence state fits in LDS (the variance model 20 B a row, 81 920 B at the limit;
+# the transport model 36 B a row, 147 456 B)
+SEG_MAX_LEN = 4096
+TRANSPORT_MAX_LEN = SEG_MAX_LEN
 MARKOV_MAX_K = 8             # csrc/segment.hip: states of mivit_markov_states; csrc/hmm.hip: of mivit_hmm_estep / _viterbi
 
 
@@ -1090,35 +1093,61 @@ def _seg_tensor(t, dtype, ndim, name, what):
     return t
 
 
+def _partition_args(name, limit_name, pos, offsets, min_len, penalty, min_var):
+    """What segment_tracks and segment_transport check alike -> (N, n_tracks, the rows of the longest track: read back from
+    offsets, 0 without a track)."""
+    _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
+    _seg_tensor(offsets, torch.int32, 1, name, "offsets [n_tracks + 1]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"{name}: pos must be [N, 2], got {tuple(pos.shape)}")
+    if offsets.numel() < 1:
+        raise ValueError(f"{name}: offsets must have n_tracks + 1 entries")
+    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
+        raise ValueError(f"{name}: min_len must be an integer >= 2, got {min_len}")
+    if not float(penalty) >= 0.0:
+        raise ValueError(f"{name}: penalty must be >= 0, got {penalty}")
+    if not 0.0 < float(min_var) < float("inf"):
+        raise ValueError(f"{name}: min_var must be positive and finite, got {min_var}")
+    n, n_tracks = pos.shape[0], offsets.numel() - 1
+    if n_tracks == 0:
+        return n, 0, 0
+    off = offsets.cpu()
+    if int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+        raise ValueError(f"{name}: offsets must rise from 0 to the number of rows {n}")
+    max_len = int((off[1:] - off[:-1]).max())
+    if max_len > SEG_MAX_LEN:
+        raise ValueError(f"{name}: a track of {max_len} rows, the kernel's limit is {SEG_MAX_LEN} ({limit_name})")
+    return n, n_tracks, max_len
+
+
+def _stretch_stats_args(name, pos, seg_offsets, seg_track_end, dt, blur):
+    """What segment_stats and transport_stats check alike -> n_seg."""
+    _seg_tensor(pos, torch.float64, 2, name, "pos [N, 2]")
+    _seg_tensor(seg_offsets, torch.int32, 1, name, "seg_offsets [n_seg + 1]")
+    _seg_tensor(seg_track_end, torch.int32, 1, name, "seg_track_end [n_seg]")
+    if pos.shape[1] != 2:
+        raise ValueError(f"{name}: pos must be [N, 2], got {tuple(pos.shape)}")
+    if seg_offsets.numel() != seg_track_end.numel() + 1:
+        raise ValueError(f"{name}: seg_offsets must have one entry more than seg_track_end, got {seg_offsets.numel()} and "
+                         f"{seg_track_end.numel()}")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"{name}: dt must be positive and finite, got {dt}")
+    if not 0.0 <= float(blur) <= 0.25:
+        raise ValueError(f"{name}: the blur coefficient must lie in [0, 1/4], got {blur}")
+    return seg_track_end.numel()
+
+
 def segment_tracks(pos: torch.Tensor, offsets: torch.Tensor, min_len: int = 4, penalty: float = 3.0, min_var: float = 1e-12):
     """The optimal partition of every track into stretches of constant step variance (csrc/segment.hip,
     mivit_segment_tracks): pos [N, 2] float64 on the GPU, sorted by track and by frame; offsets [n_tracks + 1] int32 (CSR, from
     0 to N) -> (seg_start [N] int32, 1 on the first row of every segment; cost [n_tracks] float64, NaN for a track without an
     increment).  A track has at most SEG_MAX_LEN rows.  The longest track is read back (one number) to size the kernel's LDS.
     See include/mivit_hip.h for the recurrence and helpers/msd.segment_tracks for the front end."""
-    pos = _seg_tensor(pos, torch.float64, 2, "segment_tracks", "pos [N, 2]")
-    offsets = _seg_tensor(offsets, torch.int32, 1, "segment_tracks", "offsets [n_tracks + 1]")
-    if pos.shape[1] != 2:
-        raise ValueError(f"segment_tracks: pos must be [N, 2], got {tuple(pos.shape)}")
-    if offsets.numel() < 1:
-        raise ValueError("segment_tracks: offsets must have n_tracks + 1 entries")
-    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
-        raise ValueError(f"segment_tracks: min_len must be an integer >= 2, got {min_len}")
-    if not float(penalty) >= 0.0:
-        raise ValueError(f"segment_tracks: penalty must be >= 0, got {penalty}")
-    if not 0.0 < float(min_var) < float("inf"):
-        raise ValueError(f"segment_tracks: min_var must be positive and finite, got {min_var}")
-    n, n_tracks = pos.shape[0], offsets.numel() - 1
+    n, n_tracks, max_len = _partition_args("segment_tracks", "SEG_MAX_LEN", pos, offsets, min_len, penalty, min_var)
     seg_start = torch.zeros(n, dtype=torch.int32, device=pos.device)
     cost = torch.empty(n_tracks, dtype=torch.float64, device=pos.device)
     if n_tracks == 0:
         return seg_start, cost
-    off = offsets.cpu()
-    if int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
-        raise ValueError(f"segment_tracks: offsets must rise from 0 to the number of rows {n}")
-    max_len = int((off[1:] - off[:-1]).max())
-    if max_len > SEG_MAX_LEN:
-        raise ValueError(f"segment_tracks: a track of {max_len} rows, the kernel's limit is {SEG_MAX_LEN} (SEG_MAX_LEN)")
     N.check(N.lib.mivit_segment_tracks(_p(pos), n, _p(offsets), n_tracks, max_len, int(min_len), float(penalty), float(min_var),
                                        _p(seg_start), _p(cost), _s(pos)), "mivit_segment_tracks")
     return seg_start, cost
@@ -1129,19 +1158,7 @@ def segment_stats(pos: torch.Tensor, seg_offsets: torch.Tensor, seg_track_end: t
     [n_seg + 1] int32 (the CSR of the segments over the rows), seg_track_end [n_seg] int32 (the row at which each segment's
     track ends), blur the motion-blur coefficient R in [0, 1/4] -> (D_cve, D_mle, sigma2 [n_seg] float64, n_increments [n_seg]
     int32).  See include/mivit_hip.h for the arithmetic."""
-    pos = _seg_tensor(pos, torch.float64, 2, "segment_stats", "pos [N, 2]")
-    seg_offsets = _seg_tensor(seg_offsets, torch.int32, 1, "segment_stats", "seg_offsets [n_seg + 1]")
-    seg_track_end = _seg_tensor(seg_track_end, torch.int32, 1, "segment_stats", "seg_track_end [n_seg]")
-    if pos.shape[1] != 2:
-        raise ValueError(f"segment_stats: pos must be [N, 2], got {tuple(pos.shape)}")
-    if seg_offsets.numel() != seg_track_end.numel() + 1:
-        raise ValueError(f"segment_stats: seg_offsets must have one entry more than seg_track_end, got {seg_offsets.numel()} and "
-                         f"{seg_track_end.numel()}")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"segment_stats: dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(blur) <= 0.25:
-        raise ValueError(f"segment_stats: the blur coefficient must lie in [0, 1/4], got {blur}")
-    n_seg = seg_track_end.numel()
+    n_seg = _stretch_stats_args("segment_stats", pos, seg_offsets, seg_track_end, dt, blur)
     d_cve, d_mle, sigma2 = (torch.empty(n_seg, dtype=torch.float64, device=pos.device) for _ in range(3))
     n_inc = torch.empty(n_seg, dtype=torch.int32, device=pos.device)
     N.check(N.lib.mivit_segment_stats(_p(pos), pos.shape[0], _p(seg_offsets), _p(seg_track_end), n_seg, float(dt), float(blur),
@@ -1539,48 +1556,28 @@ def render_movie(pos: torch.Tensor, amp: torch.Tensor, sigma_hr: float, up: int,
     return movie
 
 
-TRANSPORT_MAX_LEN = 4096     # csrc/transport.hip: rows of a track whose recurrence state (36 B a row, 147 456 B) fits in LDS
 TRANSPORT_CLASSES = {"both": 0, "directed": 1, "diffusive": 2}
 
 
 def segment_transport(pos: torch.Tensor, offsets: torch.Tensor, min_len: int = 4, penalty: float = 3.0,
                       velocity_penalty: float = 3.0, min_var: float = 1e-12, classes: str = "both"):
     """The optimal partition of every track into stretches that are each diffusive (class 0) or directed (class 1: one variance
-    about a constant velocity) (csrc/transport.hip, mivit_segment_transport): pos [N, 2] float64 on the GPU, sorted by track and
+    about a constant velocity) (csrc/segment.hip, mivit_segment_transport): pos [N, 2] float64 on the GPU, sorted by track and
     by frame; offsets [n_tracks + 1] int32 (CSR, from 0 to N); classes "both", "directed" (every stretch has a velocity) or
     "diffusive" (none has: ops.segment_tracks bit for bit) -> (seg_start [N] int32, 1 on the first row of every stretch;
     seg_class [N] int32, the class of the stretch each row belongs to; cost [n_tracks] float64, NaN for a track without an
     increment).  A track has at most TRANSPORT_MAX_LEN rows.  The longest track is read back (one number) to size the kernel's
     LDS.  See include/mivit_hip.h for the recurrence and helpers/msd.segment_transport for the front end."""
-    pos = _seg_tensor(pos, torch.float64, 2, "segment_transport", "pos [N, 2]")
-    offsets = _seg_tensor(offsets, torch.int32, 1, "segment_transport", "offsets [n_tracks + 1]")
-    if pos.shape[1] != 2:
-        raise ValueError(f"segment_transport: pos must be [N, 2], got {tuple(pos.shape)}")
-    if offsets.numel() < 1:
-        raise ValueError("segment_transport: offsets must have n_tracks + 1 entries")
-    if isinstance(min_len, bool) or int(min_len) != min_len or min_len < 2:
-        raise ValueError(f"segment_transport: min_len must be an integer >= 2, got {min_len}")
-    if not float(penalty) >= 0.0:
-        raise ValueError(f"segment_transport: penalty must be >= 0, got {penalty}")
     if not float(velocity_penalty) >= 0.0:
         raise ValueError(f"segment_transport: velocity_penalty must be >= 0, got {velocity_penalty}")
-    if not 0.0 < float(min_var) < float("inf"):
-        raise ValueError(f"segment_transport: min_var must be positive and finite, got {min_var}")
     if not isinstance(classes, str) or classes not in TRANSPORT_CLASSES:
         raise ValueError(f"segment_transport: classes must be one of {', '.join(TRANSPORT_CLASSES)}, got {classes!r}")
-    n, n_tracks = pos.shape[0], offsets.numel() - 1
+    n, n_tracks, max_len = _partition_args("segment_transport", "TRANSPORT_MAX_LEN", pos, offsets, min_len, penalty, min_var)
     seg_start = torch.zeros(n, dtype=torch.int32, device=pos.device)
     seg_class = torch.zeros(n, dtype=torch.int32, device=pos.device)
     cost = torch.empty(n_tracks, dtype=torch.float64, device=pos.device)
     if n_tracks == 0:
         return seg_start, seg_class, cost
-    off = offsets.cpu()
-    if int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
-        raise ValueError(f"segment_transport: offsets must rise from 0 to the number of rows {n}")
-    max_len = int((off[1:] - off[:-1]).max())
-    if max_len > TRANSPORT_MAX_LEN:
-        raise ValueError(f"segment_transport: a track of {max_len} rows, the kernel's limit is {TRANSPORT_MAX_LEN} "
-                         f"(TRANSPORT_MAX_LEN)")
     N.check(N.lib.mivit_segment_transport(_p(pos), n, _p(offsets), n_tracks, max_len, int(min_len), float(penalty),
                                           float(velocity_penalty), float(min_var), TRANSPORT_CLASSES[classes], _p(seg_start),
                                           _p(seg_class), _p(cost), _s(pos)), "mivit_segment_transport")
@@ -1588,22 +1585,10 @@ def segment_transport(pos: torch.Tensor, offsets: torch.Tensor, min_len: int = 4
 
 
 def transport_stats(pos: torch.Tensor, seg_offsets: torch.Tensor, seg_track_end: torch.Tensor, dt: float = 1.0, blur: float = 0.0):
-    """One row of estimates per stretch about the stretch's own velocity (csrc/transport.hip, mivit_transport_stats): pos,
+    """One row of estimates per stretch about the stretch's own velocity (csrc/segment.hip, mivit_transport_stats): pos,
     seg_offsets, seg_track_end and blur as segment_stats takes them -> (velocity [n_seg, 2] float64 (y, x) per unit of dt,
     D_res, D_cve, sigma2 [n_seg] float64, n_increments [n_seg] int32).  See include/mivit_hip.h for the arithmetic."""
-    pos = _seg_tensor(pos, torch.float64, 2, "transport_stats", "pos [N, 2]")
-    seg_offsets = _seg_tensor(seg_offsets, torch.int32, 1, "transport_stats", "seg_offsets [n_seg + 1]")
-    seg_track_end = _seg_tensor(seg_track_end, torch.int32, 1, "transport_stats", "seg_track_end [n_seg]")
-    if pos.shape[1] != 2:
-        raise ValueError(f"transport_stats: pos must be [N, 2], got {tuple(pos.shape)}")
-    if seg_offsets.numel() != seg_track_end.numel() + 1:
-        raise ValueError(f"transport_stats: seg_offsets must have one entry more than seg_track_end, got {seg_offsets.numel()} "
-                         f"and {seg_track_end.numel()}")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"transport_stats: dt must be positive and finite, got {dt}")
-    if not 0.0 <= float(blur) <= 0.25:
-        raise ValueError(f"transport_stats: the blur coefficient must lie in [0, 1/4], got {blur}")
-    n_seg = seg_track_end.numel()
+    n_seg = _stretch_stats_args("transport_stats", pos, seg_offsets, seg_track_end, dt, blur)
     velocity = torch.empty(n_seg, 2, dtype=torch.float64, device=pos.device)
     d_res, d_cve, sigma2 = (torch.empty(n_seg, dtype=torch.float64, device=pos.device) for _ in range(3))
     n_inc = torch.empty(n_seg, dtype=torch.int32, device=pos.device)

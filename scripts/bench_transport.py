@@ -1,6 +1,7 @@
-"""Time of the run-and-pause segmenter (ops.segment_transport -> csrc/transport.hip) next to the kernel it is modelled on
-(ops.segment_tracks -> csrc/segment.hip), in ONE process on the same input: the track sets of scripts/bench_segment.py (two-state
-tracks, D 0.05 / 1.0, a change every 40 rows: 20 tracks of 1000 rows, 4096 of 100, 352 of 300, and 64 at the limit of 4096 rows).
+"""Time of the run-and-pause segmenter (ops.segment_transport) next to the variance-change segmenter whose recurrence kernel
+it shares (ops.segment_tracks; both csrc/segment.hip), in ONE process on the same input: the track sets of
+scripts/bench_segment.py (two-state tracks, D 0.05 / 1.0, a change every 40 rows: 20 tracks of 1000 rows, 4096 of 100, 352 of
+300, and 64 at the limit of 4096 rows).
 Events on the stream after a warm-up, minimum of 5 windows.  Each time is the ops call: the launch, the allocation of its
 outputs and the read-back of the longest track that sizes its LDS.  segment_transport is timed in its three modes; "both" and
 "directed" take two logs per candidate where segment_tracks takes one, "diffusive" takes one and must reproduce
@@ -56,7 +57,8 @@ def bench_shape(n_tracks, rows):
     offsets = np.arange(n_tracks + 1, dtype=np.int64) * rows
     dp, do = checked("upload", lambda: (torch.from_numpy(pos).cuda(), torch.from_numpy(offsets).cuda()))
     do32 = checked("upload", lambda: do.int())
-    out = {"n_tracks": n_tracks, "rows": rows, "lds_bytes_segment_tracks": 20 * rows, "lds_bytes_segment_transport": 36 * rows}
+    out = {"n_tracks": n_tracks, "rows": rows, "lds_bytes_segment_tracks": 20 * rows,           # "diffusive" runs its kernel
+           "lds_bytes_segment_transport": {"both": 36 * rows, "directed": 36 * rows, "diffusive": 20 * rows}}
     t_seg = checked(f"segment_tracks {n_tracks} x {rows}", lambda: t_events(lambda: ops.segment_tracks(dp, do32)))
     out["segment_tracks_ms"] = t_seg * 1e3
     for mode in ("both", "directed", "diffusive"):

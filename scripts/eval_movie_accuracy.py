@@ -69,7 +69,7 @@ Gaussians and of the likelihood-ratio detector at the per-pixel false-alarm prob
 track_particles_tensors(..., detector={...})) on the same movie with the same linking, also printed to stderr.
 --states D1 D2 P_STAY --state-velocity "VY,VX[;VY,VX]" --transport gives the states a velocity each in pixels per frame (one
 pair: the first state pauses and the second runs at it; simulate_movie's states["velocity"]), runs
-estimate_track_diffusion(..., transport={}, directed={}) (helpers/msd.segment_transport, csrc/transport.hip) and adds
+estimate_track_diffusion(..., transport={}, directed={}) (helpers/msd.segment_transport, csrc/segment.hip) and adds
 "transport": over the tracks matched to a particle the recall and precision of the planted switches of the velocity, the
 share of rows whose stretch has the right class, and the speed of the directed stretches against the truth.  A tool, not a
 test: it asserts no accuracy.

@@ -14,8 +14,8 @@ Run by `__graft_entry__.build()` and by tests/test_isa_invariants.py (CPU, needs
   4. No inline-asm VALU instruction is the first reader of an MFMA result (no hazard wait states would separate them).
   5. The kernels of csrc/confined_ml.hip keep the whole Kalman state of a candidate in registers, and those of
      csrc/directed_ml.hip both recurrences and the three sums per axis: no scratch and no LDS (include/mivit_hip.h promises both).
-  6. The kernels of csrc/transport.hip (the three instances of transport_kernel and transport_stats_kernel) use no scratch:
-     a spill inside the candidate loop would put memory traffic behind each of its two logs.
+  6. The partition and stretch kernels of csrc/segment.hip (the three instances of partition_kernel, the two of
+     stretch_stats_kernel) use no scratch: a spill inside the candidate loop would put memory traffic behind each of its logs.
 
 Exit status 0 = all invariants hold; otherwise the violations are listed and the status is 1.
 """
@@ -295,12 +295,12 @@ def main():
                 sb, lds = scratch_bytes(kc[n][1]), kc[n][1].get("amdhsa_group_segment_fixed_size", kc[n][1].get("group_segment_fixed_size"))
                 if sb != 0 or lds is None or int(lds, 0) != 0:
                     errs.append(f"{n}: scratch bytes = {sb}, LDS bytes = {lds} (both must be 0)")
-    # ---- transport.hip: the recurrence's state lives in LDS and registers, the per-stretch sums in registers ----
-    kt = kernels(device_asm("transport.hip"))
-    for want, count in (("transport_kernelILi", 3), ("transport_stats_kernelE", 1)):
+    # ---- segment.hip: the recurrence's state lives in LDS and registers, the per-stretch sums in registers ----
+    kt = kernels(device_asm("segment.hip"))
+    for want, count in (("partition_kernelI", 3), ("stretch_stats_kernelILb", 2)):
         found = [n for n in kt if want in n]
         if len(found) != count:
-            errs.append(f"transport.hip: {len(found)} kernels match {want}, {count} expected")
+            errs.append(f"segment.hip: {len(found)} kernels match {want}, {count} expected")
         for n in found:
             sb = scratch_bytes(kt[n][1])
             if sb != 0:

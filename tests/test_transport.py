@@ -1,4 +1,4 @@
-"""CPU: the numpy restatements of csrc/transport.hip (helpers/msd._transport_numpy, _transport_stats_numpy) against the oracle
+"""CPU: the numpy restatements of csrc/segment.hip (helpers/msd._transport_numpy, _transport_stats_numpy) against the oracle
 and the formulas of tests/transport_common.py, the statistics of the segmenter on planted run-and-pause tracks and on free
 walks, the front end helpers/msd.segment_transport, and the simulator's per-state velocities (generation.multi_state,
 simulate_movie(states={..., "velocity": ...})).  No kernel is launched here; tests/test_transport_gpu.py holds the kernels

@@ -1,4 +1,4 @@
-"""GPU: the kernels of csrc/transport.hip (ops.segment_transport, ops.transport_stats) against the numpy restatements of
+"""GPU: the kernels of csrc/segment.hip (ops.segment_transport, ops.transport_stats) against the numpy restatements of
 helpers/msd.py, which tests/test_transport.py holds against the oracle of tests/transport_common.py, and the paths that reach
 them: helpers/msd.segment_transport, the raw C-ABI inside the guarded buffers of tests/abi_guard.py, and
 tracking.estimate_track_diffusion(transport=...) on a simulated run-and-pause movie.
