@@ -13,6 +13,7 @@ ROOT = os.path.dirname(PKG)
 SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_fast.hip", "embed.hip", "rowstream.hip", "wavestream.hip", "gemm_dma.hip", "wgrad_dma.hip", "wgrad_small.hip", "fused_fwd.hip", "fused_bwd.hip", "render.hip", "movie.hip", "features.hip", "deconv.hip", "tracking.hip", "detect.hip", "localize.hip", "localize2.hip", "linking.hip", "diffusion.hip", "fbm.hip", "confine.hip", "segment.hip", "hmm.hip", "likelihood.hip", "fbm_ml.hip", "confined_ml.hip", "directed_ml.hip", "drift.hip", "deepresnet.hip", "deepresnet_train.hip", "misc.hip", "engine.hip"]
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "stream_prims.h"), os.path.join(HERE, "elem.h"),
            os.path.join(HERE, "trajfeat.h"), os.path.join(HERE, "slab_defer.h"), os.path.join(HERE, "track_ml.h"), os.path.join(HERE, "peaks.h"),
+           os.path.join(HERE, "spot_fit.h"),
            os.path.join(ROOT, "include", "mivit_hip.h")]
 # the streaming kernels whose element type is chosen per translation unit (elem.h): each is compiled a second time with
 # -DMIVIT_ELEM_F16 (IEEE half instead of bf16, every external suffixed _f16) and both objects go into the library

@@ -3,7 +3,7 @@
 // Methods 5, 687 (2008); Smith et al., Nat. Methods 12, 717 (2015)).  It stands beside the difference-of-Gaussians rule of
 // csrc/tracking.hip, whose threshold is a fraction of the frame's own maximum, and shares its peak selection (csrc/peaks.h).
 //
-// Data d = max((adu - offset) / gain, 0) + read_var as csrc/localize.hip::ml_data.  Template g(dy, dx) = e[dy] e[dx] with e the
+// Data d = max((adu - offset) / gain, 0) + read_var (csrc/spot_fit.h::sf_data).  Template g(dy, dx) = e[dy] e[dx] with e the
 // pixel-integrated Gaussian centred on a pixel centre, 2 r + 1 values computed by the caller on the host.  The window of a
 // pixel is the in-frame pixels with |dy|, |dx| <= r: clipped at the frame edge, not reflected.
 //
@@ -23,8 +23,8 @@
 //
 // mivit_lrt_peaks: the exact Poisson likelihood ratio at every candidate of stage 1.  One wave per frame, one lane per
 // candidate, 64 candidates at a time in stage-1 order: the fit is a short serial damped Newton loop on two parameters over at
-// most 15 x 15 pixels (the loop of csrc/localize.hip::ml_kernel: lambda schedule, slack of the summed magnitudes, stopping
-// rule on the undamped step, iteration cap, status codes), so a lane owns every sum and no order has to be pinned across lanes;
+// most 15 x 15 pixels (csrc/spot_fit.h::sf_damped_fit with ml_kernel's slack of the summed magnitudes), so a lane owns every
+// sum and no order has to be pinned across lanes;
 // the wave's ballot of "T > t" gives each kept candidate its slot, so a frame's survivors are compacted in stage-1 order
 // without a second kernel or a read-back.  A movie has many frames, which is what fills the device; a frame has a few dozen
 // candidates, which half-fill one wave.  The window is read from the movie in every evaluation (it is in L2 after stage 1); the
@@ -35,22 +35,12 @@
 
 #include "common.h"
 #include "peaks.h"
+#include "spot_fit.h"
 
 namespace {
 
 constexpr int SC_MAX_R = 7;
-constexpr int LR_MAX_ITER = 100;              // ML_MAX_ITER
-constexpr double LR_COST_SLACK = 1e-13;       // ML_COST_SLACK
 constexpr double LR_XTOL = 1e-11;             // helpers/tracking.FIT_XTOL
-
-struct Camera {
-    double gain, offset, read_var;
-};
-
-__device__ __forceinline__ double sc_data(float v, const Camera &c) {
-    const double e = ((double)v - c.offset) / c.gain;
-    return (e > 0.0 ? e : 0.0) + c.read_var;
-}
 
 struct ScoreArgs {
     const float *movie;       // [F, H, W]
@@ -83,7 +73,7 @@ __global__ __launch_bounds__(256) void sc_map_kernel(const ScoreArgs a) {
     for (int t = threadIdx.x; t < LH * LW; t += blockDim.x) {
         const int ly = t / LW, lx = t - ly * LW;
         const int y = y0 + ly - R, x = x0 + lx - R;
-        in[t] = (y >= 0 && y < H && x >= 0 && x < W) ? sc_data(src[(int64_t)y * W + x], a.cam) : 0.0;
+        in[t] = (y >= 0 && y < H && x >= 0 && x < W) ? sf_data(src[(int64_t)y * W + x], a.cam) : 0.0;
     }
     if (threadIdx.x < TK_TY + TK_TX) {
         const bool row = threadIdx.x < TK_TY;
@@ -172,31 +162,31 @@ struct Window {
 struct LrEval {
     double cost;              // the deviance against the data
     double mag;               // 2 sum(mu + d)
-    double g0, g1;            // sum (1 - d / mu) (g, 1)
-    double a00, a10, a11;     // sum (g, 1)(g, 1)^T / mu
+    double g[2];              // sum (1 - d / mu) (g, 1)
+    double A[3];              // sum (g, 1)(g, 1)^T / mu, lower triangle row by row
     bool bad;                 // theta <= 0 or a pixel with mu <= 0
 };
 
 __device__ void lr_eval(const Window &w, const Camera &cam, double theta, double beta, LrEval &n) {
-    n.cost = n.mag = n.g0 = n.g1 = n.a00 = n.a10 = n.a11 = 0.0;
+    n.cost = n.mag = n.g[0] = n.g[1] = n.A[0] = n.A[1] = n.A[2] = 0.0;
     bool bad = !(theta > 0.0);
     for (int yy = w.ya; yy <= w.yb; ++yy) {
         const double ey = w.e[yy - w.y + w.r];
         for (int xx = w.xa; xx <= w.xb; ++xx) {
             const double g = ey * w.e[xx - w.x + w.r];
-            const double d = sc_data(w.frame[(int64_t)yy * w.W + xx], cam);
+            const double d = sf_data(w.frame[(int64_t)yy * w.W + xx], cam);
             const double mu = theta * g + beta;
             bad = bad || !(mu > 0.0);
             const double rm = 1.0 / mu, r = d * rm;
             n.cost = n.cost + (d > 0.0 ? (mu - d) + d * log(r) : mu);
             n.mag = n.mag + (mu + d);
             const double wt = 1.0 - r;
-            n.g0 = n.g0 + g * wt;
-            n.g1 = n.g1 + wt;
+            n.g[0] = n.g[0] + g * wt;
+            n.g[1] = n.g[1] + wt;
             const double gr = g * rm;
-            n.a00 = n.a00 + gr * g;
-            n.a10 = n.a10 + rm * g;
-            n.a11 = n.a11 + rm;
+            n.A[0] = n.A[0] + gr * g;
+            n.A[1] = n.A[1] + rm * g;
+            n.A[2] = n.A[2] + rm;
         }
     }
     n.cost = 2.0 * n.cost;
@@ -204,24 +194,22 @@ __device__ void lr_eval(const Window &w, const Camera &cam, double theta, double
     n.bad = bad;
 }
 
-// solves (A + lambda diag(A)) d = -g by Cholesky; false if the matrix is not positive definite (or not finite)
-__device__ bool lr_solve(const LrEval &n, double lambda, double &d0, double &d1) {
-    double s = n.a00;
-    s = s + lambda * s;
-    if (!(s > 0.0) || !(s < 1e300)) return false;
-    const double L00 = sqrt(s);
-    const double L10 = n.a10 / L00;
-    s = n.a11;
-    s = s + lambda * s;
-    s = s - L10 * L10;
-    if (!(s > 0.0) || !(s < 1e300)) return false;
-    const double L11 = sqrt(s);
-    const double z0 = -n.g0 / L00;
-    const double z1 = (-n.g1 - L10 * z0) / L11;
-    d1 = z1 / L11;
-    d0 = (z0 - L10 * d1) / L00;
-    return true;
-}
+// the two-parameter fit p = (theta, beta) as sf_damped_fit sees it
+struct LrFit {
+    const Window &w;
+    const Camera &cam;
+    LrEval cur, nxt;
+    __device__ const double *A() const { return cur.A; }
+    __device__ const double *g() const { return cur.g; }
+    // one scale for both: at a faint candidate theta is far below beta, and its own magnitude would ask for less than the
+    // gradient's rounding error
+    __device__ void scales(const double *p, double *sc) const { sc[0] = sc[1] = fmax(fabs(p[0]), fabs(p[1])); }
+    __device__ bool step(const double *q) {
+        lr_eval(w, cam, q[0], q[1], nxt);
+        return !nxt.bad && nxt.cost <= cur.cost + SF_COST_SLACK * cur.mag;
+    }
+    __device__ void accept() { cur = nxt; }
+};
 
 // -> status; T, theta, beta of the last accepted point
 __device__ int lr_fit(const Window &w, const Camera &cam, double &T, double &theta, double &beta) {
@@ -230,7 +218,7 @@ __device__ int lr_fit(const Window &w, const Camera &cam, double &T, double &the
         const double ey = w.e[yy - w.y + w.r];
         for (int xx = w.xa; xx <= w.xb; ++xx) {
             const double g = ey * w.e[xx - w.x + w.r];
-            const double d = sc_data(w.frame[(int64_t)yy * w.W + xx], cam);
+            const double d = sf_data(w.frame[(int64_t)yy * w.W + xx], cam);
             n = n + 1.0;
             Sd = Sd + d;
             Sgd = Sgd + g * d;
@@ -253,37 +241,14 @@ __device__ int lr_fit(const Window &w, const Camera &cam, double &T, double &the
         beta = 1e-3 * mu0;
         theta = (Sd - n * beta) / Sg;
     }
-    LrEval cur, nxt;
-    lr_eval(w, cam, theta, beta, cur);
-    int st = cur.bad ? 1 : 2;
-    double lambda = 1e-3;
-    for (int it = 0; it < LR_MAX_ITER && st == 2; ++it) {
-        double d0, d1;
-        if (!lr_solve(cur, lambda, d0, d1)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e10) st = 1;
-            continue;
-        }
-        // ml_kernel's stopping rule: the undamped step against the scale of the parameters (one scale for both: at a faint
-        // candidate theta is far below beta, and its own magnitude would ask for less than the gradient's rounding error)
-        const double sc = fmax(fabs(theta), fabs(beta));
-        double u0, u1;
-        bool small = lr_solve(cur, 0.0, u0, u1);
-        small = small && fabs(u0) <= LR_XTOL * sc && fabs(u1) <= LR_XTOL * sc;
-        const double qt = theta + d0, qb = beta + d1;
-        lr_eval(w, cam, qt, qb, nxt);
-        if (!nxt.bad && nxt.cost <= cur.cost + LR_COST_SLACK * cur.mag) {
-            theta = qt;
-            beta = qb;
-            cur = nxt;
-            lambda = fmax(lambda * 0.1, 1e-12);
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > 1e10) st = 1;
-        }
-        if (small) st = 0;
-    }
-    if (cur.bad) {
+    LrFit fit{w, cam};
+    lr_eval(w, cam, theta, beta, fit.cur);
+    int st = fit.cur.bad ? 1 : 2, it = 0;
+    double p[2] = {theta, beta};
+    sf_damped_fit<2>(fit, p, LR_XTOL, st, it);
+    theta = p[0];
+    beta = p[1];
+    if (fit.cur.bad) {
         theta = 0.0;
         beta = mu0;
         return st;
@@ -293,7 +258,7 @@ __device__ int lr_fit(const Window &w, const Camera &cam, double &T, double &the
         const double ey = w.e[yy - w.y + w.r];
         for (int xx = w.xa; xx <= w.xb; ++xx) {
             const double g = ey * w.e[xx - w.x + w.r];
-            const double d = sc_data(w.frame[(int64_t)yy * w.W + xx], cam);
+            const double d = sf_data(w.frame[(int64_t)yy * w.W + xx], cam);
             const double mu = theta * g + beta;
             s1 = s1 + (d > 0.0 ? d * log(mu / mu0) : 0.0);
             s2 = s2 + mu;
@@ -375,9 +340,7 @@ extern "C" size_t mivit_score_peaks_workspace_bytes(int F, int H, int W, int cap
     MIVIT_CHECK(r >= 1 && r <= SC_MAX_R, name ": radius %d (1 .. %d)", r, SC_MAX_R);                                    \
     MIVIT_CHECK(H > r && W > r, name ": frames of %d x %d are not larger than the radius %d", H, W, r);                 \
     MIVIT_CHECK((int64_t)H * W <= INT32_MAX, name ": frames of %d x %d pixels", H, W);                                  \
-    MIVIT_CHECK(gain > 0.0 && gain < 1e300, name ": gain = %g (need a finite gain > 0)", gain);                         \
-    MIVIT_CHECK(offset - offset == 0.0, name ": offset = %g is not finite", offset);                                    \
-    MIVIT_CHECK(read_var >= 0.0 && read_var < 1e300, name ": read_var = %g (need a finite read_var >= 0)", read_var);   \
+    if (sf_check_camera(name, gain, offset, read_var)) return 1;                                                        \
     MIVIT_CHECK(threshold >= 0 && threshold < 1e30f, name ": threshold = %g (need a finite threshold >= 0)",            \
                 (double)threshold);                                                                                     \
     MIVIT_CHECK(cap >= 1 && cap <= TK_MAX_CAP, name ": capacity of %d peaks per frame (1 .. %d)", cap, TK_MAX_CAP);     \

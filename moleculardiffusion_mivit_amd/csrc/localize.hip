@@ -2,7 +2,9 @@
 // Rieger & Lidke, Nat. Methods 7, 373 (2010) with the Levenberg-Marquardt form of Laurence & Chromy, Nat. Methods 7, 338
 // (2010) and the readout variance added to data and model as Huang et al., Nat. Methods 10, 653 (2013) do.  The least-squares
 // fit it stands beside is csrc/tracking.hip::rg_kernel; the damped loop (lambda schedule, stopping rule, status codes, and the
-// cost slack, taken here of the magnitude of the summed terms) is that one's, the cost, gradient and matrix are the Poisson ones.
+// cost slack, taken here of the magnitude of the summed terms) is the one csrc/spot_fit.h::sf_damped_fit describes, written out
+// here with its own factorisation because this kernel measured about 1 % slower on the shared templates: a change
+// to the loop is made there, here and in rg_kernel.  The cost, gradient and matrix are the Poisson ones.
 //
 // Model of a patch [P, P] with pixel centres at integers, p = (N photons, x0, y0, s, b):
 //   mu(iy, ix) = b + N E(ix; x0, s) E(iy; y0, s) + read_var,   E(i; c, s) = 1/2 [erf((i + 1/2 - c) / (sqrt(2) s)) - erf((i - 1/2 - c) / (sqrt(2) s))]
@@ -25,14 +27,9 @@
 #pragma clang fp contract(off)
 
 #include "common.h"
+#include "spot_fit.h"
 
 namespace {
-
-constexpr int ML_MAX_P = 15;          // RG_MAX_P of csrc/tracking.hip
-constexpr int ML_MAX_ITER = 100;
-constexpr double ML_COST_SLACK = 1e-13;    // rg_kernel's, of the summed magnitudes (see ml_kernel)
-constexpr double ML_SQRT2 = 1.4142135623730951, ML_SQRT_2PI = 2.5066282746310002;
-constexpr double ML_MIN_SIGMA = 0.2;
 
 // A/B switch, measurement only: -DMIVIT_ML_STAGE_PATCH copies each lane's raw patch into LDS once, as [pixel][lane]
 // floats behind the tables, and every evaluation reads it from there; the arithmetic, and so every bit of the result, is the
@@ -43,10 +40,6 @@ constexpr double ML_MIN_SIGMA = 0.2;
 #define ML_PIXEL(patch, t, L) (patch)[t]
 #endif
 
-struct Camera {
-    double gain, offset, read_var;
-};
-
 struct Fisher {
     double cost;              // the deviance
     double mag;               // 2 sum(mu + d): what the rounding error of the deviance scales with
@@ -55,14 +48,9 @@ struct Fisher {
     bool bad;                 // outside the model's domain: N <= 0, s outside (0.2, P), or a pixel with mu <= 0
 };
 
-__device__ __forceinline__ double ml_data(float v, const Camera &c) {
-    const double e = ((double)v - c.offset) / c.gain;
-    return (e > 0.0 ? e : 0.0) + c.read_var;
-}
-
 // the three tables of one axis for the centre c: tab[k L] = E(k), tab[(P + k) L] = dE/dc, tab[(2 P + k) L] = dE/ds (0 with fs = 0)
 __device__ void ml_axis(double *tab, int L, int P, double c, double s, bool fs) {
-    const double w = ML_SQRT2 * s, nc = 1.0 / (ML_SQRT_2PI * s), ns = nc / s;
+    const double w = SF_SQRT2 * s, nc = 1.0 / (SF_SQRT_2PI * s), ns = nc / s;
     double t0 = (0.0 - 0.5) - c;
     double u = t0 / w;
     double e0 = erf(u), g0 = exp(-(u * u));
@@ -84,7 +72,7 @@ __device__ void ml_eval(const float *patch, int P, const Camera &cam, const doub
     n.mag = 0.0;
     for (int i = 0; i < 5; ++i) n.g[i] = 0.0;
     for (int i = 0; i < 15; ++i) n.A[i] = 0.0;
-    n.bad = !(p[0] > 0.0) || !(p[3] > ML_MIN_SIGMA) || !(p[3] < (double)P);
+    n.bad = !(p[0] > 0.0) || !(p[3] > SF_MIN_SIGMA) || !(p[3] < (double)P);
     if (n.bad) return;
     double *tx = tab, *ty = tab + 3 * P * L;
     ml_axis(tx, L, P, p[1], p[3], fs);
@@ -97,7 +85,7 @@ __device__ void ml_eval(const float *patch, int P, const Camera &cam, const doub
             const double Ex = tx[ix * L], dEx = tx[(P + ix) * L], sEx = tx[(2 * P + ix) * L];
             const double mu = (p[4] + nEy * Ex) + cam.read_var;
             bad = bad || !(mu > 0.0);
-            const double d = ml_data(ML_PIXEL(patch, iy * P + ix, L), cam);
+            const double d = sf_data(ML_PIXEL(patch, iy * P + ix, L), cam);
             const double rm = 1.0 / mu, r = d * rm;
             n.cost = n.cost + (d > 0.0 ? (mu - d) + d * log(r) : mu);
             n.mag = n.mag + (mu + d);
@@ -185,14 +173,14 @@ __global__ __launch_bounds__(64) void ml_kernel(const float *__restrict__ patche
 #endif
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     bool finite = true;
-    double mx = ml_data(patch[0], cam), mn = mx, sum = 0.0;
+    double mx = sf_data(patch[0], cam), mn = mx, sum = 0.0;
     for (int t = 0; t < P * P; ++t) {
         const float v = patch[t];
         finite = finite && (v - v == 0.f);
 #ifdef MIVIT_ML_STAGE_PATCH
         stage[t * L] = v;
 #endif
-        const double d = ml_data(v, cam);
+        const double d = sf_data(v, cam);
         mx = d > mx ? d : mx;
         mn = d < mn ? d : mn;
         sum = sum + d;
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(64) void ml_kernel(const float *__restrict__ patche
         else if (!(cur.cost < 1e300)) st = 3;
     }
     double lambda = 1e-3;
-    for (; it < ML_MAX_ITER && st == 2; ++it) {
+    for (; it < SF_MAX_ITER && st == 2; ++it) {
         double d[5];
         if (!ml_solve(cur, lambda, d)) {
             lambda = lambda * 10.0;
@@ -233,12 +221,9 @@ __global__ __launch_bounds__(64) void ml_kernel(const float *__restrict__ patche
         double q[5];
         for (int k = 0; k < 5; ++k) q[k] = p[k] + d[k];
         ml_eval(patch, P, cam, q, fs, tab, L, nxt);
-        // accepted unless the cost rises by more than its own rounding error, as in rg_kernel.  There the cost is a sum of
-        // squares and its error is relative to the cost; the deviance is a sum of differences mu - d + d log(d / mu) of terms
-        // hundreds of times larger than itself, and its error is relative to those: measured against the cost alone, a
-        // converged patch with a small deviance (P = 3: 0.3) had its last steps (1e-11 of the parameters, a "rise" of 1e-13 of
-        // the cost, all rounding) rejected four times over, and the count depended on the last bit of log().
-        if (!nxt.bad && nxt.cost <= cur.cost + ML_COST_SLACK * cur.mag) {
+        // accepted unless the cost rises by more than its own rounding error, which for a deviance is relative to the magnitude
+        // of the summed terms (csrc/spot_fit.h, "the slack")
+        if (!nxt.bad && nxt.cost <= cur.cost + SF_COST_SLACK * cur.mag) {
             for (int k = 0; k < 5; ++k) p[k] = q[k];
             cur = nxt;
             lambda = fmax(lambda * 0.1, 1e-12);
@@ -266,19 +251,12 @@ extern "C" int mivit_fit_spots_mle(const float *patches, int N, int P, double ga
                                    double sigma0, int fit_sigma, double xtol, double *params, double *crlb, double *deviance,
                                    int *status, int *iterations, void *stream) {
     MIVIT_CHECK(N >= 0, "fit_spots_mle: N = %d < 0", N);
-    MIVIT_CHECK(P >= 3 && P <= ML_MAX_P && (P & 1), "fit_spots_mle: patch side %d (odd, 3 .. %d)", P, ML_MAX_P);
-    MIVIT_CHECK(gain > 0.0 && gain < 1e300, "fit_spots_mle: gain = %g (need a finite gain > 0)", gain);
-    MIVIT_CHECK(offset - offset == 0.0, "fit_spots_mle: offset = %g is not finite", offset);
-    MIVIT_CHECK(read_var >= 0.0 && read_var < 1e300, "fit_spots_mle: read_var = %g (need a finite read_var >= 0)", read_var);
-    MIVIT_CHECK(sigma0 > ML_MIN_SIGMA && sigma0 < (double)P, "fit_spots_mle: sigma0 = %g (need %g < sigma0 < P = %d)", sigma0,
-                ML_MIN_SIGMA, P);
+    if (sf_check_patch_fit("fit_spots_mle", P, xtol, &sigma0)) return 1;
+    if (sf_check_camera("fit_spots_mle", gain, offset, read_var)) return 1;
     MIVIT_CHECK(fit_sigma == 0 || fit_sigma == 1, "fit_spots_mle: fit_sigma = %d (0 or 1)", fit_sigma);
-    MIVIT_CHECK(xtol > 0.0 && xtol <= 1.49012e-8, "fit_spots_mle: xtol = %g (0 < xtol <= 1.49012e-8, MINPACK's default)", xtol);
     if (N == 0) return 0;
     MIVIT_CHECK(patches && params && crlb && deviance && status && iterations, "fit_spots_mle: null pointer");
-    // lanes per wave as mivit_refine_gaussian: reach every CU (256) before filling waves
-    int tpb = 64;
-    while (tpb > 1 && (int64_t)tpb * 256 > N) tpb >>= 1;
+    const int tpb = sf_lanes_per_workgroup(N);
     size_t lds = (size_t)6 * P * tpb * sizeof(double);                    // <= 46 080 bytes
 #ifdef MIVIT_ML_STAGE_PATCH
     lds += (size_t)P * P * tpb * sizeof(float);

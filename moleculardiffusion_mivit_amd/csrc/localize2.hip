@@ -1,8 +1,9 @@
 // Joint Poisson maximum-likelihood fit of a localisation and its nearest same-frame neighbour, with a Cramer-Rao bound per
 // parameter, and the neighbour search that feeds it.  The single-emitter fit it stands beside is csrc/localize.hip::ml_kernel;
 // the damped loop (lambda schedule, stopping rule on the undamped step, status codes, the cost slack 1e-13 taken of
-// 2 sum(mu + d), the Fisher information as the matrix, the bound through the Cholesky factor of the undamped matrix at the
-// returned point, fit_sigma = 0 by zero dE/ds and a 1 on the diagonal) is that one's.
+// 2 sum(mu + d)) is csrc/spot_fit.h::sf_damped_fit for both; the Fisher information as the matrix, the bound through the
+// Cholesky factor of the undamped matrix at the returned point, fit_sigma = 0 by zero dE/ds and a 1 on the diagonal are that
+// one's.
 //
 // Model of a patch [P, P] with pixel centres at integers, p = (N1, x1, y1, N2, x2, y2, s, b), k = count in {1, 2} emitters:
 //   mu(iy, ix) = b + sum_{e < k} N_e E(ix; x_e, s) E(iy; y_e, s) + read_var,   E as in csrc/localize.hip
@@ -33,14 +34,10 @@
 #pragma clang fp contract(off)
 
 #include "common.h"
+#include "spot_fit.h"
 
 namespace {
 
-constexpr int M2_MAX_P = 15;          // ML_MAX_P of csrc/localize.hip
-constexpr int M2_MAX_ITER = 100;
-constexpr double M2_COST_SLACK = 1e-13;
-constexpr double M2_SQRT2 = 1.4142135623730951, M2_SQRT_2PI = 2.5066282746310002;
-constexpr double M2_MIN_SIGMA = 0.2;
 constexpr int M2_NP = 8;              // parameters
 constexpr int M2_NA = 36;             // lower triangle
 constexpr int M2_NSUM = 46;           // + 8 gradient entries + deviance + magnitude
@@ -49,20 +46,11 @@ constexpr int M2_NQ = 12;             // per-pixel quantities: J_0 .. J_7, 1 / m
 constexpr int M2_WAVE = 64;
 constexpr int M2_MAX_GRID = 1 << 20;  // workgroups of a launch
 
-struct Camera {
-    double gain, offset, read_var;
-};
-
-__device__ __forceinline__ double m2_data(float v, const Camera &c) {
-    const double e = ((double)v - c.offset) / c.gain;
-    return (e > 0.0 ? e : 0.0) + c.read_var;
-}
-
 __host__ __device__ constexpr int m2_lds_doubles(int P) { return 8 * (P + 1) + 12 * P + M2_NQ * P * P + 2 * M2_SLOT; }
 
 // outside the model's domain: an N_e <= 0, s outside (0.2, P), a centre outside [-1, P]
 __device__ __forceinline__ bool m2_outside(const double *p, int P, bool two) {
-    bool bad = !(p[0] > 0.0) || !(p[6] > M2_MIN_SIGMA) || !(p[6] < (double)P);
+    bool bad = !(p[0] > 0.0) || !(p[6] > SF_MIN_SIGMA) || !(p[6] < (double)P);
     bad = bad || !(p[1] >= -1.0) || !(p[1] <= (double)P) || !(p[2] >= -1.0) || !(p[2] <= (double)P);
     if (two) bad = bad || !(p[3] > 0.0) || !(p[4] >= -1.0) || !(p[4] <= (double)P) || !(p[5] >= -1.0) || !(p[5] <= (double)P);
     return bad;
@@ -75,7 +63,7 @@ __device__ bool m2_eval(const float *patch, int P, const Camera &cam, const doub
     const int PP = P * P, E1 = P + 1;
     double *edge_e = lds, *edge_g = lds + 4 * E1, *tab = lds + 8 * E1, *pix = tab + 12 * P;
     const double s = p[6];
-    const double w = M2_SQRT2 * s, nc = 1.0 / (M2_SQRT_2PI * s), ns = nc / s;
+    const double w = SF_SQRT2 * s, nc = 1.0 / (SF_SQRT_2PI * s), ns = nc / s;
     if (lane < 4 * E1) {
         const int a = lane / E1, k = lane - a * E1;
         const double c = a == 0 ? p[1] : a == 1 ? p[2] : a == 2 ? p[4] : p[5];
@@ -114,7 +102,7 @@ __device__ bool m2_eval(const float *patch, int P, const Camera &cam, const doub
         }
         mu = mu + cam.read_var;
         nonpos = nonpos || !(mu > 0.0);
-        const double d = m2_data(patch[t], cam);
+        const double d = sf_data(patch[t], cam);
         const double rm = 1.0 / mu, r = d * rm;
         pix[0 * PP + t] = Ex1 * Ey1;
         pix[1 * PP + t] = nEy1 * dEx1;
@@ -143,70 +131,40 @@ __device__ bool m2_eval(const float *patch, int P, const Camera &cam, const doub
     return any;
 }
 
-// Cholesky factor of A + lambda diag(A), A = S[0 .. 35] in LDS; false if the matrix is not positive definite (or not finite)
-__device__ __forceinline__ bool m2_chol(const double *S, double lambda, double *L) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < M2_NP; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = S[i * (i + 1) / 2 + j];
-            if (i == j) s = s + lambda * s;
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = s - L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
-            if (i == j) {
-                ok = ok && (s > 0.0) && (s < 1e300);
-                L[i * (i + 1) / 2 + i] = sqrt(ok ? s : 1.0);
-            } else {
-                L[i * (i + 1) / 2 + j] = s / L[j * (j + 1) / 2 + j];
-            }
-        }
-    return ok;
-}
-
-// solves (A + lambda diag(A)) d = -g, g = S[36 .. 43]
-__device__ __forceinline__ bool m2_solve(const double *S, double lambda, double *d) {
-    double L[M2_NA];
-    if (!m2_chol(S, lambda, L)) return false;
-    double z[M2_NP];
-#pragma unroll
-    for (int i = 0; i < M2_NP; ++i) {
-        double s = -S[M2_NA + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - L[i * (i + 1) / 2 + k] * z[k];
-        z[i] = s / L[i * (i + 1) / 2 + i];
+// The joint fit as sf_damped_fit sees it.  The two sets of sums in LDS are the current point's and the spare one's: accepting
+// flips which is which.  Every lane holds the same numbers, so the loop's branches are uniform and step's barriers are met
+// by the whole wave.
+struct M2Fit {
+    const float *patch;
+    int P;
+    const Camera &cam;
+    bool two, fs;
+    double *lds, *sums;
+    int lane;
+    const double *sa, *sm, *sb;
+    int c;                    // which set of sums is the current point's
+    double cost, mag;         // the current point's
+    __device__ const double *S() const { return sums + c * M2_SLOT; }
+    __device__ const double *A() const { return S(); }
+    __device__ const double *g() const { return S() + M2_NA; }
+    // ml_kernel's scales, the photons of the brighter emitter for the background
+    __device__ void scales(const double *p, double *sc) const {
+        const double a0 = fmax(fabs(p[0]), fabs(p[3]));
+        sc[0] = fabs(p[0]), sc[1] = fmax(fabs(p[1]), 1.0), sc[2] = fmax(fabs(p[2]), 1.0), sc[3] = fabs(p[3]);
+        sc[4] = fmax(fabs(p[4]), 1.0), sc[5] = fmax(fabs(p[5]), 1.0), sc[6] = fabs(p[6]), sc[7] = fmax(fabs(p[7]), a0);
     }
-#pragma unroll
-    for (int i = M2_NP - 1; i >= 0; --i) {
-        double s = z[i];
-#pragma unroll
-        for (int k = i + 1; k < M2_NP; ++k) s = s - L[k * (k + 1) / 2 + i] * d[k];
-        d[i] = s / L[i * (i + 1) / 2 + i];
+    __device__ bool step(const double *q) {
+        bool bad = m2_outside(q, P, two);
+        double *T = sums + (1 - c) * M2_SLOT;
+        if (!bad) bad = m2_eval(patch, P, cam, q, two, fs, lds, T, lane, sa, sm, sb);
+        return !bad && T[44] <= cost + SF_COST_SLACK * mag;
     }
-    return true;
-}
-
-// diagonal of A^-1 = L^-T L^-1: column j of X = L^-1 by forward substitution, v[j] = sum_i X[i][j]^2 (i ascending)
-__device__ __forceinline__ bool m2_crlb(const double *S, double *v) {
-    double L[M2_NA];
-    if (!m2_chol(S, 0.0, L)) return false;
-#pragma unroll
-    for (int j = 0; j < M2_NP; ++j) {
-        double X[M2_NP];
-        X[j] = 1.0 / L[j * (j + 1) / 2 + j];
-        double acc = X[j] * X[j];
-#pragma unroll
-        for (int i = j + 1; i < M2_NP; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = j; k < i; ++k) s = s - L[i * (i + 1) / 2 + k] * X[k];
-            X[i] = s / L[i * (i + 1) / 2 + i];
-            acc = acc + X[i] * X[i];
-        }
-        v[j] = acc;
+    __device__ void accept() {
+        c = 1 - c;
+        cost = S()[44];
+        mag = S()[45];
     }
-    return true;
-}
+};
 
 // the fit of patch i by the whole wave
 __device__ void m2_patch(int64_t i, double *m2_lds, const float *__restrict__ patches, const int *__restrict__ count,
@@ -236,11 +194,11 @@ __device__ void m2_patch(int64_t i, double *m2_lds, const float *__restrict__ pa
     // start, every lane on every pixel (the same address in all lanes: one request): background = the smallest pixel (at
     // least 1e-3 of the largest), photons = what lies above it, in pixel order, split evenly between the emitters
     bool finite = cnt == 1 || cnt == 2;
-    double mx = m2_data(patch[0], cam), mn = mx, sum = 0.0;
+    double mx = sf_data(patch[0], cam), mn = mx, sum = 0.0;
     for (int t = 0; t < PP; ++t) {
         const float v = patch[t];
         finite = finite && (v - v == 0.f);
-        const double d = m2_data(v, cam);
+        const double d = sf_data(v, cam);
         mx = d > mx ? d : mx;
         mn = d < mn ? d : mn;
         sum = sum + d;
@@ -255,13 +213,12 @@ __device__ void m2_patch(int64_t i, double *m2_lds, const float *__restrict__ pa
     sum = sum - (double)PP * b0;
     const double n0 = fmax(sum, mx);
     double p[M2_NP] = {two ? 0.5 * n0 : n0, g4[0], g4[1], two ? 0.5 * n0 : 0.0, g4[2], g4[3], sigma0, b0};
-    int c = 0;                                                            // which set of sums is the current point's
-    double cost = 0.0, mag = 0.0;
+    M2Fit fit{patch, P, cam, two, fs, m2_lds, sums, lane, sa, sm, sb, 0, 0.0, 0.0};
     int st = 2, it = 0;                                                   // iteration cap
     if (!finite) {
         st = 3;
         for (int k = 0; k < M2_NP; ++k) p[k] = nan;
-        cost = nan;
+        fit.cost = nan;
     } else if (m2_outside(p, P, two) || (two && p[1] == p[4] && p[2] == p[5])) {
         // no photons at all, a guess outside the patch, or two guesses on one point: there the emitters are interchangeable, the
         // matrix is singular by symmetry and the gradient cannot tell them apart; only rounding would, differently on every
@@ -269,50 +226,14 @@ __device__ void m2_patch(int64_t i, double *m2_lds, const float *__restrict__ pa
         st = 1;
     } else {
         const bool bad = m2_eval(patch, P, cam, p, two, fs, m2_lds, sums, lane, sa, sm, sb);
-        cost = sums[44];
-        mag = sums[45];
+        fit.cost = sums[44];
+        fit.mag = sums[45];
         if (bad) st = 1;
-        else if (!(cost < 1e300)) st = 3;
+        else if (!(fit.cost < 1e300)) st = 3;
     }
-    double lambda = 1e-3;
-    for (; it < M2_MAX_ITER && st == 2; ++it) {
-        const double *S = sums + c * M2_SLOT;
-        double d[M2_NP];
-        if (!m2_solve(S, lambda, d)) {
-            lambda = lambda * 10.0;
-            if (lambda > 1e10) st = 1;
-            continue;
-        }
-        // ml_kernel's stopping rule: the undamped step against each parameter's scale
-        const double a0 = fmax(fabs(p[0]), fabs(p[3]));
-        const double sc[M2_NP] = {fabs(p[0]), fmax(fabs(p[1]), 1.0), fmax(fabs(p[2]), 1.0), fabs(p[3]), fmax(fabs(p[4]), 1.0),
-                                  fmax(fabs(p[5]), 1.0), fabs(p[6]), fmax(fabs(p[7]), a0)};
-        double d0[M2_NP];
-        bool small = m2_solve(S, 0.0, d0);
-#pragma unroll
-        for (int k = 0; k < M2_NP; ++k) small = small && fabs(d0[k]) <= xtol * sc[k];
-        double q[M2_NP];
-#pragma unroll
-        for (int k = 0; k < M2_NP; ++k) q[k] = p[k] + d[k];
-        bool bad = m2_outside(q, P, two);
-        double *T = sums + (1 - c) * M2_SLOT;
-        if (!bad) bad = m2_eval(patch, P, cam, q, two, fs, m2_lds, T, lane, sa, sm, sb);
-        // accepted unless the cost rises by more than its own rounding error (ml_kernel)
-        if (!bad && T[44] <= cost + M2_COST_SLACK * mag) {
-#pragma unroll
-            for (int k = 0; k < M2_NP; ++k) p[k] = q[k];
-            cost = T[44];
-            mag = T[45];
-            c = 1 - c;
-            lambda = fmax(lambda * 0.1, 1e-12);
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > 1e10) st = 1;
-        }
-        if (small) st = 0;
-    }
+    sf_damped_fit<M2_NP>(fit, p, xtol, st, it);
     double v[M2_NP];
-    const bool have = st == 0 && m2_crlb(sums + c * M2_SLOT, v);
+    const bool have = st == 0 && sf_crlb<M2_NP>(fit.A(), v);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < M2_NP; ++k) {
@@ -320,7 +241,7 @@ __device__ void m2_patch(int64_t i, double *m2_lds, const float *__restrict__ pa
             params[i * M2_NP + k] = dead ? nan : p[k];
             crlb[i * M2_NP + k] = !have || dead ? nan : (!fs && k == 6 ? 0.0 : v[k]);
         }
-        deviance[i] = cost;
+        deviance[i] = fit.cost;
         status[i] = st;
         iterations[i] = it;
     }
@@ -379,14 +300,9 @@ extern "C" int mivit_fit_spots_mle2(const float *patches, const int *count, cons
                                     double offset, double read_var, double sigma0, int fit_sigma, double xtol, double *params,
                                     double *crlb, double *deviance, int *status, int *iterations, void *stream) {
     MIVIT_CHECK(N >= 0, "fit_spots_mle2: N = %d < 0", N);
-    MIVIT_CHECK(P >= 3 && P <= M2_MAX_P && (P & 1), "fit_spots_mle2: patch side %d (odd, 3 .. %d)", P, M2_MAX_P);
-    MIVIT_CHECK(gain > 0.0 && gain < 1e300, "fit_spots_mle2: gain = %g (need a finite gain > 0)", gain);
-    MIVIT_CHECK(offset - offset == 0.0, "fit_spots_mle2: offset = %g is not finite", offset);
-    MIVIT_CHECK(read_var >= 0.0 && read_var < 1e300, "fit_spots_mle2: read_var = %g (need a finite read_var >= 0)", read_var);
-    MIVIT_CHECK(sigma0 > M2_MIN_SIGMA && sigma0 < (double)P, "fit_spots_mle2: sigma0 = %g (need %g < sigma0 < P = %d)", sigma0,
-                M2_MIN_SIGMA, P);
+    if (sf_check_patch_fit("fit_spots_mle2", P, xtol, &sigma0)) return 1;
+    if (sf_check_camera("fit_spots_mle2", gain, offset, read_var)) return 1;
     MIVIT_CHECK(fit_sigma == 0 || fit_sigma == 1, "fit_spots_mle2: fit_sigma = %d (0 or 1)", fit_sigma);
-    MIVIT_CHECK(xtol > 0.0 && xtol <= 1.49012e-8, "fit_spots_mle2: xtol = %g (0 < xtol <= 1.49012e-8, MINPACK's default)", xtol);
     if (N == 0) return 0;
     MIVIT_CHECK(patches && count && guess && params && crlb && deviance && status && iterations, "fit_spots_mle2: null pointer");
     const size_t lds = (size_t)m2_lds_doubles(P) * sizeof(double);        // <= 24 832 bytes

@@ -25,20 +25,20 @@
 //
 // mivit_refine_gaussian: one thread per patch (as csrc/features.hip does per trajectory).  A patch has at most 15 x 15 pixels
 // and five parameters; the fit is a short serial Levenberg-Marquardt loop, and a movie yields thousands of patches, so the
-// lanes are filled by patches rather than by pixels and no cross-lane reduction order has to be pinned.
+// lanes are filled by patches rather than by pixels and no cross-lane reduction order has to be pinned.  The loop is the one
+// csrc/spot_fit.h::sf_damped_fit describes, written out here with its own factorisation (rg_solve) because this kernel
+// measured about 1 % slower on the shared templates: a change to the loop is made there, here and in ml_kernel.
 //
 // No contraction into FMA anywhere in this file: the filter agrees bitwise with the host restatement (helpers/tracking.py).
 #pragma clang fp contract(off)
 
 #include "common.h"
 #include "peaks.h"
+#include "spot_fit.h"
 
 namespace {
 
 constexpr int TK_MAX_RADIUS = 16;     // int(4 sigma + 0.5) of the wider Gaussian
-constexpr int RG_MAX_P = 15;
-constexpr int RG_MAX_ITER = 100;
-constexpr double RG_COST_SLACK = 1.0 + 1e-13;
 
 // scipy 'reflect' (half-sample symmetric), one reflection; clamped so that rows / columns of a tile that lie outside the frame
 // (their results are discarded) still read inside it
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64) void rg_kernel(const float *__restrict__ patche
     double lambda = 1e-3;
     int st = 2;                                                           // iteration cap
     if (!(cur.cost < 1e300)) st = 3;                                      // not finite at the start
-    for (int it = 0; it < RG_MAX_ITER && st == 2; ++it) {
+    for (int it = 0; it < SF_MAX_ITER && st == 2; ++it) {
         double d[5];
         if (!rg_solve(cur, lambda, d)) {
             lambda = lambda * 10.0;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(64) void rg_kernel(const float *__restrict__ patche
         rg_eval(patch, P, q, nxt);
         // accepted unless the cost rises by more than its own rounding error: close to the optimum a step changes the cost
         // by less than that, and a strict test would stop the iteration at sqrt(eps) of the parameters
-        if (nxt.cost <= cur.cost * RG_COST_SLACK) {
+        if (nxt.cost <= cur.cost * (1.0 + SF_COST_SLACK)) {
             for (int k = 0; k < 5; ++k) p[k] = q[k];
             cur = nxt;
             lambda = fmax(lambda * 0.1, 1e-12);
@@ -297,14 +297,10 @@ extern "C" int mivit_dog_peaks(const float *movie, int F, int H, int W, const do
 extern "C" int mivit_refine_gaussian(const float *patches, int N, int P, double xtol, double *params, float *peak,
                                      int *status, void *stream) {
     MIVIT_CHECK(N >= 0, "refine_gaussian: N = %d < 0", N);
-    MIVIT_CHECK(P >= 3 && P <= RG_MAX_P && (P & 1), "refine_gaussian: patch side %d (odd, 3 .. %d)", P, RG_MAX_P);
-    MIVIT_CHECK(xtol > 0.0 && xtol <= 1.49012e-8, "refine_gaussian: xtol = %g (0 < xtol <= 1.49012e-8, MINPACK's default)",
-                xtol);
+    if (sf_check_patch_fit("refine_gaussian", P, xtol, nullptr)) return 1;
     if (N == 0) return 0;
     MIVIT_CHECK(patches && params && peak && status, "refine_gaussian: null pointer");
-    // lanes per wave as in mivit_trajectory_features: reach every CU (256) before filling waves
-    int tpb = 64;
-    while (tpb > 1 && (int64_t)tpb * 256 > N) tpb >>= 1;
+    const int tpb = sf_lanes_per_workgroup(N);
     prof_set_tag(MIVIT_PROF_OP);
     hipLaunchKernelGGL(rg_kernel, dim3((N + tpb - 1) / tpb), dim3(tpb), 0, static_cast<hipStream_t>(stream), patches, N, P,
                        xtol, params, peak, status);

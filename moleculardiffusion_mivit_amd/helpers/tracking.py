@@ -279,7 +279,7 @@ def _score_numpy(movie32, e, gain=1.0, offset=0.0, read_var=0.0, chunk=16, dtype
 
 
 def _lrt_solve(n, lam):
-    """(A + lam diag(A)) step = -g of the 2 x 2 system by Cholesky (lr_solve) -> (d_theta, d_beta, ok)."""
+    """(A + lam diag(A)) step = -g of the 2 x 2 system by Cholesky (csrc/spot_fit.h::sf_solve<2>) -> (d_theta, d_beta, ok)."""
     with np.errstate(all="ignore"):
         s = n["a00"] + lam * n["a00"]
         ok = (s > 0.0) & (s < 1e300)
@@ -1334,7 +1334,7 @@ def _mle_normal(d, p, read_var, fs):
 
 
 def _mle_crlb(A):
-    """Diagonal of A^-1 through the Cholesky factor (ml_crlb) -> (variances [n, 5], ok [n])."""
+    """Diagonal of A^-1 through the Cholesky factor (csrc/spot_fit.h::sf_crlb<5>) -> (variances [n, 5], ok [n])."""
     n = len(A)
     L = np.zeros((n, 5, 5))
     ok = np.ones(n, bool)
@@ -1436,7 +1436,7 @@ def _fit_mle_numpy(patches, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_
         q = pa + dstep
         cq, gq, Aq, badq, mq = _mle_normal(d[act], q, read_var, fs)
         # the slack of the least-squares loop, taken of the magnitude of the summed terms: the deviance is a sum of differences
-        # far larger than itself, and its rounding error is relative to those (csrc/localize.hip::ml_kernel)
+        # far larger than itself, and its rounding error is relative to those (csrc/spot_fit.h::sf_damped_fit)
         with np.errstate(invalid="ignore"):
             better = ~badq & (cq <= cost[act] + MLE_COST_SLACK * mag[act])
         up = act[better]
@@ -1541,7 +1541,7 @@ def _mle2_normal(d, p, two, read_var, fs):
 
 
 def _mle2_chol(A, lam):
-    """Cholesky factor of A + lam diag(A) for every patch (m2_chol) -> (L [n, 8, 8], ok [n])."""
+    """Cholesky factor of A + lam diag(A) for every patch (csrc/spot_fit.h::sf_chol<8>) -> (L [n, 8, 8], ok [n])."""
     n = len(A)
     L = np.zeros((n, 8, 8))
     ok = np.ones(n, bool)
@@ -1561,7 +1561,7 @@ def _mle2_chol(A, lam):
 
 
 def _mle2_solve(A, g, lam):
-    """(A + lam diag(A)) d = -g by Cholesky for every patch (m2_solve) -> (d [n, 8], ok [n])."""
+    """(A + lam diag(A)) d = -g by Cholesky for every patch (csrc/spot_fit.h::sf_solve<8>) -> (d [n, 8], ok [n])."""
     n = len(g)
     with np.errstate(all="ignore"):
         L, ok = _mle2_chol(A, lam)
@@ -1581,7 +1581,7 @@ def _mle2_solve(A, g, lam):
 
 
 def _mle2_crlb(A):
-    """Diagonal of A^-1 through the Cholesky factor (m2_crlb) -> (variances [n, 8], ok [n])."""
+    """Diagonal of A^-1 through the Cholesky factor (csrc/spot_fit.h::sf_crlb<8>) -> (variances [n, 8], ok [n])."""
     n = len(A)
     v = np.zeros((n, 8))
     with np.errstate(all="ignore"):

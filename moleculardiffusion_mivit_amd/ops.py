@@ -609,6 +609,19 @@ def dog_peaks(movie: torch.Tensor, w1, w2, threshold_percentage: float = 0.1, mi
 SCORE_PEAKS_MAX_RADIUS = 7
 
 
+def _camera_args(gain, offset, read_var):
+    """The scalars of the photon-counting camera, checked -> (gain, offset, read_var) as floats."""
+    import math
+    gain, offset, read_var = float(gain), float(offset), float(read_var)
+    if not (gain > 0 and math.isfinite(gain)):
+        raise ValueError(f"gain must be finite and > 0, got {gain}")
+    if not math.isfinite(offset):
+        raise ValueError(f"offset must be finite, got {offset}")
+    if not (read_var >= 0 and math.isfinite(read_var)):
+        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    return gain, offset, read_var
+
+
 def _score_args(name, movie, e, gain, offset, read_var, threshold, cap):
     """The checks the two stages of the likelihood-ratio detector share -> (movie, e as float64, radius, cap)."""
     import math
@@ -625,12 +638,7 @@ def _score_args(name, movie, e, gain, offset, read_var, threshold, cap):
         raise ValueError("e must lie in (0, 1]")
     if movie.shape[1] <= r or movie.shape[2] <= r:
         raise ValueError(f"frames of {movie.shape[1]} x {movie.shape[2]} are not larger than the radius {r}")
-    if not (gain > 0 and math.isfinite(gain)):
-        raise ValueError(f"gain must be finite and > 0, got {gain}")
-    if not math.isfinite(offset):
-        raise ValueError(f"offset must be finite, got {offset}")
-    if not (read_var >= 0 and math.isfinite(read_var)):
-        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
+    _camera_args(gain, offset, read_var)
     if not (threshold >= 0 and math.isfinite(threshold)):
         raise ValueError(f"threshold must be finite and >= 0, got {threshold}")
     cap = int(cap)
@@ -715,6 +723,27 @@ def refine_gaussian(patches: torch.Tensor, xtol: float = 1e-11):
     return params, peak, status
 
 
+def _spot_fit_args(name, patches, gain, offset, read_var, sigma0, xtol, n_params):
+    """What the Poisson fits share: patches [N, P, P], the camera, sigma0 and xtol checked, and the outputs allocated ->
+    (patches, (gain, offset, read_var, sigma0, xtol) as floats, (params [N, n_params], crlb [N, n_params], deviance [N],
+    status [N], iterations [N]))."""
+    patches = _frames_f32(patches, name)
+    if patches.dim() != 3 or patches.shape[1] != patches.shape[2]:
+        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    n, P, _ = patches.shape
+    gain, offset, read_var = _camera_args(gain, offset, read_var)
+    sigma0, xtol = float(sigma0), float(xtol)
+    if not 0.2 < sigma0 < P:
+        raise ValueError(f"sigma0 must lie in (0.2, {P}), got {sigma0}")
+    if not 0 < xtol <= 1.49012e-8:
+        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
+    dev = patches.device
+    out = (torch.zeros(n, n_params, dtype=torch.float64, device=dev), torch.zeros(n, n_params, dtype=torch.float64, device=dev),
+           torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+           torch.zeros(n, dtype=torch.int32, device=dev))
+    return patches, (gain, offset, read_var, sigma0, xtol), out
+
+
 def fit_spots_mle(patches: torch.Tensor, gain: float = 1.0, offset: float = 0.0, read_var: float = 0.0, sigma0: float = 1.0,
                   fit_sigma: bool = True, xtol: float = 1e-11):
     """Poisson maximum-likelihood fit of every patch with its Cramer-Rao bound (csrc/localize.hip, mivit_fit_spots_mle):
@@ -722,32 +751,12 @@ def fit_spots_mle(patches: torch.Tensor, gain: float = 1.0, offset: float = 0.0,
     the readout variance in photons^2 -> (params [N, 5] float64 (photons, x0, y0, sigma, background per pixel), crlb [N, 5]
     float64 (variances; NaN where status != 0), deviance [N] float64, status [N] int32 (0 where the fit converged),
     iterations [N] int32).  fit_sigma=False holds sigma at sigma0."""
-    import math
-    patches = _frames_f32(patches, "fit_spots_mle")
-    if patches.dim() != 3 or patches.shape[1] != patches.shape[2]:
-        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    patches, scalars, out = _spot_fit_args("fit_spots_mle", patches, gain, offset, read_var, sigma0, xtol, 5)
     n, P, _ = patches.shape
-    gain, offset, read_var, sigma0, xtol = float(gain), float(offset), float(read_var), float(sigma0), float(xtol)
-    if not (gain > 0 and math.isfinite(gain)):
-        raise ValueError(f"gain must be finite and > 0, got {gain}")
-    if not math.isfinite(offset):
-        raise ValueError(f"offset must be finite, got {offset}")
-    if not (read_var >= 0 and math.isfinite(read_var)):
-        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
-    if not 0.2 < sigma0 < P:
-        raise ValueError(f"sigma0 must lie in (0.2, {P}), got {sigma0}")
-    if not 0 < xtol <= 1.49012e-8:
-        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
-    dev = patches.device
-    params = torch.zeros(n, 5, dtype=torch.float64, device=dev)
-    crlb = torch.zeros(n, 5, dtype=torch.float64, device=dev)
-    deviance = torch.zeros(n, dtype=torch.float64, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    iterations = torch.zeros(n, dtype=torch.int32, device=dev)
+    gain, offset, read_var, sigma0, xtol = scalars
     N.check(N.lib.mivit_fit_spots_mle(_p(patches), n, P, gain, offset, read_var, sigma0, 1 if fit_sigma else 0, xtol,
-                                      _p(params), _p(crlb), _p(deviance), _p(status), _p(iterations), _s(patches)),
-            "mivit_fit_spots_mle")
-    return params, crlb, deviance, status, iterations
+                                      *map(_p, out), _s(patches)), "mivit_fit_spots_mle")
+    return out
 
 
 def fit_spots_mle2(patches: torch.Tensor, count: torch.Tensor, guess: torch.Tensor, gain: float = 1.0, offset: float = 0.0,
@@ -758,38 +767,18 @@ def fit_spots_mle2(patches: torch.Tensor, count: torch.Tensor, guess: torch.Tens
     starting centres x1, y1, x2, y2 in patch coordinates; the last two are not read where count = 1) -> (params [N, 8] float64
     (N1, x1, y1, N2, x2, y2, sigma, background), crlb [N, 8] float64 (variances; NaN where status != 0), deviance [N] float64,
     status [N] int32, iterations [N] int32).  Where count = 1 the entries of emitter 2 are NaN."""
-    import math
-    patches = _frames_f32(patches, "fit_spots_mle2")
-    if patches.dim() != 3 or patches.shape[1] != patches.shape[2]:
-        raise ValueError(f"patches must be [N, P, P], got {tuple(patches.shape)}")
+    patches, scalars, out = _spot_fit_args("fit_spots_mle2", patches, gain, offset, read_var, sigma0, xtol, 8)
     n, P, _ = patches.shape
+    gain, offset, read_var, sigma0, xtol = scalars
     for t, name, dtype, shape in ((count, "count", torch.int32, (n,)), (guess, "guess", torch.float64, (n, 4))):
         if not torch.is_tensor(t) or t.device != patches.device:
             raise RuntimeError(f"fit_spots_mle2: {name} must be a GPU tensor on the patches' device")
         if t.dtype != dtype or tuple(t.shape) != shape:
             raise ValueError(f"fit_spots_mle2: {name} must be {dtype} of shape {shape}, got {t.dtype} {tuple(t.shape)}")
     count, guess = count.contiguous(), guess.contiguous()
-    gain, offset, read_var, sigma0, xtol = float(gain), float(offset), float(read_var), float(sigma0), float(xtol)
-    if not (gain > 0 and math.isfinite(gain)):
-        raise ValueError(f"gain must be finite and > 0, got {gain}")
-    if not math.isfinite(offset):
-        raise ValueError(f"offset must be finite, got {offset}")
-    if not (read_var >= 0 and math.isfinite(read_var)):
-        raise ValueError(f"read_var must be finite and >= 0, got {read_var}")
-    if not 0.2 < sigma0 < P:
-        raise ValueError(f"sigma0 must lie in (0.2, {P}), got {sigma0}")
-    if not 0 < xtol <= 1.49012e-8:
-        raise ValueError(f"xtol must be in (0, 1.49012e-8], got {xtol}")
-    dev = patches.device
-    params = torch.zeros(n, 8, dtype=torch.float64, device=dev)
-    crlb = torch.zeros(n, 8, dtype=torch.float64, device=dev)
-    deviance = torch.zeros(n, dtype=torch.float64, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    iterations = torch.zeros(n, dtype=torch.int32, device=dev)
     N.check(N.lib.mivit_fit_spots_mle2(_p(patches), _p(count), _p(guess), n, P, gain, offset, read_var, sigma0,
-                                       1 if fit_sigma else 0, xtol, _p(params), _p(crlb), _p(deviance), _p(status),
-                                       _p(iterations), _s(patches)), "mivit_fit_spots_mle2")
-    return params, crlb, deviance, status, iterations
+                                       1 if fit_sigma else 0, xtol, *map(_p, out), _s(patches)), "mivit_fit_spots_mle2")
+    return out
 
 
 def spot_neighbours(frame_offsets: torch.Tensor, ys: torch.Tensor, xs: torch.Tensor, reach: int):

@@ -69,6 +69,43 @@ def test_kernel_against_the_restatement(name, n):
         assert (got[0][:, 6] == kw["sigma0"]).all() and (got[1][got[3] == 0][:, 6] == 0.0).all()
 
 
+def _exits(P):
+    """Inputs for the two exits of the damped loop that no row of the tables takes -> [(patches, count, guess, kw, status,
+    iterations)].  With xtol = 1e-300 no step is ever small, so a fit runs to the iteration cap at its optimum (status 2, 100
+    iterations): at P = 15 the first rows of the table, at P = 3, where nine pixels cannot hold two emitters, single spots with
+    the width held.  A noiseless patch whose brightest pixel is 1.5e300 photons through a gain of 1e-291 has a deviance below
+    1e300 and position entries of the Fisher matrix (about N^2 / mu) above it, both by factors of about 5, so no damping
+    makes it factor: 14 failed factorisations, each counted as an iteration, take lambda past 1e10 (status 1)."""
+    c = float(P // 2)
+    if P == 3:
+        import localize_common as LC
+        kw = LC.camera_kwargs("p3_fixed")
+        patches, count = LC.case_patches("p3_fixed", 5), np.ones(5, np.int32)
+        guess = np.tile([c, c, c, c], (5, 1))
+    else:
+        kw = L2.camera_kwargs("p15_camera")
+        patches, count, guess = (a[:4] for a in L2.case_table("p15_camera"))
+    truth = np.array([[1000.0, c - 0.04, c + 0.03, 600.0, c + 0.95, c - 1.03, kw["sigma0"], 10.0]] * 2)
+    two = np.array([1, 1 if P == 3 else 2], np.int32)
+    img = np.stack([L2.model(P, truth[k:k + 1], int(two[k]))[0] for k in range(2)])
+    bright = (img * (1.5e9 / img.max(axis=(1, 2), keepdims=True))).astype(np.float32)
+    start = np.tile([c, c, c + 1.0, c - 1.0], (2, 1))
+    return [(patches, count, guess, dict(kw, xtol=1e-300), 2, 100),
+            (bright, two, start, dict(kw, gain=1e-291, offset=0.0, read_var=0.0), 1, 14)]
+
+
+@pytest.mark.parametrize("P", [3, 15])
+def test_the_iteration_cap_and_a_matrix_that_never_factors(P):
+    for patches, count, guess, kw, status, iters in _exits(P):
+        want = T._fit_mle2_numpy(patches, count, guess, **kw)
+        assert (want[3] == status).all() and (want[4] == iters).all() and np.isnan(want[1]).all()
+        got = _kernel(patches, count, guess, **kw)
+        assert np.array_equal(got[3], want[3]) and np.array_equal(got[4], want[4]) and np.isnan(got[1]).all()
+        wp, wd = _worst(got[0], want[0]), _worst(got[2], want[2])
+        print(f"P = {P} status {status}: worst relative difference, parameters", dict(zip(NAMES, wp)), "deviance", float(wd[0]))
+        assert (wp <= tc.KERNEL_FIT_RTOL).all() and (wd <= tc.KERNEL_FIT_RTOL).all()
+
+
 def _entry(patches, count, guess, n, P, outs, gain=1.0, offset=0.0, read_var=0.0, sigma0=1.0, fit_sigma=1, xtol=T.FIT_XTOL):
     return N.lib.mivit_fit_spots_mle2(patches, count, guess, n, P, gain, offset, read_var, sigma0, fit_sigma, xtol, *outs, None)
 

@@ -81,6 +81,34 @@ def test_same_bits_alone_in_a_batch_and_twice(name):
             assert dc.same_bits(a[:LC.TABLE_N].astype(np.float64), a[LC.TABLE_N:2 * LC.TABLE_N].astype(np.float64))
 
 
+def _unfactorable(P, sigma):
+    """([2, P, P] patches, gain): two noiseless spots whose brightest pixel is 1.5e300 photons through a gain of 1e-291.  The
+    deviance of the start stays below 1e300 (2e299 at P = 3, where it is largest), the position entries of the Fisher matrix
+    (about N^2 / mu) do not, so no damping makes it factor: 14 failed factorisations, each counted as an iteration, take lambda
+    past 1e10.  Both margins are factors of about 5, far from anything rounding decides."""
+    img = LC.expected_image(P, 1000.0, 10.0, sigma, P // 2 + np.array([0.05, -0.04]), P // 2 + np.array([-0.03, 0.02]))
+    return (img * (1.5e9 / img.max(axis=(1, 2), keepdims=True))).astype(np.float32), 1e-291
+
+
+@pytest.mark.parametrize("name", ["p3_fixed", "p15_camera"])
+def test_the_iteration_cap_and_a_matrix_that_never_factors(name):
+    """The two exits of the damped loop that no patch of the table takes: with xtol = 1e-300 no step is ever small, so the
+    fit runs to the iteration cap at its optimum (status 2, 100 iterations); a matrix past 1e300 ends as status 1 after 14."""
+    kw = LC.camera_kwargs(name)
+    P = LC.CASES[name][0]
+    patches, gain = _unfactorable(P, kw["sigma0"])
+    for pat, k, status, iters in ((LC.case_patches(name, 5), dict(kw, xtol=1e-300), 2, 100),
+                                  (patches, dict(kw, gain=gain, offset=0.0, read_var=0.0), 1, 14)):
+        want = T._fit_mle_numpy(pat, **k)
+        assert (want[3] == status).all() and (want[4] == iters).all()
+        params, crlb, deviance, st, it = _kernel(pat, **k)
+        assert np.array_equal(st, want[3]) and np.array_equal(it, want[4])
+        wp, wd = _worst(params, want[0]), _worst(deviance, want[2])
+        print(f"{name} status {status}: worst relative difference, parameters", dict(zip(COLUMNS, wp)), "deviance", float(wd[0]))
+        assert (wp <= tc.KERNEL_FIT_RTOL).all() and (wd <= tc.KERNEL_FIT_RTOL).all()
+        assert np.isnan(crlb).all() and np.isnan(want[1]).all()
+
+
 def test_a_nan_patch_has_status_3_and_leaves_its_neighbours_alone():
     name = "p9_camera"
     kw = LC.camera_kwargs(name)

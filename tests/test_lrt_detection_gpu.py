@@ -89,6 +89,43 @@ def test_likelihood_ratio_at_the_candidates(shape, r, flat, zero):
     assert bits_equal(got[:, :, 3], stats[:, :, 3])                        # the stage-1 statistic is handed through
 
 
+SPOTS = [(8, 8, 2000.0), (5, 30, 500.0), (2, 50, 1000.0), (12, 60, 300.0)]
+
+
+@pytest.mark.parametrize("kind", ["cap", "unfactorable"])
+def test_stage2_at_the_iteration_cap_and_with_a_matrix_that_never_factors(kind):
+    """The two exits of the damped loop that no candidate of the movies above takes, on one 16 x 64 frame with the candidates
+    given.  "cap": Poisson spots on no background and no read noise; the outer pixels of a window hold 0 photons, the deviance
+    falls all the way to the edge of the domain (mu = 0 there), every step across it is refused and the undamped step never
+    gets small: status 2 where the draw puts the optimum on the edge.  "unfactorable": a gain of 1e298 turns the frame into
+    photons of 1e-304, the matrix entries sum 1 / mu pass 1e300, no damping makes the matrix factor and 14 failed
+    factorisations take lambda past 1e10: status 1, with the start as the answer."""
+    r = 3
+    e = T.psf_profile(SIGMA[r], r)
+    rng = np.random.default_rng(5)
+    if kind == "cap":
+        movie, cam = rng.poisson(spot_image(16, 64, SPOTS, 0.0)).astype(np.float32)[None], (1.0, 0.0, 0.0)
+    else:
+        movie, cam = (rng.poisson(spot_image(16, 64, SPOTS, 5.0)) * 1e-6).astype(np.float32)[None], (1e298, 0.0, 0.0)
+    count = np.array([len(SPOTS)], np.int32)
+    coords = np.zeros((1, CAP, 2), np.int32)
+    coords[0, :len(SPOTS)] = [s[:2] for s in SPOTS]
+    values = np.zeros((1, CAP), np.float32)
+    kept, kcoords, stats, status, _ = restated_stage2(movie, e, 0.0, count, coords, values, *cam)
+    assert kept[0] == len(SPOTS)
+    assert (status[0, :4] == 2).sum() >= 2 if kind == "cap" else (status[0, :4] == 1).all()
+    dev = "cuda"
+    g_kept, g_coords, g_stats, g_status = ops.lrt_peaks(torch.from_numpy(movie).to(dev), e, *cam, 0.0, torch.from_numpy(count).to(dev),
+                                                        torch.from_numpy(coords).to(dev), torch.from_numpy(values).to(dev))
+    assert np.array_equal(g_kept.cpu().numpy(), kept) and np.array_equal(g_coords.cpu().numpy(), kcoords)
+    assert np.array_equal(g_status.cpu().numpy(), status)
+    got = g_stats.cpu().numpy()
+    for k, name in enumerate(("T", "photons", "background")):
+        err = np.abs(got[:, :, k] - stats[:, :, k])
+        print(f"{kind} {name}: worst relative difference {float(np.nanmax(err[0, :4] / np.abs(stats[0, :4, k])))}")
+        assert np.all(err <= 1e-9 * np.abs(stats[:, :, k])), (name, float(err.max()))
+
+
 def test_stage2_rejects_some_candidates():
     """the two stages differ: over the movies of this file, some stage-1 candidates fail the likelihood ratio"""
     shape, r, flat, zero = STAGE2[1]

@@ -197,6 +197,27 @@ def test_refine_gaussian_against_the_restatement(P):
     assert (hp[:, 3] > 0.5).all() and (np.abs(hp[:, 1] - P // 2) < 2).all()
 
 
+@pytest.mark.parametrize("P", [3, 15])
+def test_refine_gaussian_at_the_iteration_cap_and_past_the_damping(P):
+    """The two exits of the damped loop that no spot takes.  With xtol = 1e-300 no step is ever small, so a spot runs to the
+    iteration cap (status 2) at its optimum.  A patch whose largest value is 0 starts with amplitude 0: the derivatives of x0,
+    y0 and sigma are exactly 0, no damping makes the matrix factor, and 14 failed factorisations, each counted as an
+    iteration, take lambda past 1e10 (status 1) with the parameters where they started."""
+    dark = -np.random.default_rng(P).poisson(20.0, (5, P, P)).astype(np.float32)
+    dark[:, P // 2, P // 2] = 0.0
+    for patches, xtol, status in ((tc.spot_patches(5, P, seed=P), 1e-300, 2), (dark, T.FIT_XTOL, 1)):
+        hp, hpeak, hst = T._refine_numpy(patches, xtol)
+        assert (hst == status).all()
+        kp, kpeak, kst = (t.cpu().numpy() for t in ops.refine_gaussian(torch.from_numpy(patches).cuda(), xtol))
+        assert np.array_equal(kpeak, hpeak) and np.array_equal(kst, hst)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rel = np.where(kp == hp, 0.0, np.abs(kp - hp) / np.abs(hp))
+        print(f"fit, P = {P}, status {status}: worst relative difference per parameter {rel.max(axis=0)}")
+        assert rel.max() <= tc.KERNEL_FIT_RTOL, rel.max(axis=0)
+        if status == 1:
+            assert (kp[:, 0] == 0.0).all() and (kp[:, 3] == 1.0).all()
+
+
 def test_refine_fixture_patches_and_flat_path():
     mov = tc.movie("main")
     tracks, _, _ = T.track_particles_flat(mov, min_track_length=5)
